@@ -1,7 +1,17 @@
 #!/usr/bin/env python
 """Benchmark of the hot path on MI355X.  Contract: prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|frontend|train|vocoder]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload full|frontend|train|vocoder] [--full]
+                  [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the outputs if asked,
+print the line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall-clock ms of one timed step).
+--full adds every side measurement of the line: roofline, stages, single-stream, float32, front-end alone, training
+step, CPU baseline (--no-cpu-baseline / --no-f32 / --no-side switch single legs off again).
+--dump-outputs DIR writes, after the timed steps, what the timed path handed its caller in its LAST step as
+DIR/<name>.npy (float32; float64 where the path returns float64), at most 64 MB in all: beyond that each large
+array is cut to a fixed, seeded sample of its elements (small ones stay whole).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Launch forms.  (1) Under torch.distributed.run (RANK / WORLD_SIZE in the environment): this process is one rank.
 (2) Plain `python bench.py --gpus N` with N > 1: this process makes NO GPU call; it starts
@@ -21,7 +31,7 @@ Workloads
             (bf16 MFMA, f32 accumulate; --dtype float32 for the exact-f32 path); 25,600 frames
             per step and rank.
   frontend  BASELINE.json configs[1] alone: STFT+mel front-end, fp32 (25,632 frames).
-Extra objects on the line: "roofline" (dominant kernel, HIP-event timed on the launch stream),
+Extra objects on the line (--full): "roofline" (dominant kernel, HIP-event timed on the launch stream),
 "cpu_baseline" (oracle timed on the host, rank 0, N=1 only), "stages".
 """
 import argparse
@@ -70,6 +80,39 @@ def synth_audio(B, L, seed):
     x += 0.05 * torch.randn(B, L, generator=g, dtype=torch.float64)
     x *= 0.5 / x.abs().amax(dim=1, keepdim=True)
     return x.float()
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def host_outputs(args, rank, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, copied to the host right after the timed
+    loop (before any --full measurement can reuse their buffers); None when not asked for or not rank 0."""
+    if not args.dump_outputs or rank != 0:
+        return None
+    out = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        out[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32)
+    return out
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy for every array.  Above DUMP_LIMIT_BYTES in all, arrays of at most 1/64 of the limit are kept
+    whole and each larger one keeps the same share of its flat elements, chosen by a fixed seed (identical from run
+    to run and build to build)."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    small = DUMP_LIMIT_BYTES // 64
+    budget = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values() if a.nbytes <= small)
+    large = sum(a.nbytes for a in arrays.values() if a.nbytes > small)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.nbytes > small:
+            keep = a.size * budget // large
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(d, name + '.npy'), a)
 
 
 def _pmc_traffic(kernel):
@@ -143,6 +186,11 @@ def bench_frontend(args, rank, world):
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    outputs = host_outputs(args, rank, dict(zip(('mfcc', 'mel_db', 'power_db'), out)))
+    cfg = {'workload': 'frontend: STFT+mel+MFCC, batch 32 x 4 s @ 16 kHz (BASELINE configs[1])',
+           'batch': B, 'samples': L, 'frames_per_step_per_gpu': frames}
+    if not args.full:
+        return frames, dt, {}, cfg, outputs
 
     extra = {}
     if rank == 0:
@@ -162,8 +210,7 @@ def bench_frontend(args, rank, world):
                                                 '(DESIGN.md section 6)'}
         extra['stages'] = {'kernel_ms': {n: round(v, 5) for n, v in k.items()},
                            'frontend_pipeline_GBps': round(alg / (k['all'] * 1e-3) / 1e9, 1)}
-    return frames, dt, extra, {'workload': 'frontend: STFT+mel+MFCC, batch 32 x 4 s @ 16 kHz (BASELINE configs[1])',
-                               'batch': B, 'samples': L, 'frames_per_step_per_gpu': frames}
+    return frames, dt, extra, cfg, outputs
 
 
 def frontend_side_measurement(wav):
@@ -255,6 +302,17 @@ class _Pipeline:
                 ev.record(st_)
                 self.fe_done[k].append(ev)
 
+    def last_outputs(self):
+        """What the last step's decoder launches returned (y_mel, y_stft, y_phn over all its windows, in window
+        order).  step() files chunk i of a step under i, or with streams under (i, its chunk number mod 2 x streams)."""
+        idx = range(0, self.nwin, self.wb)
+        if self.streams is None:
+            chunks = [self.res[i] for i in idx]
+        else:
+            first = self.chunk_no - len(idx)
+            chunks = [self.res[(i, (first + j + 1) % (2 * len(self.streams)))] for j, i in enumerate(idx)]
+        return {n: torch.cat([c[k] for c in chunks]) for k, n in enumerate(('y_mel', 'y_stft', 'y_phn'))}
+
     def setup(self):
         # like loading the model: every stream's allocator pool and every weight-layout cache is built once
         for _ in range(2 * self.n_streams if self.streams else 1):
@@ -319,6 +377,14 @@ def bench_full(args, rank, world):
     pipe = _Pipeline(wav, dec, args.window_batch, args.streams)
     pipe.setup()
     dt = pipe.timed(args.steps, args.warmup, world)
+    outputs = host_outputs(args, rank, pipe.last_outputs()) if args.dump_outputs else None
+    cfg = {'workload': 'full: STFT+mel front-end on batch %d x 4 s @ 16 kHz (configs[1] input) -> %d windows of 400 '
+                       'frames -> encoder (enc_14 weights) + decoder (hp/decoder_cfg_d.json sizes, random init), '
+                       '%d windows per launch, independent steps pipelined over %d HIP streams' % (B, nwin, args.window_batch, args.streams),
+           'batch': B, 'samples': L, 'windows': nwin, 'frames_per_step_per_gpu': frames, 'model_dtype': args.dtype,
+           'streams': args.streams}
+    if not args.full:
+        return frames, dt, {}, cfg, outputs
     fe_out = pipe.fe_ring[0]
 
     extra = {}
@@ -403,12 +469,7 @@ def bench_full(args, rank, world):
         tr_line = train_side_measurement(rank, world, 'cpu' if args.backend == 'gloo' else 'cuda')
         if rank == 0:
             extra['train'] = tr_line
-    cfg = {'workload': 'full: STFT+mel front-end on batch %d x 4 s @ 16 kHz (configs[1] input) -> %d windows of 400 '
-                       'frames -> encoder (enc_14 weights) + decoder (hp/decoder_cfg_d.json sizes, random init), '
-                       '%d windows per launch, independent steps pipelined over %d HIP streams' % (B, nwin, args.window_batch, args.streams),
-           'batch': B, 'samples': L, 'windows': nwin, 'frames_per_step_per_gpu': frames, 'model_dtype': args.dtype,
-           'streams': args.streams}
-    return frames, dt, extra, cfg
+    return frames, dt, extra, cfg, outputs
 
 
 def rccl_info(backend):
@@ -421,11 +482,12 @@ def rccl_info(backend):
     return info
 
 
-def train_measure(rank, world, steps, warmup):
+def train_measure(rank, world, steps, warmup, full=True, args=None):
     """BASELINE configs[4] per-GPU shape: `steps` decoder training steps (fwd + bwd + Adam, float32, 32 windows x 400
     frames; under data parallelism the two gradient buckets are all-reduced, overlapped with the backward pass) timed
-    wall-clock between barriers + synchronize; then the exchange alone (whole arena and bucket by bucket, HIP events)
-    and, on rank 0, the dominant kernel.  Returns (frames per step, seconds, stages dict, roofline dict or None)."""
+    wall-clock between barriers + synchronize; then (`full`) the exchange alone (whole arena and bucket by bucket, HIP
+    events) and, on rank 0, the dominant kernel.  Returns (frames per step, seconds, stages dict, roofline dict or None,
+    host copies of the last step's results for --dump-outputs or None)."""
     import contextlib
     import io
     B, T = 32, 400
@@ -459,6 +521,13 @@ def train_measure(rank, world, steps, warmup):
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     tr = dec._trainer
+    # what the caller holds after the last step: its losses and the trained parameters (the flat float32 arena)
+    outputs = None if args is None else host_outputs(args, rank, {'mel_loss': last[0], 'stft_loss': last[1],
+                                                                  'loss': last[2], 'params': tr.flat})
+    if not full:
+        del dec, enc, tr
+        torch.cuda.empty_cache()
+        return B * T, dt, {}, None, outputs
     # the one exchange step of the path, alone: all-reduce of the flat gradient arena (every rank takes part), and the
     # two buckets forward_backward puts on the wire (stage 2 first, under stage 1's backward)
     ar_ms, buckets = None, None
@@ -530,19 +599,19 @@ def train_measure(rank, world, steps, warmup):
         stages['step_frac_of_f32_mfma_peak'] = round(stages['step_TFLOPs_at_3x_forward'] / MFMA_F32_PEAK_TF, 4)
     del dec, enc, tr
     torch.cuda.empty_cache()
-    return B * T, dt, stages, roof
+    return B * T, dt, stages, roof, outputs
 
 
 def bench_train(args, rank, world):
     """BASELINE configs[4]: decoder training step (fwd + bwd + Adam, float32) on synthetic
     ARCTIC-slt-shaped targets, 32 windows per GPU, gradients all-reduced over RCCL."""
-    frames, dt, stages, roof = train_measure(rank, world, args.steps, args.warmup)
-    extra = {'stages': stages}
+    frames, dt, stages, roof, outputs = train_measure(rank, world, args.steps, args.warmup, args.full, args)
+    extra = {'stages': stages} if args.full else {}
     if roof is not None:
         extra['roofline'] = roof
     cfg = {'workload': 'train: decoder fwd+bwd+Adam (float32) on 32 windows x 400 frames per GPU, encoder frozen '
                        '(BASELINE configs[4])', 'global_batch': 32 * world, 'frames_per_step_per_gpu': frames}
-    return frames, dt, extra, cfg
+    return frames, dt, extra, cfg, outputs
 
 
 def train_side_measurement(rank, world, reduce_device='cuda'):
@@ -550,7 +619,7 @@ def train_side_measurement(rank, world, reduce_device='cuda'):
     exchange is a collective), max over ranks; rank 0 reports."""
     import dist_util
     steps, warmup = 10, 3
-    frames, dt, stages, roof = train_measure(rank, world, steps, warmup)
+    frames, dt, stages, roof, _ = train_measure(rank, world, steps, warmup)
     dt = dist_util.max_over_ranks(dt, device=reduce_device) if world > 1 else dt
     return {'workload': 'BASELINE configs[4] per-GPU shape: decoder fwd+bwd+Adam, float32, 32 windows x 400 frames per GPU, '
                         'encoder frozen; data parallel x%d' % world,
@@ -588,6 +657,11 @@ def bench_vocoder(args, rank, world):
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    outputs = host_outputs(args, rank, {'wav': out})
+    cfg = {'workload': 'vocoder: from_power_to_wav, %d utterances x %d frames (5 s each), %d Griffin-Lim iterations, '
+                       'n_fft 400 hop 80' % (B, F, n_iter), 'frames_per_step_per_gpu': B * F}
+    if not args.full:
+        return B * F, dt, {}, cfg, outputs
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     out = audio_lib.from_power_to_wav_batch(P, None, **kw)
@@ -602,9 +676,7 @@ def bench_vocoder(args, rank, world):
                           'unit': 'GB/s', 'frac': round(alg_bytes / (us_iter * 1e-6) / 8e12, 4), 'traffic': None,
                           'kernel': 'gl_iter400_kernel<false> (time per iteration from events around the 200-launch '
                                     'chain; transform arithmetic and LDS traffic, not HBM, set its duration)'}}
-    cfg = {'workload': 'vocoder: from_power_to_wav, %d utterances x %d frames (5 s each), %d Griffin-Lim iterations, '
-                       'n_fft 400 hop 80' % (B, F, n_iter), 'frames_per_step_per_gpu': B * F}
-    return B * F, dt, extra, cfg
+    return B * F, dt, extra, cfg, outputs
 
 
 def cpu_baseline_vocoder():
@@ -741,7 +813,7 @@ def bench_stub(args, rank, world):
     dt = time.perf_counter() - t0
     assert float(x[0, 0]) == 1.0
     return 25600, dt, {}, {'workload': 'stub: launcher self-test on the CPU (no kernels, not a measurement)',
-                           'frames_per_step_per_gpu': 25600}
+                           'frames_per_step_per_gpu': 25600}, host_outputs(args, rank, {'x': x})
 
 
 def dist_util_barrier():
@@ -799,6 +871,12 @@ def main(argv=None):
                     help='HIP streams the independent window chunks / consecutive steps are pipelined over')
     ap.add_argument('--backend', default=None, choices=['nccl', 'gloo'],
                     help='process-group backend (default: nccl = RCCL; the stub workload uses gloo)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements of the line (roofline, stages, single-stream, float32, '
+                         'front-end alone, training step, CPU baseline); a plain run times the headline steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32/float64, "
+                         "<= 64 MB in all: a fixed, seeded sample beyond that)")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-f32', action='store_true', help='skip the float32 side measurement of the full workload')
     ap.add_argument('--no-side', action='store_true',
@@ -830,15 +908,15 @@ def main(argv=None):
         raise SystemExit('bench.py: %d ranks joined the process group, --gpus %d' % (joined, args.gpus))
 
     if args.workload == 'frontend':
-        frames, dt, extra, cfg = bench_frontend(args, rank, world)
+        frames, dt, extra, cfg, outputs = bench_frontend(args, rank, world)
     elif args.workload == 'train':
-        frames, dt, extra, cfg = bench_train(args, rank, world)
+        frames, dt, extra, cfg, outputs = bench_train(args, rank, world)
     elif args.workload == 'vocoder':
-        frames, dt, extra, cfg = bench_vocoder(args, rank, world)
+        frames, dt, extra, cfg, outputs = bench_vocoder(args, rank, world)
     elif stub:
-        frames, dt, extra, cfg = bench_stub(args, rank, world)
+        frames, dt, extra, cfg, outputs = bench_stub(args, rank, world)
     else:
-        frames, dt, extra, cfg = bench_full(args, rank, world)
+        frames, dt, extra, cfg, outputs = bench_full(args, rank, world)
 
     dt = dist_util.max_over_ranks(dt, device='cpu' if backend == 'gloo' else 'cuda')
     if rank == 0:
@@ -853,9 +931,11 @@ def main(argv=None):
         line.update(extra)
         if not stub:
             line['rccl'] = rccl_info(backend)
-        if joined == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and joined == 1 and not args.no_cpu_baseline and not stub:
             line['cpu_baseline'] = {'frontend': cpu_baseline_frontend, 'vocoder': cpu_baseline_vocoder,
                                     'train': cpu_baseline_train}.get(args.workload, cpu_baseline_full)()
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
     dist_util.finalize()
 

@@ -16,7 +16,6 @@ for p in (ROOT, PKG):
         sys.path.insert(0, p)
 
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
-REFERENCE = '/root/reference'
 
 
 def poison_gpu_state():
@@ -54,13 +53,6 @@ def pytest_collection_modifyitems(config, items):
 @pytest.fixture(scope='session')
 def golden_dir():
     return GOLDEN
-
-
-@pytest.fixture(scope='session')
-def reference_dir():
-    if not os.path.isdir(REFERENCE):
-        pytest.skip('/root/reference not present on this machine')
-    return REFERENCE
 
 
 FE_KW = dict(sr=16000, pre_emphasis=0.97, hop_length=80, win_length=400, n_mels=80, n_mfcc=40,

@@ -268,17 +268,6 @@ def test_loss_metrics_and_learning_rate_schedule(graph):
     assert abs(float(sc['opt/learning_rate']) - lr) < 1e-9
 
 
-def test_fixture_is_the_reference_graph(graph, reference_dir):
-    """Provenance (build container only; skipped where /root/reference is absent): the committed fixture is
-    exactly what tools/make_graph_fixture.py extracts from the reference's .meta file."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('make_graph_fixture', os.path.join(ROOT, 'tools', 'make_graph_fixture.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    fresh = json.loads(json.dumps(mod.extract(reference_dir)))
-    assert fresh['nodes'] == graph['nodes'] and fresh['meta_info'] == graph['meta_info']
-
-
 # ------------------------------------------------------------------------------------------------------
 # The WHOLE forward graph, as the reference saved it (training mode: dropout, batch statistics), evaluated
 # on the reference's trained weights and compared with the oracle's forward.  What the interpreter below

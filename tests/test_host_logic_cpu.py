@@ -97,10 +97,10 @@ def test_aux_func_config_roundtrip(tmp_path, capsys, monkeypatch):
     assert aux_func.show_diff({'a': 1, 'b': {'c': 1}}, {'a': 2, 'b': {'c': 2}, 'z': 0}) == 3
 
 
-def test_hp_configs_keep_reference_key_sets(reference_dir):
+def test_hp_configs_keep_reference_key_sets(golden_dir):
     for f in ('encoder_cfg_d.json', 'decoder_cfg_d.json', 'ds_enc_cfg_d.json', 'ds_dec_cfg_d.json'):
         mine = json.load(open(os.path.join(HP, f)))
-        ref = json.load(open(os.path.join(reference_dir, 'hp', f)))
+        ref = json.load(open(os.path.join(golden_dir, 'reference_hp', f)))      # the reference's hp/, verbatim
         assert mine == ref, f
 
 
@@ -295,6 +295,9 @@ def test_gradient_buckets_cover_the_arena_exactly_once(monkeypatch):
         calls.append((t.data_ptr(), t.numel(), async_op))
         return Work() if async_op else None
 
+    # host-only bookkeeping on CPU-device models, also on a machine with a GPU (which would otherwise hand the
+    # trainers a device stream for a CPU device)
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     monkeypatch.setattr(torch.distributed, 'is_initialized', lambda: True)
     monkeypatch.setattr(torch.distributed, 'get_world_size', lambda *a: 2)
     monkeypatch.setattr(torch.distributed, 'all_reduce', fake_all_reduce)

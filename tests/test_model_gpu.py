@@ -37,7 +37,7 @@ def test_encoder_restore_and_golden_forward(golden_dir, capsys):
     # float32 tolerances (SURVEY.md section 8c suggests logits 1e-4, softmax 1e-5; the f32 MFMA
     # path sums K = 2304 products per output in a different order than the oracle, which moves
     # probabilities near 1 by up to ~1.2e-5, so the softmax bound is stated as 2e-5)
-    assert np.abs(cbhg - g['CBHG_out']).max() < 1e-4
+    assert np.abs(cbhg - np.load(os.path.join(golden_dir, 'encoder_fwd_cbhg.npz'))['CBHG_out']).max() < 1e-4
     assert np.abs(y_logits - g['y_logits']).max() < 1e-4 * max(1.0, np.abs(g['y_logits']).max())
     assert np.abs(y_pred - g['y_pred']).max() < 2e-5
     # argmax: exact wherever the oracle's top-2 margin exceeds 1e-4
@@ -92,7 +92,8 @@ def _load_small_decoder(golden_dir, dtype):
     cfg = json.loads(str(g['cfg']))
     cfg['compute_dtype'] = dtype
     dec = decoder_specs(cfg, None, None)
-    w = {k[2:]: g[k] for k in g.files if k.startswith('w:')}
+    g2 = np.load(os.path.join(golden_dir, 'decoder_fwd_small_step2.npz'))          # stage 2's weights
+    w = {k[2:]: h[k] for h in (g, g2) for k in h.files if k.startswith('w:')}
     assert set(w) == set(dec.store.vars), set(w) ^ set(dec.store.vars)      # TF variable names line up
     dec.store.load_dict(w)
     return dec, g

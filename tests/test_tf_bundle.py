@@ -42,20 +42,50 @@ def test_golden_enc14_bundle(golden_dir):
     assert w['opt/epoch'].shape == () and w['opt/epoch'].dtype == np.int32
 
 
-def test_reference_checkpoints_readable(reference_dir):
-    for ck, n in (('enc_14_ckpt/encoder-136512', 109), ('enc_6_ckpt/encoder-184032', None)):
-        prefix = os.path.join(reference_dir, ck)
+def _reference_bundle(golden_dir, tmp_path, ck):
+    """The reference's checkpoint `ck` rebuilt from tests/golden/reference_ckpt/<ck> (tools/make_golden.py): its
+    TF-written .index verbatim, and its data blob re-assembled byte for byte -- every tensor at the offset TF's index
+    gives it, checked against the blob's recorded size and SHA-256.  Returns the bundle prefix."""
+    import glob
+    import hashlib
+    import shutil
+    src = os.path.join(golden_dir, 'reference_ckpt', ck)
+    meta = json.load(open(os.path.join(src, 'bundle.json')))
+    dst = tmp_path / ck
+    dst.mkdir()
+    prefix = str(dst / meta['prefix'])
+    shutil.copyfile(os.path.join(src, meta['prefix'] + '.index'), prefix + '.index')
+    tensors = {}
+    if meta['model_tensors_from']:
+        tensors.update(tf_bundle.read_bundle(os.path.join(golden_dir, meta['model_tensors_from'], meta['prefix'])))
+    for f in sorted(glob.glob(os.path.join(src, 'tensors_*.npz'))):
+        tensors.update(np.load(f))
+    blob = bytearray(meta['data_size'])
+    for name, e in tf_bundle.list_bundle(prefix).items():
+        raw = np.ascontiguousarray(tensors[name]).tobytes()
+        assert len(raw) == e.size, name
+        blob[e.offset:e.offset + e.size] = raw
+    assert hashlib.sha256(blob).hexdigest() == meta['data_sha256']
+    with open(prefix + '.data-00000-of-00001', 'wb') as f:
+        f.write(blob)
+    return prefix
+
+
+def test_reference_checkpoints_readable(golden_dir, tmp_path):
+    for ck, n in (('enc_14_ckpt', 109), ('enc_6_ckpt', None)):
+        prefix = _reference_bundle(golden_dir, tmp_path, ck)
         w = tf_bundle.read_bundle(prefix, verify_crc=True)          # every tensor CRC-checked
         if n is not None:
             assert len(w) == n
-    assert tf_bundle.latest_checkpoint(os.path.join(reference_dir, 'enc_14_ckpt')).endswith('encoder-136512')
+    ref = os.path.join(golden_dir, 'reference_ckpt')
+    assert tf_bundle.latest_checkpoint(os.path.join(ref, 'enc_14_ckpt')).endswith('encoder-136512')
     # enc_2_ckpt ships an index but no data blob (.MISSING_LARGE_BLOBS)
     with pytest.raises(Exception):
-        tf_bundle.read_bundle(os.path.join(reference_dir, 'enc_2_ckpt', 'encoder-136152'))
+        tf_bundle.read_bundle(os.path.join(ref, 'enc_2_ckpt', 'encoder-136152'))
 
 
-def test_writer_is_byte_compatible_with_tf(reference_dir, tmp_path):
-    src = os.path.join(reference_dir, 'enc_14_ckpt', 'encoder-136512')
+def test_writer_is_byte_compatible_with_tf(golden_dir, tmp_path):
+    src = _reference_bundle(golden_dir, tmp_path, 'enc_14_ckpt')
     w = tf_bundle.read_bundle(src, verify_crc=False)
     dst = str(tmp_path / 'encoder-1')
     tf_bundle.write_bundle(dst, w)

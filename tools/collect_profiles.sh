@@ -8,15 +8,15 @@ O=$R/gpurun_out/$RND
 rm -rf $O; mkdir -p $O
 cd $R
 timeout -k 10 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench_full.log 2>&1
-timeout -k 10 200 python bench.py --workload frontend --steps 50 --warmup 5 > $O/bench_frontend.log 2>&1
-timeout -k 10 300 python bench.py --workload train --steps 10 --warmup 3 > $O/bench_train.log 2>&1
-timeout -k 10 200 python bench.py --workload vocoder --steps 5 --warmup 1 > $O/bench_vocoder.log 2>&1
+timeout -k 10 400 python bench.py --full > $O/bench_full.log 2>&1
+timeout -k 10 200 python bench.py --full --workload frontend --steps 50 --warmup 5 > $O/bench_frontend.log 2>&1
+timeout -k 10 300 python bench.py --full --workload train --steps 10 --warmup 3 > $O/bench_train.log 2>&1
+timeout -k 10 200 python bench.py --full --workload vocoder --steps 5 --warmup 1 > $O/bench_vocoder.log 2>&1
 for f in bench_full bench_frontend bench_train bench_vocoder; do tail -1 $O/$f.log > $O/$f.json; done
 cd /tmp && export TMPDIR=/tmp
 for W in full frontend train vocoder; do
-  EXTRA="--steps 5 --warmup 1 --no-cpu-baseline --no-f32 --no-side"; [ $W = train ] && EXTRA="--steps 2 --warmup 1 --no-cpu-baseline"; [ $W = vocoder ] && EXTRA="--steps 2 --warmup 1 --no-cpu-baseline"
-  [ $W = frontend ] && EXTRA="--steps 50 --warmup 5 --no-cpu-baseline"
+  EXTRA="--full --steps 5 --warmup 1 --no-cpu-baseline --no-f32 --no-side"; [ $W = train ] && EXTRA="--full --steps 2 --warmup 1 --no-cpu-baseline"; [ $W = vocoder ] && EXTRA="--full --steps 2 --warmup 1 --no-cpu-baseline"
+  [ $W = frontend ] && EXTRA="--full --steps 50 --warmup 5 --no-cpu-baseline"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$W -- python3 $R/bench.py --workload $W $EXTRA > $O/trace_$W.log 2>&1
   cp $O/trace_$W/*/*kernel_stats.csv $O/${W}_kernel_stats.csv 2>/dev/null
 done

@@ -11,7 +11,11 @@
   tests/golden/frontend_*.npz        seeded synthetic audio + the CPU oracle's features
                                      (oracle/frontend_oracle.py; "parity unpinned", see its header)
   tests/golden/encoder_fwd.npz       seeded features + oracle encoder outputs with enc_14 weights
+                                     (CBHG_out in encoder_fwd_cbhg.npz)
   tests/golden/decoder_fwd_small.npz small-config decoder: seeded weights/inputs + oracle outputs
+                                     (stage 2's weights in decoder_fwd_small_step2.npz)
+  tests/golden/reference_hp/,        verbatim copies for the reference-facing CPU tests,
+  tests/golden/reference_ckpt/       see make_reference_copies()
 """
 import json
 import os
@@ -85,11 +89,13 @@ def make_encoder(enc_w):
         wt = mo.to_torch({k: v for k, v in enc_w.items() if k.startswith('encoder/')}, dt)
         taps = {}
         lg, pr, cl, out = mo.encoder_forward(torch.from_numpy(x).to(dt), wt, enc_cfg, taps=taps)
+    # two files, each under the 1 MiB limit of a committed file: CBHG_out lives on its own
     np.savez_compressed(os.path.join(GOLD, 'encoder_fwd.npz'), x=x,
                         y_logits=lg.numpy().astype(np.float32), y_pred=pr.numpy().astype(np.float32),
-                        y_pred_class=cl.numpy(), CBHG_out=out.numpy().astype(np.float32),
+                        y_pred_class=cl.numpy(),
                         prenet=taps['prenet'].numpy().astype(np.float32),
                         highway=taps['highway'].numpy().astype(np.float32))
+    np.savez_compressed(os.path.join(GOLD, 'encoder_fwd_cbhg.npz'), CBHG_out=out.numpy().astype(np.float32))
     print('encoder: logits', lg.shape, 'classes', np.unique(cl.numpy()).size)
 
 
@@ -108,10 +114,60 @@ def make_decoder_small():
     logits = rng.standard_normal((2, 40, 61)).astype(np.float32) * 2
     ppg = torch.softmax(torch.from_numpy(logits).double(), -1)
     ym, ys = mo.decoder_forward(ppg, mo.to_torch(w, torch.float64), cfg)
+    # stage 2's weights in a second file (each file under the 1 MiB limit of a committed file)
+    s2 = 'decoder/step2/'
     np.savez_compressed(os.path.join(GOLD, 'decoder_fwd_small.npz'), ppg=ppg.numpy().astype(np.float32),
                         y_mel=ym.numpy().astype(np.float32), y_stft=ys.numpy().astype(np.float32),
-                        cfg=json.dumps(cfg), **{'w:' + k: v for k, v in w.items()})
+                        cfg=json.dumps(cfg), **{'w:' + k: v for k, v in w.items() if not k.startswith(s2)})
+    np.savez_compressed(os.path.join(GOLD, 'decoder_fwd_small_step2.npz'),
+                        **{'w:' + k: v for k, v in w.items() if k.startswith(s2)})
     print('decoder small:', ym.shape, ys.shape)
+
+
+def make_reference_copies(enc_w):
+    """What the reference-facing CPU tests read, so that they need nothing outside the repository:
+      reference_hp/*.json            the reference's four hyper-parameter files, verbatim
+      reference_ckpt/<ckpt>/         each checkpoint's TF-written .index (and `checkpoint` state file) verbatim, the
+                                     tensors of its data blob as tensors_<i>.npz (< 1 MiB each; enc_14's 43 model
+                                     tensors are those of golden enc_14_ckpt and are not repeated), and bundle.json
+                                     with the blob's size and SHA-256, so that a test rebuilds the blob byte for byte
+    """
+    import hashlib
+    import shutil
+    hp_dir = os.path.join(GOLD, 'reference_hp')
+    os.makedirs(hp_dir, exist_ok=True)
+    for f in ('encoder_cfg_d.json', 'decoder_cfg_d.json', 'ds_enc_cfg_d.json', 'ds_dec_cfg_d.json'):
+        shutil.copyfile(os.path.join(REF, 'hp', f), os.path.join(hp_dir, f))
+    for ck, base, with_state in (('enc_14_ckpt', 'encoder-136512', True), ('enc_6_ckpt', 'encoder-184032', False),
+                                 ('enc_2_ckpt', 'encoder-136152', False)):
+        src = os.path.join(REF, ck, base)
+        dst_dir = os.path.join(GOLD, 'reference_ckpt', ck)
+        os.makedirs(dst_dir, exist_ok=True)
+        shutil.copyfile(src + '.index', os.path.join(dst_dir, base + '.index'))
+        if with_state:
+            shutil.copyfile(os.path.join(REF, ck, 'checkpoint'), os.path.join(dst_dir, 'checkpoint'))
+        blob = src + '.data-00000-of-00001'
+        if not os.path.exists(blob):                   # enc_2_ckpt ships no data blob (.MISSING_LARGE_BLOBS)
+            continue
+        w = tf_bundle.read_bundle(src, verify_crc=True)
+        shared = set(enc_w) if ck == 'enc_14_ckpt' else set()
+        parts, cur, nbytes = [], {}, 0
+        for k in tf_bundle.list_bundle(src):
+            if k in shared:
+                continue
+            if cur and nbytes + w[k].nbytes > 900000:
+                parts.append(cur)
+                cur, nbytes = {}, 0
+            cur[k] = w[k]
+            nbytes += w[k].nbytes
+        parts.append(cur)
+        for i, p in enumerate(parts):
+            np.savez_compressed(os.path.join(dst_dir, 'tensors_%d.npz' % i), **p)
+        data = open(blob, 'rb').read()
+        json.dump({'prefix': base, 'data_size': len(data), 'data_sha256': hashlib.sha256(data).hexdigest(),
+                   'model_tensors_from': 'enc_14_ckpt' if shared else None},
+                  open(os.path.join(dst_dir, 'bundle.json'), 'w'), indent=1)
+        print('%s: %d tensors in %d file(s)' % (ck, sum(len(p) for p in parts), len(parts)))
 
 
 if __name__ == '__main__':
@@ -120,3 +176,4 @@ if __name__ == '__main__':
     make_frontend()
     make_encoder(enc_w)
     make_decoder_small()
+    make_reference_copies(enc_w)

@@ -8,7 +8,7 @@ for C in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ
          "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
          "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM"; do
   i=$((i+1))
-  timeout -k 10 200 rocprofv3 --pmc $C --output-format csv -d $R/$O/p$i -- python3 $R/bench.py --workload frontend --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/p$i.log 2>&1
+  timeout -k 10 200 rocprofv3 --pmc $C --output-format csv -d $R/$O/p$i -- python3 $R/bench.py --full --workload frontend --steps 10 --warmup 2 --no-cpu-baseline > $R/$O/p$i.log 2>&1
 done
 python3 - <<PY
 import csv, glob, collections
