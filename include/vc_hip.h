@@ -39,8 +39,9 @@ extern "C" {
  *    sum_groups.  Bump on EVERY change of an exported signature or struct layout: the Python binding (_vc.py) refuses
  *    to load a library whose vc_version() differs from its own constant.
  * 3: vc_gemm_desc ends with d_workspace / workspace_bytes (vc_conv_gemm_workspace_bytes); vc_bn_post_routing added.
- * 4: vc_split16 / vc_weights16 / vc_gemm16 (training convolutions on split-float16 operands). */
-#define VC_ABI_VERSION 4
+ * 4: vc_split16 / vc_weights16 / vc_gemm16 (training convolutions on split-float16 operands).
+ * 5: vc_mx8_quantize / vc_mx8_conv / vc_mx8_conv_workspace_bytes and vc_mx8_conv_desc (MX-FP8 inference). */
+#define VC_ABI_VERSION 5
 
 int vc_version(void);
 const char* vc_last_error(void);
@@ -415,6 +416,56 @@ int vc_transpose_split16(const float* d_X, int32_t M, int32_t C, int32_t ldx, in
                          const float* d_shift, int32_t relu, int32_t pool, int32_t shift0, int32_t n_shifts, void* d_out16,
                          float* d_row_scale, void* stream);
 int vc_gemm16(const vc_gemm16_desc* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MX-FP8 inference of the decoder's filter banks and the projection behind them (csrc/vc_mx8.hip; opt-in through
+ * VariableStore(compute_dtype='mxfp8')).  Format: OCP MX-FP8, e4m3fn elements, one E8M0 scale byte 2^(code - 127) per
+ * 32 consecutive K elements of a row.  Scale rule: the smallest e with amax <= 448 * 2^e (clamped to [-127, 127]),
+ * elements RNE(x * 2^-e) with subnormals kept, nothing saturates; an all-zero block has scale code 0 and 0x00
+ * elements (csrc/vc_mx8.h holds the one device definition, tests/mx8_ref.py the CPU reference).
+ * ------------------------------------------------------------------------------------------ */
+/* X [M, C] bf16 (x_dtype VC_BF16) or float32 (VC_F32), row stride ldx elements -> d_Q [M, C] e4m3fn codes and d_S
+ * [M, C / 32] E8M0 scales, both dense.  C: a multiple of 32.  Used for the filter-bank input
+ * (the reference's modules.py:160, the bank's tf.layers.conv1d input) and for packing the weights, transposed to
+ * [Cout, taps * Cin] the way vc_conv_gemm stores them (blocks = (output channel, tap, 32 input channels)). */
+int vc_mx8_quantize(const void* d_X, int32_t x_dtype, int32_t M, int32_t C, int32_t ldx, void* d_Q, void* d_S, void* stream);
+#define VC_MX8_MAX_GROUPS 32
+#define VC_MX8_OUT_MX 0         /* out_mode: MX-FP8 codes d_C [M, n_out] + scales d_Cs [M, n_out / 32] */
+#define VC_MX8_OUT_BF16 1       /* bf16 d_C [M, n_out] */
+#define VC_MX8_OUT_F32 2        /* float32 d_C [M, n_out] (the epilogue's values before any quantisation: tests) */
+/* One 128-channel filter of a launch: d_W [128][taps * Cin] e4m3fn and d_Ws [128][taps * Cin / 32] from
+ * vc_mx8_quantize, output channels [c_off, c_off + 128), SAME left padding pad_l. */
+typedef struct vc_mx8_group {
+    const void* d_W;
+    const void* d_Ws;
+    int32_t taps, pad_l, c_off, reserved;
+} vc_mx8_group;
+/* Y[m, c_off + n] = epi( sum over taps j, channels c of X[m + j - pad_l, c] * W[n][j][c] ), X and W the dequantised MX
+ * operands, SAME zero padding inside each window of T rows, float32 accumulation.  Groups are taken two at a time
+ * (2g, 2g + 1) by one workgroup over 128 frames, so they must come in pairs that share pad_l -- filter-bank widths
+ * (2p+1, 2p+2) -- or be the halves of one 256-channel filter; a single group (128 outputs) is allowed.
+ * epi = d_epi_scale[ch] * acc + d_epi_shift[ch] (folded inference BatchNorm), then relu (act = VC_ACT_RELU), then with
+ * pool != 0 max_pooling1d(2, 1, 'same') along time inside each window (the reference's modules.py:331), then the
+ * output conversion of out_mode.  Shapes: Cin a multiple of 64, n_out a multiple of 32, taps 1..32.
+ * Replaces: conv1d_banks + max_pooling1d (the reference's modules.py:144-166, 331) as ONE launch writing MX-FP8, and
+ * conv1d_1 (the reference's modules.py:333-335) reading it and writing bf16.  A launch without pool and with at most
+ * two groups splits K over workgroups when given vc_mx8_conv_workspace_bytes() of workspace (float32 partial sums,
+ * reduced in a fixed order by a second launch: bit-identical run to run; out_mode BF16 / F32 only). */
+typedef struct vc_mx8_conv_desc {
+    const void* d_X;            /* [M, Cin] e4m3fn codes */
+    const void* d_Xs;           /* [M, Cin / 32] E8M0 */
+    int32_t M, T, Cin, n_groups;
+    vc_mx8_group groups[VC_MX8_MAX_GROUPS];
+    const float* d_epi_scale;   /* [n_out] */
+    const float* d_epi_shift;   /* [n_out] */
+    int32_t act, pool, out_mode, n_out;
+    void* d_C;
+    void* d_Cs;                 /* VC_MX8_OUT_MX only */
+    void* d_workspace;          /* 256-byte aligned, or NULL (no split) */
+    size_t workspace_bytes;
+} vc_mx8_conv_desc;
+size_t vc_mx8_conv_workspace_bytes(const vc_mx8_conv_desc* desc);
+int vc_mx8_conv(const vc_mx8_conv_desc* desc, void* stream);
 
 /* Train-mode FusedBatchNorm bookkeeping (modules.py:77-84, is_training): batch mean / biased
  * variance of X [M, C] -> scale/shift (consumed by the next launch's prologue or vc_affine_act),

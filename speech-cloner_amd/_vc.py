@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VC_LIB_PATH', os.path.join(_HERE, 'libvc_hip.so'))   # override: kernel A/B experiments
 
 VC_OK = 0
-VC_ABI_VERSION = 4      # include/vc_hip.h: VC_ABI_VERSION -- lib() refuses a library that reports another one
+VC_ABI_VERSION = 5      # include/vc_hip.h: VC_ABI_VERSION -- lib() refuses a library that reports another one
 
 
 class VCError(RuntimeError):
@@ -107,6 +107,25 @@ class Gemm16Desc(C.Structure):
                 ('workspace_bytes', C.c_size_t)]
 
 
+MX8_MAX_GROUPS = 32
+MX8_OUT_MX, MX8_OUT_BF16, MX8_OUT_F32 = 0, 1, 2
+
+
+class Mx8Group(C.Structure):
+    """struct vc_mx8_group (include/vc_hip.h)."""
+    _fields_ = [('d_W', C.c_void_p), ('d_Ws', C.c_void_p), ('taps', C.c_int32), ('pad_l', C.c_int32),
+                ('c_off', C.c_int32), ('reserved', C.c_int32)]
+
+
+class Mx8ConvDesc(C.Structure):
+    """struct vc_mx8_conv_desc (include/vc_hip.h)."""
+    _fields_ = [('d_X', C.c_void_p), ('d_Xs', C.c_void_p), ('M', C.c_int32), ('T', C.c_int32), ('Cin', C.c_int32),
+                ('n_groups', C.c_int32), ('groups', Mx8Group * MX8_MAX_GROUPS), ('d_epi_scale', C.c_void_p),
+                ('d_epi_shift', C.c_void_p), ('act', C.c_int32), ('pool', C.c_int32), ('out_mode', C.c_int32),
+                ('n_out', C.c_int32), ('d_C', C.c_void_p), ('d_Cs', C.c_void_p), ('d_workspace', C.c_void_p),
+                ('workspace_bytes', C.c_size_t)]
+
+
 class WgradGroup(C.Structure):
     """struct vc_wgrad_group (include/vc_hip.h)."""
     _fields_ = [('d_dYT', C.c_void_p), ('d_dW', C.c_void_p), ('N', C.c_int32), ('taps', C.c_int32),
@@ -176,6 +195,9 @@ _SIGS = {
                                        C.c_int32, _P, _P, _P]),
     'vc_gemm16_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     'vc_gemm16': (C.c_int, [C.POINTER(Gemm16Desc), _P]),
+    'vc_mx8_quantize': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    'vc_mx8_conv_workspace_bytes': (C.c_size_t, [C.POINTER(Mx8ConvDesc)]),
+    'vc_mx8_conv': (C.c_int, [C.POINTER(Mx8ConvDesc), _P]),
     'vc_axpby': (C.c_int, [_P, C.c_int32, C.c_float, _P, C.c_int32, C.c_float, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     'vc_mse_loss': (C.c_int, [_P, _P, C.c_size_t, C.c_float, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     'vc_softmax_ce': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),

@@ -52,6 +52,9 @@ class decoder_specs:
             self.store = modules.VariableStore(self.cfg_d.get('compute_dtype', 'float32'),
                                                device=self.cfg_d.get('device', 'cuda'))
         else:
+            if self.cfg_d.get('compute_dtype') == 'mxfp8':
+                raise ValueError(" - ERROR, decoder_specs: compute_dtype 'mxfp8' needs a decoder with its own store "
+                                 "(no encoder: the encoder's store is shared and cannot be mxfp8)")
             self.store = self.encoder.store
         self.sess = self.store
         return None

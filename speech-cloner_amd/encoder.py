@@ -10,7 +10,7 @@ the reference's own ``enc_14_ckpt``.
 Differences a caller can see (documented, deliberate):
   * ``inputs``, ``y_pred`` ... are light-weight handles (there is no graph); ``run(var, feed_dict)``
     evaluates the handles this class defines.
-  * optional config key ``compute_dtype`` ('float32' default | 'bfloat16').
+  * optional config key ``compute_dtype`` ('float32' default | 'bfloat16'; 'mxfp8' is refused: decoder only).
   * training (``exec_train_step`` / ``exec_calc_metrics`` / ``train``, encoder.py:256-356) runs in
     float32 through training.EncoderTrainer; TensorBoard summaries are not written.
 """
@@ -45,6 +45,9 @@ class encoder_spec_phn:
         self.i_epoch = 0
         self.summary_v = []
 
+        if cfg_d.get('compute_dtype') == 'mxfp8' or getattr(store, 'mx8', False):
+            # the bank input (40 channels) does not form 32-channel blocks, and the encoder is 0.7 % of the MACs
+            raise ValueError(" - ERROR, encoder_spec_phn: compute_dtype 'mxfp8' covers the decoder only; use 'bfloat16'")
         self.store = store if store is not None else modules.VariableStore(
             cfg_d.get('compute_dtype', 'float32'),
             device=cfg_d.get('device', 'cuda'))

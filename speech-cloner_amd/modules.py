@@ -25,6 +25,7 @@ import threading
 import numpy as np
 
 import _vc
+import mx8
 
 # Host-side fusion choices (one launch vs several for the same arithmetic).  Not read from the environment: set them
 # here (modules.OPTIONS['prenet_chain'] = False) or per model through the optional config key 'kernel_options'.
@@ -59,10 +60,14 @@ class VariableStore:
 
     def __init__(self, compute_dtype='float32', device='cuda', seed=0):
         torch = _torch()
+        self.mx8 = False
         if compute_dtype in ('float32', 'f32', torch.float32):
             self.dtype, self.vc_dtype = torch.float32, _vc.VC_F32
         elif compute_dtype in ('bfloat16', 'bf16', torch.bfloat16):
             self.dtype, self.vc_dtype = torch.bfloat16, _vc.VC_BF16
+        elif compute_dtype == 'mxfp8':
+            # bf16 everywhere, except the filter banks and the projection behind them: MX-FP8 (mx8.py)
+            self.dtype, self.vc_dtype, self.mx8 = torch.bfloat16, _vc.VC_BF16, True
         else:
             raise ValueError(' - ERROR, compute_dtype {} not understood'.format(compute_dtype))
         self.device = torch.device(device)
@@ -430,6 +435,12 @@ def _f32_split_ok(store):
     return store.dtype == _torch().float32 and _vc.get_option('f32_f16x3') != 0
 
 
+def _mx8_ok(store):
+    """MX-FP8 inference (VariableStore(compute_dtype='mxfp8'), mx8.py): the filter banks write MX-FP8 (pooled) and the
+    projection behind them reads it; the shapes mx8.bank_supported / conv_supported leave out stay on bf16."""
+    return getattr(store, 'mx8', False)
+
+
 def conv1d(inputs, filters=None, size=1, rate=1, padding="SAME", use_bias=False, activation_fn=None,
            scope="conv1d", reuse=None, bn_scope=None, residual=None, pool_input=False):
     """modules.py:104-140 (tf.layers.conv1d, stride 1, no bias).  Extra keyword arguments fuse
@@ -444,6 +455,24 @@ def conv1d(inputs, filters=None, size=1, rate=1, padding="SAME", use_bias=False,
         raise NotImplementedError(' - ERROR, conv1d: only rate=1, padding=SAME, use_bias=False are used by the reference')
     torch = _torch()
     store = _store()
+    if isinstance(inputs, mx8.MxTensor):
+        # MX-FP8 bank output (already pooled): the projection conv1d_1 on the MX kernel, bf16 out
+        N_, T_, Cin = inputs.shape
+        filters = Cin if filters is None else filters
+        if not (_mx8_ok(store) and mx8.conv_supported(Cin, filters, size) and residual is None and not pool_input):
+            raise ValueError(' - ERROR, conv1d {}: an MX-FP8 input needs mxfp8 mode, a multiple of 128 filters, no '
+                             'residual and no input pooling'.format(_scope(scope)))
+        with variable_scope(scope):
+            kscope = _scope()
+            store.get(kscope + '/conv1d/kernel', (size, Cin, filters), 'glorot')
+        if bn_scope is not None:
+            s, sh = _prep_bn(store, _scope(bn_scope), filters)
+        else:
+            s = store.cached(('ones', filters), lambda: torch.ones(filters, dtype=torch.float32, device=store.device))
+            sh = store.cached(('zeros', filters), lambda: torch.zeros(filters, dtype=torch.float32, device=store.device))
+        packed = store.cached(('mx8conv', kscope, bn_scope), lambda: mx8.pack_kernel(store.vars[kscope + '/conv1d/kernel']))
+        act = {None: _vc.ACT_NONE, 'relu': _vc.ACT_RELU}[activation_fn]
+        return mx8.conv(inputs, packed, size, filters, s, sh, act)
     x = _as3(inputs)
     N_, T_, Cin = x.shape
     if filters is None:
@@ -476,12 +505,14 @@ def conv1d(inputs, filters=None, size=1, rate=1, padding="SAME", use_bias=False,
     return out
 
 
-def conv1d_banks(inputs, K=16, embed_size=256, is_training=True, scope="conv1d_banks", reuse=None, pool_output=None):
+def conv1d_banks(inputs, K=16, embed_size=256, is_training=True, scope="conv1d_banks", reuse=None, pool_output=None,
+                 mx8_out=False):
     """modules.py:144-166: K convolutions of width 1..K (embed_size//2 filters each), concat,
     batch norm, relu -- ONE grouped launch, heaviest bank first, norm+relu in the epilogue.
     pool_output='auto' lets the launch also apply the max_pooling1d(2, 1, 'same') that follows the
     banks in CBHG (modules.py:331) where the kernel supports it; the return value is then
-    (output, pooled: bool)."""
+    (output, pooled: bool).  mx8_out (with pool_output='auto', in mxfp8 mode, on shapes mx8.bank_supported accepts):
+    the output is an mx8.MxTensor, pooled, that conv1d() consumes."""
     if is_training:
         raise NotImplementedError(' - ERROR, conv1d_banks: training mode runs through the fused training step')
     torch = _torch()
@@ -491,14 +522,23 @@ def conv1d_banks(inputs, K=16, embed_size=256, is_training=True, scope="conv1d_b
     F_ = embed_size // 2
     if K > _vc.GEMM_MAX_GROUPS:
         raise ValueError(' - ERROR, conv1d_banks: K={} > {}'.format(K, _vc.GEMM_MAX_GROUPS))
+    use_mx8 = mx8_out and pool_output == 'auto' and _mx8_ok(store) and mx8.bank_supported(K, Cin, F_)
     groups = []
     with variable_scope(scope):
         for k in range(1, K + 1):
             sub = 'conv1d' if k == 1 else 'num_{}/conv1d'.format(k)
             with variable_scope(sub):
-                bt = _prep_conv(store, _scope(), k, Cin, F_)
-            groups.append((bt, k * Cin, k, (k - 1) // 2, F_ * (k - 1)))
+                if use_mx8:       # the MX path packs its own weights: no bf16 layout copy
+                    store.get(_scope() + '/conv1d/kernel', (k, Cin, F_), 'glorot')
+                else:
+                    bt = _prep_conv(store, _scope(), k, Cin, F_)
+                    groups.append((bt, k * Cin, k, (k - 1) // 2, F_ * (k - 1)))
         s, sh = _prep_bn(store, _scope('bn'), F_ * K)
+    if use_mx8:
+        bscope = _scope(scope)
+        packed = store.cached(('mx8bank', bscope), lambda: [mx8.pack_kernel(store.vars[
+            bscope + ('/conv1d' if k == 1 else '/num_{}/conv1d'.format(k)) + '/conv1d/kernel']) for k in range(1, K + 1)])
+        return mx8.bank(x, packed, K, s, sh), True
     out = torch.empty((N_, T_, F_ * K), dtype=store.dtype, device=x.device)
     if _f32_split_ok(store) and K % 2 == 0 and K <= 32 and Cin % 64 == 0 and F_ == BANK_FILTERS == 128:
         # float32 result from float16 products; pairs of filter widths as in the bf16 bank kernel.  The pool stays with
@@ -746,7 +786,8 @@ def CBHG(inputs, embed_size=256, num_conv_banks=16, num_highwaynet_blocks=4, dro
     with variable_scope(scope):
         # max pooling (modules.py:331) rides on the bank launch's stores where that kernel can do it,
         # else on conv1d_1's operand load (2: operand is post-ReLU (>= 0), integer-ordered max)
-        enc, pooled = conv1d_banks(inputs, K=num_conv_banks, is_training=is_training, pool_output='auto')   # (N, T, K*128)
+        enc, pooled = conv1d_banks(inputs, K=num_conv_banks, is_training=is_training, pool_output='auto',
+                                   mx8_out=(embed_size // 2) % 128 == 0)                       # (N, T, K*128)
         enc = conv1d(enc, filters=embed_size // 2, size=3, scope="conv1d_1", bn_scope="conv1d_1",
                      activation_fn='relu', pool_input=0 if pooled else 2)                  # (N, T, E/2)
         enc = conv1d(enc, filters=embed_size // 2, size=3, scope="conv1d_2", bn_scope="conv1d_2",
