@@ -40,8 +40,9 @@ extern "C" {
  *    to load a library whose vc_version() differs from its own constant.
  * 3: vc_gemm_desc ends with d_workspace / workspace_bytes (vc_conv_gemm_workspace_bytes); vc_bn_post_routing added.
  * 4: vc_split16 / vc_weights16 / vc_gemm16 (training convolutions on split-float16 operands).
- * 5: vc_mx8_quantize / vc_mx8_conv / vc_mx8_conv_workspace_bytes and vc_mx8_conv_desc (MX-FP8 inference). */
-#define VC_ABI_VERSION 5
+ * 5: vc_mx8_quantize / vc_mx8_conv / vc_mx8_conv_workspace_bytes and vc_mx8_conv_desc (MX-FP8 inference).
+ * 6: vc_griffin_lim_momentum_f32 / vc_vocoder_workspace_bytes_momentum (fast Griffin-Lim). */
+#define VC_ABI_VERSION 6
 
 int vc_version(void);
 const char* vc_last_error(void);
@@ -596,6 +597,26 @@ int vc_griffin_lim_f32(const vc_vocoder_plan* plan, const float* d_amp, const fl
                        const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t num_iters,
                        float* d_wav, int32_t wav_stride, float* d_trace, void* d_workspace, size_t workspace_bytes,
                        void* stream);
+
+/* Fast Griffin-Lim (Perraudin, Balazs & Sondergaard 2013), librosa's / torchaudio's formulation, with the
+ * state and iteration count of audio_lib.py:249-274 (num_iters ISTFTs, num_iters - 1 projections).  With
+ * beta = momentum / (1 + momentum) and R_0 = 0, for i = 1 .. num_iters - 1:
+ *     R_i = STFT(ISTFT(S_{i-1}))        (complex)
+ *     C_i = R_i - beta * R_{i-1}
+ *     S_i = amp * C_i / |C_i|           (a zero C_i gets phase 0)
+ * and wav = ISTFT(S_{num_iters-1}).  momentum must be finite and in [0, 1), else VC_ERR_INVALID before any
+ * launch.  momentum == 0 launches exactly what vc_griffin_lim_f32 launches (bit-identical, and needs only
+ * vc_vocoder_workspace_bytes); with num_iters <= 2 the momentum never acts and the result is bit-identical
+ * to momentum 0.  momentum > 0 needs vc_vocoder_workspace_bytes_momentum bytes, 16-byte aligned: R_{i-1}
+ * per frame, 13 x 16 float2 (1,664 bytes) on the 400-point path, 1 + n_fft/2 float2 on the generic one,
+ * read and rewritten once per iteration.  Other arguments, the trace and the launch count as
+ * vc_griffin_lim_f32; hipGraph-capturable like every launch call here. */
+size_t vc_vocoder_workspace_bytes_momentum(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames,
+                                           int32_t trace);
+int vc_griffin_lim_momentum_f32(const vc_vocoder_plan* plan, const float* d_amp, const float* d_phase0,
+                                const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t num_iters,
+                                float momentum, float* d_wav, int32_t wav_stride, float* d_trace, void* d_workspace,
+                                size_t workspace_bytes, void* stream);
 
 /* audio_lib.py:301-306 in place on d_wav [batch, wav_stride] (first hop*(n_frames[b]-1) samples):
  * y[n] = x[n] + coeff*y[n-1] (skipped when coeff == 0), then y *= mean_abs_amp_norm / mean|y|

@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VC_LIB_PATH', os.path.join(_HERE, 'libvc_hip.so'))   # override: kernel A/B experiments
 
 VC_OK = 0
-VC_ABI_VERSION = 5      # include/vc_hip.h: VC_ABI_VERSION -- lib() refuses a library that reports another one
+VC_ABI_VERSION = 6      # include/vc_hip.h: VC_ABI_VERSION -- lib() refuses a library that reports another one
 
 
 class VCError(RuntimeError):
@@ -223,6 +223,9 @@ _SIGS = {
     'vc_power_to_amp': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     'vc_griffin_lim_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P,
                                      C.c_size_t, _P]),
+    'vc_vocoder_workspace_bytes_momentum': (C.c_size_t, [_P, C.c_int32, C.c_int32, C.c_int32]),
+    'vc_griffin_lim_momentum_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, C.c_int32,
+                                              _P, _P, C.c_size_t, _P]),
     'vc_inv_preemphasis_normalize': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
 }
 

@@ -17,11 +17,16 @@ cases of them):
   calc_MFCC_input_batch(wav [B, L], lens=None, ...) -> three torch.cuda tensors [B, Fmax, C]
   from_power_to_wav_batch(P [B, Fmax, bins], n_frames=None, ...) -> torch.cuda tensor [B, hop*(Fmax-1)]
 
+The Griffin-Lim entry points take ``momentum`` (default 0.0, the reference's algorithm): fast
+Griffin-Lim as in librosa.griffinlim / torchaudio GriffinLim, see include/vc_hip.h
+vc_griffin_lim_momentum_f32.
+
 All arithmetic runs in hand-written HIP kernels (csrc/vc_frontend.hip) through the C ABI
 ``vc_frontend_f32`` (include/vc_hip.h); torch only owns the device buffers.  There is no
 CPU path: without the native library or a GPU the calls raise.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -240,12 +245,22 @@ class _VocPlan:
         self.n_bins = 1 + self.n_fft // 2
         self._ws = None
 
-    def workspace(self, batch, max_frames, trace, device):
+    def workspace(self, batch, max_frames, trace, device, momentum=False):
         import torch
-        need = _vc.lib().vc_vocoder_workspace_bytes(self.handle, batch, max_frames, int(trace))
+        lib = _vc.lib()
+        size = lib.vc_vocoder_workspace_bytes_momentum if momentum else lib.vc_vocoder_workspace_bytes
+        need = size(self.handle, batch, max_frames, int(trace))
         if self._ws is None or self._ws.numel() < need or self._ws.device != device:
             self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
+
+
+def check_momentum(momentum):
+    """Fast Griffin-Lim momentum as a float; ValueError unless finite and in [0, 1) (torchaudio's rule)."""
+    m = float(momentum)
+    if not (math.isfinite(m) and 0.0 <= m < 1.0):
+        raise ValueError(' - ERROR, griffin_lim: momentum must be finite and in [0, 1), got {!r}'.format(momentum))
+    return m
 
 
 def _get_voc_plan(win_length, hop_length, n_fft):
@@ -276,13 +291,15 @@ def _frames_arg(n_frames, B, Fmax, plan):
 
 
 def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_iters=300, n_fft=None, phase0=None,
-                      trace=False):
+                      trace=False, momentum=0.0):
     """Batched Griffin-Lim on the GPU.  amp: float32 [B, Fmax, bins] magnitudes (frame-major, the
     decoder's y_stft layout); phase0: same shape, radians (default: pi * np.random.rand drawn per
-    utterance in the reference's [bins, F] order, audio_lib.py:255).
+    utterance in the reference's [bins, F] order, audio_lib.py:255).  momentum: fast Griffin-Lim
+    (0 <= momentum < 1; 0 = the reference's algorithm, 0.99 = librosa's default).
     Returns wav [B, hop*(Fmax-1)] cuda float32 (zero beyond an utterance's hop*(frames-1) samples)
     and, with ``trace``, the per-iteration sum of squared waveform changes [num_iters, B]."""
     import torch
+    momentum = check_momentum(momentum)
     if not torch.cuda.is_available():
         raise _vc.VCError('griffin_lim needs a GPU (no CPU fallback)')
     plan = _get_voc_plan(win_length, hop_length, n_fft)
@@ -306,24 +323,33 @@ def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_ite
     L = plan.hop_length * (Fmax - 1)
     wav = torch.empty((B, L), dtype=torch.float32, device=amp.device)
     tr = torch.empty((int(num_iters), B), dtype=torch.float32, device=amp.device) if trace else None
-    ws = plan.workspace(B, Fmax, trace, amp.device)
-    _vc.check(_vc.lib().vc_griffin_lim_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B, Fmax,
-                                           int(num_iters), _vc.ptr(wav), L, _vc.ptr(tr), _vc.ptr(ws), ws.numel(),
-                                           _vc.current_stream()))
+    ws = plan.workspace(B, Fmax, trace, amp.device, momentum=momentum > 0.0)
+    if momentum == 0.0:
+        _vc.check(_vc.lib().vc_griffin_lim_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B, Fmax,
+                                               int(num_iters), _vc.ptr(wav), L, _vc.ptr(tr), _vc.ptr(ws), ws.numel(),
+                                               _vc.current_stream()))
+    else:
+        _vc.check(_vc.lib().vc_griffin_lim_momentum_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B,
+                                                        Fmax, int(num_iters), momentum, _vc.ptr(wav), L, _vc.ptr(tr),
+                                                        _vc.ptr(ws), ws.numel(), _vc.current_stream()))
     return (wav, tr) if trace else wav
 
 
-def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None, verbose=True, phase0=None):
+def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None, verbose=True, phase0=None,
+                    momentum=0.0):
     """audio_lib.py:249-274.  stft_amp [1+n_fft//2, F] -> wav [hop*(F-1)].  The initial phase comes
     from the global numpy generator exactly like the reference (``np.random.seed`` makes both
     reproducible) unless ``phase0`` [bins, F] is given.  verbose prints the reference's
-    per-iteration ``mrse_delta`` lines (after the run: the iterations are queued asynchronously)."""
+    per-iteration ``mrse_delta`` lines (after the run: the iterations are queued asynchronously).
+    momentum: fast Griffin-Lim, see griffin_lim_batch."""
+    momentum = check_momentum(momentum)
     stft_amp = np.asarray(stft_amp)
     if phase0 is None:
         phase0 = np.pi * np.random.rand(*stft_amp.shape)
     amp = np.ascontiguousarray(stft_amp.T, dtype=np.float32)[None]
     ph = np.ascontiguousarray(np.asarray(phase0).T, dtype=np.float32)[None]
-    r = griffin_lim_batch(amp, None, win_length, hop_length, num_iters, n_fft, ph, trace=bool(verbose))
+    r = griffin_lim_batch(amp, None, win_length, hop_length, num_iters, n_fft, ph, trace=bool(verbose),
+                          momentum=momentum)
     if verbose:
         wav, tr = r
         tr = tr.cpu().numpy()[:, 0]
@@ -336,10 +362,12 @@ def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None,
 
 def from_power_to_wav_batch(P, n_frames=None, P_dB_norm_factor=0.01, pre_emphasis=0.97, hop_length=40,
                             win_length=800, mean_abs_amp_norm=0.01, n_iter=200, n_fft=None, realse=1.0,
-                            phase0=None, trace=False):
+                            phase0=None, trace=False, momentum=0.0):
     """Batched from_power_to_wav: P [B, Fmax, bins] normalised power dB (the decoder's y_stft) ->
-    wav [B, hop*(Fmax-1)] cuda float32; utterance b is valid up to hop*(n_frames[b]-1) samples."""
+    wav [B, hop*(Fmax-1)] cuda float32; utterance b is valid up to hop*(n_frames[b]-1) samples.
+    momentum: fast Griffin-Lim, see griffin_lim_batch."""
     import torch
+    momentum = check_momentum(momentum)
     if not torch.cuda.is_available():
         raise _vc.VCError('from_power_to_wav needs a GPU (no CPU fallback)')
     plan = _get_voc_plan(win_length, hop_length, n_fft)
@@ -353,7 +381,7 @@ def from_power_to_wav_batch(P, n_frames=None, P_dB_norm_factor=0.01, pre_emphasi
     amp = torch.empty_like(P)
     _vc.check(_vc.lib().vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nf), B, Fmax, nb, float(P_dB_norm_factor), float(realse),
                                         _vc.ptr(amp), _vc.current_stream()))
-    r = griffin_lim_batch(amp, n_frames, win_length, hop_length, n_iter, n_fft, phase0, trace)
+    r = griffin_lim_batch(amp, n_frames, win_length, hop_length, n_iter, n_fft, phase0, trace, momentum)
     wav = r[0] if trace else r
     _vc.check(_vc.lib().vc_inv_preemphasis_normalize(plan.handle, _vc.ptr(wav), _vc.ptr(d_nf), B, Fmax, wav.shape[1],
                                                      float(pre_emphasis), float(mean_abs_amp_norm), _vc.current_stream()))
@@ -361,14 +389,18 @@ def from_power_to_wav_batch(P, n_frames=None, P_dB_norm_factor=0.01, pre_emphasi
 
 
 def from_power_to_wav(P, P_dB_norm_factor=0.01, pre_emphasis=0.97, hop_length=40, win_length=800,
-                      mean_abs_amp_norm=0.01, n_iter=200, n_fft=None, realse=1.0, verbose=True, phase0=None):
-    """audio_lib.py:278-308.  P [F, bins] -> wav float32 numpy [hop*(F-1)]."""
+                      mean_abs_amp_norm=0.01, n_iter=200, n_fft=None, realse=1.0, verbose=True, phase0=None,
+                      momentum=0.0):
+    """audio_lib.py:278-308.  P [F, bins] -> wav float32 numpy [hop*(F-1)].  momentum: fast
+    Griffin-Lim, see griffin_lim_batch."""
+    momentum = check_momentum(momentum)
     P = np.asarray(P)
     if phase0 is None:
         phase0 = np.pi * np.random.rand(P.shape[1], P.shape[0])          # [bins, F] like audio_lib.py:255
     ph = np.ascontiguousarray(np.asarray(phase0).T, dtype=np.float32)[None]
     r = from_power_to_wav_batch(np.ascontiguousarray(P, dtype=np.float32)[None], None, P_dB_norm_factor, pre_emphasis,
-                                hop_length, win_length, mean_abs_amp_norm, n_iter, n_fft, realse, ph, trace=bool(verbose))
+                                hop_length, win_length, mean_abs_amp_norm, n_iter, n_fft, realse, ph, trace=bool(verbose),
+                                momentum=momentum)
     if verbose:
         wav, tr = r
         tr = tr.cpu().numpy()[:, 0]

@@ -7,7 +7,8 @@ half a window, stitched) -- the pure integer framing that turns an utterance's f
 (audio_lib.from_power_to_wav on the GPU, test.py:146-168).  Plotting, audio playback and wav
 writing (test.py:28-43, 171-188) are UI side effects and out of scope.  ``vocoder``: 'default' =
 audio_lib.from_power_to_wav, any callable with that signature, or None to skip audio synthesis
-(``y_wav_true`` / ``y_wav_pred`` are then None).
+(``y_wav_true`` / ``y_wav_pred`` are then None).  ``momentum`` (default 0.0): fast Griffin-Lim; a
+callable receives ``momentum=`` only when it is not 0, so a reference-signature vocoder keeps working.
 """
 from collections import namedtuple
 
@@ -75,7 +76,12 @@ def _pad_all(mfcc, mel, stft, pad_len):
     return out
 
 
-def _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_input):
+def _check_momentum(momentum):
+    import audio_lib
+    return audio_lib.check_momentum(momentum)
+
+
+def _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_input, momentum=0.0):
     if vocoder is None:
         return None, None
     if vocoder == 'default':
@@ -84,14 +90,17 @@ def _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_inp
     kw = dict(P_dB_norm_factor=cfg_d['P_dB_norm_factor'], pre_emphasis=cfg_d['pre_emphasis'],
               hop_length=cfg_d['hop_length'], win_length=cfg_d['win_length'],
               mean_abs_amp_norm=15 * cfg_d['mean_abs_amp_norm'], n_iter=n_iter, n_fft=cfg_d['n_fft'])
+    if momentum != 0.0:
+        kw['momentum'] = momentum
     y_true = vocoder(stft_true, realse=1.0, **kw) if giffin_lim_input else None
     return y_true, vocoder(stft_pred, realse=realse, **kw)
 
 
 def conversion2(decoder, mfcc, mel, stft, cfg_d, t_s=5, t_e=60, n_iter=200, output_path='./output',
                 file_name='y_wav', realse=1.0, save_output=False, giffin_lim_input=True, play_conversion=False,
-                vocoder='default'):
+                vocoder='default', momentum=0.0):
     """test.py:87-201: half-overlapped double pass + ``compound``."""
+    momentum = _check_momentum(momentum)
     n_times = cfg_d['n_timesteps']
     pad_len, n_s, n_e = window_plan(mfcc.shape[0], cfg_d, t_s, t_e)
     mfcc, mel, stft = _pad_all(mfcc, mel, stft, pad_len)
@@ -112,15 +121,17 @@ def conversion2(decoder, mfcc, mel, stft, cfg_d, t_s=5, t_e=60, n_iter=200, outp
 
     mel_true = mel[n_s:n_e]
     stft_true = stft[n_s:n_e]
-    y_wav_true, y_wav_pred = _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_input)
+    y_wav_true, y_wav_pred = _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_input,
+                                     momentum)
     ret_tuple = namedtuple('conversion', 'y_wav_true y_wav_pred mel_true mel_pred stft_true stft_pred phn_pred')
     return ret_tuple(y_wav_true, y_wav_pred, mel_true, mel_pred, stft_true, stft_pred, phn_pred)
 
 
 def conversion(decoder, mfcc, mel, stft, cfg_d, t_s=5, t_e=60, n_iter=200, output_path='./output',
                file_name='y_wav', realse=1.0, save_output=False, giffin_lim_input=True, play_conversion=False,
-               vocoder='default'):
+               vocoder='default', momentum=0.0):
     """test.py:206-306: single pass over non-overlapping windows."""
+    momentum = _check_momentum(momentum)
     n_times = cfg_d['n_timesteps']
     pad_len, n_s, n_e = window_plan(mfcc.shape[0], cfg_d, t_s, t_e)
     mfcc, mel, stft = _pad_all(mfcc, mel, stft, pad_len)
@@ -129,6 +140,7 @@ def conversion(decoder, mfcc, mel, stft, cfg_d, t_s=5, t_e=60, n_iter=200, outpu
     mel_pred = y_pred.y_mel.reshape((-1, y_pred.y_mel.shape[-1]))
     stft_true = stft[n_s:n_e]
     stft_pred = y_pred.y_stft.reshape((-1, y_pred.y_stft.shape[-1]))
-    y_wav_true, y_wav_pred = _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_input)
+    y_wav_true, y_wav_pred = _vocode(vocoder, stft_true, stft_pred, cfg_d, n_iter, realse, giffin_lim_input,
+                                     momentum)
     ret_tuple = namedtuple('conversion', 'y_wav_true y_wav_pred mel_true mel_pred stft_true stft_pred')
     return ret_tuple(y_wav_true, y_wav_pred, mel_true, mel_pred, stft_true, stft_pred)

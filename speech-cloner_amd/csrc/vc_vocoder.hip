@@ -16,6 +16,11 @@
 // S[k1 + 25 k2] the inverse needs, so the spectrum never leaves registers.
 // The kernel is bound by LDS traffic and launch latency (a 1000-frame utterance is 63 blocks);
 // HBM sees 2 x frames x n_fft x 4 bytes per iteration, all L2-resident.
+//
+// Fast Griffin-Lim (Perraudin, Balazs & Sondergaard 2013; librosa's formulation): the projection
+// takes the phase of  C_i = R_i - beta R_{i-1}  instead of R_i = stft(istft(S_{i-1})), with
+// beta = momentum / (1 + momentum).  The kernels carry R between iterations in a per-frame state
+// (MOM template flavours); the first projection sees R_0 = 0 and never reads the state.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -29,6 +34,12 @@ constexpr int VG = 16;             // frames per block (400-point path)
 constexpr int VGG = 4;             // frames per block (generic path)
 constexpr int VA_STRIDE = 17;
 constexpr float F32_TINY = 1.17549435e-38f;
+constexpr int NSLOT400 = 13 * 16;  // momentum state slots per frame (400-point path): [k1][k2]
+
+// Momentum flavour of an iteration kernel.  MOM_OFF is the plain algorithm (the only flavour
+// vc_griffin_lim_f32 launches); MOM_FIRST stores R_1 and projects it unchanged (R_0 = 0);
+// MOM_ON reads R_{i-1}, projects C_i = R_i - beta R_{i-1}, stores R_i in place.
+enum : int { MOM_OFF = 0, MOM_FIRST = 1, MOM_ON = 2 };
 
 struct GlArgs {
     const float* amp;        // [B][maxF][nb]
@@ -38,6 +49,8 @@ struct GlArgs {
     const int32_t* n_frames; // [B] or null
     const float* window;     // [N] | tw400[416] | twg[2N]
     int maxF, nb, N, hop, span, nov;
+    float2* mom;             // R_{i-1}: [B][maxF][13][16] (400-point slot order) | [B][maxF][nb]; MOM != MOM_OFF only
+    float beta;              // momentum / (1 + momentum)
 };
 
 __device__ __forceinline__ int utt_frames(const GlArgs& a, int b) {
@@ -85,9 +98,10 @@ __device__ __forceinline__ void gather_tile(const GlArgs& a, const float* fr, co
 }
 
 // 400-point iteration (INIT: spectrum = amp * exp(i phase0) instead of the analysis of prev).
-template <bool INIT>
+template <bool INIT, int MOM>
 __global__ void __launch_bounds__(VT)
 gl_iter400_kernel(GlArgs a) {
+    static_assert(!INIT || MOM == MOM_OFF, "the initial spectrum has no momentum");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NROW = VG * 13;
     float* win = reinterpret_cast<float*>(smem);       // [400]
@@ -154,6 +168,25 @@ gl_iter400_kernel(GlArgs a) {
             for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = Are[VA_STRIDE * tid + n2]; zi[n2] = Aim[VA_STRIDE * tid + n2]; }
             vcfe::cdft16(zr, zi, yr, yi);
         }
+        if constexpr (MOM != MOM_OFF) {
+            // this thread's 16 slots of R_i (bins k1 + 25 k2, conjugate copies included) are its own:
+            // read R_{i-1}, store R_i in place (128 contiguous bytes), project C = R_i - beta R_{i-1}
+            if (g < nvalid) {
+                float4* st = reinterpret_cast<float4*>(a.mom + (((size_t)b * a.maxF + f0 + g) * 13 + k1) * 16);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float4 r = make_float4(yr[2 * j], yi[2 * j], yr[2 * j + 1], yi[2 * j + 1]);
+                    if constexpr (MOM == MOM_ON) {
+                        const float4 q = st[j];
+                        yr[2 * j] = fmaf(-a.beta, q.x, r.x);
+                        yi[2 * j] = fmaf(-a.beta, q.y, r.y);
+                        yr[2 * j + 1] = fmaf(-a.beta, q.z, r.z);
+                        yi[2 * j + 1] = fmaf(-a.beta, q.w, r.w);
+                    }
+                    st[j] = r;
+                }
+            }
+        }
 #pragma unroll
         for (int k2 = 0; k2 < 16; ++k2) {
             bool cj;
@@ -200,9 +233,10 @@ gl_iter400_kernel(GlArgs a) {
 
 // Generic path (any even n_fft): direct O(N^2) DFTs from the LDS twiddle table twg[m] =
 // exp(-2 pi i m / N).  VGG frames per block.
-template <bool INIT>
+template <bool INIT, int MOM>
 __global__ void __launch_bounds__(VT)
 gl_iter_generic_kernel(GlArgs a) {
+    static_assert(!INIT || MOM == MOM_OFF, "the initial spectrum has no momentum");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, nb = a.nb;
     float* win = reinterpret_cast<float*>(smem);       // [N]
@@ -241,6 +275,16 @@ gl_iter_generic_kernel(GlArgs a) {
                 re = fmaf(xv, twr[m], re);
                 im = fmaf(xv, twi[m], im);
                 m += k; if (m >= N) m -= N;
+            }
+            if constexpr (MOM != MOM_OFF) {
+                float2* st = a.mom + ((size_t)b * a.maxF + f0 + g) * nb + k;
+                const float2 r = make_float2(re, im);
+                if constexpr (MOM == MOM_ON) {
+                    const float2 q = *st;
+                    re = fmaf(-a.beta, q.x, re);
+                    im = fmaf(-a.beta, q.y, im);
+                }
+                *st = r;
             }
             const float m2 = re * re + im * im;
             const float inv = m2 > 0.0f ? rsqrtf(m2) : 0.0f;
@@ -382,6 +426,107 @@ struct vc_vocoder_plan {
     size_t smem400, smem400_init, smem_gen;
 };
 
+// Bytes of the ping-pong frames and (trace) the two scratch waveforms, each rounded to 256.
+static size_t gl_state_offset(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames, int32_t trace) {
+    size_t frames = (size_t)batch * max_frames * plan->N * sizeof(float);
+    frames = (frames + 255) & ~(size_t)255;
+    size_t wav = trace ? (((size_t)batch * plan->hop * (max_frames - 1) * sizeof(float) + 255) & ~(size_t)255) : 0;
+    return 2 * frames + 2 * wav;
+}
+
+// Momentum state: one float2 per slot the iteration kernel projects (400: 13 x 16, generic: nb).
+static size_t gl_mom_bytes(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames) {
+    const size_t slots = plan->N == 400 ? (size_t)NSLOT400 : (size_t)plan->nb;
+    return ((size_t)batch * max_frames * slots * sizeof(float2) + 255) & ~(size_t)255;
+}
+
+// Both entry points: momentum == 0 launches exactly the plain instantiations (MOM_OFF).
+static int griffin_lim_run(const char* fn, const vc_vocoder_plan* p, const float* d_amp, const float* d_phase0,
+                           const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t num_iters,
+                           float momentum, float* d_wav, int32_t wav_stride, float* d_trace, void* d_workspace,
+                           size_t workspace_bytes, void* stream) {
+    VC_REQUIRE(p && d_amp && d_phase0 && d_wav && d_workspace, "%s: NULL argument", fn);
+    VC_REQUIRE(batch > 0 && max_frames >= 2 && num_iters >= 1, "%s: need batch > 0, frames >= 2, num_iters >= 1", fn);
+    VC_REQUIRE(std::isfinite(momentum) && momentum >= 0.0f && momentum < 1.0f,
+               "%s: momentum must be finite and in [0, 1) (got %g)", fn, (double)momentum);
+    VC_REQUIRE(p->hop * (max_frames - 1) > p->N / 2, "%s: %d frames are shorter than the reflect padding", fn, max_frames);
+    VC_REQUIRE(wav_stride >= p->hop * (max_frames - 1), "%s: wav_stride %d < %d samples", fn, wav_stride,
+               p->hop * (max_frames - 1));
+    const bool mom = momentum > 0.0f;
+    const int32_t tr = d_trace != nullptr;
+    const size_t need = mom ? vc_vocoder_workspace_bytes_momentum(p, batch, max_frames, tr)
+                            : vc_vocoder_workspace_bytes(p, batch, max_frames, tr);
+    VC_REQUIRE(workspace_bytes >= need, "%s: workspace too small", fn);
+    VC_REQUIRE(!mom || ((uintptr_t)d_workspace & 15) == 0, "%s: workspace must be 16-byte aligned", fn);
+    hipStream_t st = (hipStream_t)stream;
+    size_t fbytes = ((size_t)batch * max_frames * p->N * sizeof(float) + 255) & ~(size_t)255;
+    float* fr[2] = {reinterpret_cast<float*>(d_workspace), reinterpret_cast<float*>((char*)d_workspace + fbytes)};
+    const int L = p->hop * (max_frames - 1);
+    const size_t wbytes = ((size_t)batch * L * sizeof(float) + 255) & ~(size_t)255;
+    float* wavs[2] = {reinterpret_cast<float*>((char*)d_workspace + 2 * fbytes),
+                      reinterpret_cast<float*>((char*)d_workspace + 2 * fbytes + wbytes)};
+    const bool fast = (p->N == 400);
+    GlArgs a;
+    a.amp = d_amp; a.phase0 = d_phase0; a.n_frames = d_n_frames; a.window = p->d_tables;
+    a.maxF = max_frames; a.nb = p->nb; a.N = p->N; a.hop = p->hop; a.nov = p->nov;
+    a.span = fast ? p->span : p->span_g;
+    a.mom = mom ? reinterpret_cast<float2*>((char*)d_workspace + gl_state_offset(p, batch, max_frames, tr))
+                : nullptr;
+    a.beta = (float)((double)momentum / (1.0 + (double)momentum));
+    const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
+    const size_t smem = fast ? p->smem400 : p->smem_gen;
+    static bool attr_done = false;
+    if (!attr_done) {
+        const void* kernels[] = {
+            reinterpret_cast<const void*>(gl_iter_generic_kernel<true, MOM_OFF>),
+            reinterpret_cast<const void*>(gl_iter_generic_kernel<false, MOM_OFF>),
+            reinterpret_cast<const void*>(gl_iter_generic_kernel<false, MOM_FIRST>),
+            reinterpret_cast<const void*>(gl_iter_generic_kernel<false, MOM_ON>),
+            reinterpret_cast<const void*>(gl_iter400_kernel<true, MOM_OFF>),
+            reinterpret_cast<const void*>(gl_iter400_kernel<false, MOM_OFF>),
+            reinterpret_cast<const void*>(gl_iter400_kernel<false, MOM_FIRST>),
+            reinterpret_cast<const void*>(gl_iter400_kernel<false, MOM_ON>)};
+        for (const void* k : kernels)
+            VC_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_done = true;
+    }
+    const dim3 ogrid(((unsigned)wav_stride + VT - 1) / VT, (unsigned)batch);
+    const dim3 sgrid(((unsigned)L + VT - 1) / VT, (unsigned)batch);
+    const size_t osmem = (size_t)p->N * sizeof(float);
+    const bool trace = d_trace != nullptr;
+    if (trace) VC_HIP_CHECK(hipMemsetAsync(d_trace, 0, sizeof(float) * (size_t)num_iters * batch, st));
+    // iteration i leaves the frames of waveform i in fr[cur]; trace mode also materialises every
+    // intermediate waveform (scratch, stride L) to accumulate sum (wav_i - wav_{i-1})^2.
+    int cur = 0;
+    for (int i = 0; i < num_iters; ++i) {
+        a.prev = fr[cur]; a.next = fr[cur ^ 1];
+        if (i == 0) {
+            if (fast) hipLaunchKernelGGL((gl_iter400_kernel<true, MOM_OFF>), grid, dim3(VT), p->smem400_init, st, a);
+            else hipLaunchKernelGGL((gl_iter_generic_kernel<true, MOM_OFF>), grid, dim3(VT), smem, st, a);
+        } else if (!mom) {
+            if (fast) hipLaunchKernelGGL((gl_iter400_kernel<false, MOM_OFF>), grid, dim3(VT), smem, st, a);
+            else hipLaunchKernelGGL((gl_iter_generic_kernel<false, MOM_OFF>), grid, dim3(VT), smem, st, a);
+        } else if (i == 1) {                           // R_0 = 0: the state is written, not read
+            if (fast) hipLaunchKernelGGL((gl_iter400_kernel<false, MOM_FIRST>), grid, dim3(VT), smem, st, a);
+            else hipLaunchKernelGGL((gl_iter_generic_kernel<false, MOM_FIRST>), grid, dim3(VT), smem, st, a);
+        } else {
+            if (fast) hipLaunchKernelGGL((gl_iter400_kernel<false, MOM_ON>), grid, dim3(VT), smem, st, a);
+            else hipLaunchKernelGGL((gl_iter_generic_kernel<false, MOM_ON>), grid, dim3(VT), smem, st, a);
+        }
+        cur ^= 1;
+        if (trace && i < num_iters - 1)
+            hipLaunchKernelGGL(gl_ola_kernel, sgrid, dim3(VT), osmem, st, fr[cur], d_n_frames, p->d_tables, max_frames,
+                               p->N, p->hop, p->nov, wavs[i & 1], L, (const float*)(i > 0 ? wavs[(i - 1) & 1] : nullptr), L,
+                               i > 0 ? d_trace + (size_t)i * batch : (float*)nullptr);
+    }
+    const bool last_delta = trace && num_iters > 1;
+    hipLaunchKernelGGL(gl_ola_kernel, ogrid, dim3(VT), osmem, st, fr[cur], d_n_frames, p->d_tables, max_frames, p->N,
+                       p->hop, p->nov, d_wav, wav_stride, (const float*)(last_delta ? wavs[(num_iters - 2) & 1] : nullptr), L,
+                       last_delta ? d_trace + (size_t)(num_iters - 1) * batch : (float*)nullptr);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
 extern "C" {
 
 int vc_vocoder_plan_create(int32_t win_length, int32_t hop_length, int32_t n_fft, const double* h_window,
@@ -446,10 +591,13 @@ int32_t vc_vocoder_num_samples(const vc_vocoder_plan* plan, int32_t n_frames) {
 
 size_t vc_vocoder_workspace_bytes(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames, int32_t trace) {
     if (!plan || batch <= 0 || max_frames <= 0) return 0;
-    size_t frames = (size_t)batch * max_frames * plan->N * sizeof(float);
-    frames = (frames + 255) & ~(size_t)255;
-    size_t wav = trace ? (((size_t)batch * plan->hop * (max_frames - 1) * sizeof(float) + 255) & ~(size_t)255) : 0;
-    return 2 * frames + 2 * wav + 256;
+    return gl_state_offset(plan, batch, max_frames, trace) + 256;
+}
+
+size_t vc_vocoder_workspace_bytes_momentum(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames,
+                                           int32_t trace) {
+    if (!plan || batch <= 0 || max_frames <= 0) return 0;
+    return gl_state_offset(plan, batch, max_frames, trace) + gl_mom_bytes(plan, batch, max_frames) + 256;
 }
 
 int vc_power_to_amp(const float* d_P, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t n_bins,
@@ -465,68 +613,16 @@ int vc_power_to_amp(const float* d_P, const int32_t* d_n_frames, int32_t batch, 
 int vc_griffin_lim_f32(const vc_vocoder_plan* p, const float* d_amp, const float* d_phase0, const int32_t* d_n_frames,
                        int32_t batch, int32_t max_frames, int32_t num_iters, float* d_wav, int32_t wav_stride,
                        float* d_trace, void* d_workspace, size_t workspace_bytes, void* stream) {
-    VC_REQUIRE(p && d_amp && d_phase0 && d_wav && d_workspace, "vc_griffin_lim_f32: NULL argument");
-    VC_REQUIRE(batch > 0 && max_frames >= 2 && num_iters >= 1, "vc_griffin_lim_f32: need batch > 0, frames >= 2, num_iters >= 1");
-    VC_REQUIRE(p->hop * (max_frames - 1) > p->N / 2, "vc_griffin_lim_f32: %d frames are shorter than the reflect padding", max_frames);
-    VC_REQUIRE(wav_stride >= p->hop * (max_frames - 1), "vc_griffin_lim_f32: wav_stride %d < %d samples", wav_stride,
-               p->hop * (max_frames - 1));
-    VC_REQUIRE(workspace_bytes >= vc_vocoder_workspace_bytes(p, batch, max_frames, d_trace != nullptr),
-               "vc_griffin_lim_f32: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    size_t fbytes = ((size_t)batch * max_frames * p->N * sizeof(float) + 255) & ~(size_t)255;
-    float* fr[2] = {reinterpret_cast<float*>(d_workspace), reinterpret_cast<float*>((char*)d_workspace + fbytes)};
-    const int L = p->hop * (max_frames - 1);
-    const size_t wbytes = ((size_t)batch * L * sizeof(float) + 255) & ~(size_t)255;
-    float* wavs[2] = {reinterpret_cast<float*>((char*)d_workspace + 2 * fbytes),
-                      reinterpret_cast<float*>((char*)d_workspace + 2 * fbytes + wbytes)};
-    const bool fast = (p->N == 400);
-    GlArgs a;
-    a.amp = d_amp; a.phase0 = d_phase0; a.n_frames = d_n_frames; a.window = p->d_tables;
-    a.maxF = max_frames; a.nb = p->nb; a.N = p->N; a.hop = p->hop; a.nov = p->nov;
-    a.span = fast ? p->span : p->span_g;
-    const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
-    const size_t smem = fast ? p->smem400 : p->smem_gen;
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_generic_kernel<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter_generic_kernel<false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter400_kernel<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gl_iter400_kernel<false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
-    const dim3 ogrid(((unsigned)wav_stride + VT - 1) / VT, (unsigned)batch);
-    const dim3 sgrid(((unsigned)L + VT - 1) / VT, (unsigned)batch);
-    const size_t osmem = (size_t)p->N * sizeof(float);
-    const bool trace = d_trace != nullptr;
-    if (trace) VC_HIP_CHECK(hipMemsetAsync(d_trace, 0, sizeof(float) * (size_t)num_iters * batch, st));
-    // iteration i leaves the frames of waveform i in fr[cur]; trace mode also materialises every
-    // intermediate waveform (scratch, stride L) to accumulate sum (wav_i - wav_{i-1})^2.
-    int cur = 0;
-    for (int i = 0; i < num_iters; ++i) {
-        a.prev = fr[cur]; a.next = fr[cur ^ 1];
-        if (i == 0) {
-            if (fast) hipLaunchKernelGGL(gl_iter400_kernel<true>, grid, dim3(VT), p->smem400_init, st, a);
-            else hipLaunchKernelGGL(gl_iter_generic_kernel<true>, grid, dim3(VT), smem, st, a);
-        } else {
-            if (fast) hipLaunchKernelGGL(gl_iter400_kernel<false>, grid, dim3(VT), smem, st, a);
-            else hipLaunchKernelGGL(gl_iter_generic_kernel<false>, grid, dim3(VT), smem, st, a);
-        }
-        cur ^= 1;
-        if (trace && i < num_iters - 1)
-            hipLaunchKernelGGL(gl_ola_kernel, sgrid, dim3(VT), osmem, st, fr[cur], d_n_frames, p->d_tables, max_frames,
-                               p->N, p->hop, p->nov, wavs[i & 1], L, (const float*)(i > 0 ? wavs[(i - 1) & 1] : nullptr), L,
-                               i > 0 ? d_trace + (size_t)i * batch : (float*)nullptr);
-    }
-    const bool last_delta = trace && num_iters > 1;
-    hipLaunchKernelGGL(gl_ola_kernel, ogrid, dim3(VT), osmem, st, fr[cur], d_n_frames, p->d_tables, max_frames, p->N,
-                       p->hop, p->nov, d_wav, wav_stride, (const float*)(last_delta ? wavs[(num_iters - 2) & 1] : nullptr), L,
-                       last_delta ? d_trace + (size_t)(num_iters - 1) * batch : (float*)nullptr);
-    VC_HIP_CHECK(hipGetLastError());
-    return VC_OK;
+    return griffin_lim_run("vc_griffin_lim_f32", p, d_amp, d_phase0, d_n_frames, batch, max_frames, num_iters, 0.0f,
+                           d_wav, wav_stride, d_trace, d_workspace, workspace_bytes, stream);
+}
+
+int vc_griffin_lim_momentum_f32(const vc_vocoder_plan* p, const float* d_amp, const float* d_phase0,
+                                const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t num_iters,
+                                float momentum, float* d_wav, int32_t wav_stride, float* d_trace, void* d_workspace,
+                                size_t workspace_bytes, void* stream) {
+    return griffin_lim_run("vc_griffin_lim_momentum_f32", p, d_amp, d_phase0, d_n_frames, batch, max_frames, num_iters,
+                           momentum, d_wav, wav_stride, d_trace, d_workspace, workspace_bytes, stream);
 }
 
 int vc_inv_preemphasis_normalize(const vc_vocoder_plan* p, float* d_wav, const int32_t* d_n_frames, int32_t batch,
