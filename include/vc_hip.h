@@ -82,7 +82,9 @@ const char* vc_target_arch(void);
  * All alternatives compute the same function (tests compare them).  Three more names, "ablate_bank256",
  * "ablate_bank256_only" and "ablate_cbhg_front", skip parts of a kernel for timing and give WRONG results: they
  * exist only in a library built with -DVC_ABLATE (tools/build_ablate.sh; vc_ablate_build() returns 1 there) and
- * are rejected with VC_ERR_INVALID by the shipped build.  Options are process-global; set them between launches. */
+ * are rejected with VC_ERR_INVALID by the shipped build.  Options are process-global; set them between launches.
+ * They are read when a launch call is made, so a captured graph keeps the values of its capture: setting an option
+ * afterwards does not change what the graph replays. */
 int vc_set_option(const char* name, int value);
 int vc_get_option(const char* name, int* value);
 int vc_ablate_build(void);
@@ -149,15 +151,20 @@ size_t vc_frontend_workspace_bytes(const vc_frontend_plan* plan, int32_t batch, 
  *              frames (the later ones still count for the utterance's normalisation statistics, as in the reference,
  *              which computes the whole utterance and then cuts windows: /root/reference/test.py:121-123, 240-241) -- e.g.
  *              800 for 4 s at hop 80, so that [batch, 800, n_mels] IS the [2 * batch, 400, n_mels] window batch of the
- *              encoder without a copy.  Needs the two-pass 400-point path when < max_frames.
+ *              encoder without a copy.  Needs the shipped configuration (either of its forms) when < max_frames.
  *   d_mfcc     float32 [batch, out_rows, mfcc_width]
  *   d_mel_db   float32 [batch, out_rows, n_mels]
  *   d_pow_db   float32 [batch, out_rows, 1 + n_fft/2]
  *              rows f >= 1 + lens[b]/hop of utterance b are zero-filled.
- *   d_workspace / workspace_bytes: scratch of at least vc_frontend_workspace_bytes().
- * Two launches on `stream`: STFT power + mel + raw dB with per-tile max / min / sum|x| partials;
- * finalize (amplitude normalisation as a dB offset, amin and top_db clips, min shift, DCT, delta,
- * clip).  With hop_length > n_fft/2 a third launch computes the per-utterance sum|x| first. */
+ *   d_workspace / workspace_bytes: scratch of at least vc_frontend_workspace_bytes(), owned by this call until it
+ *              completes on `stream`: concurrent calls of one plan need separate workspaces.  The plan itself is
+ *              read-only after vc_frontend_plan_create.
+ * Shipped configuration (n_fft 400, hop 80, 80 mels, 40 cepstra): by default ONE launch (fe400_fused_kernel), preceded
+ * on `stream` by a small kernel that zeroes the per-utterance arrival counters at the start of the workspace (a node of
+ * its own under graph capture, replayed before the main one); with vc_set_option("fe_fused", 0) two launches, a
+ * statistics pass and a feature pass.  Other configurations: STFT power + mel + raw dB with per-tile max / min / sum|x|
+ * partials, then finalize (amplitude normalisation as a dB offset, amin and top_db clips, min shift, DCT, delta, clip);
+ * with hop_length > n_fft/2 a third launch computes the per-utterance sum|x| first. */
 int vc_frontend_f32(const vc_frontend_plan* plan, const float* d_wav, const int32_t* d_lens,
                     int32_t batch, int32_t max_samples, int32_t wav_stride, int32_t out_rows,
                     float* d_mfcc, float* d_mel_db, float* d_pow_db,

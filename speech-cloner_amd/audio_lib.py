@@ -52,14 +52,13 @@ class _Plan:
         self.handle = h
         self.mfcc_width = lib.vc_frontend_mfcc_width(h)
         self.n_bins = lib.vc_frontend_power_width(h)
-        self._ws = None
 
     def workspace(self, batch, max_samples, device):
+        """Scratch for ONE call, from the caching allocator of the current stream: calls of this plan on other
+        streams (or in a captured graph) each get their own."""
         import torch
         need = _vc.lib().vc_frontend_workspace_bytes(self.handle, batch, max_samples)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return torch.empty(need, dtype=torch.uint8, device=device)
 
 
 def _get_plan(sr, pre_emphasis, hop_length, win_length, n_mels, n_mfcc, n_fft, window,
@@ -243,16 +242,13 @@ class _VocPlan:
         self.handle = h
         self.win_length, self.hop_length, self.n_fft = int(win_length), int(hop_length), int(n_fft)
         self.n_bins = 1 + self.n_fft // 2
-        self._ws = None
 
     def workspace(self, batch, max_frames, trace, device, momentum=False):
+        """Scratch for ONE call, from the caching allocator of the current stream (see _Plan.workspace)."""
         import torch
         lib = _vc.lib()
         size = lib.vc_vocoder_workspace_bytes_momentum if momentum else lib.vc_vocoder_workspace_bytes
-        need = size(self.handle, batch, max_frames, int(trace))
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return torch.empty(size(self.handle, batch, max_frames, int(trace)), dtype=torch.uint8, device=device)
 
 
 def check_momentum(momentum):

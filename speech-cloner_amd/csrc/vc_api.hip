@@ -31,6 +31,20 @@ static struct OptInit { OptInit() { for (auto& o : g_opt) o.store(-1); } } g_opt
 
 int opt(Option o) { return g_opt[o].load(std::memory_order_relaxed); }
 
+static __global__ void zero_words_kernel(unsigned* __restrict__ p, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+hipError_t zero_async(void* d_p, size_t bytes, hipStream_t st) {
+    if (bytes % 4) return hipErrorInvalidValue;
+    const size_t n = bytes / 4;
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st,
+                       static_cast<unsigned*>(d_p), n);
+    return hipGetLastError();
+}
+
 }  // namespace vc
 
 extern "C" {

@@ -503,7 +503,7 @@ int vc_launch_bank256(const Bank256Args& a, hipStream_t st) {
                    "split K: one pair, no pooled output, 256-byte aligned workspace");
         b.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(a.tick) + tick_bytes(ntm));
         b.xcd_tiles = 0;
-        VC_HIP_CHECK(hipMemsetAsync(a.tick, 0, tick_bytes(ntm), st));
+        VC_HIP_CHECK(vc::zero_async(a.tick, tick_bytes(ntm), st));
         hipLaunchKernelGGL(bank256_kernel, dim3((unsigned)(8 * a.ksplit * ((ntm + 7) / 8))), dim3(NT), LDS_BYTES, st, b);
         VC_HIP_CHECK(hipGetLastError());
         return VC_OK;

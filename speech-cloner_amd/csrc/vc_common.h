@@ -56,6 +56,12 @@ enum Option {
 };
 int opt(Option o);        // current value, -1 if unset
 
+// Zeroes `bytes` (a multiple of 4) at d_p with a kernel on `st`.  Every per-launch word that a kernel polls or
+// accumulates into is cleared this way and not with hipMemsetAsync: under graph capture a memset node of the HIP
+// runtime this library is built against cleared only three quarters of its bytes from the second replay on
+// (tests/test_graph_replay_gpu.py), while a kernel node is replayed like any other launch.
+hipError_t zero_async(void* d_p, size_t bytes, hipStream_t st);
+
 #if defined(__HIPCC__)
 // Wave-wide reductions on DPP (data-parallel primitives: the cross-lane operand of a VALU instruction), result in every
 // lane.  __shfl_xor lowers to ds_bpermute_b32 on gfx950 -- an LDS-path round trip of ~100 cycles per step, 6 dependent

@@ -629,12 +629,8 @@ struct vc_frontend_plan {
     void* d_blob;
     FeDev dev;
     const float* d_dct_half;      // [n_mfcc][n_mels / 2] (fast400 only)
-    // one-launch form (fast400): two sets of per-utterance arrival counters owned by the plan, zero from creation on.
-    // Launch n counts in set n & 1 and zeroes the other one, which launch n - 1 used and -- the launches of a plan being
-    // ordered on their stream -- has finished with: no memset between launches, and a late arrival of a launch whose
-    // waiters had given up still lands before anybody reads that set again.
-    unsigned* d_fcount;
-    mutable unsigned fused_launches;
+    // Read-only after vc_frontend_plan_create: every per-launch word (the one-launch form's arrival counters included)
+    // lives in the caller's workspace.
 };
 
 extern "C" {
@@ -656,8 +652,6 @@ int vc_frontend_plan_create(const vc_frontend_cfg* cfg, const double* h_window, 
     p->mfcc_width = cfg->n_mfcc * (cfg->calc_mfcc_derivate ? 2 : 1);
     p->fft400 = (cfg->n_fft == 400);
     p->d_blob = nullptr;
-    p->d_fcount = nullptr;
-    p->fused_launches = 0;
     build_mel(cfg->sample_rate, cfg->n_fft, cfg->n_mels, p->mel);
     build_dct(cfg->n_mfcc, cfg->n_mels, p->dct);
 
@@ -736,12 +730,6 @@ int vc_frontend_plan_create(const vc_frontend_cfg* cfg, const double* h_window, 
     p->d_dct_half = df + o_dcth;
     p->dev.mel_start = reinterpret_cast<int32_t*>(df + o);
     p->dev.mel_off = p->dev.mel_start + NM;
-    if (p->fast400) {
-        const size_t nb = 2 * (size_t)vc_fe400_fused_count_bytes(FE400_FUSED_MAX_BATCH);
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_fcount), nb);
-        if (e == hipSuccess) e = hipMemset(p->d_fcount, 0, nb);
-        if (e != hipSuccess) { (void)hipFree(p->d_blob); delete p; return vc::set_error(VC_ERR_HIP, "front-end counters: %s", hipGetErrorString(e)); }
-    }
     *out_plan = p;
     return VC_OK;
 }
@@ -749,7 +737,6 @@ int vc_frontend_plan_create(const vc_frontend_cfg* cfg, const double* h_window, 
 void vc_frontend_plan_destroy(vc_frontend_plan* plan) {
     if (!plan) return;
     if (plan->d_blob) (void)hipFree(plan->d_blob);
-    if (plan->d_fcount) (void)hipFree(plan->d_fcount);
     delete plan;
 }
 
@@ -772,12 +759,14 @@ int vc_frontend_get_dct(const vc_frontend_plan* plan, double* h_out) {
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// Workspace: [fast400: the one-launch form's arrival counters, batch x 256 B at offset 0, zeroed before each of its
+// launches] | |x| partials | statistics | mel, each 256-byte aligned.
 static void ws_layout(const vc_frontend_plan* p, int32_t batch, int32_t max_samples, size_t* o_partial,
                       size_t* o_stats, size_t* o_mel, size_t* total, int* ntiles, int* max_frames) {
     const int mf = 1 + max_samples / p->cfg.hop_length;
     const int g = p->fft400 ? FE_G400 : FE_GGEN;
     const int nt = (mf + g - 1) / g;
-    size_t o = 0;
+    size_t o = p->fast400 ? align256((size_t)vc_fe400_fused_count_bytes(batch)) : 0;
     *o_partial = o; o = align256(o + (size_t)batch * FE_NPART * 4);
     *o_stats = o;   o = align256(o + (size_t)batch * nt * 8 * 4);
     *o_mel = o;     o = align256(o + (size_t)batch * mf * p->cfg.n_mels * 4);
@@ -823,20 +812,16 @@ int vc_frontend_stages_f32(const vc_frontend_plan* plan, const float* d_wav, con
         f.mel0 = reinterpret_cast<float*>(wsb + o_mel);
         f.nt1 = ntiles;
         // one-launch form: tile records in the mel slot (batch x max_frames x 80 floats, of which this path uses only frame
-        // 0's rows): [mel0 | records]; arrival counters in the plan's own double-buffered block
+        // 0's rows): [mel0 | records]; arrival counters in the workspace's first block (ws_layout)
         const size_t o_rec = align256((size_t)batch * c.n_mels * 4);
         f.fstride = vc_fe400_fused_stride(max_frames);
         f.fstats = reinterpret_cast<float*>(wsb + o_mel + o_rec);
-        const bool room = o_rec + (size_t)batch * f.fstride * 4 <= total - o_mel && batch <= FE400_FUSED_MAX_BATCH;
+        f.fcount = reinterpret_cast<unsigned*>(wsb);
+        const bool room = o_rec + (size_t)batch * f.fstride * 4 <= total - o_mel;
         // One launch unless switched off (vc_set_option("fe_fused", 0): two launches, statistics pass + feature pass) or an
         // utterance is too long for it (vc_fe400_fused_ok).  Measured against the two launches with all rows stored: 23.6 vs
         // 29.8 us at 16 utterances of 4 s, 40.2 vs 46.7 at 32, 70.9 vs 76.6 at 64 (tools/fe_fused_probe.py).
         const bool fused = room && (stage_mask & 6) == 6 && vc_fe400_fused_ok(max_frames) && vc::opt(vc::OPT_FE_FUSED) != 0;
-        const unsigned par = plan->fused_launches & 1;
-        const size_t set_words = (size_t)vc_fe400_fused_count_bytes(FE400_FUSED_MAX_BATCH) / 4;
-        f.fcount = plan->d_fcount + par * set_words;
-        f.fcount_other = plan->d_fcount + (par ^ 1) * set_words;
-        if (fused) ++plan->fused_launches;
         f.mfcc = d_mfcc; f.mel_db = d_mel_db; f.pow_db = d_pow_db;
         return vc_fe400_launch(f, batch, stage_mask, fused ? 1 : 0, static_cast<hipStream_t>(stream));
     }

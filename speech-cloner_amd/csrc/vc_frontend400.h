@@ -4,8 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-constexpr int FE400_FUSED_MAX_BATCH = 1024;   // utterances per launch the plan's counter sets are sized for
-
 struct Fe400Args {
     const float* wav;
     const int32_t* lens;
@@ -24,8 +22,8 @@ struct Fe400Args {
     // one-launch form (vc_frontend400.hip, fe400_fused_kernel): 14-frame tiles
     float* fstats;                // [B][fstride] floats: tile records of 8 floats, each utterance's array padded to whole 128-B lines
     int32_t fstride;              // floats per utterance in fstats (a multiple of 32)
-    unsigned* fcount;             // [FE400_FUSED_MAX_BATCH] (one per 256 bytes): tiles of the utterance that have published (zero at launch)
-    unsigned* fcount_other;       // the set the previous launch used: zeroed by this launch for the next one
+    unsigned* fcount;             // [batch] (one per 256 bytes, READY word 32 words in): tiles of the utterance that have published;
+                                  // the block at the start of the caller's workspace, zeroed by vc_fe400_launch (vc::zero_async)
     int32_t spin_limit;           // polls before a waiting block computes the utterance's records itself (set by the launcher)
     float* mfcc;
     float* mel_db;
@@ -33,9 +31,9 @@ struct Fe400Args {
 };
 
 // stage_mask: 2 = statistics pass, 4 = feature pass; with `fused` != 0 (both stages asked for, vc_fe400_fused_ok) they run
-// as ONE launch (fe400_fused_kernel)
+// as ONE launch (fe400_fused_kernel), preceded by the zeroing of the counter block a.fcount on `st`
 int vc_fe400_launch(const Fe400Args& a, int batch, int stage_mask, int fused, hipStream_t st);
 // floats of fstats per utterance for max_frames frames, and whether the one-launch form takes such utterances
 int vc_fe400_fused_stride(int max_frames);
-int vc_fe400_fused_count_bytes(int batch);
+int vc_fe400_fused_count_bytes(int batch);   // the counter block: a multiple of 256 bytes
 bool vc_fe400_fused_ok(int max_frames);

@@ -511,7 +511,9 @@ fe400_kernel(Fe400Args a) {
 // whose add completes the count reduces the utterance's records to one line (write-through, drained) and raises the
 // utterance's READY word; the consumers poll that word relaxed from one lane and read the line with sc1 loads only (they
 // bypass this CU's L1: nothing here can be stale; every utterance's records, its line, its counter and its READY word
-// sit on cache lines of their own).
+// sit on cache lines of their own).  The counters and READY words are the first block of the caller's workspace, zeroed
+// by a small kernel on the launch's stream right before this one: no state outlives a launch or is shared by two of them,
+// so a captured graph replays correctly and launches of one plan with separate workspaces may run concurrently.
 //
 // Forward progress without any assumption about dispatch order or residency: a publisher never waits, and a waiter
 // whose poll runs out (4 ms; an utterance's tiles normally arrive within microseconds of each other because workgroups
@@ -561,10 +563,6 @@ fe400_fused_kernel(Fe400Args a) {
         for (int i = tid; i < nrows * NM; i += NT) o2[i] = 0.0f;
         for (int i = tid; i < nrows * NB; i += NT) o3[i] = 0.0f;
         return;
-    }
-    if (own == 0) {                                     // the previous launch's counters, for the launch after this one
-        for (int u = b + (int)gridDim.y * tid; u < FE400_FUSED_MAX_BATCH; u += (int)gridDim.y * NT)
-            { a.fcount_other[(size_t)u * FCOUNT_PITCH] = 0u; a.fcount_other[(size_t)u * FCOUNT_PITCH + 32] = 0u; }
     }
     const int nt_b = (F + GO - 1) / GO;                 // tiles of this utterance that publish
     const bool has_out = fo_own < a.out_rows;
@@ -974,6 +972,9 @@ int vc_fe400_launch(const Fe400Args& a, int batch, int stage_mask, int fused, hi
         Fe400Args f = a;
         const int sl = vc::opt(vc::OPT_FE_FUSED_SPIN);          // tests: 0 = every waiting block takes the no-wait path
         f.spin_limit = sl >= 0 ? sl : (int)FUSED_SPIN_LIMIT;
+        // every counter and READY word the launch polls starts at zero: a node of its own under graph capture, replayed
+        // before the kernel (nothing is carried from one launch to the next; vc::zero_async, not hipMemsetAsync)
+        VC_HIP_CHECK(vc::zero_async(a.fcount, (size_t)vc_fe400_fused_count_bytes(batch), st));
         hipLaunchKernelGGL(fe400_fused_kernel, dim3(ntf, batch), dim3(NT), lds, st, f);
         VC_HIP_CHECK(hipGetLastError());
         return VC_OK;

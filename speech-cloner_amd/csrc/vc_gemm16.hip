@@ -791,7 +791,7 @@ int vc_split16(const float* d_X, int32_t M, int32_t C, int32_t ldx, int32_t T, c
     const int rpb = 256 >> tl;
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned* wmax = reinterpret_cast<unsigned*>(d_row_scale + M);       // scratch behind the M scales: one word per window
-    VC_HIP_CHECK(hipMemsetAsync(wmax, 0, (size_t)(M / T) * 4, st));
+    VC_HIP_CHECK(vc::zero_async(wmax, (size_t)(M / T) * 4, st));
     const int nwin = M / T;
     int seg = 1024 / nwin;
     seg = seg < 1 ? 1 : (seg > T ? T : seg);
@@ -812,7 +812,7 @@ int vc_transpose_split16(const float* d_X, int32_t M, int32_t C, int32_t ldx, in
                "vc_transpose_split16: bad shape M=%d T=%d C=%d ldx=%d shifts %d+%d (M, C: multiples of 64)", M, T, C, ldx, shift0, n_shifts);
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned* cmax = reinterpret_cast<unsigned*>(d_row_scale + (size_t)n_shifts * C);    // scratch behind the scales
-    VC_HIP_CHECK(hipMemsetAsync(cmax, 0, (size_t)C * 4, st));
+    VC_HIP_CHECK(vc::zero_async(cmax, (size_t)C * 4, st));
     int yb = 2048 / ((C + 255) / 256);
     yb = yb < 1 ? 1 : (yb > (M + 63) / 64 ? (M + 63) / 64 : yb);
     hipLaunchKernelGGL(col_absmax_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)yb), dim3(256), 0, st, d_X, M, C, ldx,
@@ -827,7 +827,7 @@ int vc_transpose_split16(const float* d_X, int32_t M, int32_t C, int32_t ldx, in
 int vc_weights16(const vc_w16_item* d_items, int32_t n_items, uint32_t* d_gmax, int32_t n_groups, void* stream) {
     VC_REQUIRE(d_items && d_gmax && n_items > 0 && n_items <= 65535 && n_groups > 0, "vc_weights16: bad argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    VC_HIP_CHECK(hipMemsetAsync(d_gmax, 0, (size_t)n_groups * 4, st));
+    VC_HIP_CHECK(vc::zero_async(d_gmax, (size_t)n_groups * 4, st));
     hipLaunchKernelGGL(w16_absmax_kernel, dim3((unsigned)n_items, 16), dim3(256), 0, st, d_items, d_gmax);
     hipLaunchKernelGGL(w16_split_kernel, dim3((unsigned)n_items, 16), dim3(256), 0, st, d_items, d_gmax);
     VC_HIP_CHECK(hipGetLastError());
@@ -936,7 +936,7 @@ int vc_gemm16(const vc_gemm16_desc* d, void* stream) {
             VC_REQUIRE(a.split_cs[i + 1] > a.split_cs[i], "vc_gemm16: empty K split (internal)");
         a.tick = reinterpret_cast<unsigned*>(d->d_workspace);
         a.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->d_workspace) + tick_bytes(ntm));
-        VC_HIP_CHECK(hipMemsetAsync(a.tick, 0, tick_bytes(ntm), st));
+        VC_HIP_CHECK(vc::zero_async(a.tick, tick_bytes(ntm), st));
         const unsigned nblk = split_map ? 8u * (unsigned)((ntm + 8 / ks - 1) / (8 / ks)) : (unsigned)(ntm * ks);
         hipLaunchKernelGGL(gemm16_kernel, dim3(nblk), dim3(NT), LDS_BYTES, st, a);
         VC_HIP_CHECK(hipGetLastError());

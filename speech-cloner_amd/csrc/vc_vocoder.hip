@@ -494,7 +494,7 @@ static int griffin_lim_run(const char* fn, const vc_vocoder_plan* p, const float
     const dim3 sgrid(((unsigned)L + VT - 1) / VT, (unsigned)batch);
     const size_t osmem = (size_t)p->N * sizeof(float);
     const bool trace = d_trace != nullptr;
-    if (trace) VC_HIP_CHECK(hipMemsetAsync(d_trace, 0, sizeof(float) * (size_t)num_iters * batch, st));
+    if (trace) VC_HIP_CHECK(vc::zero_async(d_trace, sizeof(float) * (size_t)num_iters * batch, st));
     // iteration i leaves the frames of waveform i in fr[cur]; trace mode also materialises every
     // intermediate waveform (scratch, stride L) to accumulate sum (wav_i - wav_{i-1})^2.
     int cur = 0;
