@@ -41,8 +41,9 @@ extern "C" {
  * 3: vc_gemm_desc ends with d_workspace / workspace_bytes (vc_conv_gemm_workspace_bytes); vc_bn_post_routing added.
  * 4: vc_split16 / vc_weights16 / vc_gemm16 (training convolutions on split-float16 operands).
  * 5: vc_mx8_quantize / vc_mx8_conv / vc_mx8_conv_workspace_bytes and vc_mx8_conv_desc (MX-FP8 inference).
- * 6: vc_griffin_lim_momentum_f32 / vc_vocoder_workspace_bytes_momentum (fast Griffin-Lim). */
-#define VC_ABI_VERSION 6
+ * 6: vc_griffin_lim_momentum_f32 / vc_vocoder_workspace_bytes_momentum (fast Griffin-Lim).
+ * 7: vc_cut_windows / vc_compound_stitch / vc_phase_init (device-resident batched conversion). */
+#define VC_ABI_VERSION 7
 
 int vc_version(void);
 const char* vc_last_error(void);
@@ -720,6 +721,56 @@ int vc_gather_rows(const void* d_src, const int64_t* d_index, const void* d_pad_
 
 /* float32 <-> bf16 conversion of a contiguous buffer (weights preparation, I/O). */
 int vc_convert(const void* d_src, int32_t src_dtype, void* d_dst, int32_t dst_dtype, size_t n, void* stream);
+
+/* ---- device-resident batched conversion (conversion.convert_batch; test.py:46-138 without the host) -----------
+ * Three streaming launches between the front-end, the decoder and the vocoder.  Each validates on the host, allocates
+ * nothing, writes every destination element exactly once (no memset, no atomics) and is hipGraph-capturable.  Their
+ * tables live on the device and are read by the kernel: an entry that points outside the source yields zero rows,
+ * never a read outside it.  16-byte stores whenever a destination slab (T * C, out_frames * C, max_frames * n_bins
+ * floats) is a multiple of 4 floats; 16-byte loads when, in addition, C % 4 == 0 (80, 64); rows of 201 or 61 values
+ * are read element by element (their rows do not start on 16-byte boundaries).
+ *
+ * vc_cut_windows: d_dst [n_windows, T, C] <- d_src [batch, max_frames, C] float32.  d_win_tab int32 [n_windows][2] =
+ * (utterance, first frame): window w, row t is row first_frame + t of that utterance, or zeros where
+ * first_frame + t >= min(n_frames[utterance], max_frames) -- the reference's zero padding of the features to a
+ * multiple of T (test.py:92-101) without a padded copy.  d_n_frames int32 [batch], NULL = max_frames everywhere.  One
+ * launch cuts pass 0 and the half-shifted pass 1 of every utterance.  (vc_gather_rows computes the same function from
+ * one int64 per ROW: 8 * n_windows * T bytes of index to build and upload per call, 256 KB for 16 utterances of 5 s,
+ * against 8 bytes per WINDOW here, 640 bytes; it also moves 4 bytes per lane.  Hence this export.) */
+int vc_cut_windows(const float* d_src, const int32_t* d_win_tab, const int32_t* d_n_frames, int32_t batch,
+                   int32_t max_frames, int32_t n_windows, int32_t T, int32_t C, float* d_dst, void* stream);
+
+/* vc_compound_stitch: d_dst [batch, out_frames, C] float32 <- d_src [n_windows, T, C] (src_dtype VC_F32 or VC_BF16,
+ * bf16 widened exactly), T a multiple of 4.  d_utt_tab int32 [batch][3] = (first pass-0 window w0, first pass-1
+ * window w1 or -1, N): the utterance owns pass-0 windows w0 .. w0+N-1 and pass-1 windows w1 .. w1+N-2.  With q = T/4,
+ * h = T/2, output row t of utterance b is
+ *     t >= N*T                  zeros
+ *     N == 1 or w1 < 0          pass 0, window t / T, frame t % T (the plain reshape, test.py:134-138)
+ *     t < T-q                   pass 0, window 0, frame t
+ *     t >= N*T - (T-q)          pass 0, window N-1, frame t - (N-1)*T
+ *     otherwise                 j = (t-(T-q)) / h, r = (t-(T-q)) % h: even j -> pass 1, window j/2, frame q+r;
+ *                               odd j -> pass 0, window (j+1)/2, frame q+r
+ * which is `compound` (test.py:46-84).  Pure data movement: bit-exact.  d_amp (NULL, or float32 like d_dst; source
+ * must be VC_F32): the fused flavour for the power spectrum also writes the vocoder's magnitude,
+ * amp = exp10(0.05 * (max(0, P) / P_dB_norm_factor - 80)) in the rows t < N*T and 0 beyond -- what vc_power_to_amp
+ * writes for realse == 1 and n_frames = N*T, bit for bit, in one pass over the data instead of three.  For
+ * realse != 1 the two means over the utterance are needed first: the caller passes d_amp = NULL and runs the
+ * stitched spectrum through vc_power_to_amp (the existing launch is reused; no reduction pre-pass here).
+ * Grid: (tiles of 1,024 values, utterance). */
+int vc_compound_stitch(const void* d_src, int32_t src_dtype, const int32_t* d_utt_tab, int32_t batch, int32_t n_windows,
+                       int32_t T, int32_t C, int32_t out_frames, float* d_dst, float* d_amp, float P_dB_norm_factor,
+                       void* stream);
+
+/* vc_phase_init: Griffin-Lim's initial phase (audio_lib.py:255: pi * U[0, 1)) drawn on the device.
+ * d_phase [batch, max_frames, n_bins] float32: phase[b, f, k] = float32(pi) * u for f < n_frames[b], 0 beyond, with
+ * u = (x >> 8) * 2^-24 (exact in float32, so the value is one correctly rounded product) and x a word of
+ * Philox4x32-10 (Salmon, Moraes, Dror & Shaw, SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ * 0xBB67AE85): with e = f * n_bins + k, counter = (e / 4, utt_id[b], 0, 0), key = (low, high 32 bits of seed; any 64-bit pattern),
+ * x = output word e % 4.  An utterance's phase therefore depends on (seed, utt_id, f, k) alone: not on its place in
+ * the batch, on max_frames or on the other utterances.  d_utt_id int32 [batch], NULL = 0 .. batch-1; d_n_frames int32
+ * [batch], NULL = max_frames.  max_frames * n_bins < 2^34. */
+int vc_phase_init(const int32_t* d_n_frames, const int32_t* d_utt_id, int32_t batch, int32_t max_frames, int32_t n_bins,
+                  int64_t seed, float* d_phase, void* stream);
 
 #ifdef __cplusplus
 }

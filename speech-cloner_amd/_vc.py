@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('VC_LIB_PATH', os.path.join(_HERE, 'libvc_hip.so'))   # override: kernel A/B experiments
 
 VC_OK = 0
-VC_ABI_VERSION = 6      # include/vc_hip.h: VC_ABI_VERSION -- lib() refuses a library that reports another one
+VC_ABI_VERSION = 7      # include/vc_hip.h: VC_ABI_VERSION -- lib() refuses a library that reports another one
 
 
 class VCError(RuntimeError):
@@ -227,6 +227,10 @@ _SIGS = {
     'vc_griffin_lim_momentum_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, C.c_int32,
                                               _P, _P, C.c_size_t, _P]),
     'vc_inv_preemphasis_normalize': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
+    'vc_cut_windows': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'vc_compound_stitch': (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                     C.c_float, _P]),
+    'vc_phase_init': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
 }
 
 

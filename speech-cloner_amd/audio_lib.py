@@ -16,6 +16,9 @@ cases of them):
 
   calc_MFCC_input_batch(wav [B, L], lens=None, ...) -> three torch.cuda tensors [B, Fmax, C]
   from_power_to_wav_batch(P [B, Fmax, bins], n_frames=None, ...) -> torch.cuda tensor [B, hop*(Fmax-1)]
+  phase_init(n_frames, Fmax, n_bins, seed, utt_ids) -> torch.cuda tensor [B, Fmax, bins], Griffin-Lim's initial
+                              phase drawn on the device (Philox4x32-10; include/vc_hip.h vc_phase_init);
+                              the batched vocoder calls take it as ``phase0='device'``
 
 The Griffin-Lim entry points take ``momentum`` (default 0.0, the reference's algorithm): fast
 Griffin-Lim as in librosa.griffinlim / torchaudio GriffinLim, see include/vc_hip.h
@@ -286,11 +289,78 @@ def _frames_arg(n_frames, B, Fmax, plan):
     return d, h
 
 
+def _int32_device(v, n, what):
+    """int32 [n] on the device from a host sequence or a tensor (a cuda tensor is used as it is: no copy, no wait)."""
+    import torch
+    if torch.is_tensor(v):
+        if tuple(v.shape) != (n,):
+            raise ValueError(' - ERROR, {} must have {} entries'.format(what, n))
+        return v.to(device='cuda', dtype=torch.int32).contiguous()
+    h = np.asarray(v, dtype=np.int64)
+    if h.shape != (n,) or h.min() < -2 ** 31 or h.max() >= 2 ** 31:
+        raise ValueError(' - ERROR, {} must be {} int32 values'.format(what, n))
+    return torch.from_numpy(h.astype(np.int32)).to('cuda')
+
+
+def check_seed(seed):
+    s = int(seed)
+    if not 0 <= s < 2 ** 64:
+        raise ValueError(' - ERROR, seed must be in [0, 2**64), got {!r}'.format(seed))
+    return s
+
+
+def phase_init(n_frames, Fmax, n_bins, seed=0, utt_ids=None, out=None):
+    """Griffin-Lim's initial phase on the device (vc_phase_init, include/vc_hip.h): float32 [B, Fmax, n_bins] cuda,
+    phase[b, f, k] = float32(pi) * U[0, 1) for f < n_frames[b] and 0 beyond, from Philox4x32-10 addressed by
+    (seed, utt_ids[b], f * n_bins + k) -- an utterance's phase does not depend on its place in the batch, on Fmax or on
+    the other utterances.  n_frames: [B] host ints or int32 cuda tensor; utt_ids likewise (default 0 .. B-1)."""
+    import torch
+    seed = check_seed(seed)
+    B = int(n_frames.shape[0]) if torch.is_tensor(n_frames) else len(n_frames)
+    if utt_ids is not None and (int(utt_ids.shape[0]) if torch.is_tensor(utt_ids) else len(utt_ids)) != B:
+        raise ValueError(' - ERROR, phase_init: utt_ids must have one entry per utterance ({})'.format(B))
+    if not torch.is_tensor(n_frames) and (B == 0 or max(n_frames) > Fmax or min(n_frames) < 0):
+        raise ValueError(' - ERROR, phase_init: n_frames must be [B] with values in [0, {}]'.format(Fmax))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('phase_init needs a GPU (no CPU fallback)')
+    d_nf = _int32_device(n_frames, B, 'n_frames')
+    d_id = None if utt_ids is None else _int32_device(utt_ids, B, 'utt_ids')
+    if out is None:
+        out = torch.empty((B, int(Fmax), int(n_bins)), dtype=torch.float32, device='cuda')
+    elif tuple(out.shape) != (B, int(Fmax), int(n_bins)) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(' - ERROR, phase_init: out must be contiguous float32 [B, Fmax, n_bins]')
+    _vc.check(_vc.lib().vc_phase_init(_vc.ptr(d_nf), _vc.ptr(d_id), B, int(Fmax), int(n_bins),
+                                      seed - 2 ** 64 if seed >= 2 ** 63 else seed, _vc.ptr(out),
+                                      _vc.current_stream()))
+    return out
+
+
+def _griffin_lim_launch(plan, amp, phase0, d_nf, num_iters, trace, momentum):
+    """The launches of griffin_lim_batch on validated device tensors (amp, phase0 [B, Fmax, bins] float32 contiguous,
+    d_nf int32 [B] or None): no host check, copy or wait in here."""
+    import torch
+    B, Fmax, _ = amp.shape
+    L = plan.hop_length * (Fmax - 1)
+    wav = torch.empty((B, L), dtype=torch.float32, device=amp.device)
+    tr = torch.empty((int(num_iters), B), dtype=torch.float32, device=amp.device) if trace else None
+    ws = plan.workspace(B, Fmax, trace, amp.device, momentum=momentum > 0.0)
+    if momentum == 0.0:
+        _vc.check(_vc.lib().vc_griffin_lim_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B, Fmax,
+                                               int(num_iters), _vc.ptr(wav), L, _vc.ptr(tr), _vc.ptr(ws), ws.numel(),
+                                               _vc.current_stream()))
+    else:
+        _vc.check(_vc.lib().vc_griffin_lim_momentum_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B,
+                                                        Fmax, int(num_iters), momentum, _vc.ptr(wav), L, _vc.ptr(tr),
+                                                        _vc.ptr(ws), ws.numel(), _vc.current_stream()))
+    return (wav, tr) if trace else wav
+
+
 def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_iters=300, n_fft=None, phase0=None,
-                      trace=False, momentum=0.0):
+                      trace=False, momentum=0.0, seed=0, utt_ids=None):
     """Batched Griffin-Lim on the GPU.  amp: float32 [B, Fmax, bins] magnitudes (frame-major, the
     decoder's y_stft layout); phase0: same shape, radians (default: pi * np.random.rand drawn per
-    utterance in the reference's [bins, F] order, audio_lib.py:255).  momentum: fast Griffin-Lim
+    utterance in the reference's [bins, F] order, audio_lib.py:255), or 'device': drawn by
+    phase_init(n_frames, Fmax, bins, seed, utt_ids) without touching the host generator.  momentum: fast Griffin-Lim
     (0 <= momentum < 1; 0 = the reference's algorithm, 0.99 = librosa's default).
     Returns wav [B, hop*(Fmax-1)] cuda float32 (zero beyond an utterance's hop*(frames-1) samples)
     and, with ``trace``, the per-iteration sum of squared waveform changes [num_iters, B]."""
@@ -306,7 +376,11 @@ def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_ite
         raise ValueError(' - ERROR, griffin_lim_batch: amp must be [B, F, {}]'.format(plan.n_bins))
     B, Fmax, nb = amp.shape
     d_nf, h_nf = _frames_arg(n_frames, B, Fmax, plan)
-    if phase0 is None:
+    if isinstance(phase0, str):
+        if phase0 != 'device':
+            raise ValueError(" - ERROR, griffin_lim_batch: phase0 must be None, 'device' or an array, got {!r}".format(phase0))
+        phase0 = phase_init(h_nf if d_nf is None else d_nf, Fmax, nb, seed, utt_ids)
+    elif phase0 is None:
         ph = np.zeros((B, Fmax, nb), dtype=np.float32)
         for b in range(B):
             ph[b, :h_nf[b]] = (np.pi * np.random.rand(nb, int(h_nf[b]))).T
@@ -316,19 +390,7 @@ def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_ite
     phase0 = phase0.to(device='cuda', dtype=torch.float32).contiguous()
     if phase0.shape != amp.shape:
         raise ValueError(' - ERROR, griffin_lim_batch: phase0 must have the shape of amp')
-    L = plan.hop_length * (Fmax - 1)
-    wav = torch.empty((B, L), dtype=torch.float32, device=amp.device)
-    tr = torch.empty((int(num_iters), B), dtype=torch.float32, device=amp.device) if trace else None
-    ws = plan.workspace(B, Fmax, trace, amp.device, momentum=momentum > 0.0)
-    if momentum == 0.0:
-        _vc.check(_vc.lib().vc_griffin_lim_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B, Fmax,
-                                               int(num_iters), _vc.ptr(wav), L, _vc.ptr(tr), _vc.ptr(ws), ws.numel(),
-                                               _vc.current_stream()))
-    else:
-        _vc.check(_vc.lib().vc_griffin_lim_momentum_f32(plan.handle, _vc.ptr(amp), _vc.ptr(phase0), _vc.ptr(d_nf), B,
-                                                        Fmax, int(num_iters), momentum, _vc.ptr(wav), L, _vc.ptr(tr),
-                                                        _vc.ptr(ws), ws.numel(), _vc.current_stream()))
-    return (wav, tr) if trace else wav
+    return _griffin_lim_launch(plan, amp, phase0, d_nf, num_iters, trace, momentum)
 
 
 def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None, verbose=True, phase0=None,
@@ -358,10 +420,10 @@ def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None,
 
 def from_power_to_wav_batch(P, n_frames=None, P_dB_norm_factor=0.01, pre_emphasis=0.97, hop_length=40,
                             win_length=800, mean_abs_amp_norm=0.01, n_iter=200, n_fft=None, realse=1.0,
-                            phase0=None, trace=False, momentum=0.0):
+                            phase0=None, trace=False, momentum=0.0, seed=0, utt_ids=None):
     """Batched from_power_to_wav: P [B, Fmax, bins] normalised power dB (the decoder's y_stft) ->
     wav [B, hop*(Fmax-1)] cuda float32; utterance b is valid up to hop*(n_frames[b]-1) samples.
-    momentum: fast Griffin-Lim, see griffin_lim_batch."""
+    momentum: fast Griffin-Lim; phase0 / seed / utt_ids: see griffin_lim_batch."""
     import torch
     momentum = check_momentum(momentum)
     if not torch.cuda.is_available():
@@ -377,7 +439,7 @@ def from_power_to_wav_batch(P, n_frames=None, P_dB_norm_factor=0.01, pre_emphasi
     amp = torch.empty_like(P)
     _vc.check(_vc.lib().vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nf), B, Fmax, nb, float(P_dB_norm_factor), float(realse),
                                         _vc.ptr(amp), _vc.current_stream()))
-    r = griffin_lim_batch(amp, n_frames, win_length, hop_length, n_iter, n_fft, phase0, trace, momentum)
+    r = griffin_lim_batch(amp, n_frames, win_length, hop_length, n_iter, n_fft, phase0, trace, momentum, seed, utt_ids)
     wav = r[0] if trace else r
     _vc.check(_vc.lib().vc_inv_preemphasis_normalize(plan.handle, _vc.ptr(wav), _vc.ptr(d_nf), B, Fmax, wav.shape[1],
                                                      float(pre_emphasis), float(mean_abs_amp_norm), _vc.current_stream()))

@@ -9,6 +9,11 @@ writing (test.py:28-43, 171-188) are UI side effects and out of scope.  ``vocode
 audio_lib.from_power_to_wav, any callable with that signature, or None to skip audio synthesis
 (``y_wav_true`` / ``y_wav_pred`` are then None).  ``momentum`` (default 0.0): fast Griffin-Lim; a
 callable receives ``momentum=`` only when it is not 0, so a reference-signature vocoder keeps working.
+
+``convert_batch`` is the same conversion for a ragged batch of waveforms with nothing leaving the
+device: front-end -> vc_cut_windows -> encoder + decoder over window chunks -> vc_compound_stitch ->
+vc_phase_init -> Griffin-Lim, all tables computed on the host from the lengths before the first
+launch (``convert_plan``) and uploaded once; it returns cuda tensors.
 """
 from collections import namedtuple
 
@@ -144,3 +149,229 @@ def conversion(decoder, mfcc, mel, stft, cfg_d, t_s=5, t_e=60, n_iter=200, outpu
                                      momentum)
     ret_tuple = namedtuple('conversion', 'y_wav_true y_wav_pred mel_true mel_pred stft_true stft_pred')
     return ret_tuple(y_wav_true, y_wav_pred, mel_true, mel_pred, stft_true, stft_pred)
+
+
+# --------------------------------------------------------------------------- batched, device-resident
+_PLAN_NT = namedtuple('convert_plan', 'B T Fout W n_src n_s n_e N n_clip n_out win_tab utt_tab true_tab')
+_BATCH_NT = namedtuple('convert_batch', 'y_wav_true y_wav_pred n_samples mel_true mel_pred stft_true stft_pred '
+                                        'phn_pred n_frames')
+
+
+def convert_plan(lens, cfg_d, t_s=0, t_e=60, two_pass=True):
+    """Host tables of ``convert_batch`` for utterances of ``lens`` samples (pure integer work, no GPU):
+      n_src [B]       front-end frames 1 + len // hop
+      n_s, n_e, N [B] ``window_plan`` per utterance and its window count (n_e - n_s) // T
+      n_clip [B]      min(n_src, n_e): source rows at or beyond it read as zeros (the reference's padding, and its cut at t_e)
+      n_out [B]       N * T output frames; Fout = max(n_out)
+      win_tab [W, 2]  (utterance, first frame) of every window: per utterance its N pass-0 windows from n_s, then, with
+                      two_pass and N > 1, its N - 1 pass-1 windows from n_s + T // 2
+      utt_tab [B, 3]  (first pass-0 window, first pass-1 window or -1, N)
+      true_tab [B, 2] (utterance, n_s): the one Fout-row "window" that cuts mel_true / stft_true
+    An empty span raises the reference's error (test.py:117-119) with the utterance's index."""
+    T, hop = int(cfg_d['n_timesteps']), int(cfg_d['hop_length'])
+    if T <= 0 or T % 4 != 0:
+        raise ValueError(' - ERROR, convert_batch: n_timesteps must be a positive multiple of 4 (compound cuts quarters)')
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    B = len(lens)
+    n_src = 1 + lens // hop
+    n_s, n_e, N = np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.int64)
+    win, utt = [], []
+    for b in range(B):
+        try:
+            _, n_s[b], n_e[b] = window_plan(int(n_src[b]), cfg_d, t_s, t_e)
+        except Exception as e:
+            raise Exception('{} (utterance {} of the batch, {} frames)'.format(e, b, int(n_src[b]))) from None
+        N[b] = (n_e[b] - n_s[b]) // T
+        w0 = len(win)
+        win += [(b, n_s[b] + i * T) for i in range(N[b])]
+        w1 = -1
+        if two_pass and N[b] > 1:
+            w1 = len(win)
+            win += [(b, n_s[b] + T // 2 + i * T) for i in range(N[b] - 1)]
+        utt.append((w0, w1, N[b]))
+    n_out = N * T
+    i32 = lambda a, shape: np.asarray(a, dtype=np.int32).reshape(shape)
+    return _PLAN_NT(B, T, int(n_out.max()), len(win), i32(n_src, (B,)), i32(n_s, (B,)), i32(n_e, (B,)), i32(N, (B,)),
+                    i32(np.minimum(n_src, n_e), (B,)), i32(n_out, (B,)), i32(win, (-1, 2)), i32(utt, (B, 3)),
+                    i32(np.stack([np.arange(B), n_s], 1), (B, 2)))
+
+
+def cut_windows(src, win_tab, n_frames, T, out=None):
+    """vc_cut_windows (include/vc_hip.h): src [B, Fmax, C] float32 cuda -> [W, T, C]; win_tab int32 [W, 2] cuda
+    (utterance, first frame); rows at or beyond n_frames[utterance] (int32 [B] cuda, or None) are zeros."""
+    import torch
+    import _vc
+    B, Fmax, C = src.shape
+    W = win_tab.shape[0]
+    if out is None:
+        out = torch.empty((W, int(T), C), dtype=torch.float32, device=src.device)
+    _vc.check(_vc.lib().vc_cut_windows(_vc.ptr(src), _vc.ptr(win_tab), _vc.ptr(n_frames), B, Fmax, W, int(T), C,
+                                       _vc.ptr(out), _vc.current_stream()))
+    return out
+
+
+def compound_stitch(src, utt_tab, Fout, P_dB_norm_factor=None, out=None, amp=None):
+    """vc_compound_stitch (include/vc_hip.h): window batch src [W, T, C] (float32 or bfloat16 cuda) -> [B, Fout, C]
+    float32; utt_tab int32 [B, 3] cuda.  With P_dB_norm_factor also the vocoder's magnitude (realse == 1): returns
+    (stitched, amp)."""
+    import torch
+    import _vc
+    W, T, C = src.shape
+    B = utt_tab.shape[0]
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        src = src.float()
+    if out is None:
+        out = torch.empty((B, int(Fout), C), dtype=torch.float32, device=src.device)
+    if P_dB_norm_factor is not None and amp is None:
+        amp = torch.empty((B, int(Fout), C), dtype=torch.float32, device=src.device)
+    _vc.check(_vc.lib().vc_compound_stitch(_vc.ptr(src), _vc.VC_BF16 if src.dtype == torch.bfloat16 else _vc.VC_F32,
+                                           _vc.ptr(utt_tab), B, W, T, C, int(Fout), _vc.ptr(out), _vc.ptr(amp),
+                                           float(P_dB_norm_factor or 0.0), _vc.current_stream()))
+    return out if P_dB_norm_factor is None else (out, amp)
+
+
+def _numpy_phase(plan, n_bins, both):
+    """The reference's draws (audio_lib.py:255) from the global generator, per utterance in batch order, the true
+    spectrum's first, then the predicted one's: what a loop of conversion2 calls draws."""
+    ph = np.zeros((2 if both else 1, plan.B, plan.Fout, n_bins), dtype=np.float32)
+    for b in range(plan.B):
+        n = int(plan.n_out[b])
+        for k in range(ph.shape[0]):
+            ph[k, b, :n] = (np.pi * np.random.rand(n_bins, n)).T
+    return ph
+
+
+def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True,
+                  giffin_lim_input=False, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64,
+                  vocode=True, encoder=None):
+    """``conversion2`` (two_pass) / ``conversion`` for a ragged batch, waveforms in, waveforms out, on the device.
+
+    wav [B, Lmax] float32 (numpy or cuda tensor), lens: host ints (None = all Lmax).  cfg_d: the data-set
+    configuration of test.py (sample_rate, hop_length, win_length, n_fft, n_timesteps, the front-end's settings).
+    phase: 'device' (vc_phase_init from ``seed`` and ``utt_ids``, default 0 .. B-1; the true and the predicted
+    spectrum start from the same phase), 'numpy' (the reference's draws from the global generator, in the order of a
+    loop of conversion2 calls) or a [B, Fout, bins] array.  window_batch: windows per decoder chunk (utterances and
+    passes mixed), issued round-robin on the decoder's streams.  vocode=False stops after the stitch.
+    encoder: only for a decoder built WITHOUT one (an MX-FP8 decoder owns its store and takes posteriors): the
+    encoder whose posteriors feed it, chunk by chunk on the same streams.
+    Returns a namedtuple of cuda tensors -- y_wav_pred, y_wav_true (None unless giffin_lim_input) [B, hop*(Fout-1)],
+    mel_pred / stft_pred / phn_pred and mel_true / stft_true [B, Fout, C], zero beyond an utterance's own extent --
+    and the host counts n_frames [B] (= N_b * n_timesteps) and n_samples [B] (= hop * (n_frames - 1)).
+    Every check and every table is made on the host from ``lens`` before the first launch; after that nothing is
+    copied to the host and the host waits for nothing."""
+    import torch
+    import audio_lib
+    import _vc
+    momentum = _check_momentum(momentum)
+    seed = audio_lib.check_seed(seed)
+    if cfg_d is None:
+        raise ValueError(' - ERROR, convert_batch: cfg_d (the data-set configuration) is required')
+    if isinstance(phase, str) and phase not in ('device', 'numpy'):
+        raise ValueError(" - ERROR, convert_batch: phase must be 'device', 'numpy' or a [B, Fout, bins] array, got {!r}".format(phase))
+    if getattr(wav, 'ndim', 0) != 2:
+        raise ValueError(' - ERROR, convert_batch: wav must be [B, Lmax]')
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
+    h_lens = np.full((B,), Lmax, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    if h_lens.shape != (B,) or h_lens.min() <= n_fft // 2 or h_lens.max() > Lmax:
+        raise ValueError(' - ERROR, convert_batch: lens must be [B] with n_fft//2 < len <= Lmax')
+    if utt_ids is None:
+        utt_ids = np.arange(B)
+    utt_ids = np.asarray(utt_ids, dtype=np.int64).reshape(-1)
+    if utt_ids.shape != (B,) or utt_ids.min() < -2 ** 31 or utt_ids.max() >= 2 ** 31:
+        raise ValueError(' - ERROR, convert_batch: utt_ids must be {} int32 values, one per utterance'.format(B))
+    window_batch = int(window_batch)
+    if window_batch <= 0:
+        raise ValueError(' - ERROR, convert_batch: window_batch must be positive')
+    if (decoder.encoder is None) == (encoder is None):
+        raise ValueError(' - ERROR, convert_batch: pass encoder= exactly when the decoder was built without one')
+    plan = convert_plan(h_lens, cfg_d, t_s, t_e, two_pass)
+    hop, T, Fout = int(cfg_d['hop_length']), plan.T, plan.Fout
+    n_bins = 1 + n_fft // 2
+    if vocode and hop * (int(plan.n_out.min()) - 1) <= n_fft // 2:
+        raise ValueError(' - ERROR, convert_batch: every utterance needs hop_length*(frames-1) > n_fft//2 samples')
+    both = bool(giffin_lim_input)
+    h_phase = None
+    if not isinstance(phase, str):
+        if tuple(phase.shape) != (B, Fout, n_bins):
+            raise ValueError(' - ERROR, convert_batch: phase must be [{}, {}, {}]'.format(B, Fout, n_bins))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('convert_batch needs a GPU (no CPU fallback)')
+
+    # ---- uploads: the waveforms if they are on the host, one table, the host-drawn phase if asked for
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
+    parts = [h_lens, plan.n_clip, plan.n_out, utt_ids, plan.win_tab, plan.utt_tab, plan.true_tab]
+    h_tab = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in parts])).pin_memory()
+    d_tab = h_tab.to('cuda', non_blocking=True)
+    offs = np.cumsum([0] + [a.size for a in parts])
+    d_lens, d_clip, d_nout, d_ids, d_win, d_utt, d_true = (d_tab[offs[i]:offs[i + 1]] for i in range(len(parts)))
+    d_win, d_utt, d_true = d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)
+    if vocode and isinstance(phase, str) and phase == 'numpy':
+        h_phase = torch.from_numpy(_numpy_phase(plan, n_bins, both)).pin_memory()
+        d_phase = h_phase.to('cuda', non_blocking=True)
+        ph_true, ph_pred = d_phase[0], d_phase[-1]
+    elif vocode and not isinstance(phase, str):
+        if not torch.is_tensor(phase):
+            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
+        ph_true = ph_pred = phase.to(device='cuda', dtype=torch.float32).contiguous()
+
+    # ---- front-end, windows, model, stitch
+    mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(
+        wav, d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
+        win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
+        window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
+        mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
+        M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
+        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'], clip_output=cfg_d['clip_output'])
+    x = cut_windows(mfcc, d_win, d_clip, T)
+    mel_true = cut_windows(mel, d_true, d_clip, Fout)
+    stft_true = cut_windows(pdb, d_true, d_clip, Fout)
+    if encoder is None:
+        outs = decoder.forward_chunks(x, window_batch, n_streams=2)
+    else:
+        outs = decoder.forward_chunks(x, window_batch, n_streams=2, width=x.shape[2],
+                                      fn=lambda xb: decoder.forward(encoder.forward(xb)['y_pred']))
+    main = torch.cuda.current_stream()
+    cols = []
+    for key in ('y_mel', 'y_stft', 'y_phn'):
+        ts = [o[key] for o in outs]
+        for t in ts:
+            t.record_stream(main)
+        cols.append(ts[0] if len(ts) == 1 else torch.cat(ts, 0))
+    y_mel, y_stft, y_phn = cols
+    mel_pred = compound_stitch(y_mel, d_utt, Fout)
+    phn_pred = compound_stitch(y_phn, d_utt, Fout)
+    fused = vocode and float(realse) == 1.0
+    if fused:
+        stft_pred, amp_pred = compound_stitch(y_stft, d_utt, Fout, P_dB_norm_factor=cfg_d['P_dB_norm_factor'])
+    else:
+        stft_pred = compound_stitch(y_stft, d_utt, Fout)
+    n_frames = [int(v) for v in plan.n_out]
+    n_samples = [hop * (v - 1) for v in n_frames]
+    if not vocode:
+        return _BATCH_NT(None, None, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
+
+    # ---- vocoder
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
+    lib = _vc.lib()
+    if isinstance(phase, str) and phase == 'device':
+        ph_true = ph_pred = audio_lib.phase_init(d_nout, Fout, n_bins, seed, d_ids)
+
+    def power_to_amp(P, rl):
+        amp = torch.empty_like(P)
+        _vc.check(lib.vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nout), B, Fout, n_bins, float(cfg_d['P_dB_norm_factor']),
+                                      float(rl), _vc.ptr(amp), _vc.current_stream()))
+        return amp
+
+    def to_wav(amp, ph):
+        w = audio_lib._griffin_lim_launch(vplan, amp, ph, d_nout, n_iter, False, momentum)
+        _vc.check(lib.vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(w), _vc.ptr(d_nout), B, Fout, w.shape[1],
+                                                   float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
+                                                   _vc.current_stream()))
+        return w
+
+    y_wav_true = to_wav(power_to_amp(stft_true, 1.0), ph_true) if both else None
+    y_wav_pred = to_wav(amp_pred if fused else power_to_amp(stft_pred, realse), ph_pred)
+    return _BATCH_NT(y_wav_true, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)

@@ -237,6 +237,23 @@ class decoder_specs:
         The chunks are independent, so they are issued round-robin on ``n_streams`` HIP streams:
         one chunk's latency-bound recurrences overlap with another chunk's GEMMs (results are
         identical to the sequential order)."""
+        outs = self.forward_chunks(x, batch_size, n_streams)
+        y_mel_v, y_stft_v, y_phn_v = [], [], []
+        for o in outs:
+            y_mel_v.append(o['y_mel'].cpu().numpy())
+            y_stft_v.append(o['y_stft'].cpu().numpy())
+            y_phn_v.append(o['y_phn'].float().cpu().numpy())
+        predict_nt = namedtuple('predict', 'y_mel y_stft y_phn')
+        return predict_nt(np.concatenate(y_mel_v, axis=0), np.concatenate(y_stft_v, axis=0),
+                          np.concatenate(y_phn_v, axis=0))
+
+    def forward_chunks(self, x, batch_size=32, n_streams=2, fn=None, width=None):
+        """``forward`` (or ``fn``, for chunks ``width`` wide) over chunks of ``batch_size`` windows of x [N, T, width]
+        (numpy or device tensor), issued round-robin on ``n_streams`` HIP streams; the current stream waits for all of
+        them before this returns.
+        Returns the list of forward()'s dicts (device tensors, nothing copied to the host).  A caller that goes on
+        using a chunk's tensors on the current stream calls ``record_stream`` on them: they were allocated on the
+        chunk's stream."""
         import torch
         if self.cfg_d.get('use_target_mel_step2', False):
             raise Exception(' - ERROR, predict: a model built with use_target_mel_step2 needs target_mel for its second '
@@ -248,26 +265,19 @@ class decoder_specs:
         outs = []
         main = torch.cuda.current_stream() if torch.cuda.is_available() else None
         for k, i_s in enumerate(range(0, x.shape[0], batch_size)):
-            x_batch = self._to_device(x[i_s:min(i_s + batch_size, x.shape[0])], self._input_width(), 'decoder input')
+            x_batch = self._to_device(x[i_s:min(i_s + batch_size, x.shape[0])], width or self._input_width(), 'decoder input')
             if use_streams:
                 st = self._streams[k % len(self._streams)]
                 st.wait_stream(main)
                 with torch.cuda.stream(st):
                     x_batch.record_stream(st)
-                    outs.append(self.forward(x_batch))
+                    outs.append((fn or self.forward)(x_batch))
             else:
-                outs.append(self.forward(x_batch))
+                outs.append((fn or self.forward)(x_batch))
         if use_streams:
             for st in self._streams:
                 main.wait_stream(st)
-        y_mel_v, y_stft_v, y_phn_v = [], [], []
-        for o in outs:
-            y_mel_v.append(o['y_mel'].cpu().numpy())
-            y_stft_v.append(o['y_stft'].cpu().numpy())
-            y_phn_v.append(o['y_phn'].float().cpu().numpy())
-        predict_nt = namedtuple('predict', 'y_mel y_stft y_phn')
-        return predict_nt(np.concatenate(y_mel_v, axis=0), np.concatenate(y_stft_v, axis=0),
-                          np.concatenate(y_phn_v, axis=0))
+        return outs
 
     def _losses(self, o, target_mel, target_stft):
         """decoder.py:185-199 on the host (scalars for eval; the training step fuses this)."""
