@@ -772,6 +772,33 @@ int vc_compound_stitch(const void* d_src, int32_t src_dtype, const int32_t* d_ut
 int vc_phase_init(const int32_t* d_n_frames, const int32_t* d_utt_id, int32_t batch, int32_t max_frames, int32_t n_bins,
                   int64_t seed, float* d_phase, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Resampling: what librosa.load(path, cfg['sample_rate']) does to a file of another rate before the reference sees it
+ * (test.py:472, ARCTIC_reader.py:233, TIMIT_reader.py:308, TARGET_spk_reader.py:108), for a ragged batch on the device.
+ * Added without a version bump: no existing signature moved, a library without these symbols fails to bind them by name.
+ *
+ * Band-limited interpolation with a Kaiser-windowed sinc, evaluated exactly at every phase (no interpolated table).
+ * For integer rates, g = gcd(sr_in, sr_out), up = sr_out / g, down = sr_in / g, fc = rolloff * min(1, up / down):
+ *     h(t) = fc * sinc(fc t) * I0(beta * sqrt(1 - u^2)) / I0(beta),  u = t * fc / Z,  |u| < 1, else 0   (t in input samples)
+ *     y[m] = sum_{0 <= n < len_in} x[n] * h((m * down - n * up) / up),      0 <= m < len_out = ceil(len_in * up / down)
+ * The caller passes the taps of the up-sampled domain, h_taps[k + half] = h(k / up) for |k| <= half (float64, 2*half+1
+ * values; audio_lib.resample_taps builds them); the plan rounds them to float32 and stores, per phase p = (m * down) % up,
+ * the row of taps k = p + j * up.  VC_ERR_UNSUPPORTED (before any HIP call) when the table exceeds 2^24 floats or the
+ * input span of one tile (4 * down + taps per phase, at least) exceeds 16,000 samples of LDS.
+ *
+ * vc_resample_f32: d_in [batch] rows of max_in samples, row stride ld_in >= max_in; d_lens_in int32 [batch] (NULL =
+ * max_in; values are clamped to [0, max_in]); d_out [batch] rows of max_out >= ceil(max_in * up / down) samples, stride
+ * ld_out.  One launch, no workspace, no memset, no atomics: every element of every output row up to max_out is written
+ * exactly once, zeros from the row's own len_out on.  float32 taps, samples and accumulation; the accumulation is
+ * compensated (the rounding error of every product and of every addition is carried in a second float32 word and added
+ * at the end), so an output is the float32 rounding of the exact sum of its float32 products, and it runs in a fixed
+ * order per output: an utterance's output is bit-identical alone and in any batch.  m * down is formed in 64 bits. */
+typedef struct vc_resample_plan vc_resample_plan;
+int vc_resample_plan_create(int32_t up, int32_t down, int32_t half, const double* h_taps, vc_resample_plan** out_plan);
+void vc_resample_plan_destroy(vc_resample_plan* plan);
+int vc_resample_f32(const vc_resample_plan* plan, const float* d_in, const int32_t* d_lens_in, int32_t batch, int32_t max_in,
+                    int32_t ld_in, float* d_out, int32_t max_out, int32_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

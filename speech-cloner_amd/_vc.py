@@ -231,6 +231,9 @@ _SIGS = {
     'vc_compound_stitch': (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                      C.c_float, _P]),
     'vc_phase_init': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
+    'vc_resample_plan_create': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    'vc_resample_plan_destroy': (None, [_P]),
+    'vc_resample_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
 }
 
 
@@ -259,7 +262,12 @@ def lib():
             raise VCError('native library %s reports ABI version %d, this binding is written for %d -- rebuild it '
                           '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, got, VC_ABI_VERSION))
         for name, (res, args) in _SIGS.items():
-            fn = getattr(h, name)
+            try:
+                fn = getattr(h, name)
+            except AttributeError:
+                # exports added without a version bump (vc_resample_*): a build older than this binding lacks them
+                raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
+                              '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None
             fn.restype = res
             fn.argtypes = args
         _lib = h

@@ -467,3 +467,151 @@ def from_power_to_wav(P, P_dB_norm_factor=0.01, pre_emphasis=0.97, hop_length=40
     else:
         wav = r
     return wav[0].cpu().numpy()
+
+
+# --------------------------------------------------------------------------- resampling
+# res_type -> (zero crossings per side, roll-off, Kaiser beta): resampy's published presets.
+RES_TYPES = {'kaiser_best': (64, 0.9475937167399596, 14.769656459379492),
+             'kaiser_fast': (16, 0.85, 8.555504641634386)}
+_RES_PLANS = {}
+
+
+def _check_rate(sr, what):
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or int(sr) <= 0:
+        raise ValueError(' - ERROR, resample: {} must be a positive integer rate, got {!r}'.format(what, sr))
+    return int(sr)
+
+
+def _res_params(res_type):
+    if isinstance(res_type, str):
+        if res_type not in RES_TYPES:
+            raise ValueError(' - ERROR, resample: unknown res_type {!r} (known: {}, or a (Z, rolloff, beta) tuple)'
+                             .format(res_type, ', '.join(sorted(RES_TYPES))))
+        return RES_TYPES[res_type]
+    try:
+        z, rolloff, beta = res_type
+        z, rolloff, beta = int(z), float(rolloff), float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(' - ERROR, resample: unknown res_type {!r}'.format(res_type)) from None
+    if z <= 0 or not 0.0 < rolloff <= 1.0 or not (math.isfinite(beta) and beta >= 0.0):
+        raise ValueError(' - ERROR, resample: res_type (Z, rolloff, beta) needs Z > 0, 0 < rolloff <= 1, beta >= 0, got {!r}'
+                         .format(res_type))
+    return z, rolloff, beta
+
+
+def _ratio(sr_in, sr_out):
+    sr_in, sr_out = _check_rate(sr_in, 'sr_in'), _check_rate(sr_out, 'sr_out')
+    g = math.gcd(sr_in, sr_out)
+    return sr_out // g, sr_in // g
+
+
+def resample_taps(sr_in, sr_out, res_type='kaiser_best'):
+    """(up, down, half, taps): the Kaiser-windowed sinc of include/vc_hip.h ("Resampling") sampled in the up-sampled
+    domain, taps[k + half] = h(k / up) for |k| <= half = ceil(Z * up / fc) - 1, float64.  Host only."""
+    from scipy import special
+    up, down = _ratio(sr_in, sr_out)
+    z, rolloff, beta = _res_params(res_type)
+    fc = rolloff * min(1.0, up / down)
+    half = int(math.ceil(z * up / fc)) - 1
+    t = np.arange(-half, half + 1, dtype=np.float64) / up
+    w = 1.0 - (t * fc / z) ** 2
+    inside = w > 0.0
+    taps = np.where(inside, fc * np.sinc(fc * t) * special.i0(beta * np.sqrt(np.where(inside, w, 0.0))) / special.i0(beta), 0.0)
+    return up, down, half, taps
+
+
+def resample_len(n, sr_in, sr_out):
+    """ceil(n * sr_out / sr_in) in exact integers (librosa.load's length); n an int or an integer array."""
+    up, down = _ratio(sr_in, sr_out)
+    if isinstance(n, (int, np.integer)):
+        return (int(n) * up + down - 1) // down
+    return (np.asarray(n, dtype=np.int64) * up + down - 1) // down
+
+
+class _ResPlan:
+    def __init__(self, sr_in, sr_out, res_type):
+        self.up, self.down, self.half, taps = resample_taps(sr_in, sr_out, res_type)
+        self._taps = np.ascontiguousarray(taps, dtype=np.float64)
+        h = C.c_void_p()
+        _vc.check(_vc.lib().vc_resample_plan_create(self.up, self.down, self.half, _vc.ptr(self._taps), C.byref(h)))
+        self.handle = h
+
+
+def _get_res_plan(sr_in, sr_out, res_type):
+    up, down = _ratio(sr_in, sr_out)
+    key = (up, down, res_type if isinstance(res_type, str) else tuple(res_type))
+    p = _RES_PLANS.get(key)
+    if p is None:
+        p = _RES_PLANS[key] = _ResPlan(down, up, res_type)      # the taps depend on the ratio alone: rates down -> up
+    return p
+
+
+def _resample_launch(plan, wav, d_lens, out=None):
+    """The one launch of resample_batch on validated device tensors (wav float32 [B, L] with unit sample stride, d_lens
+    int32 [B] or None): no host check, copy or wait in here."""
+    import torch
+    B, L = wav.shape
+    Lout = (L * plan.up + plan.down - 1) // plan.down
+    if out is None:
+        out = torch.empty((B, Lout), dtype=torch.float32, device=wav.device)
+    # (the stride of a one-row tensor is arbitrary)
+    _vc.check(_vc.lib().vc_resample_f32(plan.handle, _vc.ptr(wav), _vc.ptr(d_lens), B, L, wav.stride(0) if B > 1 else L,
+                                        _vc.ptr(out), Lout, out.stride(0) if B > 1 else Lout, _vc.current_stream()))
+    return out
+
+
+def resample_batch(wav, lens=None, sr_in=None, sr_out=16000, res_type='kaiser_best', out=None):
+    """Sample-rate conversion of a ragged batch on the GPU (vc_resample_f32, include/vc_hip.h): what
+    librosa.load(path, sr_out) does to a file recorded at sr_in.
+
+    wav  : float32 [B, Lmax] torch.cuda tensor (rows may be strided, samples contiguous) or numpy array (uploaded).
+    lens : optional per-utterance sample counts at sr_in (host ints); None = all Lmax.
+    res_type : 'kaiser_best', 'kaiser_fast' or a (Z, rolloff, beta) tuple.
+    out  : optional preallocated float32 cuda tensor [B, resample_len(Lmax, sr_in, sr_out)].
+    Returns (wav_out cuda float32 [B, resample_len(Lmax)], lens_out host int64 array); rows are zero from their own
+    lens_out on.  sr_in == sr_out is the identity: nothing is launched and ``wav`` itself comes back."""
+    import torch
+    if sr_in is None:
+        raise ValueError(' - ERROR, resample_batch: sr_in (the rate of wav) is required')
+    up, down = _ratio(sr_in, sr_out)
+    _res_params(res_type)
+    if getattr(wav, 'ndim', 0) != 2:
+        raise ValueError(' - ERROR, resample_batch: wav must be [B, Lmax]')
+    B, L = int(wav.shape[0]), int(wav.shape[1])
+    if B <= 0 or L <= 0:
+        raise ValueError(' - ERROR, resample_batch: wav must be [B, Lmax] with B > 0 and Lmax > 0')
+    h_lens = np.full((B,), L, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    if h_lens.shape != (B,) or h_lens.min() <= 0 or h_lens.max() > L:
+        raise ValueError(' - ERROR, resample_batch: lens must be [B] with 0 < len <= Lmax')
+    if up == down:
+        return wav, h_lens
+    Lout = (L * up + down - 1) // down
+    if Lout >= 2 ** 31:
+        raise ValueError(' - ERROR, resample_batch: {} output samples per row exceed int32'.format(Lout))
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (B, Lout) or out.dtype != torch.float32
+                            or not out.is_cuda or out.stride(1) != 1):
+        raise ValueError(' - ERROR, resample_batch: out must be a float32 cuda tensor [{}, {}]'.format(B, Lout))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('resample_batch needs a GPU (no CPU fallback)')
+    plan = _get_res_plan(sr_in, sr_out, res_type)
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32)
+    if wav.stride(1) != 1 or (B > 1 and wav.stride(0) < L):
+        wav = wav.contiguous()
+    d_lens = None
+    if lens is not None:
+        d_lens = torch.from_numpy(h_lens.astype(np.int32)).pin_memory().to('cuda', non_blocking=True)
+    return _resample_launch(plan, wav, d_lens, out), (h_lens * up + down - 1) // down
+
+
+def resample(y, orig_sr, target_sr, res_type='kaiser_best'):
+    """One utterance, numpy in, numpy float32 out [ceil(len * target_sr / orig_sr)]: the resampling half of
+    librosa.load(path, target_sr).  Equal rates return ``y`` itself."""
+    up, down = _ratio(orig_sr, target_sr)
+    _res_params(res_type)
+    if up == down:
+        return y
+    y = np.ascontiguousarray(np.asarray(y).reshape(1, -1), dtype=np.float32)
+    out, _ = resample_batch(y, None, orig_sr, target_sr, res_type)
+    return out[0].cpu().numpy()

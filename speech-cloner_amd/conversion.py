@@ -13,7 +13,8 @@ callable receives ``momentum=`` only when it is not 0, so a reference-signature 
 ``convert_batch`` is the same conversion for a ragged batch of waveforms with nothing leaving the
 device: front-end -> vc_cut_windows -> encoder + decoder over window chunks -> vc_compound_stitch ->
 vc_phase_init -> Griffin-Lim, all tables computed on the host from the lengths before the first
-launch (``convert_plan``) and uploaded once; it returns cuda tensors.
+launch (``convert_plan``) and uploaded once; it returns cuda tensors.  ``wav_sr`` / ``out_sr`` put
+audio_lib's device resampler in front of and behind that chain for audio at another sample rate.
 """
 from collections import namedtuple
 
@@ -243,7 +244,7 @@ def _numpy_phase(plan, n_bins, both):
 
 def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True,
                   giffin_lim_input=False, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64,
-                  vocode=True, encoder=None):
+                  vocode=True, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
     """``conversion2`` (two_pass) / ``conversion`` for a ragged batch, waveforms in, waveforms out, on the device.
 
     wav [B, Lmax] float32 (numpy or cuda tensor), lens: host ints (None = all Lmax).  cfg_d: the data-set
@@ -254,6 +255,9 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     passes mixed), issued round-robin on the decoder's streams.  vocode=False stops after the stitch.
     encoder: only for a decoder built WITHOUT one (an MX-FP8 decoder owns its store and takes posteriors): the
     encoder whose posteriors feed it, chunk by chunk on the same streams.
+    wav_sr: the sample rate of ``wav`` (None = cfg_d['sample_rate']); another rate is resampled on the device first
+    (audio_lib.resample_batch, ``res_type``), and ``lens`` then count samples at wav_sr.  out_sr: the rate of the returned
+    waveforms (None = cfg_d['sample_rate']); n_samples is then reported at out_sr.
     Returns a namedtuple of cuda tensors -- y_wav_pred, y_wav_true (None unless giffin_lim_input) [B, hop*(Fout-1)],
     mel_pred / stft_pred / phn_pred and mel_true / stft_true [B, Fout, C], zero beyond an utterance's own extent --
     and the host counts n_frames [B] (= N_b * n_timesteps) and n_samples [B] (= hop * (n_frames - 1)).
@@ -273,6 +277,19 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     B, Lmax = int(wav.shape[0]), int(wav.shape[1])
     n_fft = cfg_d['n_fft'] or cfg_d['win_length']
     h_lens = np.full((B,), Lmax, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    sr = cfg_d['sample_rate']
+    audio_lib._res_params(res_type)
+    res_in = wav_sr is not None and audio_lib._ratio(wav_sr, sr) != (1, 1)
+    res_out = vocode and out_sr is not None and audio_lib._ratio(sr, out_sr) != (1, 1)
+    if res_in:
+        # lens count samples at wav_sr; everything below (checks, tables) works on the resampled lengths
+        if h_lens.shape != (B,) or h_lens.min() <= 0 or h_lens.max() > Lmax:
+            raise ValueError(' - ERROR, convert_batch: lens must be [B] with 0 < len <= Lmax')
+        h_lens_in, Lmax_in = h_lens, Lmax
+        h_lens, Lmax = audio_lib.resample_len(h_lens_in, wav_sr, sr), audio_lib.resample_len(Lmax_in, wav_sr, sr)
+        if h_lens.min() <= n_fft // 2:
+            raise ValueError(' - ERROR, convert_batch: every utterance needs more than n_fft//2 = {} samples at {} Hz '
+                             '(shortest: {} after resampling from {} Hz)'.format(n_fft // 2, sr, int(h_lens.min()), wav_sr))
     if h_lens.shape != (B,) or h_lens.min() <= n_fft // 2 or h_lens.max() > Lmax:
         raise ValueError(' - ERROR, convert_batch: lens must be [B] with n_fft//2 < len <= Lmax')
     if utt_ids is None:
@@ -303,10 +320,16 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
         wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
     wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
     parts = [h_lens, plan.n_clip, plan.n_out, utt_ids, plan.win_tab, plan.utt_tab, plan.true_tab]
+    h_nsamp = hop * (plan.n_out.astype(np.int64) - 1)
+    if res_in:
+        parts.append(h_lens_in)
+    if res_out:
+        parts.append(h_nsamp)
     h_tab = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in parts])).pin_memory()
     d_tab = h_tab.to('cuda', non_blocking=True)
     offs = np.cumsum([0] + [a.size for a in parts])
-    d_lens, d_clip, d_nout, d_ids, d_win, d_utt, d_true = (d_tab[offs[i]:offs[i + 1]] for i in range(len(parts)))
+    d_lens, d_clip, d_nout, d_ids, d_win, d_utt, d_true = (d_tab[offs[i]:offs[i + 1]] for i in range(7))
+    d_extra = [d_tab[offs[i]:offs[i + 1]] for i in range(7, len(parts))]
     d_win, d_utt, d_true = d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)
     if vocode and isinstance(phase, str) and phase == 'numpy':
         h_phase = torch.from_numpy(_numpy_phase(plan, n_bins, both)).pin_memory()
@@ -318,6 +341,8 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
         ph_true = ph_pred = phase.to(device='cuda', dtype=torch.float32).contiguous()
 
     # ---- front-end, windows, model, stitch
+    if res_in:
+        wav = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), wav, d_extra[0])
     mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(
         wav, d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
         win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
@@ -349,7 +374,7 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     else:
         stft_pred = compound_stitch(y_stft, d_utt, Fout)
     n_frames = [int(v) for v in plan.n_out]
-    n_samples = [hop * (v - 1) for v in n_frames]
+    n_samples = [int(v) for v in h_nsamp]
     if not vocode:
         return _BATCH_NT(None, None, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
 
@@ -374,4 +399,10 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
 
     y_wav_true = to_wav(power_to_amp(stft_true, 1.0), ph_true) if both else None
     y_wav_pred = to_wav(amp_pred if fused else power_to_amp(stft_pred, realse), ph_pred)
+    if res_out:
+        rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
+        y_wav_pred = audio_lib._resample_launch(rplan, y_wav_pred, d_extra[-1])
+        if both:
+            y_wav_true = audio_lib._resample_launch(rplan, y_wav_true, d_extra[-1])
+        n_samples = [int(v) for v in audio_lib.resample_len(h_nsamp, sr, out_sr)]
     return _BATCH_NT(y_wav_true, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
