@@ -799,6 +799,56 @@ void vc_resample_plan_destroy(vc_resample_plan* plan);
 int vc_resample_f32(const vc_resample_plan* plan, const float* d_in, const int32_t* d_lens_in, int32_t batch, int32_t max_in,
                     int32_t ld_in, float* d_out, int32_t max_out, int32_t ld_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Evaluation: how close a converted utterance is to the target speaker's own recording of the sentence -- mel-cepstral
+ * distortion (MCD, in dB) along a dynamic-time-warping (DTW) path, or frame by frame for two conversions of one input.
+ * Added without a version bump, like the resampler: no existing signature moved.
+ *
+ * Cepstra.  For mel [rows, n_mels] (the front-end's M_dB or the decoder's mel output, float32 or bf16):
+ *     c[row, d] = sum_m dct[d, m] * mel[row, m],  d = 0 .. n_coef-1,  m ascending, float32 fused multiply-adds.
+ * d_dct is [n_coef, n_mels] float32 ON THE DEVICE: the rows first_coef .. first_coef + n_coef - 1 of the orthonormal
+ * DCT-II (dct[k, m] = sqrt(2 / n_mels) * cos(pi * k * (2 m + 1) / (2 n_mels)), row 0 scaled by sqrt(1/2): the table of
+ * vc_frontend_host_tables), built on the host in float64 and rounded once.  1 <= n_coef <= min(n_mels, 32), n_mels <= 512.
+ *
+ * Frame distance:  d(i, j) = scale * sqrt(2 * sum_d (ca[i, d] - cb[j, d])^2), the sum over d ascending, fused
+ * multiply-adds, a correctly rounded square root.  With mel = M_dB_norm_factor * (20 log10(mel power) - min), the natural
+ * logarithm of the mel amplitude is mel * ln 10 / (40 * M_dB_norm_factor) + const, and the textbook
+ * (10 / ln 10) * sqrt(2 * sum (delta mc)^2) becomes scale = 1 / (4 * M_dB_norm_factor): 25 for the shipped 0.01.
+ *
+ * DTW.  D(0, 0) = d(0, 0);  D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)); on exact equality the
+ * predecessor is taken in that order (diagonal, up, left).  L(i, j) = 1 + L(predecessor), L(0, 0) = 1.  Per pair:
+ * total = D(Fa-1, Fb-1), path_len = L(Fa-1, Fb-1), mcd = total / path_len (float32 division).  band >= 0 allows cell
+ * (i, j) iff |j * (Fa-1) - i * (Fb-1)| <= band * max(Fa-1, Fb-1), tested in 64-bit integers; every other cell has
+ * D = +inf and L = 0; the end cell is always allowed.  band = -1: no band.  A band that disconnects the end from the
+ * start gives total = +inf.
+ *
+ * vc_dtw_f32: d_ca [batch, max_a, n_coef], d_cb [batch, max_b, n_coef] float32, contiguous; d_len_a / d_len_b int32
+ * [batch] ON THE DEVICE, clamped to [1, max]; 1 <= max_a, max_b <= 16,384, n_coef <= 32 (else VC_ERR_UNSUPPORTED);
+ * scale finite and > 0.  One launch, one workgroup per pair; no matrix of costs or distances is ever stored: score mode
+ * (want_path = 0) uses 16 bytes of workspace per column of B and pair.  want_path = 1 also stores two bits per cell
+ * (0 diagonal, 1 up, 2 left; row-major, sixteen columns to a word) and gives bit-identical total / path_len;
+ * VC_ERR_UNSUPPORTED when the codes of the batch exceed 2^31 bytes (one pair of 16,384 x 16,384 takes 2^26).
+ * vc_dtw_workspace_size: bytes for either mode (host arithmetic only; 0 for a shape the launch would refuse).
+ * vc_dtw_backtrack: from the workspace a want_path launch filled (same batch, max_a, max_b) and its d_total /
+ * d_path_len, d_path [batch, max_a + max_b - 1, 2] int32: the cells (i, j) from (0, 0) to (Fa-1, Fb-1), rows from
+ * path_len on filled with -1 (all rows when total is not finite).
+ * vc_frame_mcd_f32: mcd = (1 / n) * sum_{i < n} d(i, i), n = min(Fa, Fb): lane t of 256 adds frames t, t + 256, ... in
+ * that order and the 256 partial sums are added in a fixed tree.
+ *
+ * Every result is a function of its own pair alone: bit-identical alone, inside any batch, from run to run and under
+ * graph replay.  No atomics.  Every launch is capturable; arguments are checked before any HIP call. */
+int vc_mel_cepstra(const void* d_mel, int32_t mel_dtype, int32_t rows, int32_t n_mels, const float* d_dct, int32_t n_coef,
+                   float* d_cep, void* stream);
+size_t vc_dtw_workspace_size(int32_t batch, int32_t max_a, int32_t max_b, int32_t want_path);
+int vc_dtw_f32(const float* d_ca, const float* d_cb, const int32_t* d_len_a, const int32_t* d_len_b, int32_t batch,
+               int32_t max_a, int32_t max_b, int32_t n_coef, float scale, int32_t band, int32_t want_path, float* d_total,
+               int32_t* d_path_len, float* d_mcd, void* d_workspace, size_t workspace_bytes, void* stream);
+int vc_dtw_backtrack(const void* d_workspace, size_t workspace_bytes, const int32_t* d_len_a, const int32_t* d_len_b,
+                     const float* d_total, const int32_t* d_path_len, int32_t batch, int32_t max_a, int32_t max_b, int32_t* d_path,
+                     void* stream);
+int vc_frame_mcd_f32(const float* d_ca, const float* d_cb, const int32_t* d_len_a, const int32_t* d_len_b, int32_t batch,
+                     int32_t max_a, int32_t max_b, int32_t n_coef, float scale, float* d_mcd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,312 @@
+"""Scoring a conversion on the MI355X: mel-cepstral distortion (MCD, dB) along a dynamic-time-warping (DTW) path.
+
+The reference judges a conversion by eye and by ear (test.py:338-343, ``show_spec_comp`` and ``sd.play``).  Its TEST 3
+(test.py:379-413) converts CMU-ARCTIC speaker ``rms``, sentence ``a0407``, to ``bdl``; ``bdl``'s own recording of that
+sentence exists and has another length, and the usual number for such a pair is the MCD along the DTW path between the
+two.  The same number, frame by frame (``align='frame'``), compares two conversions of one input: what ``mxfp8`` or
+32 iterations of fast Griffin-Lim cost.
+
+  mel_cepstra(mel [B, F, n_mels]) -> c [B, F, n_coef]           c = Dct[first_coef : first_coef + n_coef] @ mel
+  dtw_batch(ca, cb, len_a, len_b, band, return_path)            -> (total [B], path_len [B], mcd [B], path | None)
+  mcd_batch(mel_a, mel_b, len_a, len_b, cfg_d, ...)             the two above in one; mel as convert_batch returns it
+  mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)       resampler and front-end on both sides first
+
+Definitions (include/vc_hip.h, "Evaluation"):
+  d(i, j) = scale * sqrt(2 * sum_d (ca[i, d] - cb[j, d])^2),  scale = 1 / (4 * M_dB_norm_factor) by default
+  D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), ties in that order;  mcd = D(end) / path length
+
+Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
+the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip; there is no CPU path.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+import _vc
+
+MAX_FRAMES = 16384          # vc_dtw_f32
+MAX_COEF = 32
+
+_RESULT = namedtuple('mcd', 'total path_len mcd path')
+_DCT = {}
+
+
+def dct_rows(n_mels, n_coef=24, first_coef=1):
+    """Rows first_coef .. first_coef + n_coef - 1 of the orthonormal DCT-II over n_mels points, float32 [n_coef, n_mels]:
+    audio_lib.host_tables' table (float64), rounded once.  Host only."""
+    import audio_lib
+    n_mels, n_coef, first_coef = int(n_mels), int(n_coef), int(first_coef)
+    if n_coef < 1 or first_coef < 0 or n_coef + first_coef > n_mels:
+        raise ValueError(' - ERROR, mel_cepstra: need n_coef >= 1, first_coef >= 0 and n_coef + first_coef <= n_mels = {} '
+                         '(got n_coef {}, first_coef {})'.format(n_mels, n_coef, first_coef))
+    if n_coef > MAX_COEF:
+        raise ValueError(' - ERROR, mel_cepstra: at most {} coefficients (got {})'.format(MAX_COEF, n_coef))
+    dct = audio_lib.host_tables(16000, 2 * n_mels + 2, n_mels, n_coef + first_coef)[1]
+    return np.ascontiguousarray(dct[first_coef:first_coef + n_coef].astype(np.float32))
+
+
+def _check_mel(mel, what):
+    import torch
+    if getattr(mel, 'ndim', 0) != 3 or min(mel.shape) < 1:
+        raise ValueError(' - ERROR, {} must be [B, F, n_mels]'.format(what))
+    if torch.is_tensor(mel):
+        if mel.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(' - ERROR, {} must be float32 or bfloat16, got {}'.format(what, mel.dtype))
+    return tuple(int(v) for v in mel.shape)
+
+
+def _check_lens(lens, B, Fmax, what):
+    h = np.asarray(lens)
+    if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 1 or h.max() > Fmax:
+        raise ValueError(' - ERROR, {} must be {} integers in [1, {}]'.format(what, B, Fmax))
+    return h.astype(np.int64)
+
+
+def _check_band(band):
+    if band is None:
+        return -1
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or band < 0 or band >= 2 ** 31:
+        raise ValueError(' - ERROR, dtw: band must be None or a non-negative integer number of frames, got {!r}'.format(band))
+    return int(band)
+
+
+def _check_scale(scale):
+    s = float(scale)
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError(' - ERROR, mcd: scale must be finite and positive, got {!r}'.format(scale))
+    return s
+
+
+def _check_pairs(B, Fa, Fb, n_coef, return_path):
+    if B > 65535 or Fa > MAX_FRAMES or Fb > MAX_FRAMES:
+        raise ValueError(' - ERROR, dtw: at most 65535 pairs of at most {} frames (got {} pairs of {} x {})'.format(MAX_FRAMES, B, Fa, Fb))
+    if n_coef > MAX_COEF:
+        raise ValueError(' - ERROR, dtw: at most {} coefficients (got {})'.format(MAX_COEF, n_coef))
+    if return_path and B * Fa * ((Fb + 15) // 16) * 4 > 2 ** 31:
+        raise ValueError(' - ERROR, dtw: the paths of {} pairs of {} x {} frames need more than 2 GiB of predecessor codes; '
+                         'score fewer pairs per call'.format(B, Fa, Fb))
+
+
+def _to_device(t, dtype=None):
+    import torch
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
+    return t.to(device='cuda', dtype=dtype).contiguous()
+
+
+def _upload_lens(*arrays):
+    """One pinned upload of several host int arrays; returns the device slices (no wait)."""
+    import torch
+    h = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in arrays])).pin_memory()
+    d = h.to('cuda', non_blocking=True)
+    offs = np.cumsum([0] + [np.asarray(a).size for a in arrays])
+    return [d[offs[i]:offs[i + 1]] for i in range(len(arrays))]
+
+
+def _dct_device(n_mels, n_coef, first_coef):
+    import torch
+    key = (n_mels, n_coef, first_coef)
+    t = _DCT.get(key)
+    if t is None:
+        t = _DCT[key] = torch.from_numpy(dct_rows(n_mels, n_coef, first_coef)).pin_memory().to('cuda', non_blocking=True)
+    return t
+
+
+def _cepstra_launch(mel, n_coef, first_coef):
+    """mel: cuda, contiguous, float32 or bf16 [B, F, n_mels] -> float32 [B, F, n_coef].  No host check in here."""
+    import torch
+    B, F, n_mels = mel.shape
+    out = torch.empty((B, F, n_coef), dtype=torch.float32, device=mel.device)
+    _vc.check(_vc.lib().vc_mel_cepstra(_vc.ptr(mel), _vc.VC_BF16 if mel.dtype == torch.bfloat16 else _vc.VC_F32, B * F, n_mels,
+                                       _vc.ptr(_dct_device(n_mels, n_coef, first_coef)), n_coef, _vc.ptr(out), _vc.current_stream()))
+    return out
+
+
+def _dtw_launch(ca, cb, d_la, d_lb, scale, band, return_path):
+    import torch
+    lib = _vc.lib()
+    B, Fa, n_coef = ca.shape
+    Fb = cb.shape[1]
+    dev = ca.device
+    total = torch.empty((B,), dtype=torch.float32, device=dev)
+    mcd = torch.empty((B,), dtype=torch.float32, device=dev)
+    plen = torch.empty((B,), dtype=torch.int32, device=dev)
+    need = lib.vc_dtw_workspace_size(B, Fa, Fb, int(return_path))
+    if need == 0:
+        raise _vc.VCError('vc_dtw_workspace_size refused {} pairs of {} x {} frames'.format(B, Fa, Fb))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    st = _vc.current_stream()
+    _vc.check(lib.vc_dtw_f32(_vc.ptr(ca), _vc.ptr(cb), _vc.ptr(d_la), _vc.ptr(d_lb), B, Fa, Fb, n_coef, scale, band, int(return_path),
+                             _vc.ptr(total), _vc.ptr(plen), _vc.ptr(mcd), _vc.ptr(ws), need, st))
+    path = None
+    if return_path:
+        path = torch.empty((B, Fa + Fb - 1, 2), dtype=torch.int32, device=dev)
+        _vc.check(lib.vc_dtw_backtrack(_vc.ptr(ws), need, _vc.ptr(d_la), _vc.ptr(d_lb), _vc.ptr(total), _vc.ptr(plen), B, Fa, Fb,
+                                       _vc.ptr(path), st))
+    return _RESULT(total, plen, mcd, path)
+
+
+def _frame_launch(ca, cb, d_la, d_lb, scale):
+    import torch
+    B, Fa, n_coef = ca.shape
+    mcd = torch.empty((B,), dtype=torch.float32, device=ca.device)
+    _vc.check(_vc.lib().vc_frame_mcd_f32(_vc.ptr(ca), _vc.ptr(cb), _vc.ptr(d_la), _vc.ptr(d_lb), B, Fa, cb.shape[1], n_coef, scale,
+                                         _vc.ptr(mcd), _vc.current_stream()))
+    return _RESULT(None, None, mcd, None)
+
+
+def _need_gpu(what):
+    import torch
+    if not torch.cuda.is_available():
+        raise _vc.VCError('{} needs a GPU (no CPU fallback)'.format(what))
+
+
+def mel_cepstra(mel, n_coef=24, first_coef=1):
+    """c[b, f, d] = sum_m Dct[first_coef + d, m] * mel[b, f, m]: float32 [B, F, n_coef] on the device.  mel: float32 or
+    bfloat16 [B, F, n_mels], cuda tensor or numpy array (uploaded).  first_coef = 1 leaves out c0, which carries the
+    gain: the front-end's amplitude normalisation and per-utterance minimum move c0 alone."""
+    B, F, n_mels = _check_mel(mel, 'mel_cepstra: mel')
+    dct_rows(n_mels, n_coef, first_coef)                            # validates n_coef / first_coef against n_mels
+    if B * F >= 2 ** 31:
+        raise ValueError(' - ERROR, mel_cepstra: {} frames exceed int32'.format(B * F))
+    _need_gpu('mel_cepstra')
+    return _cepstra_launch(_to_device(mel), int(n_coef), int(first_coef))
+
+
+def dtw_batch(ca, cb, len_a, len_b, band=None, return_path=False, scale=1.0):
+    """DTW of B pairs of cepstra over the frame distance scale * sqrt(2 * sum (ca[i] - cb[j])^2) (vc_dtw_f32); ``scale``
+    defaults to 1, so ``mcd`` is in dB only when the caller passes the dB scale (mcd_batch does: 25 for the shipped
+    M_dB_norm_factor).
+
+    ca [B, Fa_max, n_coef], cb [B, Fb_max, n_coef] float32; len_a, len_b: host integers in [1, F_max].
+    band: None, or the half width in frames of the allowed stripe around the straight line from (0, 0) to the end.
+    Returns a namedtuple of device tensors: total [B] float32, path_len [B] int32, mcd [B] float32 = total / path_len, and
+    path: None, or with return_path int32 [B, Fa_max + Fb_max - 1, 2], the cells (i, j) from (0, 0) to the end, rows from
+    path_len on filled with -1."""
+    import torch
+    for x, what in ((ca, 'ca'), (cb, 'cb')):
+        if getattr(x, 'ndim', 0) != 3 or min(x.shape) < 1:
+            raise ValueError(' - ERROR, dtw_batch: {} must be [B, F, n_coef]'.format(what))
+        if torch.is_tensor(x) and x.dtype != torch.float32:
+            raise ValueError(' - ERROR, dtw_batch: {} must be float32'.format(what))
+    B, Fa, n_coef = (int(v) for v in ca.shape)
+    if int(cb.shape[0]) != B or int(cb.shape[2]) != n_coef:
+        raise ValueError(' - ERROR, dtw_batch: ca {} and cb {} must agree in B and n_coef'.format(tuple(ca.shape), tuple(cb.shape)))
+    Fb = int(cb.shape[1])
+    h_la, h_lb = _check_lens(len_a, B, Fa, 'dtw_batch: len_a'), _check_lens(len_b, B, Fb, 'dtw_batch: len_b')
+    band, scale = _check_band(band), _check_scale(scale)
+    _check_pairs(B, Fa, Fb, n_coef, return_path)
+    _need_gpu('dtw_batch')
+    d_la, d_lb = _upload_lens(h_la, h_lb)
+    return _dtw_launch(_to_device(ca, torch.float32), _to_device(cb, torch.float32), d_la, d_lb, scale, band, bool(return_path))
+
+
+def _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, n_mels):
+    if align not in ('dtw', 'frame'):
+        raise ValueError(" - ERROR, mcd_batch: align must be 'dtw' or 'frame', got {!r}".format(align))
+    if scale is None:
+        if cfg_d is None:
+            raise ValueError(' - ERROR, mcd_batch: pass cfg_d (for M_dB_norm_factor) or scale')
+        scale = 1.0 / (4.0 * float(cfg_d['M_dB_norm_factor']))
+    dct_rows(n_mels, n_coef, first_coef)                            # validates n_coef / first_coef against n_mels
+    return _check_scale(scale), _check_band(band)
+
+
+def mcd_batch(mel_a, mel_b, len_a, len_b, cfg_d=None, scale=None, n_coef=24, align='dtw', band=None, return_path=False,
+              first_coef=1):
+    """Mel-cepstral distortion in dB of B pairs of mel spectrograms, as convert_batch returns them (mel_pred, mel_true,
+    n_frames): mel_a [B, Fa_max, n_mels], mel_b [B, Fb_max, n_mels], float32 or bfloat16; len_a, len_b host integers.
+
+    align='dtw': along the DTW path (``band``, ``return_path`` as in dtw_batch).  align='frame': the mean over the first
+    min(len_a, len_b) frames of d(i, i); total, path_len and path are then None.
+    scale: None = 1 / (4 * cfg_d['M_dB_norm_factor']), which turns differences of the project's normalised mel into the
+    textbook (10 / ln 10) * sqrt(2 * sum (delta mc)^2)."""
+    import torch
+    Ba, Fa, n_mels = _check_mel(mel_a, 'mcd_batch: mel_a')
+    Bb, Fb, n_mels_b = _check_mel(mel_b, 'mcd_batch: mel_b')
+    if Ba != Bb or n_mels != n_mels_b:
+        raise ValueError(' - ERROR, mcd_batch: mel_a {} and mel_b {} must agree in B and n_mels'.format(tuple(mel_a.shape), tuple(mel_b.shape)))
+    n_coef, first_coef = int(n_coef), int(first_coef)
+    scale, band = _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, n_mels)
+    h_la, h_lb = _check_lens(len_a, Ba, Fa, 'mcd_batch: len_a'), _check_lens(len_b, Ba, Fb, 'mcd_batch: len_b')
+    if align == 'dtw':
+        _check_pairs(Ba, Fa, Fb, n_coef, return_path)
+    elif Ba > 65535:
+        raise ValueError(' - ERROR, mcd_batch: at most 65535 pairs')
+    _need_gpu('mcd_batch')
+    d_la, d_lb = _upload_lens(h_la, h_lb)
+    ca = _cepstra_launch(_to_device(mel_a), n_coef, first_coef)
+    cb = _cepstra_launch(_to_device(mel_b), n_coef, first_coef)
+    if align == 'frame':
+        return _frame_launch(ca, cb, d_la, d_lb, scale)
+    return _dtw_launch(ca, cb, d_la, d_lb, scale, band, bool(return_path))
+
+
+def _wav_side(wav, lens, cfg_d, wav_sr, what):
+    """Host checks of one side of mcd_wav_batch; returns what its launches need."""
+    import audio_lib
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, mcd_wav_batch: {} must be [B, Lmax]'.format(what))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    h = np.full((B,), Lmax, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    if h.shape != (B,) or h.min() <= 0 or h.max() > Lmax:
+        raise ValueError(' - ERROR, mcd_wav_batch: lens of {} must be [B] with 0 < len <= Lmax'.format(what))
+    sr = cfg_d['sample_rate']
+    res = wav_sr is not None and audio_lib._ratio(wav_sr, sr) != (1, 1)
+    h_in = h
+    if res:
+        h, Lmax = audio_lib.resample_len(h_in, wav_sr, sr), audio_lib.resample_len(Lmax, wav_sr, sr)
+    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
+    if h.min() <= n_fft // 2:
+        raise ValueError(' - ERROR, mcd_wav_batch: every utterance of {} needs more than n_fft//2 = {} samples at {} Hz'
+                         .format(what, n_fft // 2, sr))
+    hop = int(cfg_d['hop_length'])
+    return dict(B=B, res=res, sr_in=wav_sr, h_in=h_in, h=h, n_frames=1 + h // hop, Fmax=1 + Lmax // hop)
+
+
+def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
+    import torch
+    import audio_lib
+    wav = _to_device(wav, torch.float32)
+    if wav.shape[0] == 1:                                           # (the stride of a one-row tensor is arbitrary)
+        wav = wav.as_strided(wav.shape, (wav.shape[1], 1))
+    if side['res']:
+        wav = audio_lib._resample_launch(audio_lib._get_res_plan(side['sr_in'], cfg_d['sample_rate'], res_type), wav, d_in)
+    return audio_lib.calc_MFCC_input_batch(
+        wav, d_len, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=cfg_d['hop_length'],
+        win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
+        window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
+        mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
+        M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
+        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'], clip_output=cfg_d['clip_output'])[1]
+
+
+def mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best', scale=None,
+                  n_coef=24, align='dtw', band=None, return_path=False, first_coef=1):
+    """"Score my conversion against the target's recording" in one call: both sides go through the resampler (when
+    their rate wav_sr_a / wav_sr_b differs from cfg_d['sample_rate']) and the front-end, then through mcd_batch.
+
+    wav_a [B, La_max], wav_b [B, Lb_max] float32 (cuda tensor or numpy array); lens_a, lens_b host integers counting
+    samples at the side's own rate (None = the whole row); cfg_d: the data-set configuration of test.py.
+    Returns mcd_batch's namedtuple; frame counts are 1 + len // hop_length of the (resampled) lengths."""
+    import audio_lib
+    if cfg_d is None:
+        raise ValueError(' - ERROR, mcd_wav_batch: cfg_d (the data-set configuration) is required')
+    audio_lib._res_params(res_type)
+    a = _wav_side(wav_a, lens_a, cfg_d, wav_sr_a, 'wav_a')
+    b = _wav_side(wav_b, lens_b, cfg_d, wav_sr_b, 'wav_b')
+    if a['B'] != b['B']:
+        raise ValueError(' - ERROR, mcd_wav_batch: wav_a and wav_b must hold the same number of utterances')
+    n_coef, first_coef = int(n_coef), int(first_coef)
+    scale, band = _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, int(cfg_d['n_mels']))
+    if align == 'dtw':
+        _check_pairs(a['B'], a['Fmax'], b['Fmax'], n_coef, return_path)
+    _need_gpu('mcd_wav_batch')
+    d_in_a, d_len_a, d_fa, d_in_b, d_len_b, d_fb = _upload_lens(a['h_in'], a['h'], a['n_frames'], b['h_in'], b['h'], b['n_frames'])
+    mel_a = _wav_mel(wav_a, a, d_in_a, d_len_a, cfg_d, res_type)
+    mel_b = _wav_mel(wav_b, b, d_in_b, d_len_b, cfg_d, res_type)
+    ca = _cepstra_launch(mel_a, n_coef, first_coef)
+    cb = _cepstra_launch(mel_b, n_coef, first_coef)
+    if align == 'frame':
+        return _frame_launch(ca, cb, d_fa, d_fb, scale)
+    return _dtw_launch(ca, cb, d_fa, d_fb, scale, band, bool(return_path))
