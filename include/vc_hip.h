@@ -849,6 +849,59 @@ int vc_dtw_backtrack(const void* d_workspace, size_t workspace_bytes, const int3
 int vc_frame_mcd_f32(const float* d_ca, const float* d_cb, const int32_t* d_len_a, const int32_t* d_len_b, int32_t batch,
                      int32_t max_a, int32_t max_b, int32_t n_coef, float scale, float* d_mcd, void* stream);
 
+/* Pitch.  MCD leaves out the gain term and sees the spectral envelope only; the other two figures reported for a pair of
+ * utterances are the F0 error and the voiced / unvoiced error along the same path.  Added without a version bump.
+ *
+ * F0 is YIN (de Cheveigne and Kawahara 2002), steps 2 to 5, on the raw waveform: no pre-emphasis, no amplitude
+ * normalisation (the normalised difference does not change under a gain; a power-of-two gain leaves every output bit
+ * for bit).  Parameters: sample_rate, hop, the integration length W = frame_length, tau_min = floor(sr / fmax),
+ * tau_max = ceil(sr / fmin) (40 and 267 for 400 and 60 Hz at 16 kHz), threshold (0.15).
+ *   Frames      F = 1 + len / hop, the front-end's count: frame f of the track and frame f of the mel spectrogram sit at
+ *               the same time.  Frame f reads x[s .. s + W + tau_max], s = f * hop - (W + tau_max) / 2, zeros outside
+ *               [0, len).
+ *   Difference  d(tau) = sum_{j < W} (x[s + j] - x[s + j + tau])^2, tau = 0 .. tau_max + 1: the DIRECT form (the
+ *               energy-minus-correlation form cancels where this one adds non-negative terms), j ascending, one chain of
+ *               float32 fused multiply-adds per lag.
+ *   Normalised  d'(0) = 1, d'(tau) = d(tau) * tau / sum_{k = 1..tau} d(k) (one rounded product, one correctly rounded
+ *               division), and 1 where that sum is zero: digital silence gives d' = 1 everywhere.  The running sum is a
+ *               scan in a fixed order: inside groups of 64 lags, six steps of lag t adding lag t - 2^k; then the totals
+ *               of the groups before this one, added in order.
+ *   Pick        the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then on while tau + 1 <= tau_max and
+ *               d'(tau + 1) < d'(tau).  None: the frame is unvoiced, f0 = 0.
+ *   Refine      a parabola through d'(tau - 1), d'(tau), d'(tau + 1): offset = 0.5 (y0 - y2) / (y0 - 2 y1 + y2) when the
+ *               denominator is positive, else 0, clamped to [-0.5, 0.5]; f0 = sample_rate / (tau + offset).
+ *   Aperiodicity  min over tau_min <= tau <= tau_max of d'(tau), for every frame, voiced or not.
+ * No smoothing, no octave correction (pYIN and its kin are not built).  Samples are expected to be finite.
+ *
+ * vc_f0_yin_f32: d_wav [batch] rows of max_len samples, row stride ld >= max_len; d_lens int32 [batch] ON THE DEVICE
+ * (NULL = max_len), clamped to [0, max_len]; d_f0, d_aperiodicity [batch, max_frames] float32, max_frames >=
+ * 1 + max_len / hop.  One launch, one workgroup per (utterance, tile of up to 16 frames), the tile's samples staged once
+ * in at most 64 KB of LDS, one lane per lag; no workspace, no atomics.  Every element of both outputs is written exactly
+ * once: f0 = 0 and aperiodicity = 1 from the row's own frame count on.  Limits (VC_ERR_UNSUPPORTED beyond them):
+ * batch <= 65,535, max_len <= 2^30 (sample indices stay in int32), frame_length <= 2,048, tau_max <= 1,022 (one lane per
+ * lag, 1,024 lanes: fmin >= 15.7 Hz at 16 kHz), hop <= 65,536, max_frames <= 2^30 + 1.
+ *
+ * vc_f0_metrics_f32: the figures of `batch` pairs of tracks d_f0_a [batch, max_a], d_f0_b [batch, max_b] (0 = unvoiced)
+ * with d_len_a / d_len_b int32 [batch] on the device, clamped to [1, max].  The cells are d_path [batch, max_path, 2]
+ * int32 with d_path_len [batch] -- exactly what vc_dtw_backtrack and vc_dtw_f32 write -- or, with d_path = d_path_len =
+ * NULL and max_path = 0, the cells (i, i), i < min(len_a, len_b).  A cell outside [0, len_a) x [0, len_b) is skipped and
+ * not counted.  Per pair: d_counts [batch, 3] int32 = n_cells, n_both_voiced, n_vuv_mismatch (one side voiced, the other
+ * not); d_values [batch, 4] float32 = vuv_error (n_vuv_mismatch / n_cells), f0_rmse_cents
+ * (sqrt(mean (1200 log2(fa / fb))^2) over the both-voiced cells), f0_rmse_hz, logf0_corr (Pearson correlation of log2 f0
+ * over the both-voiced cells, taken about the means).  NaN where undefined: vuv_error without a cell, the RMSE values
+ * without a both-voiced cell, the correlation with fewer than two of them or when one side has the same f0 in all of
+ * them.  One workgroup per pair; cells dealt to 256 lanes by stride, sums in float64 added in a fixed tree, rounded to
+ * float32 once.  Limits: batch <= 65,535; max_a, max_b, max_path <= 2^30.
+ *
+ * Both are functions of their own utterance / pair alone, bit-identical alone, in any batch, from run to run and under
+ * graph replay; capturable from the first call; arguments are checked before any HIP call. */
+int vc_f0_yin_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, float sample_rate,
+                  int32_t hop, int32_t frame_length, int32_t tau_min, int32_t tau_max, float threshold, float* d_f0,
+                  float* d_aperiodicity, int32_t max_frames, void* stream);
+int vc_f0_metrics_f32(const float* d_f0_a, const float* d_f0_b, const int32_t* d_len_a, const int32_t* d_len_b, int32_t batch,
+                      int32_t max_a, int32_t max_b, const int32_t* d_path, const int32_t* d_path_len, int32_t max_path,
+                      int32_t* d_counts, float* d_values, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

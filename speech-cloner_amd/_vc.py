@@ -240,6 +240,9 @@ _SIGS = {
                              _P, C.c_size_t, _P]),
     'vc_dtw_backtrack': (C.c_int, [_P, C.c_size_t, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'vc_frame_mcd_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_float, _P, _P, C.c_int32, _P]),
+    'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
 }
 
 
@@ -271,8 +274,8 @@ def lib():
             try:
                 fn = getattr(h, name)
             except AttributeError:
-                # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32): a
-                # build older than this binding lacks them
+                # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
+                # vc_f0_*): a build older than this binding lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
                               '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None
             fn.restype = res

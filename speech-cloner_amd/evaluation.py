@@ -1,4 +1,5 @@
-"""Scoring a conversion on the MI355X: mel-cepstral distortion (MCD, dB) along a dynamic-time-warping (DTW) path.
+"""Scoring a conversion on the MI355X: mel-cepstral distortion (MCD, dB) along a dynamic-time-warping (DTW) path, and the
+F0 error and voiced / unvoiced error along the same path.
 
 The reference judges a conversion by eye and by ear (test.py:338-343, ``show_spec_comp`` and ``sd.play``).  Its TEST 3
 (test.py:379-413) converts CMU-ARCTIC speaker ``rms``, sentence ``a0407``, to ``bdl``; ``bdl``'s own recording of that
@@ -10,13 +11,17 @@ two.  The same number, frame by frame (``align='frame'``), compares two conversi
   dtw_batch(ca, cb, len_a, len_b, band, return_path)            -> (total [B], path_len [B], mcd [B], path | None)
   mcd_batch(mel_a, mel_b, len_a, len_b, cfg_d, ...)             the two above in one; mel as convert_batch returns it
   mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)       resampler and front-end on both sides first
+  f0_batch(wav, lens, sr, hop_length, ...)                      -> (f0 [B, F] Hz, 0 = unvoiced; aperiodicity; n_frames): YIN
+  f0_metrics_batch(f0_a, f0_b, len_a, len_b, path, path_len)    voicing error, F0 RMSE (cents, Hz), log-F0 correlation
+  score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)     MCD and the F0 figures along one DTW path in one call
 
 Definitions (include/vc_hip.h, "Evaluation"):
   d(i, j) = scale * sqrt(2 * sum_d (ca[i, d] - cb[j, d])^2),  scale = 1 / (4 * M_dB_norm_factor) by default
   D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), ties in that order;  mcd = D(end) / path length
 
 Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
-the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip; there is no CPU path.
+the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip and csrc/vc_f0.hip (the pitch tracker
+and its figures); there is no CPU path.
 """
 from collections import namedtuple
 
@@ -27,7 +32,16 @@ import _vc
 MAX_FRAMES = 16384          # vc_dtw_f32
 MAX_COEF = 32
 
+F0_MAX_LAG = 1022           # vc_f0_yin_f32: one lane per lag
+F0_MAX_W = 2048
+F0_MAX_HOP = 65536
+F0_MAX_SAMPLES = 2 ** 30
+
 _RESULT = namedtuple('mcd', 'total path_len mcd path')
+_F0 = namedtuple('f0', 'f0 aperiodicity n_frames')
+_F0_FIELDS = 'n_cells n_both_voiced n_vuv_mismatch vuv_error f0_rmse_cents f0_rmse_hz logf0_corr'
+_F0_METRICS = namedtuple('f0_metrics', _F0_FIELDS)
+_SCORE = namedtuple('score', 'mcd total path_len path ' + _F0_FIELDS + ' f0_a f0_b')
 _DCT = {}
 
 
@@ -264,7 +278,8 @@ def _wav_side(wav, lens, cfg_d, wav_sr, what):
     return dict(B=B, res=res, sr_in=wav_sr, h_in=h_in, h=h, n_frames=1 + h // hop, Fmax=1 + Lmax // hop)
 
 
-def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
+def _wav_at_rate(wav, side, d_in, cfg_d, res_type):
+    """One side's waveform on the device at cfg_d['sample_rate'] (through the resampler when its rate differs)."""
     import torch
     import audio_lib
     wav = _to_device(wav, torch.float32)
@@ -272,6 +287,11 @@ def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
         wav = wav.as_strided(wav.shape, (wav.shape[1], 1))
     if side['res']:
         wav = audio_lib._resample_launch(audio_lib._get_res_plan(side['sr_in'], cfg_d['sample_rate'], res_type), wav, d_in)
+    return wav
+
+
+def _mel_launch(wav, d_len, cfg_d):
+    import audio_lib
     return audio_lib.calc_MFCC_input_batch(
         wav, d_len, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=cfg_d['hop_length'],
         win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
@@ -279,6 +299,10 @@ def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
         mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
         M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
         mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'], clip_output=cfg_d['clip_output'])[1]
+
+
+def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
+    return _mel_launch(_wav_at_rate(wav, side, d_in, cfg_d, res_type), d_len, cfg_d)
 
 
 def mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best', scale=None,
@@ -310,3 +334,149 @@ def mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=N
     if align == 'frame':
         return _frame_launch(ca, cb, d_fa, d_fb, scale)
     return _dtw_launch(ca, cb, d_fa, d_fb, scale, band, bool(return_path))
+
+
+# ------------------------------------------------------------------------------------------------ pitch (csrc/vc_f0.hip)
+def _f0_args(sr, hop_length, frame_length, fmin, fmax, threshold, what):
+    """Host checks of the tracker's parameters; returns (sr, hop, W, tau_min, tau_max, threshold)."""
+    for v, name in ((sr, 'sr'), (hop_length, 'hop_length'), (frame_length, 'frame_length')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(' - ERROR, {}: {} must be a positive integer, got {!r}'.format(what, name, v))
+    fmin, fmax, threshold = float(fmin), float(fmax), float(threshold)
+    if not (np.isfinite(fmin) and np.isfinite(fmax) and 0.0 < fmin < fmax <= sr):
+        raise ValueError(' - ERROR, {}: need 0 < fmin < fmax <= sr (got fmin {}, fmax {}, sr {})'.format(what, fmin, fmax, sr))
+    if not (np.isfinite(threshold) and 0.0 < threshold <= 1.0):
+        raise ValueError(' - ERROR, {}: threshold must lie in (0, 1], got {!r}'.format(what, threshold))
+    tau_min, tau_max = int(np.floor(sr / fmax)), int(np.ceil(sr / fmin))
+    if tau_max > F0_MAX_LAG:
+        raise ValueError(' - ERROR, {}: fmin {} Hz at {} Hz needs lags up to {}, the kernel holds {} (one lane per lag): raise fmin '
+                         'to {:.1f} Hz or more'.format(what, fmin, sr, tau_max, F0_MAX_LAG, sr / float(F0_MAX_LAG)))
+    if frame_length > F0_MAX_W or hop_length > F0_MAX_HOP:
+        raise ValueError(' - ERROR, {}: frame_length at most {} and hop_length at most {} (got {}, {})'
+                         .format(what, F0_MAX_W, F0_MAX_HOP, frame_length, hop_length))
+    return int(sr), int(hop_length), int(frame_length), tau_min, tau_max, threshold
+
+
+def _f0_launch(wav, d_len, args):
+    """wav: cuda, contiguous float32 [B, Lmax]; d_len: device int32 [B] or None.  No host check in here."""
+    import torch
+    sr, hop, W, tau_min, tau_max, thr = args
+    B, Lmax = wav.shape
+    Fmax = 1 + Lmax // hop
+    f0 = torch.empty((B, Fmax), dtype=torch.float32, device=wav.device)
+    ap = torch.empty((B, Fmax), dtype=torch.float32, device=wav.device)
+    _vc.check(_vc.lib().vc_f0_yin_f32(_vc.ptr(wav), _vc.ptr(d_len), B, Lmax, Lmax, float(sr), hop, W, tau_min, tau_max, thr,
+                                      _vc.ptr(f0), _vc.ptr(ap), Fmax, _vc.current_stream()))
+    return f0, ap
+
+
+def _f0_metrics_launch(f0_a, f0_b, d_la, d_lb, path, path_len):
+    import torch
+    B = f0_a.shape[0]
+    counts = torch.empty((B, 3), dtype=torch.int32, device=f0_a.device)
+    values = torch.empty((B, 4), dtype=torch.float32, device=f0_a.device)
+    _vc.check(_vc.lib().vc_f0_metrics_f32(_vc.ptr(f0_a), _vc.ptr(f0_b), _vc.ptr(d_la), _vc.ptr(d_lb), B, f0_a.shape[1], f0_b.shape[1],
+                                          _vc.ptr(path), _vc.ptr(path_len), 0 if path is None else path.shape[1], _vc.ptr(counts),
+                                          _vc.ptr(values), _vc.current_stream()))
+    return _F0_METRICS(counts[:, 0], counts[:, 1], counts[:, 2], values[:, 0], values[:, 1], values[:, 2], values[:, 3])
+
+
+def f0_batch(wav, lens=None, sr=16000, hop_length=80, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15):
+    """F0 of B utterances by YIN on the raw waveform (vc_f0_yin_f32; the definition is in include/vc_hip.h).
+
+    wav [B, Lmax] float32 (cuda tensor or numpy array); lens: host integers in [1, Lmax] (None = the whole row).
+    Returns a namedtuple: f0 [B, Fmax] float32 in Hz, 0 = unvoiced; aperiodicity [B, Fmax] float32, the minimum of the
+    normalised difference over the lag range; n_frames, a list of 1 + len // hop_length per row, the front-end's frame
+    count.  Fmax = 1 + Lmax // hop_length; beyond a row's n_frames f0 is 0 and aperiodicity 1.  No smoothing."""
+    import torch
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, f0_batch: wav must be [B, Lmax]')
+    if torch.is_tensor(wav) and wav.dtype != torch.float32:
+        raise ValueError(' - ERROR, f0_batch: wav must be float32, got {}'.format(wav.dtype))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    args = _f0_args(sr, hop_length, frame_length, fmin, fmax, threshold, 'f0_batch')
+    h = np.full((B,), Lmax, dtype=np.int64) if lens is None else _check_lens(lens, B, Lmax, 'f0_batch: lens')
+    if B > 65535 or Lmax > F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, f0_batch: at most 65535 utterances of at most {} samples (got {} of {})'.format(F0_MAX_SAMPLES, B, Lmax))
+    _need_gpu('f0_batch')
+    d_len, = _upload_lens(h)
+    f0, ap = _f0_launch(_to_device(wav, torch.float32), d_len, args)
+    return _F0(f0, ap, [1 + int(n) // args[1] for n in h])
+
+
+def _check_track(t, what):
+    import torch
+    if getattr(t, 'ndim', 0) != 2 or min(t.shape) < 1:
+        raise ValueError(' - ERROR, f0_metrics_batch: {} must be [B, F]'.format(what))
+    if torch.is_tensor(t) and t.dtype != torch.float32:
+        raise ValueError(' - ERROR, f0_metrics_batch: {} must be float32, got {}'.format(what, t.dtype))
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def f0_metrics_batch(f0_a, f0_b, len_a, len_b, path=None, path_len=None):
+    """F0 and voicing error of B pairs of tracks (vc_f0_metrics_f32): f0_a [B, Fa_max], f0_b [B, Fb_max] float32, 0 =
+    unvoiced, as f0_batch returns them; len_a, len_b host integers.
+
+    path, path_len: what mcd_batch(..., return_path=True) returns (int32 [B, P, 2] and int32 [B], on the device), so
+    both figures are taken along one DTW path; None: the cells (i, i), i < min(len_a, len_b).
+    Returns a namedtuple of [B] device tensors: n_cells, n_both_voiced, n_vuv_mismatch (int32), vuv_error =
+    n_vuv_mismatch / n_cells, f0_rmse_cents = sqrt(mean (1200 log2(fa / fb))^2) and f0_rmse_hz over the both-voiced cells,
+    logf0_corr = Pearson correlation of log2 f0 over them.  NaN where undefined: the RMSE values without a both-voiced
+    cell, the correlation with fewer than two or when one side's f0 is the same in all of them."""
+    import torch
+    B, Fa = _check_track(f0_a, 'f0_a')
+    Bb, Fb = _check_track(f0_b, 'f0_b')
+    if B != Bb:
+        raise ValueError(' - ERROR, f0_metrics_batch: f0_a {} and f0_b {} must agree in B'.format(tuple(f0_a.shape), tuple(f0_b.shape)))
+    h_la, h_lb = _check_lens(len_a, B, Fa, 'f0_metrics_batch: len_a'), _check_lens(len_b, B, Fb, 'f0_metrics_batch: len_b')
+    if (path is None) != (path_len is None):
+        raise ValueError(' - ERROR, f0_metrics_batch: pass path and path_len together (both from mcd_batch(return_path=True)) or neither')
+    if path is not None:
+        if not (torch.is_tensor(path) and torch.is_tensor(path_len)) or path.dtype != torch.int32 or path_len.dtype != torch.int32:
+            raise ValueError(' - ERROR, f0_metrics_batch: path and path_len must be int32 tensors')
+        if path.ndim != 3 or path.shape[0] != B or path.shape[1] < 1 or path.shape[2] != 2 or tuple(path_len.shape) != (B,):
+            raise ValueError(' - ERROR, f0_metrics_batch: path must be [B, P, 2] and path_len [B] (got {} and {})'
+                             .format(tuple(path.shape), tuple(path_len.shape)))
+    if B > 65535 or max(Fa, Fb, 0 if path is None else int(path.shape[1])) > F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, f0_metrics_batch: at most 65535 pairs of at most {} frames or cells'.format(F0_MAX_SAMPLES))
+    _need_gpu('f0_metrics_batch')
+    d_la, d_lb = _upload_lens(h_la, h_lb)
+    if path is not None:
+        path, path_len = path.to('cuda').contiguous(), path_len.to('cuda').contiguous()
+    return _f0_metrics_launch(_to_device(f0_a, torch.float32), _to_device(f0_b, torch.float32), d_la, d_lb, path, path_len)
+
+
+def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best', scale=None,
+                    n_coef=24, align='dtw', band=None, first_coef=1, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15):
+    """The three figures of a pair of utterances in one call -- MCD, F0 error, voiced / unvoiced error -- along ONE path.
+
+    Arguments as mcd_wav_batch (the path is always made with align='dtw'), plus the tracker's frame_length, fmin, fmax,
+    threshold.  F0 is taken from each side's waveform at cfg_d['sample_rate'] (after the resampler) with hop_length =
+    cfg_d['hop_length'], so its frames are the mel frames the path indexes.  Returns a namedtuple of device tensors:
+    mcd, total, path_len, path exactly as mcd_wav_batch(..., return_path=True) gives them (total, path_len, path are None
+    with align='frame'), the seven fields of f0_metrics_batch, and f0_a [B, Fa_max], f0_b [B, Fb_max]."""
+    import audio_lib
+    if cfg_d is None:
+        raise ValueError(' - ERROR, score_wav_batch: cfg_d (the data-set configuration) is required')
+    audio_lib._res_params(res_type)
+    a = _wav_side(wav_a, lens_a, cfg_d, wav_sr_a, 'wav_a')
+    b = _wav_side(wav_b, lens_b, cfg_d, wav_sr_b, 'wav_b')
+    if a['B'] != b['B']:
+        raise ValueError(' - ERROR, score_wav_batch: wav_a and wav_b must hold the same number of utterances')
+    n_coef, first_coef = int(n_coef), int(first_coef)
+    scale, band = _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, int(cfg_d['n_mels']))
+    if align == 'dtw':
+        _check_pairs(a['B'], a['Fmax'], b['Fmax'], n_coef, True)
+    elif a['B'] > 65535:
+        raise ValueError(' - ERROR, score_wav_batch: at most 65535 pairs')
+    args = _f0_args(cfg_d['sample_rate'], cfg_d['hop_length'], frame_length, fmin, fmax, threshold, 'score_wav_batch')
+    _need_gpu('score_wav_batch')
+    d_in_a, d_len_a, d_fa, d_in_b, d_len_b, d_fb = _upload_lens(a['h_in'], a['h'], a['n_frames'], b['h_in'], b['h'], b['n_frames'])
+    x_a = _wav_at_rate(wav_a, a, d_in_a, cfg_d, res_type)
+    x_b = _wav_at_rate(wav_b, b, d_in_b, cfg_d, res_type)
+    ca = _cepstra_launch(_mel_launch(x_a, d_len_a, cfg_d), n_coef, first_coef)
+    cb = _cepstra_launch(_mel_launch(x_b, d_len_b, cfg_d), n_coef, first_coef)
+    f0_a, f0_b = _f0_launch(x_a.contiguous(), d_len_a, args)[0], _f0_launch(x_b.contiguous(), d_len_b, args)[0]
+    r = _frame_launch(ca, cb, d_fa, d_fb, scale) if align == 'frame' else _dtw_launch(ca, cb, d_fa, d_fb, scale, band, True)
+    m = _f0_metrics_launch(f0_a, f0_b, d_fa, d_fb, r.path, r.path_len if r.path is not None else None)
+    return _SCORE(r.mcd, r.total, r.path_len, r.path, *m, f0_a, f0_b)
