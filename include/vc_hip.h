@@ -902,6 +902,82 @@ int vc_f0_metrics_f32(const float* d_f0_a, const float* d_f0_b, const int32_t* d
                       int32_t max_a, int32_t max_b, const int32_t* d_path, const int32_t* d_path_len, int32_t max_path,
                       int32_t* d_counts, float* d_values, void* stream);
 
+/* Speech activity.  The scores above run over every frame, silence included; these five launches answer "where is the
+ * speech" on the device, so that the DTW, the MCD and the F0 figures can be taken over speech frames only.  Added without
+ * a version bump.
+ *
+ *   Frame energy  F = 1 + len / hop frames, the front-end's and the tracker's count.  e[f] = sum_{j < W} x[s + j]^2,
+ *                 s = f * hop - W / 2, zeros outside [0, len); 0 from frame F on.  Order: lane l of 64 adds the squares
+ *                 of samples j = l, l + 64, l + 128, ... of the frame in one chain of float32 fused multiply-adds; the
+ *                 64 partial sums are then added in a butterfly (every lane adds the sum of lane l ^ 32, then l ^ 16, ...
+ *                 l ^ 1).  A frame's energy depends on its own W samples alone.
+ *   Raw decision  mode 1 ('energy'): e[f] > 0 and e[f] > float32(ratio * max_f e[f]), ratio = 10^(-top_db / 10) computed
+ *                 on the host in float64 and rounded once (1e-4 for the default 40 dB); a power-of-two gain changes
+ *                 nothing.  mode 2 ('voiced'): f0[f] > 0, the tracker's output.  mode 3: both.
+ *   Smoothing     integer run-length work.  First every run of inactive frames of length <= max_gap with an active frame
+ *                 on both sides becomes active; then every run of active frames shorter than min_run becomes inactive
+ *                 (runs touching the first or the last frame count with their own length).  max_gap = 0 and
+ *                 min_run <= 1 change nothing.
+ *   Compaction    index[k] = the frame number of the k-th active frame, ascending; n_active their count; n_kept =
+ *                 n_active, except that an utterance without an active frame (digital silence, 'voiced' on noise) keeps
+ *                 all its F frames (index = 0 .. F-1, n_kept = F: vc_dtw_f32 needs lengths in [1, F]; the caller reads
+ *                 the case off n_active == 0).  index is -1 from n_kept on.  A second mask is ANDed in first over the
+ *                 frames i < F = min(F_a, F_b); frames beyond are inactive, and the fallback keeps those F frames.
+ *   Intervals     the maximal runs of active frames as [start, end) pairs, ascending, n_intervals of them, at most
+ *                 (max_a + 1) / 2; unused rows are -1; none when n_active == 0.
+ *
+ * vc_frame_energy_f32: d_wav, d_lens, max_len, ld as vc_f0_yin_f32; d_energy [batch, max_frames] float32, max_frames >=
+ * 1 + max_len / hop, every element written once.  One workgroup per (utterance, tile of vc_frame_energy_tile(hop,
+ * frame_length) frames: 64, halved until the tile's frame_length + (tile - 1) hop samples fit 64 KB of LDS), one wave per
+ * frame.  The only launch that reads the waveform.  Limits: batch <= 65,535, max_len <= 2^30, frame_length <= 8,192,
+ * hop <= 65,536.  vc_frame_energy_tile is host arithmetic (0 for values the launch would refuse).
+ * vc_activity_mask: d_energy (modes 1, 3) and d_f0 (modes 2, 3) [batch, max_frames] float32, d_n_frames int32 [batch] on
+ * the device, clamped to [1, max_frames]; d_mask [batch, max_frames] uint8, 0 from the row's frame count on.  One
+ * workgroup per utterance; max_frames <= 16,384.
+ * vc_mask_compact: d_mask_a [batch, max_a] with d_frames_a; d_mask_b [batch, max_b] with d_frames_b, or NULL, NULL, 0.
+ * d_index [batch, max_a], d_n_active, d_n_kept, d_n_intervals [batch], d_intervals [batch, (max_a + 1) / 2, 2], int32.
+ * One workgroup per utterance, positions by a sum scan in a fixed order; max_a, max_b <= 16,384.
+ * vc_compact_rows_f32: d_dst[b, k, :] = d_src[b, d_index[b, k], :] for k < min(d_n_kept[b], index_frames), zeros beyond;
+ * d_src [batch, src_frames, n_cols], d_index [batch, index_frames], d_dst [batch, dst_frames, n_cols].  The indices live
+ * on the device (vc_gather_rows takes a host-built list of the whole batch).  n_cols <= 4,096.
+ * vc_path_map: d_path_out[b, p] = (d_index_a[b, i], d_index_b[b, j]) for the cell (i, j) = d_path_in[b, p], p <
+ * d_path_len[b]; (-1, -1) beyond, and for a cell outside [0, max_a) x [0, max_b).  d_path_in NULL: the cells (p, p).
+ * d_path_out may be d_path_in.  After it the path indexes the original frames, and vc_f0_metrics_f32 runs unchanged on
+ * the original tracks and lengths.
+ *
+ *
+ * Speech-level gain.  The front-end scales an utterance to a mean |x| of mean_abs_amp_norm over ALL its samples and floors
+ * the mel power, so the mel of the same speech depends on how much silence surrounds it (2 s of speech with 2.8 s of
+ * silence added: cells 15 dB up against a fixed floor, 8.8 dB of MCD between identical speech).  The masked waveform-level
+ * scores therefore take the gain over the speech samples: sample i belongs to frame min((i + hop / 2) / hop, F - 1), and
+ *     gain = target * n / sum |x[i]|  over the n samples of active frames (all samples when no frame is active; 1 when
+ *     they are all zero),
+ * and run the front-end on gain * x with its own normalisation off (mean_abs_amp_norm = 1).
+ * vc_speech_gain_f32: d_wav, d_lens, max_len, ld as above; d_mask [batch, max_frames] and d_n_active [batch] from the two
+ * launches above; d_gain [batch] float32.  One workgroup per utterance; lane t of 1,024 adds samples t, t + 1024, ... in
+ * float64, the partial sums are added in a fixed tree, the quotient is rounded to float32 once.
+ * vc_scale_rows_f32: d_out[b, i] = d_gain[b] * d_wav[b, i] for i < len, 0 beyond; d_out [batch, max_len] contiguous.
+ *
+ * No atomics, no hand-off between workgroups, no memset, no workspace; every output is a function of its own utterance
+ * alone, bit-identical alone, in any batch, from run to run and under graph replay; capturable from the first call. */
+int vc_frame_energy_tile(int32_t hop, int32_t frame_length);
+int vc_frame_energy_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, int32_t hop,
+                        int32_t frame_length, float* d_energy, int32_t max_frames, void* stream);
+int vc_activity_mask(const float* d_energy, const float* d_f0, const int32_t* d_n_frames, int32_t batch, int32_t max_frames,
+                     int32_t mode, float ratio, int32_t max_gap, int32_t min_run, uint8_t* d_mask, void* stream);
+int vc_mask_compact(const uint8_t* d_mask_a, const int32_t* d_frames_a, int32_t max_a, const uint8_t* d_mask_b,
+                    const int32_t* d_frames_b, int32_t max_b, int32_t batch, int32_t* d_index, int32_t* d_n_active, int32_t* d_n_kept,
+                    int32_t* d_intervals, int32_t* d_n_intervals, void* stream);
+int vc_compact_rows_f32(const float* d_src, int32_t src_frames, const int32_t* d_index, int32_t index_frames, const int32_t* d_n_kept,
+                        int32_t batch, int32_t n_cols, float* d_dst, int32_t dst_frames, void* stream);
+int vc_path_map(const int32_t* d_path_in, const int32_t* d_path_len, int32_t batch, int32_t max_path, const int32_t* d_index_a,
+                int32_t max_a, const int32_t* d_index_b, int32_t max_b, int32_t* d_path_out, void* stream);
+int vc_speech_gain_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, int32_t hop,
+                       const uint8_t* d_mask, const int32_t* d_n_active, int32_t max_frames, float target, float* d_gain,
+                       void* stream);
+int vc_scale_rows_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, const float* d_gain,
+                      float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

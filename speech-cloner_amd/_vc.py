@@ -240,6 +240,15 @@ _SIGS = {
                              _P, C.c_size_t, _P]),
     'vc_dtw_backtrack': (C.c_int, [_P, C.c_size_t, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     'vc_frame_mcd_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    # speech activity (csrc/vc_activity.hip); the pitch rows stay the table's last two (tests/test_f0_cpu.py)
+    'vc_frame_energy_tile': (C.c_int, [C.c_int32, C.c_int32]),
+    'vc_frame_energy_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    'vc_activity_mask': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P]),
+    'vc_mask_compact': (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'vc_compact_rows_f32': (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    'vc_path_map': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P]),
+    'vc_speech_gain_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P]),
+    'vc_scale_rows_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -275,7 +284,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*): a build older than this binding lacks them
+                # vc_f0_*, then the speech-activity launches): a build older than this binding lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
                               '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None
             fn.restype = res

@@ -14,14 +14,19 @@ two.  The same number, frame by frame (``align='frame'``), compares two conversi
   f0_batch(wav, lens, sr, hop_length, ...)                      -> (f0 [B, F] Hz, 0 = unvoiced; aperiodicity; n_frames): YIN
   f0_metrics_batch(f0_a, f0_b, len_a, len_b, path, path_len)    voicing error, F0 RMSE (cents, Hz), log-F0 correlation
   score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)     MCD and the F0 figures along one DTW path in one call
+  activity_batch(wav, lens, hop_length, frame_length, mode, ...) -> speech-activity mask, frame list, intervals, frame energy
+  compact_batch(x [B, F, C], index, n_kept)                     the rows a frame list names, zeros beyond
+
+mcd_batch (mask_a, mask_b), mcd_wav_batch and score_wav_batch (mask='energy' | 'voiced' | 'energy+voiced') leave silent
+frames out of the DTW, the MCD and the F0 figures; without a mask they are what they were.
 
 Definitions (include/vc_hip.h, "Evaluation"):
   d(i, j) = scale * sqrt(2 * sum_d (ca[i, d] - cb[j, d])^2),  scale = 1 / (4 * M_dB_norm_factor) by default
   D(i, j) = d(i, j) + min(D(i-1, j-1), D(i-1, j), D(i, j-1)), ties in that order;  mcd = D(end) / path length
 
 Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
-the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip and csrc/vc_f0.hip (the pitch tracker
-and its figures); there is no CPU path.
+the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip, csrc/vc_f0.hip (the pitch tracker
+and its figures) and csrc/vc_activity.hip (the masks); there is no CPU path.
 """
 from collections import namedtuple
 
@@ -41,7 +46,12 @@ _RESULT = namedtuple('mcd', 'total path_len mcd path')
 _F0 = namedtuple('f0', 'f0 aperiodicity n_frames')
 _F0_FIELDS = 'n_cells n_both_voiced n_vuv_mismatch vuv_error f0_rmse_cents f0_rmse_hz logf0_corr'
 _F0_METRICS = namedtuple('f0_metrics', _F0_FIELDS)
-_SCORE = namedtuple('score', 'mcd total path_len path ' + _F0_FIELDS + ' f0_a f0_b')
+_SCORE = namedtuple('score', 'mcd total path_len path ' + _F0_FIELDS + ' f0_a f0_b n_active_a n_active_b mask_a mask_b')
+_ACTIVITY = namedtuple('activity', 'mask index n_active n_kept intervals n_intervals energy n_frames')
+_COMPACT = namedtuple('compact', 'index n_active n_kept intervals n_intervals')
+_MODES = {'energy': 1, 'voiced': 2, 'energy+voiced': 3}         # vc_activity_mask
+ACT_MAX_W = 8192            # vc_frame_energy_f32
+ACT_MAX_COLS = 4096         # vc_compact_rows_f32
 _DCT = {}
 
 
@@ -227,14 +237,18 @@ def _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, n_mels):
 
 
 def mcd_batch(mel_a, mel_b, len_a, len_b, cfg_d=None, scale=None, n_coef=24, align='dtw', band=None, return_path=False,
-              first_coef=1):
+              first_coef=1, mask_a=None, mask_b=None):
     """Mel-cepstral distortion in dB of B pairs of mel spectrograms, as convert_batch returns them (mel_pred, mel_true,
     n_frames): mel_a [B, Fa_max, n_mels], mel_b [B, Fb_max, n_mels], float32 or bfloat16; len_a, len_b host integers.
 
     align='dtw': along the DTW path (``band``, ``return_path`` as in dtw_batch).  align='frame': the mean over the first
     min(len_a, len_b) frames of d(i, i); total, path_len and path are then None.
     scale: None = 1 / (4 * cfg_d['M_dB_norm_factor']), which turns differences of the project's normalised mel into the
-    textbook (10 / ln 10) * sqrt(2 * sum (delta mc)^2)."""
+    textbook (10 / ln 10) * sqrt(2 * sum (delta mc)^2).
+    mask_a [B, Fa_max], mask_b [B, Fb_max]: uint8 or bool, numpy or cuda, 1 = the frame counts (activity_batch's mask; one
+    of them None: every frame of that side).  align='dtw': each side is compacted by its own mask and the DTW runs over
+    the kept frames; with return_path the path comes back in original frame numbers.  align='frame': one common list, the
+    frames where both masks are set, for both sides.  A side without an active frame keeps all its frames."""
     import torch
     Ba, Fa, n_mels = _check_mel(mel_a, 'mcd_batch: mel_a')
     Bb, Fb, n_mels_b = _check_mel(mel_b, 'mcd_batch: mel_b')
@@ -247,10 +261,19 @@ def mcd_batch(mel_a, mel_b, len_a, len_b, cfg_d=None, scale=None, n_coef=24, ali
         _check_pairs(Ba, Fa, Fb, n_coef, return_path)
     elif Ba > 65535:
         raise ValueError(' - ERROR, mcd_batch: at most 65535 pairs')
+    masked = mask_a is not None or mask_b is not None
+    if masked:
+        _check_mask(mask_a, Ba, Fa, 'mcd_batch: mask_a')
+        _check_mask(mask_b, Ba, Fb, 'mcd_batch: mask_b')
     _need_gpu('mcd_batch')
     d_la, d_lb = _upload_lens(h_la, h_lb)
     ca = _cepstra_launch(_to_device(mel_a), n_coef, first_coef)
     cb = _cepstra_launch(_to_device(mel_b), n_coef, first_coef)
+    if masked:
+        ma, mb = _mask_to_device(mask_a, Ba, Fa), _mask_to_device(mask_b, Ba, Fb)
+        if align == 'frame':
+            return _masked_frame(ca, cb, d_la, d_lb, ma, mb, scale)[0]
+        return _masked_dtw(ca, cb, _compact_launch(ma, d_la), _compact_launch(mb, d_lb), scale, band, bool(return_path))
     if align == 'frame':
         return _frame_launch(ca, cb, d_la, d_lb, scale)
     return _dtw_launch(ca, cb, d_la, d_lb, scale, band, bool(return_path))
@@ -290,7 +313,7 @@ def _wav_at_rate(wav, side, d_in, cfg_d, res_type):
     return wav
 
 
-def _mel_launch(wav, d_len, cfg_d):
+def _mel_launch(wav, d_len, cfg_d, amp_norm=None):
     import audio_lib
     return audio_lib.calc_MFCC_input_batch(
         wav, d_len, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=cfg_d['hop_length'],
@@ -298,7 +321,7 @@ def _mel_launch(wav, d_len, cfg_d):
         window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
         mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
         M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
-        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'], clip_output=cfg_d['clip_output'])[1]
+        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'] if amp_norm is None else amp_norm, clip_output=cfg_d['clip_output'])[1]
 
 
 def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
@@ -306,13 +329,20 @@ def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
 
 
 def mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best', scale=None,
-                  n_coef=24, align='dtw', band=None, return_path=False, first_coef=1):
+                  n_coef=24, align='dtw', band=None, return_path=False, first_coef=1, mask=None, top_db=40.0, max_gap=20,
+                  min_run=0, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15):
     """"Score my conversion against the target's recording" in one call: both sides go through the resampler (when
     their rate wav_sr_a / wav_sr_b differs from cfg_d['sample_rate']) and the front-end, then through mcd_batch.
 
     wav_a [B, La_max], wav_b [B, Lb_max] float32 (cuda tensor or numpy array); lens_a, lens_b host integers counting
     samples at the side's own rate (None = the whole row); cfg_d: the data-set configuration of test.py.
-    Returns mcd_batch's namedtuple; frame counts are 1 + len // hop_length of the (resampled) lengths."""
+    Returns mcd_batch's namedtuple; frame counts are 1 + len // hop_length of the (resampled) lengths.
+    mask: None, or 'energy', 'voiced', 'energy+voiced' (activity_batch's modes, with top_db, max_gap, min_run): the masks
+    are computed from each side's waveform at cfg_d['sample_rate'], after the resampler, the energy over
+    cfg_d['win_length'] samples, the voiced modes with the tracker's frame_length, fmin, fmax, threshold; then as
+    mcd_batch(mask_a, mask_b).  With a mask the front-end's amplitude normalisation (mean_abs_amp_norm) is taken over the
+    samples of the active frames, not over the whole waveform: the front-end floors the mel power, so a gain that depends
+    on the share of silence would change the cepstra of the same speech."""
     import audio_lib
     if cfg_d is None:
         raise ValueError(' - ERROR, mcd_wav_batch: cfg_d (the data-set configuration) is required')
@@ -325,8 +355,23 @@ def mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=N
     scale, band = _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, int(cfg_d['n_mels']))
     if align == 'dtw':
         _check_pairs(a['B'], a['Fmax'], b['Fmax'], n_coef, return_path)
+    if mask is not None:
+        act = _activity_args(mask, top_db, max_gap, min_run, 'mcd_wav_batch')
+        _check_energy(cfg_d['hop_length'], cfg_d['win_length'], max(a['Fmax'], b['Fmax']), 'mcd_wav_batch')
+        args = _f0_args(cfg_d['sample_rate'], cfg_d['hop_length'], frame_length, fmin, fmax, threshold, 'mcd_wav_batch') if act[0] & 2 else None
     _need_gpu('mcd_wav_batch')
     d_in_a, d_len_a, d_fa, d_in_b, d_len_b, d_fb = _upload_lens(a['h_in'], a['h'], a['n_frames'], b['h_in'], b['h'], b['n_frames'])
+    if mask is not None:
+        x_a = _wav_at_rate(wav_a, a, d_in_a, cfg_d, res_type).contiguous()
+        x_b = _wav_at_rate(wav_b, b, d_in_b, cfg_d, res_type).contiguous()
+        ma = _wav_mask(x_a, d_len_a, d_fa, cfg_d, act, _f0_launch(x_a, d_len_a, args)[0] if args else None)
+        mb = _wav_mask(x_b, d_len_b, d_fb, cfg_d, act, _f0_launch(x_b, d_len_b, args)[0] if args else None)
+        ia, ib = _compact_launch(ma, d_fa), _compact_launch(mb, d_fb)
+        ca = _cepstra_launch(_speech_mel(x_a, d_len_a, ma, ia.n_active, cfg_d), n_coef, first_coef)
+        cb = _cepstra_launch(_speech_mel(x_b, d_len_b, mb, ib.n_active, cfg_d), n_coef, first_coef)
+        if align == 'frame':
+            return _masked_frame(ca, cb, d_fa, d_fb, ma, mb, scale)[0]
+        return _masked_dtw(ca, cb, ia, ib, scale, band, bool(return_path))
     mel_a = _wav_mel(wav_a, a, d_in_a, d_len_a, cfg_d, res_type)
     mel_b = _wav_mel(wav_b, b, d_in_b, d_len_b, cfg_d, res_type)
     ca = _cepstra_launch(mel_a, n_coef, first_coef)
@@ -447,14 +492,21 @@ def f0_metrics_batch(f0_a, f0_b, len_a, len_b, path=None, path_len=None):
 
 
 def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best', scale=None,
-                    n_coef=24, align='dtw', band=None, first_coef=1, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15):
+                    n_coef=24, align='dtw', band=None, first_coef=1, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15,
+                    mask=None, top_db=40.0, max_gap=20, min_run=0):
     """The three figures of a pair of utterances in one call -- MCD, F0 error, voiced / unvoiced error -- along ONE path.
 
     Arguments as mcd_wav_batch (the path is always made with align='dtw'), plus the tracker's frame_length, fmin, fmax,
     threshold.  F0 is taken from each side's waveform at cfg_d['sample_rate'] (after the resampler) with hop_length =
     cfg_d['hop_length'], so its frames are the mel frames the path indexes.  Returns a namedtuple of device tensors:
     mcd, total, path_len, path exactly as mcd_wav_batch(..., return_path=True) gives them (total, path_len, path are None
-    with align='frame'), the seven fields of f0_metrics_batch, and f0_a [B, Fa_max], f0_b [B, Fb_max]."""
+    with align='frame'), the seven fields of f0_metrics_batch, f0_a [B, Fa_max], f0_b [B, Fb_max], and n_active_a,
+    n_active_b, mask_a, mask_b (None without a mask).
+
+    mask, top_db, max_gap, min_run as in mcd_wav_batch; the voiced modes reuse the tracks computed anyway.  With a mask
+    mcd, total and path_len come from the DTW over the kept frames, path is in original frame numbers and the F0 figures
+    are taken along it on the original tracks (align='frame': over the frames set in both masks).  n_active == 0 marks
+    a side that kept all its frames because none was active."""
     import audio_lib
     if cfg_d is None:
         raise ValueError(' - ERROR, score_wav_batch: cfg_d (the data-set configuration) is required')
@@ -470,13 +522,240 @@ def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b
     elif a['B'] > 65535:
         raise ValueError(' - ERROR, score_wav_batch: at most 65535 pairs')
     args = _f0_args(cfg_d['sample_rate'], cfg_d['hop_length'], frame_length, fmin, fmax, threshold, 'score_wav_batch')
+    if mask is not None:
+        act = _activity_args(mask, top_db, max_gap, min_run, 'score_wav_batch')
+        _check_energy(cfg_d['hop_length'], cfg_d['win_length'], max(a['Fmax'], b['Fmax']), 'score_wav_batch')
     _need_gpu('score_wav_batch')
     d_in_a, d_len_a, d_fa, d_in_b, d_len_b, d_fb = _upload_lens(a['h_in'], a['h'], a['n_frames'], b['h_in'], b['h'], b['n_frames'])
     x_a = _wav_at_rate(wav_a, a, d_in_a, cfg_d, res_type)
     x_b = _wav_at_rate(wav_b, b, d_in_b, cfg_d, res_type)
+    if mask is not None:
+        x_a, x_b = x_a.contiguous(), x_b.contiguous()
+        f0_a, f0_b = _f0_launch(x_a, d_len_a, args)[0], _f0_launch(x_b, d_len_b, args)[0]
+        ma = _wav_mask(x_a, d_len_a, d_fa, cfg_d, act, f0_a)
+        mb = _wav_mask(x_b, d_len_b, d_fb, cfg_d, act, f0_b)
+        ia, ib = _compact_launch(ma, d_fa), _compact_launch(mb, d_fb)
+        ca = _cepstra_launch(_speech_mel(x_a, d_len_a, ma, ia.n_active, cfg_d), n_coef, first_coef)
+        cb = _cepstra_launch(_speech_mel(x_b, d_len_b, mb, ib.n_active, cfg_d), n_coef, first_coef)
+        if align == 'frame':
+            r, ic = _masked_frame(ca, cb, d_fa, d_fb, ma, mb, scale)
+            cells = _path_map_launch(None, ic.n_kept, ic.index, ic.index, ic.index.shape[1])
+            m = _f0_metrics_launch(f0_a, f0_b, d_fa, d_fb, cells, ic.n_kept)
+            return _SCORE(r.mcd, None, None, None, *m, f0_a, f0_b, ic.n_active, ic.n_active, ma, mb)
+        r = _masked_dtw(ca, cb, ia, ib, scale, band, True)
+        m = _f0_metrics_launch(f0_a, f0_b, d_fa, d_fb, r.path, r.path_len)
+        return _SCORE(r.mcd, r.total, r.path_len, r.path, *m, f0_a, f0_b, ia.n_active, ib.n_active, ma, mb)
     ca = _cepstra_launch(_mel_launch(x_a, d_len_a, cfg_d), n_coef, first_coef)
     cb = _cepstra_launch(_mel_launch(x_b, d_len_b, cfg_d), n_coef, first_coef)
     f0_a, f0_b = _f0_launch(x_a.contiguous(), d_len_a, args)[0], _f0_launch(x_b.contiguous(), d_len_b, args)[0]
     r = _frame_launch(ca, cb, d_fa, d_fb, scale) if align == 'frame' else _dtw_launch(ca, cb, d_fa, d_fb, scale, band, True)
     m = _f0_metrics_launch(f0_a, f0_b, d_fa, d_fb, r.path, r.path_len if r.path is not None else None)
-    return _SCORE(r.mcd, r.total, r.path_len, r.path, *m, f0_a, f0_b)
+    return _SCORE(r.mcd, r.total, r.path_len, r.path, *m, f0_a, f0_b, None, None, None, None)
+
+
+# ------------------------------------------------------------------------------------- speech activity (csrc/vc_activity.hip)
+def _activity_args(mode, top_db, max_gap, min_run, what):
+    """Host checks of the mask's parameters; returns (mode bits, ratio as a float32 value, max_gap, min_run)."""
+    if mode not in _MODES:
+        raise ValueError(" - ERROR, {}: mode must be 'energy', 'voiced' or 'energy+voiced', got {!r}".format(what, mode))
+    for v, name in ((max_gap, 'max_gap'), (min_run, 'min_run')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v >= 2 ** 31:
+            raise ValueError(' - ERROR, {}: {} must be a non-negative integer number of frames, got {!r}'.format(what, name, v))
+    try:
+        db = float(top_db)
+    except (TypeError, ValueError):
+        db = float('nan')
+    ratio = np.float32(10.0 ** (-db / 10.0)) if np.isfinite(db) and db > 0.0 else np.float32(0.0)
+    if not (0.0 < float(ratio) < 1.0):
+        raise ValueError(' - ERROR, {}: top_db must be finite and positive, with 10^(-top_db / 10) a float32 inside (0, 1); got {!r}'
+                         .format(what, top_db))
+    return _MODES[mode], float(ratio), int(max_gap), int(min_run)
+
+
+def _check_energy(hop_length, frame_length, Fmax, what):
+    for v, name, top in ((hop_length, 'hop_length', F0_MAX_HOP), (frame_length, 'frame_length', ACT_MAX_W)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or v > top:
+            raise ValueError(' - ERROR, {}: {} must be an integer in [1, {}], got {!r}'.format(what, name, top, v))
+    if Fmax > MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: a mask holds at most {} frames per utterance (got {})'.format(what, MAX_FRAMES, Fmax))
+
+
+def _check_mask(mask, B, F, what):
+    import torch
+    if F > MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: a mask holds at most {} frames per utterance (got {})'.format(what, MAX_FRAMES, F))
+    if mask is None:
+        return
+    ok = (torch.uint8, torch.bool) if torch.is_tensor(mask) else (np.dtype(np.uint8), np.dtype(np.bool_))
+    if getattr(mask, 'ndim', 0) != 2 or getattr(mask, 'dtype', None) not in ok:
+        raise ValueError(' - ERROR, {} must be a uint8 or bool array [B, F], got {} {}'.format(what, getattr(mask, 'dtype', type(mask)),
+                                                                                              tuple(getattr(mask, 'shape', ()))))
+    if tuple(int(v) for v in mask.shape) != (B, F):
+        raise ValueError(' - ERROR, {} must be [{}, {}] like its spectrogram, got {}'.format(what, B, F, tuple(mask.shape)))
+
+
+def _mask_to_device(mask, B, F):
+    import torch
+    if mask is None:
+        return torch.ones((B, F), dtype=torch.uint8, device='cuda')
+    if not torch.is_tensor(mask):
+        mask = torch.from_numpy(np.ascontiguousarray(mask).astype(np.uint8))
+    return mask.to(device='cuda', dtype=torch.uint8).contiguous()
+
+
+def _energy_launch(wav, d_len, hop, W):
+    """wav: cuda, contiguous float32 [B, Lmax]; d_len: device int32 [B] or None.  No host check in here."""
+    import torch
+    B, Lmax = wav.shape
+    Fmax = 1 + Lmax // hop
+    e = torch.empty((B, Fmax), dtype=torch.float32, device=wav.device)
+    _vc.check(_vc.lib().vc_frame_energy_f32(_vc.ptr(wav), _vc.ptr(d_len), B, Lmax, Lmax, hop, W, _vc.ptr(e), Fmax, _vc.current_stream()))
+    return e
+
+
+def _mask_launch(energy, f0, d_frames, act):
+    import torch
+    mode, ratio, max_gap, min_run = act
+    B, Fmax = energy.shape
+    mask = torch.empty((B, Fmax), dtype=torch.uint8, device=energy.device)
+    _vc.check(_vc.lib().vc_activity_mask(_vc.ptr(energy), _vc.ptr(f0) if mode & 2 else None, _vc.ptr(d_frames), B, Fmax, mode, ratio,
+                                         max_gap, min_run, _vc.ptr(mask), _vc.current_stream()))
+    return mask
+
+
+def _compact_launch(mask_a, d_fa, mask_b=None, d_fb=None):
+    import torch
+    B, Fa = mask_a.shape
+    dev = mask_a.device
+    index = torch.empty((B, Fa), dtype=torch.int32, device=dev)
+    counts = torch.empty((3, B), dtype=torch.int32, device=dev)
+    intervals = torch.empty((B, (Fa + 1) // 2, 2), dtype=torch.int32, device=dev)
+    _vc.check(_vc.lib().vc_mask_compact(_vc.ptr(mask_a), _vc.ptr(d_fa), Fa, _vc.ptr(mask_b), _vc.ptr(d_fb),
+                                        0 if mask_b is None else mask_b.shape[1], B, _vc.ptr(index), _vc.ptr(counts[0]), _vc.ptr(counts[1]),
+                                        _vc.ptr(intervals), _vc.ptr(counts[2]), _vc.current_stream()))
+    return _COMPACT(index, counts[0], counts[1], intervals, counts[2])
+
+
+def _rows_launch(x, index, n_kept):
+    import torch
+    B, F, C = x.shape
+    out = torch.empty((B, F, C), dtype=torch.float32, device=x.device)
+    _vc.check(_vc.lib().vc_compact_rows_f32(_vc.ptr(x), F, _vc.ptr(index), index.shape[1], _vc.ptr(n_kept), B, C, _vc.ptr(out), F,
+                                            _vc.current_stream()))
+    return out
+
+
+def _path_map_launch(path, path_len, index_a, index_b, max_path):
+    """path None: the cells (p, p), p < path_len."""
+    import torch
+    B = index_a.shape[0]
+    out = torch.empty((B, max_path, 2), dtype=torch.int32, device=index_a.device)
+    _vc.check(_vc.lib().vc_path_map(_vc.ptr(path), _vc.ptr(path_len), B, max_path, _vc.ptr(index_a), index_a.shape[1], _vc.ptr(index_b),
+                                    index_b.shape[1], _vc.ptr(out), _vc.current_stream()))
+    return out
+
+
+def _wav_mask(x, d_len, d_frames, cfg_d, act, f0):
+    """The mask of one side of the cfg_d-level calls: x at cfg_d['sample_rate'], the energy over win_length samples."""
+    return _mask_launch(_energy_launch(x, d_len, int(cfg_d['hop_length']), int(cfg_d['win_length'])), f0, d_frames, act)
+
+
+def _speech_mel(x, d_len, mask, n_active, cfg_d):
+    """The front-end's mel of x with the amplitude normalisation taken over the samples of the active frames
+    (vc_speech_gain_f32, include/vc_hip.h): the same speech gives the same mel whatever silence surrounds it.  With
+    cfg_d['mean_abs_amp_norm'] == 1 the front-end does not normalise and nothing is to be done."""
+    import torch
+    target = float(cfg_d['mean_abs_amp_norm'])
+    if target == 1.0:
+        return _mel_launch(x, d_len, cfg_d)
+    lib, st = _vc.lib(), _vc.current_stream()
+    B, Lmax = x.shape
+    gain = torch.empty((B,), dtype=torch.float32, device=x.device)
+    _vc.check(lib.vc_speech_gain_f32(_vc.ptr(x), _vc.ptr(d_len), B, Lmax, Lmax, int(cfg_d['hop_length']), _vc.ptr(mask), _vc.ptr(n_active),
+                                     mask.shape[1], target, _vc.ptr(gain), st))
+    y = torch.empty_like(x)
+    _vc.check(lib.vc_scale_rows_f32(_vc.ptr(x), _vc.ptr(d_len), B, Lmax, Lmax, _vc.ptr(gain), _vc.ptr(y), st))
+    return _mel_launch(y, d_len, cfg_d, amp_norm=1.0)
+
+
+def _masked_dtw(ca, cb, ia, ib, scale, band, return_path):
+    """Each side compacted by its own list (ia, ib: _compact_launch), the DTW over the kept frames, the path mapped back to
+    original frame numbers."""
+    r = _dtw_launch(_rows_launch(ca, ia.index, ia.n_kept), _rows_launch(cb, ib.index, ib.n_kept), ia.n_kept, ib.n_kept, scale, band,
+                    return_path)
+    if return_path:
+        r = r._replace(path=_path_map_launch(r.path, r.path_len, ia.index, ib.index, r.path.shape[1]))
+    return r
+
+
+def _masked_frame(ca, cb, d_fa, d_fb, ma, mb, scale):
+    """One common list, the frames set in both masks, for both sides."""
+    ic = _compact_launch(ma, d_fa, mb, d_fb)
+    return _frame_launch(_rows_launch(ca, ic.index, ic.n_kept), _rows_launch(cb, ic.index, ic.n_kept), ic.n_kept, ic.n_kept, scale), ic
+
+
+def activity_batch(wav, lens=None, hop_length=80, frame_length=400, mode='energy', top_db=40.0, max_gap=20, min_run=0, f0=None,
+                   sr=16000, fmin=60.0, fmax=400.0, threshold=0.15, yin_frame_length=512):
+    """Where the speech is, per frame (the definitions are in include/vc_hip.h, "Speech activity").
+
+    wav [B, Lmax] float32 (cuda tensor or numpy array); lens: host integers in [1, Lmax] (None = the whole row).
+    Frames are the front-end's and the tracker's: 1 + len // hop_length, Fmax = 1 + Lmax // hop_length <= 16384.
+    mode 'energy': the frame's energy over frame_length samples is positive and above 10^(-top_db / 10) of the
+    utterance's largest; 'voiced': the tracker's f0 > 0 (``f0`` [B, Fmax] as f0_batch returns it, or None: the tracker is
+    run here with sr, fmin, fmax, threshold, yin_frame_length); 'energy+voiced': both.  Then gaps of at most max_gap frames
+    between active frames are filled and active runs shorter than min_run dropped.
+    Returns a namedtuple of device tensors: mask [B, Fmax] uint8; index [B, Fmax] int32, the active frames ascending, -1
+    beyond n_kept; n_active [B]; n_kept [B] = n_active, or the frame count where n_active is 0 (index = 0 .. F-1);
+    intervals [B, (Fmax + 1) // 2, 2] int32, the runs as [start, end), -1 beyond n_intervals [B]; energy [B, Fmax] float32;
+    and n_frames, a host list."""
+    import torch
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, activity_batch: wav must be [B, Lmax]')
+    if torch.is_tensor(wav) and wav.dtype != torch.float32:
+        raise ValueError(' - ERROR, activity_batch: wav must be float32, got {}'.format(wav.dtype))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    act = _activity_args(mode, top_db, max_gap, min_run, 'activity_batch')
+    if isinstance(hop_length, bool) or not isinstance(hop_length, (int, np.integer)) or hop_length < 1:
+        raise ValueError(' - ERROR, activity_batch: hop_length must be a positive integer, got {!r}'.format(hop_length))
+    Fmax = 1 + Lmax // int(hop_length)
+    _check_energy(hop_length, frame_length, Fmax, 'activity_batch')
+    hop, W = int(hop_length), int(frame_length)
+    h = np.full((B,), Lmax, dtype=np.int64) if lens is None else _check_lens(lens, B, Lmax, 'activity_batch: lens')
+    if B > 65535 or Lmax > F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, activity_batch: at most 65535 utterances of at most {} samples (got {} of {})'.format(F0_MAX_SAMPLES, B, Lmax))
+    args = None
+    if act[0] & 2:
+        if f0 is None:
+            args = _f0_args(sr, hop, yin_frame_length, fmin, fmax, threshold, 'activity_batch')
+        elif getattr(f0, 'ndim', 0) != 2 or tuple(int(v) for v in f0.shape) != (B, Fmax) or \
+                (f0.dtype != torch.float32 if torch.is_tensor(f0) else np.asarray(f0).dtype != np.float32):
+            raise ValueError(' - ERROR, activity_batch: f0 must be float32 [{}, {}], as f0_batch returns it'.format(B, Fmax))
+    _need_gpu('activity_batch')
+    n_frames = 1 + h // hop
+    d_len, d_frames = _upload_lens(h, n_frames)
+    x = _to_device(wav, torch.float32)
+    energy = _energy_launch(x, d_len, hop, W)
+    if act[0] & 2:
+        f0 = _f0_launch(x, d_len, args)[0] if f0 is None else _to_device(f0, torch.float32)
+    mask = _mask_launch(energy, f0, d_frames, act)
+    c = _compact_launch(mask, d_frames)
+    return _ACTIVITY(mask, c.index, c.n_active, c.n_kept, c.intervals, c.n_intervals, energy, [int(n) for n in n_frames])
+
+
+def compact_batch(x, index, n_kept):
+    """out[b, k, :] = x[b, index[b, k], :] for k < n_kept[b], zeros beyond (vc_compact_rows_f32): x [B, F, C] float32, index
+    [B, Fi] int32 and n_kept [B] int32 as activity_batch returns them (device tensors).  Returns [B, F, C] on the device."""
+    import torch
+    if getattr(x, 'ndim', 0) != 3 or min(x.shape) < 1:
+        raise ValueError(' - ERROR, compact_batch: x must be [B, F, C]')
+    if torch.is_tensor(x) and x.dtype != torch.float32:
+        raise ValueError(' - ERROR, compact_batch: x must be float32, got {}'.format(x.dtype))
+    B, F, C = (int(v) for v in x.shape)
+    if not (torch.is_tensor(index) and torch.is_tensor(n_kept)) or index.dtype != torch.int32 or n_kept.dtype != torch.int32:
+        raise ValueError(' - ERROR, compact_batch: index and n_kept must be int32 tensors')
+    if index.ndim != 2 or index.shape[0] != B or index.shape[1] < 1 or tuple(n_kept.shape) != (B,):
+        raise ValueError(' - ERROR, compact_batch: index must be [B, Fi] and n_kept [B] (got {} and {})'.format(tuple(index.shape), tuple(n_kept.shape)))
+    if B > 65535 or F > MAX_FRAMES or index.shape[1] > MAX_FRAMES or C > ACT_MAX_COLS:
+        raise ValueError(' - ERROR, compact_batch: at most 65535 utterances of at most {} frames of at most {} columns'.format(MAX_FRAMES, ACT_MAX_COLS))
+    _need_gpu('compact_batch')
+    return _rows_launch(_to_device(x, torch.float32), index.to('cuda').contiguous(), n_kept.to('cuda').contiguous())
