@@ -627,12 +627,13 @@ def test_training_recurrence_window_groups_match_autograd(N, T, H):
     """vc_gru_train_forward / vc_gru_backward (/root/reference/modules.py:168-204 under tf.gradients) at batch sizes that
     select the kernels which advance 2 or 4 windows per workgroup (more than 128 / 256 windows per GPU, ragged last
     group included; 3 windows: the one-window kernels): hidden states, saved gates, r*h, and the gradient w.r.t. the
-    gate pre-activations against float64 autograd of the recurrence restated here from the oracle's cell
+    gate pre-activations against float64 autograd of the recurrence restated in train_kernels_ref.gru_train from the oracle's cell
     (model_oracle.gru_direction: r, u = sigmoid([x, h] Wg + bg); c = tanh([x, r*h] Wc + bc); h' = u h + (1 - u) c), with
     the input projections given.  Tolerance 2e-5 forward, 1e-4 of the gradient's max backward (float32 sums over H
     products per step, chained over T steps)."""
     import ctypes as C
     import _vc
+    import train_kernels_ref
     rng = np.random.RandomState(N + H)
     M = N * T
     xp = torch.from_numpy(rng.standard_normal((M, 6 * H)) * 0.5)
@@ -640,19 +641,7 @@ def test_training_recurrence_window_groups_match_autograd(N, T, H):
     dG = torch.from_numpy(rng.standard_normal((M, 2 * H)))
     # float64 reference with autograd
     xr = xp.clone().requires_grad_(True)
-    outs = []
-    for d in range(2):
-        x3 = xr.view(N, T, 6 * H)[:, :, d * 3 * H:(d + 1) * 3 * H]
-        h = torch.zeros((N, H), dtype=torch.float64)
-        hs = [None] * T
-        for t in (range(T) if d == 0 else range(T - 1, -1, -1)):
-            g = torch.sigmoid(x3[:, t, :2 * H] + h @ wh[d][:, :2 * H])
-            r, u = g[:, :H], g[:, H:]
-            c = torch.tanh(x3[:, t, 2 * H:] + (r * h) @ wh[d][:, 2 * H:])
-            h = u * h + (1 - u) * c
-            hs[t] = h
-        outs.append(torch.stack(hs, 1))
-    G_ref = torch.cat(outs, 2).reshape(M, 2 * H)
+    G_ref, _, _ = train_kernels_ref.gru_train(xr, wh, N, T, H)
     (G_ref * dG).sum().backward()
     # device
     f = lambda t: t.float().cuda().contiguous()
