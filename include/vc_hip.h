@@ -978,6 +978,71 @@ int vc_speech_gain_f32(const float* d_wav, const int32_t* d_lens, int32_t batch,
 int vc_scale_rows_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, const float* d_gain,
                       float* d_out, void* stream);
 
+/* Content.  MCD sees the spectral envelope and the F0 figures the prosody; the third question asked of a conversion is
+ * whether it still says the same thing.  The encoder is a frame-level phoneme recogniser, so the answer is taken from the
+ * posteriorgrams (PPG) [frames, C] of the two sides: their frame-level agreement along a set of cells, and the edit
+ * distance of the phoneme sequences read off them.  Added without a version bump.
+ *
+ * vc_ppg_metrics_f32: d_ppg_a [batch, max_a, C], d_ppg_b [batch, max_b, C] float32, contiguous; d_len_a / d_len_b int32
+ * [batch] on the device, clamped to [1, max].  The cells are taken exactly as vc_f0_metrics_f32 takes them: d_path
+ * [batch, max_path, 2] int32 with d_path_len [batch], as vc_dtw_backtrack writes them, or, with both NULL and max_path = 0,
+ * the cells (i, i), i < min(len_a, len_b); a cell outside [0, len_a) x [0, len_b) is skipped and not counted.
+ * d_class_map: int32 [C] on the device or NULL (the identity), applied to the arg-max before the comparison.  Per cell,
+ * with p = a[i, :], q = b[j, :], m = (p + q) / 2:
+ *     js = 0.5 * sum_c (p log2(p / m) + q log2(q / m))        (the Jensen-Shannon divergence in bits)
+ * where a term whose p (or q) is <= 0 contributes 0; posteriors are taken as given, not renormalised, and are expected to
+ * be finite.  The arithmetic of a cell is float64: the float32 operands widened, float64 division and log2.  The arg-max
+ * takes the lowest index on equality.  Per pair: d_counts [batch, 2] int32 = n_cells, n_agree (cells where
+ * map[argmax p] == map[argmax q]); d_values [batch, 2] float32 = frame_agreement (n_agree / n_cells) and js_mean (the
+ * mean of js over the counted cells, in [0, 1] for distributions); both NaN without a cell.  Sums are float64 added in a
+ * fixed tree -- a lane adds its classes c = l, l + 64, ... ascending, the 64 lanes of a cell are added in a butterfly, a
+ * wave adds its cells k = w, w + 16, ... ascending, the sixteen waves are added in order -- and rounded to float32 once.
+ * Identical inputs give js_mean == 0 exactly (p / m = 1).  One workgroup per pair, one wave per cell.  Limits
+ * (VC_ERR_UNSUPPORTED beyond them): 1 <= C <= 256; batch <= 65,535; max_a, max_b, max_path <= 2^30.
+ *
+ * vc_phn_segments: d_ppg [batch, max_frames, C] float32; d_n_frames int32 [batch] on the device, clamped to
+ * [0, max_frames]; min_run >= 1; d_class_map int32 [C] on the device or NULL, values in [-1, C), -1 = "drop this class".
+ * In this order, not iterated:
+ *   1. l[f] = argmax_c ppg[f, c], the lowest index on equality; with a map l[f] = map[l[f]] (-1 is a label like any other
+ *      at this point);
+ *   2. runs are the maximal stretches of equal l;
+ *   3. runs shorter than min_run frames are removed;
+ *   4. among the survivors, neighbours with the same label merge: the segment starts at the first run's start and ends at
+ *      the last run's end;
+ *   5. segments labelled -1 are then removed; their neighbours do not merge ("a pau a" stays two "a").
+ * d_labels, d_start, d_end [batch, max_frames] int32 (end exclusive), all three -1 from the row's own count on; d_n_seg
+ * [batch].  Every output element is written exactly once.  One workgroup of 1,024 lanes per utterance; the frames go
+ * through in tiles of vc_phn_segments_tile() = 1,024 with the carried state in registers, the positions by block-wide
+ * prefix scans in a fixed order; no workspace.  Limits: C <= 256; max_frames <= 2^30; batch <= 65,535.
+ *
+ * vc_edit_distance_i32: d_seq_a [batch, max_a], d_seq_b [batch, max_b] int32; d_n_a / d_n_b int32 [batch] on the device,
+ * clamped to [0, max].  Unit costs: E(i, 0) = i (all deletions), E(0, j) = j (all insertions),
+ *     E(i, j) = min(E(i-1, j-1) + [a_i != b_j], E(i-1, j) + 1, E(i, j-1) + 1);
+ * on equality the predecessor is taken in the order diagonal, up, left (the DTW's order).  Every cell carries (n_match,
+ * n_sub, n_del, n_ins) from its chosen predecessor: a diagonal step adds a match or a substitution, an up step a deletion
+ * (a symbol of A without a partner), a left step an insertion -- as L rides with D in vc_dtw_f32, so there is no back-track
+ * and no matrix.  d_counts [batch, 5] int32 = dist, n_match, n_sub, n_del, n_ins, with dist = n_sub + n_del + n_ins and
+ * n_match + n_sub + n_del = n_a; d_per [batch] float32 = dist / n_a (A is the reference), NaN when n_a = 0.  Integer
+ * arithmetic throughout: bit-exact against the definition.  One launch, one workgroup (one wave) per pair, the wavefront
+ * over anti-diagonals, vc_edit_distance_rows() = 256 symbols of A per pass; the workspace (vc_edit_distance_workspace_bytes:
+ * host arithmetic, 0 for a shape the launch would refuse) holds 32 bytes per column of B and pair, the row between two
+ * passes.  Limits: max_a, max_b <= 16,384; batch <= 65,535.
+ *
+ * All three are functions of their own pair / utterance alone, bit-identical alone, in any batch, from run to run and
+ * under graph replay; no atomics; capturable from the first call; arguments are checked before any HIP call. */
+int vc_ppg_metrics_f32(const float* d_ppg_a, const float* d_ppg_b, const int32_t* d_len_a, const int32_t* d_len_b, int32_t batch,
+                       int32_t max_a, int32_t max_b, int32_t n_classes, const int32_t* d_path, const int32_t* d_path_len,
+                       int32_t max_path, const int32_t* d_class_map, int32_t* d_counts, float* d_values, void* stream);
+int vc_phn_segments_tile(void);
+int vc_phn_segments(const float* d_ppg, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t n_classes,
+                    int32_t min_run, const int32_t* d_class_map, int32_t* d_labels, int32_t* d_start, int32_t* d_end,
+                    int32_t* d_n_seg, void* stream);
+int vc_edit_distance_rows(void);
+size_t vc_edit_distance_workspace_bytes(int32_t batch, int32_t max_a, int32_t max_b);
+int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const int32_t* d_n_a, const int32_t* d_n_b, int32_t batch,
+                         int32_t max_a, int32_t max_b, int32_t* d_counts, float* d_per, void* d_workspace, size_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,13 @@ _SIGS = {
     'vc_path_map': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P]),
     'vc_speech_gain_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P]),
     'vc_scale_rows_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    # content preservation (csrc/vc_content.hip)
+    'vc_ppg_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    'vc_phn_segments_tile': (C.c_int, []),
+    'vc_phn_segments': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    'vc_edit_distance_rows': (C.c_int, []),
+    'vc_edit_distance_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
+    'vc_edit_distance_i32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -284,7 +291,8 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches): a build older than this binding lacks them
+                # vc_f0_*, then the speech-activity launches, then the content launches): a build older than this binding
+                # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
                               '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None
             fn.restype = res

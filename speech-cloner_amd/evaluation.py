@@ -16,6 +16,12 @@ two.  The same number, frame by frame (``align='frame'``), compares two conversi
   score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)     MCD and the F0 figures along one DTW path in one call
   activity_batch(wav, lens, hop_length, frame_length, mode, ...) -> speech-activity mask, frame list, intervals, frame energy
   compact_batch(x [B, F, C], index, n_kept)                     the rows a frame list names, zeros beyond
+  ppg_metrics_batch(ppg_a, ppg_b, len_a, len_b, path, path_len, class_map)   arg-max agreement and Jensen-Shannon divergence (bits) along the cells
+  phn_segments_batch(ppg [B, F, C], lens, class_map, min_run)   -> the phoneme sequence: labels, start, end [B, F], n_seg [B]
+  edit_distance_batch(seq_a, seq_b, n_a, n_b)                   -> dist, n_match, n_sub, n_del, n_ins, per = dist / n_a
+  content_batch(ppg_a, ppg_b, len_a, len_b, ...)                the three above in one (mask_a, mask_b as in mcd_batch)
+  content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, ...)   resampler, front-end, convert_batch's windows and the encoder on both sides first
+  class_map(names, fold=TIMIT_FOLD_39, drop=...)                the int32 table [C] of the usual 61-to-39 folding (host only)
 
 mcd_batch (mask_a, mask_b), mcd_wav_batch and score_wav_batch (mask='energy' | 'voiced' | 'energy+voiced') leave silent
 frames out of the DTW, the MCD and the F0 figures; without a mask they are what they were.
@@ -26,7 +32,8 @@ Definitions (include/vc_hip.h, "Evaluation"):
 
 Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
 the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip, csrc/vc_f0.hip (the pitch tracker
-and its figures) and csrc/vc_activity.hip (the masks); there is no CPU path.
+and its figures), csrc/vc_activity.hip (the masks) and csrc/vc_content.hip (the content scores,
+DESIGN.md section 17); there is no CPU path.
 """
 from collections import namedtuple
 
@@ -314,6 +321,11 @@ def _wav_at_rate(wav, side, d_in, cfg_d, res_type):
 
 
 def _mel_launch(wav, d_len, cfg_d, amp_norm=None):
+    return _fe_launch(wav, d_len, cfg_d, amp_norm)[1]
+
+
+def _fe_launch(wav, d_len, cfg_d, amp_norm=None):
+    """The front-end's three outputs (mfcc, mel, stft power) of wav at cfg_d['sample_rate']."""
     import audio_lib
     return audio_lib.calc_MFCC_input_batch(
         wav, d_len, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=cfg_d['hop_length'],
@@ -321,7 +333,7 @@ def _mel_launch(wav, d_len, cfg_d, amp_norm=None):
         window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
         mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
         M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
-        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'] if amp_norm is None else amp_norm, clip_output=cfg_d['clip_output'])[1]
+        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'] if amp_norm is None else amp_norm, clip_output=cfg_d['clip_output'])
 
 
 def _wav_mel(wav, side, d_in, d_len, cfg_d, res_type):
@@ -759,3 +771,398 @@ def compact_batch(x, index, n_kept):
         raise ValueError(' - ERROR, compact_batch: at most 65535 utterances of at most {} frames of at most {} columns'.format(MAX_FRAMES, ACT_MAX_COLS))
     _need_gpu('compact_batch')
     return _rows_launch(_to_device(x, torch.float32), index.to('cuda').contiguous(), n_kept.to('cuda').contiguous())
+
+
+# ------------------------------------------------------------------------------------- content (csrc/vc_content.hip)
+# The usual folding of TIMIT's 61 phones to 39 (Lee and Hon 1989): a name on the left is scored as the name on the right.
+# The closures join the pauses in one silence class, whose representative here is 'pau'; 'q' (the glottal stop) is
+# deleted (None).  A name that is not listed stands for itself.
+TIMIT_FOLD_39 = {'ao': 'aa', 'ax': 'ah', 'ax-h': 'ah', 'axr': 'er', 'hv': 'hh', 'ix': 'ih', 'el': 'l', 'em': 'm', 'en': 'n', 'nx': 'n',
+                 'eng': 'ng', 'zh': 'sh', 'ux': 'uw', 'pcl': 'pau', 'tcl': 'pau', 'kcl': 'pau', 'bcl': 'pau', 'dcl': 'pau', 'gcl': 'pau',
+                 'epi': 'pau', 'h#': 'pau', 'q': None}
+
+
+def class_map(names, fold=TIMIT_FOLD_39, drop=('pau', 'epi', 'h#')):
+    """The int32 table [C] the content calls take as ``class_map``, for a phoneme inventory ``names``
+    (sound_ds.TIMIT_PHONEMES_61, sound_ds.ARCTIC_PHONEMES_43): table[c] is the index IN ``names`` of the representative of
+    class c under ``fold`` (None or {}: every class stands for itself), so the table stays [C]; -1 for a class the fold
+    deletes and for every class NAMED in ``drop``.  A class that folds onto a dropped representative keeps that
+    representative's index: with the defaults the six closures of TIMIT score as one silence symbol (the index of 'pau')
+    while the pauses themselves ('pau', 'epi', 'h#') leave the sequence -- 39 distinct labels stay.  Names of ``fold`` and
+    ``drop`` that the inventory lacks are ignored; a representative the inventory lacks leaves the class to itself."""
+    names = list(names)
+    if not names or len(set(names)) != len(names) or not all(isinstance(n, str) for n in names):
+        raise ValueError(' - ERROR, class_map: names must be a non-empty list of distinct strings')
+    if len(names) > CONTENT_MAX_CLASSES:
+        raise ValueError(' - ERROR, class_map: at most {} classes (got {})'.format(CONTENT_MAX_CLASSES, len(names)))
+    pos = {n: i for i, n in enumerate(names)}
+    table = np.arange(len(names), dtype=np.int32)
+    for n, rep in (fold or {}).items():
+        if n in pos:
+            table[pos[n]] = -1 if rep is None else pos.get(rep, pos[n])
+    for n in drop or ():
+        if n in pos:
+            table[pos[n]] = -1
+    return table
+
+
+CONTENT_MAX_CLASSES = 256   # vc_ppg_metrics_f32, vc_phn_segments
+SEGMENT_TILE = 1024         # vc_phn_segments_tile(): frames per tile of the segment kernel
+EDIT_ROWS = 256             # vc_edit_distance_rows(): symbols of A per pass of the edit-distance kernel
+EDIT_MAX = 16384            # vc_edit_distance_i32
+_PPG_FIELDS = 'n_cells n_agree frame_agreement js_mean'
+_EDIT_FIELDS = 'dist n_match n_sub n_del n_ins per'
+_PPG = namedtuple('ppg_metrics', _PPG_FIELDS)
+_SEG = namedtuple('phn_segments', 'labels start end n_seg')
+_EDIT = namedtuple('edit_distance', _EDIT_FIELDS)
+_CONTENT = namedtuple('content', _PPG_FIELDS + ' ' + _EDIT_FIELDS + ' seg_a seg_b')
+_CONTENT_WAV = namedtuple('content_wav', _PPG_FIELDS + ' ' + _EDIT_FIELDS + ' seg_a seg_b ppg_a ppg_b len_a len_b path path_len mask_a mask_b')
+
+
+def _check_ppg(x, what):
+    import torch
+    if getattr(x, 'ndim', 0) != 3 or min(x.shape) < 1:
+        raise ValueError(' - ERROR, {} must be [B, F, C]'.format(what))
+    dt = x.dtype if torch.is_tensor(x) else np.asarray(x).dtype
+    if dt not in (torch.float32, np.dtype(np.float32)):
+        raise ValueError(' - ERROR, {} must be float32, got {}'.format(what, dt))
+    B, F, C = (int(v) for v in x.shape)
+    if C > CONTENT_MAX_CLASSES:
+        raise ValueError(' - ERROR, {}: at most {} classes (got {})'.format(what, CONTENT_MAX_CLASSES, C))
+    if B > 65535 or F > F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, {}: at most 65535 rows of at most {} frames (got {} of {})'.format(what, F0_MAX_SAMPLES, B, F))
+    return B, F, C
+
+
+def _check_class_map(cmap, C, what, allow_drop=True):
+    """None, or C integers in [-1, C) (a device tensor is taken as it is: int32 [C], its values unread)."""
+    import torch
+    if cmap is None:
+        return None
+    if torch.is_tensor(cmap) and cmap.is_cuda:
+        if cmap.dtype != torch.int32 or tuple(cmap.shape) != (C,):
+            raise ValueError(' - ERROR, {}: a class_map on the device must be int32 [{}]'.format(what, C))
+        return cmap
+    h = np.asarray(cmap.cpu() if torch.is_tensor(cmap) else cmap)
+    if h.shape != (C,) or h.dtype.kind not in 'iu' or h.min() < -1 or h.max() >= C:
+        raise ValueError(' - ERROR, {}: class_map must be {} integers in [-1, {}) (evaluation.class_map builds one)'.format(what, C, C))
+    return h.astype(np.int32)
+
+
+def _check_min_run(min_run, what):
+    if isinstance(min_run, bool) or not isinstance(min_run, (int, np.integer)) or min_run < 1 or min_run >= 2 ** 31:
+        raise ValueError(' - ERROR, {}: min_run must be a positive integer number of frames, got {!r}'.format(what, min_run))
+    return int(min_run)
+
+
+def _check_counts(n, B, lo, hi, what):
+    """Host integers in [lo, hi], or an int32 [B] tensor on the device (the launch clamps it).  Returns (host array | None,
+    device tensor | None)."""
+    import torch
+    if torch.is_tensor(n) and n.is_cuda:
+        if n.dtype != torch.int32 or tuple(n.shape) != (B,):
+            raise ValueError(' - ERROR, {} on the device must be int32 [{}]'.format(what, B))
+        return None, n.contiguous()
+    h = np.asarray(n.cpu() if torch.is_tensor(n) else n)
+    if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < lo or h.max() > hi:
+        raise ValueError(' - ERROR, {} must be {} integers in [{}, {}]'.format(what, B, lo, hi))
+    return h.astype(np.int64), None
+
+
+def _check_path(path, path_len, B, what):
+    import torch
+    if (path is None) != (path_len is None):
+        raise ValueError(' - ERROR, {}: pass path and path_len together (both from mcd_batch(return_path=True)) or neither'.format(what))
+    if path is None:
+        return
+    if not (torch.is_tensor(path) and torch.is_tensor(path_len)) or path.dtype != torch.int32 or path_len.dtype != torch.int32:
+        raise ValueError(' - ERROR, {}: path and path_len must be int32 tensors'.format(what))
+    if path.ndim != 3 or path.shape[0] != B or path.shape[1] < 1 or path.shape[2] != 2 or tuple(path_len.shape) != (B,):
+        raise ValueError(' - ERROR, {}: path must be [B, P, 2] and path_len [B] (got {} and {})'.format(what, tuple(path.shape), tuple(path_len.shape)))
+    if path.shape[1] > F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, {}: at most {} cells'.format(what, F0_MAX_SAMPLES))
+
+
+def _upload_mixed(*items):
+    """items: (host array | None, device tensor | None) pairs; the host ones go up in one pinned copy."""
+    hosts = [h for h, d in items if d is None]
+    ups = iter(_upload_lens(*hosts)) if hosts else iter(())
+    return [next(ups) if d is None else d for h, d in items]
+
+
+def _cmap_device(cmap):
+    import torch
+    if cmap is None or torch.is_tensor(cmap):
+        return cmap
+    return torch.from_numpy(cmap).pin_memory().to('cuda', non_blocking=True)
+
+
+def _ppg_metrics_launch(a, b, d_la, d_lb, path, path_len, cmap):
+    """a, b: cuda, contiguous float32 [B, F, C]; lengths, path, map on the device.  No host check in here."""
+    import torch
+    B, Fa, C = a.shape
+    counts = torch.empty((B, 2), dtype=torch.int32, device=a.device)
+    values = torch.empty((B, 2), dtype=torch.float32, device=a.device)
+    _vc.check(_vc.lib().vc_ppg_metrics_f32(_vc.ptr(a), _vc.ptr(b), _vc.ptr(d_la), _vc.ptr(d_lb), B, Fa, b.shape[1], C, _vc.ptr(path),
+                                           _vc.ptr(path_len), 0 if path is None else path.shape[1], _vc.ptr(cmap), _vc.ptr(counts),
+                                           _vc.ptr(values), _vc.current_stream()))
+    return _PPG(counts[:, 0], counts[:, 1], values[:, 0], values[:, 1])
+
+
+def _segments_launch(ppg, d_len, cmap, min_run):
+    import torch
+    B, F, C = ppg.shape
+    out = torch.empty((3, B, F), dtype=torch.int32, device=ppg.device)
+    n_seg = torch.empty((B,), dtype=torch.int32, device=ppg.device)
+    _vc.check(_vc.lib().vc_phn_segments(_vc.ptr(ppg), _vc.ptr(d_len), B, F, C, min_run, _vc.ptr(cmap), _vc.ptr(out[0]), _vc.ptr(out[1]),
+                                        _vc.ptr(out[2]), _vc.ptr(n_seg), _vc.current_stream()))
+    return _SEG(out[0], out[1], out[2], n_seg)
+
+
+def _edit_launch(seq_a, seq_b, d_na, d_nb):
+    import torch
+    lib = _vc.lib()
+    B, Ma = seq_a.shape
+    Mb = seq_b.shape[1]
+    counts = torch.empty((B, 5), dtype=torch.int32, device=seq_a.device)
+    per = torch.empty((B,), dtype=torch.float32, device=seq_a.device)
+    need = lib.vc_edit_distance_workspace_bytes(B, Ma, Mb)
+    if need == 0:
+        raise _vc.VCError('vc_edit_distance_workspace_bytes refused {} pairs of {} x {} symbols'.format(B, Ma, Mb))
+    ws = torch.empty((need,), dtype=torch.uint8, device=seq_a.device)
+    _vc.check(lib.vc_edit_distance_i32(_vc.ptr(seq_a), _vc.ptr(seq_b), _vc.ptr(d_na), _vc.ptr(d_nb), B, Ma, Mb, _vc.ptr(counts),
+                                       _vc.ptr(per), _vc.ptr(ws), need, _vc.current_stream()))
+    return _EDIT(counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3], counts[:, 4], per)
+
+
+def ppg_metrics_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_map=None):
+    """Frame-level agreement of B pairs of phoneme posteriorgrams (vc_ppg_metrics_f32): ppg_a [B, Fa_max, C], ppg_b
+    [B, Fb_max, C] float32 (cuda tensor or numpy array), C <= 256; len_a, len_b host integers in [1, F_max].
+    path, path_len: as in f0_metrics_batch (what mcd_batch(..., return_path=True) returns); None: the cells (i, i).
+    class_map: None or C integers (evaluation.class_map), applied to the arg-max before the comparison.
+    Returns a namedtuple of [B] device tensors: n_cells, n_agree (int32), frame_agreement = n_agree / n_cells and js_mean,
+    the mean Jensen-Shannon divergence of the two posteriors over the cells in bits (0 = identical, 1 = disjoint); both NaN
+    without a cell."""
+    import torch
+    B, Fa, C = _check_ppg(ppg_a, 'ppg_metrics_batch: ppg_a')
+    Bb, Fb, Cb = _check_ppg(ppg_b, 'ppg_metrics_batch: ppg_b')
+    if B != Bb or C != Cb:
+        raise ValueError(' - ERROR, ppg_metrics_batch: ppg_a {} and ppg_b {} must agree in B and C'.format(tuple(ppg_a.shape), tuple(ppg_b.shape)))
+    h_la, h_lb = _check_lens(len_a, B, Fa, 'ppg_metrics_batch: len_a'), _check_lens(len_b, B, Fb, 'ppg_metrics_batch: len_b')
+    _check_path(path, path_len, B, 'ppg_metrics_batch')
+    cmap = _check_class_map(class_map, C, 'ppg_metrics_batch')
+    _need_gpu('ppg_metrics_batch')
+    d_la, d_lb = _upload_lens(h_la, h_lb)
+    if path is not None:
+        path, path_len = path.to('cuda').contiguous(), path_len.to('cuda').contiguous()
+    return _ppg_metrics_launch(_to_device(ppg_a, torch.float32), _to_device(ppg_b, torch.float32), d_la, d_lb, path, path_len,
+                               _cmap_device(cmap))
+
+
+def phn_segments_batch(ppg, lens, class_map=None, min_run=3):
+    """The phoneme sequence of B posteriorgrams (vc_phn_segments; the five steps are in include/vc_hip.h, "Content"): the
+    arg-max label of every frame through ``class_map``, runs shorter than ``min_run`` frames removed, equal neighbours
+    merged, segments labelled -1 removed.  ppg [B, F_max, C] float32; lens: host integers in [0, F_max] or an int32 [B]
+    device tensor.  Returns a namedtuple of int32 device tensors: labels, start, end [B, F_max] (end exclusive, -1 from the
+    row's count on) and n_seg [B]."""
+    import torch
+    B, F, C = _check_ppg(ppg, 'phn_segments_batch: ppg')
+    n = _check_counts(lens, B, 0, F, 'phn_segments_batch: lens')
+    cmap = _check_class_map(class_map, C, 'phn_segments_batch')
+    min_run = _check_min_run(min_run, 'phn_segments_batch')
+    _need_gpu('phn_segments_batch')
+    d_len, = _upload_mixed(n)
+    return _segments_launch(_to_device(ppg, torch.float32), d_len, _cmap_device(cmap), min_run)
+
+
+def _check_seq(s, what):
+    import torch
+    if getattr(s, 'ndim', 0) != 2 or min(s.shape) < 1:
+        raise ValueError(' - ERROR, edit_distance_batch: {} must be [B, M]'.format(what))
+    dt = s.dtype if torch.is_tensor(s) else np.asarray(s).dtype
+    if dt not in (torch.int32, np.dtype(np.int32)):
+        raise ValueError(' - ERROR, edit_distance_batch: {} must be int32, got {}'.format(what, dt))
+    return int(s.shape[0]), int(s.shape[1])
+
+
+def edit_distance_batch(seq_a, seq_b, n_a, n_b):
+    """Levenshtein distance of B pairs of int32 sequences with the counts behind it (vc_edit_distance_i32): seq_a [B, Ma],
+    seq_b [B, Mb] (cuda tensor or numpy array, at most 16,384 columns); n_a, n_b: host integers in [0, M] or int32 [B]
+    device tensors, as phn_segments_batch returns them.  A is the reference: n_del counts symbols of A without a partner,
+    n_ins symbols of B without one.  Returns a namedtuple of [B] device tensors: dist, n_match, n_sub, n_del, n_ins (int32;
+    dist = n_sub + n_del + n_ins, n_match + n_sub + n_del = n_a) and per = dist / n_a (float32, NaN when n_a = 0)."""
+    import torch
+    B, Ma = _check_seq(seq_a, 'seq_a')
+    Bb, Mb = _check_seq(seq_b, 'seq_b')
+    if B != Bb:
+        raise ValueError(' - ERROR, edit_distance_batch: seq_a {} and seq_b {} must agree in B'.format(tuple(seq_a.shape), tuple(seq_b.shape)))
+    if B > 65535 or Ma > EDIT_MAX or Mb > EDIT_MAX:
+        raise ValueError(' - ERROR, edit_distance_batch: at most 65535 pairs of at most {} symbols (got {} pairs of {} x {})'
+                         .format(EDIT_MAX, B, Ma, Mb))
+    na, nb = _check_counts(n_a, B, 0, Ma, 'edit_distance_batch: n_a'), _check_counts(n_b, B, 0, Mb, 'edit_distance_batch: n_b')
+    _need_gpu('edit_distance_batch')
+    d_na, d_nb = _upload_mixed(na, nb)
+    dev = lambda s: (s if torch.is_tensor(s) else torch.from_numpy(np.ascontiguousarray(s))).to('cuda').contiguous()
+    return _edit_launch(dev(seq_a), dev(seq_b), d_na, d_nb)
+
+
+def _content_launch(a, b, d_la, d_lb, path, path_len, cmap, min_run, ma, mb):
+    """content_batch after its checks: everything on the device.  ma, mb: uint8 masks (both or neither)."""
+    if ma is None:
+        m = _ppg_metrics_launch(a, b, d_la, d_lb, path, path_len, cmap)
+        sa, sb = _segments_launch(a, d_la, cmap, min_run), _segments_launch(b, d_lb, cmap, min_run)
+    else:
+        ia, ib = _compact_launch(ma, d_la), _compact_launch(mb, d_lb)
+        sa = _segments_launch(_rows_launch(a, ia.index, ia.n_kept), ia.n_kept, cmap, min_run)
+        sb = _segments_launch(_rows_launch(b, ib.index, ib.n_kept), ib.n_kept, cmap, min_run)
+        if path is None:                                            # the frames set in both masks, in original frame numbers
+            ic = _compact_launch(ma, d_la, mb, d_lb)
+            path, path_len = _path_map_launch(None, ic.n_kept, ic.index, ic.index, ic.index.shape[1]), ic.n_kept
+        m = _ppg_metrics_launch(a, b, d_la, d_lb, path, path_len, cmap)
+    if a.shape[1] > EDIT_MAX or b.shape[1] > EDIT_MAX:
+        raise ValueError(' - ERROR, content_batch: the edit distance holds at most {} symbols a side'.format(EDIT_MAX))
+    e = _edit_launch(sa.labels, sb.labels, sa.n_seg, sb.n_seg)
+    return _CONTENT(*m, *e, sa, sb)
+
+
+def content_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_map=None, min_run=3, mask_a=None, mask_b=None):
+    """Does the conversion still say the same thing?  The three content figures of B pairs of posteriorgrams in one call:
+    ppg_metrics_batch along the cells, phn_segments_batch of both sides, and edit_distance_batch of the two phoneme
+    sequences with A as the reference (per = phoneme error rate).  Arguments as in those calls; F_max <= 16,384.
+
+    mask_a [B, Fa_max], mask_b [B, Fb_max]: uint8 or bool, 1 = the frame counts (activity_batch's mask; one of them None:
+    every frame of that side).  The masked frames leave each posteriorgram (compact_batch) before its sequence is read
+    off, exactly as mcd_batch compacts the cepstra; start and end of the segments then count kept frames.  The frame-level
+    figures run on the original posteriorgrams along ``path``, which is in original frame numbers (what the masked
+    mcd_batch(return_path=True) returns visits kept frames only), or, without a path, over the frames set in both masks.
+    Returns a namedtuple of device tensors: the four fields of ppg_metrics_batch, the six of edit_distance_batch, and
+    seg_a, seg_b, the two results of phn_segments_batch."""
+    import torch
+    B, Fa, C = _check_ppg(ppg_a, 'content_batch: ppg_a')
+    Bb, Fb, Cb = _check_ppg(ppg_b, 'content_batch: ppg_b')
+    if B != Bb or C != Cb:
+        raise ValueError(' - ERROR, content_batch: ppg_a {} and ppg_b {} must agree in B and C'.format(tuple(ppg_a.shape), tuple(ppg_b.shape)))
+    if Fa > EDIT_MAX or Fb > EDIT_MAX:
+        raise ValueError(' - ERROR, content_batch: at most {} frames per utterance (got {} and {})'.format(EDIT_MAX, Fa, Fb))
+    h_la, h_lb = _check_lens(len_a, B, Fa, 'content_batch: len_a'), _check_lens(len_b, B, Fb, 'content_batch: len_b')
+    _check_path(path, path_len, B, 'content_batch')
+    cmap = _check_class_map(class_map, C, 'content_batch')
+    min_run = _check_min_run(min_run, 'content_batch')
+    masked = mask_a is not None or mask_b is not None
+    if masked:
+        _check_mask(mask_a, B, Fa, 'content_batch: mask_a')
+        _check_mask(mask_b, B, Fb, 'content_batch: mask_b')
+    _need_gpu('content_batch')
+    d_la, d_lb = _upload_lens(h_la, h_lb)
+    if path is not None:
+        path, path_len = path.to('cuda').contiguous(), path_len.to('cuda').contiguous()
+    ma, mb = (_mask_to_device(mask_a, B, Fa), _mask_to_device(mask_b, B, Fb)) if masked else (None, None)
+    return _content_launch(_to_device(ppg_a, torch.float32), _to_device(ppg_b, torch.float32), d_la, d_lb, path, path_len,
+                           _cmap_device(cmap), min_run, ma, mb)
+
+
+def _content_side(encoder, wav, side, plan, tabs, cfg_d, res_type, window_batch, ppg):
+    """One side of content_wav_batch on the device: the waveform at cfg_d['sample_rate'], the front-end, the window tables
+    of convert_batch, the encoder in chunks, the stitch.  Returns (x, mel cut to the windows' frames, posteriors)."""
+    import torch
+    import conversion
+    d_in, d_len, d_clip, d_win, d_utt, d_true = tabs
+    x = _wav_at_rate(wav, side, d_in, cfg_d, res_type)
+    mfcc, mel, _ = _fe_launch(x, d_len, cfg_d)
+    mel_cut = conversion.cut_windows(mel, d_true, d_clip, plan.Fout)
+    if ppg is None:
+        win = conversion.cut_windows(mfcc, d_win, d_clip, plan.T)
+        ys = [encoder.forward(win[i:i + window_batch])['y_pred'] for i in range(0, win.shape[0], window_batch)]
+        ppg = conversion.compound_stitch(ys[0] if len(ys) == 1 else torch.cat(ys, 0), d_utt, plan.Fout)
+    return x, mel_cut, ppg
+
+
+def content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best',
+                      align='frame', band=None, scale=None, n_coef=24, first_coef=1, class_map=None, min_run=3, mask=None,
+                      top_db=40.0, max_gap=20, mask_min_run=0, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15,
+                      ppg_a=None, t_s=0, t_e=60, two_pass=True, window_batch=64):
+    """The content figures of B pairs of WAVEFORMS: typically A is the source and B is convert_batch(...).y_wav_pred; with
+    align='dtw' B may be the target speaker's own recording.  encoder: the phoneme recogniser (encoder.encoder_spec_phn;
+    decoder.encoder of a decoder built with one).
+
+    Each side goes through the resampler (wav_sr_a / wav_sr_b), audio_lib.calc_MFCC_input_batch and the window tables of
+    convert_batch (conversion.convert_plan with t_s, t_e, two_pass; cut_windows; encoder.forward in chunks of window_batch
+    windows; compound_stitch), which gives posteriors [B, Fout, n_phn] whose frame f is front-end frame n_s + f, as
+    convert_batch's phn_pred.  ppg_a: such posteriors of side A that are already there (phn_pred), instead of running the
+    encoder on A.  The frames scored are those that come from the waveform: min(n_out, min(n_src, n_e) - n_s) per
+    utterance (the zero padding that fills the last window is left out).  Then content_batch.
+    align='frame': the cells (i, i).  align='dtw': along the path of the mel-cepstral DTW (``band``, ``scale``, ``n_coef``,
+    ``first_coef`` as in mcd_batch) between the two mel spectrograms cut to the same frames.
+    mask: None, or 'energy', 'voiced', 'energy+voiced' with top_db, max_gap, mask_min_run (activity_batch's min_run) and
+    the tracker's frame_length, fmin, fmax, threshold: the masks are taken from each side's waveform as in
+    score_wav_batch (energy over cfg_d['win_length'] samples) and go to content_batch and to the DTW as in
+    mcd_batch(mask_a, mask_b); the mel is the front-end's own (no speech-level gain).
+    Returns a namedtuple of device tensors: content_batch's fields, then ppg_a, ppg_b [B, Fout, n_phn], len_a, len_b (int32
+    [B]), path, path_len (None with align='frame') and mask_a, mask_b (None without a mask)."""
+    import torch
+    import audio_lib
+    import conversion
+    if cfg_d is None:
+        raise ValueError(' - ERROR, content_wav_batch: cfg_d (the data-set configuration) is required')
+    audio_lib._res_params(res_type)
+    a = _wav_side(wav_a, lens_a, cfg_d, wav_sr_a, 'wav_a')
+    b = _wav_side(wav_b, lens_b, cfg_d, wav_sr_b, 'wav_b')
+    B = a['B']
+    if B != b['B']:
+        raise ValueError(' - ERROR, content_wav_batch: wav_a and wav_b must hold the same number of utterances')
+    n_coef, first_coef = int(n_coef), int(first_coef)
+    scale, band = _mcd_args(cfg_d, scale, n_coef, first_coef, align, band, int(cfg_d['n_mels']))
+    window_batch = int(window_batch)
+    if window_batch <= 0:
+        raise ValueError(' - ERROR, content_wav_batch: window_batch must be positive')
+    min_run = _check_min_run(min_run, 'content_wav_batch')
+    pa = conversion.convert_plan(a['h'], cfg_d, t_s, t_e, two_pass)
+    pb = conversion.convert_plan(b['h'], cfg_d, t_s, t_e, two_pass)
+    if B > 65535 or pa.Fout > MAX_FRAMES or pb.Fout > MAX_FRAMES:
+        raise ValueError(' - ERROR, content_wav_batch: at most 65535 pairs of at most {} frames (got {} pairs of {} x {})'
+                         .format(MAX_FRAMES, B, pa.Fout, pb.Fout))
+    if align == 'dtw':
+        _check_pairs(B, pa.Fout, pb.Fout, n_coef, True)
+    C = int(encoder.cfg_d['n_output'])
+    if ppg_a is not None:
+        if _check_ppg(ppg_a, 'content_wav_batch: ppg_a') != (B, pa.Fout, C):
+            raise ValueError(' - ERROR, content_wav_batch: ppg_a must be [{}, {}, {}], as convert_batch returns phn_pred for wav_a'
+                             .format(B, pa.Fout, C))
+    cmap = _check_class_map(class_map, C, 'content_wav_batch')
+    if mask is not None:
+        act = _activity_args(mask, top_db, max_gap, mask_min_run, 'content_wav_batch')
+        _check_energy(cfg_d['hop_length'], cfg_d['win_length'], max(a['Fmax'], b['Fmax']), 'content_wav_batch')
+        args = _f0_args(cfg_d['sample_rate'], cfg_d['hop_length'], frame_length, fmin, fmax, threshold, 'content_wav_batch') if act[0] & 2 else None
+    h_la, h_lb = (np.minimum(p.n_out, p.n_clip - p.n_s) for p in (pa, pb))
+    if min(h_la.min(), h_lb.min()) < 1:
+        raise ValueError(' - ERROR, content_wav_batch: every utterance needs at least one frame of its own after t_s = {} s'.format(t_s))
+    _need_gpu('content_wav_batch')
+    up = _upload_lens(a['h_in'], a['h'], a['n_frames'], pa.n_clip, pa.win_tab, pa.utt_tab, pa.true_tab, h_la,
+                      b['h_in'], b['h'], b['n_frames'], pb.n_clip, pb.win_tab, pb.utt_tab, pb.true_tab, h_lb)
+    sides = []
+    for k, (wav, side, plan, ppg) in enumerate(((wav_a, a, pa, ppg_a), (wav_b, b, pb, None))):
+        d_in, d_len, d_fr, d_clip, d_win, d_utt, d_true, d_l = up[8 * k:8 * k + 8]
+        if ppg is not None:
+            ppg = _to_device(ppg, torch.float32)
+        x, mel, ppg = _content_side(encoder, wav, side, plan, (d_in, d_len, d_clip, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)),
+                                    cfg_d, res_type, window_batch, ppg)
+        m = None
+        if mask is not None:                                        # front-end frame n_s + f is the posteriors' frame f
+            x = x.contiguous()
+            full = _wav_mask(x, d_len, d_fr, cfg_d, act, _f0_launch(x, d_len, args)[0] if args else None)
+            n_s = int(plan.n_s[0])
+            m = torch.zeros((B, plan.Fout), dtype=torch.uint8, device=full.device)
+            n = max(0, min(plan.Fout, full.shape[1] - n_s))
+            m[:, :n] = full[:, n_s:n_s + n]
+        sides.append((mel, ppg, d_l, m))
+    (mel_a, p_a, d_la, ma), (mel_b, p_b, d_lb, mb) = sides
+    path = path_len = None
+    if align == 'dtw':
+        ca, cb = _cepstra_launch(mel_a, n_coef, first_coef), _cepstra_launch(mel_b, n_coef, first_coef)
+        if mask is not None:
+            r = _masked_dtw(ca, cb, _compact_launch(ma, d_la), _compact_launch(mb, d_lb), scale, band, True)
+        else:
+            r = _dtw_launch(ca, cb, d_la, d_lb, scale, band, True)
+        path, path_len = r.path, r.path_len
+    c = _content_launch(p_a, p_b, d_la, d_lb, path, path_len, _cmap_device(cmap), min_run, ma, mb)
+    return _CONTENT_WAV(*c, p_a, p_b, d_la, d_lb, path, path_len, ma, mb)
