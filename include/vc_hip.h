@@ -210,7 +210,12 @@ int vc_frontend_stages_f32(const vc_frontend_plan* plan, const float* d_wav, con
  * Optional prologue on A (applied per element, in this order):
  *   pro_scale/pro_shift [Cin] affine, pro_relu, pro_pool: max(A[r], A[r+1]) along time with the
  *   TF "same" rule out[T-1] = x[T-1]  (tf.layers.max_pooling1d(2,1,"same"), modules.py:331);
- *   pro_pool = 2 additionally promises the pooled values are >= 0 (integer-ordered max).
+ *   pro_pool = 2 additionally promises the values that are pooled (after affine / relu) are >= 0: the maximum is then
+ *   taken on the bit patterns as SIGNED integers.  Accepted: +0.0, -0.0, every positive finite value and +inf; -0.0
+ *   orders below all of them, so max(-0.0, x) = x and the result is a zero only where both frames are zeros (of either
+ *   sign).  A negative value or a NaN breaks the promise (the result is then unspecified, as before).  pro_relu != 0
+ *   selects the same maximum, whatever sign of zero the ReLU produced.
+ *   The padding zeros of the Toeplitz view are inserted AFTER the prologue: a padding frame contributes 0, not pro_shift.
  * Epilogue: v = acc * epi_scale[c] + epi_shift[c] (NULL scale = 1, NULL shift = 0; this is the
  *   dense bias or the folded inference FusedBatchNorm of modules.py:39-102), activation,
  *   + residual R[m, n] (modules.py:340), stored as float32 (out_f32 != 0) or as `dtype`.

@@ -455,12 +455,12 @@ bank256_kernel(Bank256Args a) {
             const char* src = smem + row * EP + half * 256 + l16 * 16;
             bf16x8 vv = *reinterpret_cast<const bf16x8*>(src);
             if (a.pool && row < BM - 1) {
-                // max_pooling1d(2, 1, 'same') of the post-ReLU result: u16 order == bf16 order for x >= 0;
-                // the window's last frame pools with itself
-                typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+                // max_pooling1d(2, 1, 'same') of the post-ReLU result: signed 16-bit order == bf16 order for x >= 0
+                // (a -0.0 from fmaxf(-0.0f, 0.0f) orders below everything else); the window's last frame pools with itself
+                typedef short i16x8 __attribute__((ext_vector_type(8)));
                 const bf16x8 nx = *reinterpret_cast<const bf16x8*>(src + EP);
-                const bf16x8 mx = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(u16x8, vv),
-                                                                                      __builtin_bit_cast(u16x8, nx)));
+                const bf16x8 mx = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(i16x8, vv),
+                                                                                      __builtin_bit_cast(i16x8, nx)));
                 vv = (min(gm, a.M - 1) % a.T == a.T - 1) ? vv : mx;
             }
             // streaming store: the 210 MB output must not displace the weight tiles from L2

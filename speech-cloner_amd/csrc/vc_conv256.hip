@@ -12,8 +12,8 @@
 //     CU; WN = 4: 256 columns, 8 waves), 64 x 64 accumulators per wave;
 //   * POOL: tf.layers.max_pooling1d(pool_size=2, strides=1, padding='same') of the operand is taken
 //     on the fragments: max(row, row + 1) with the window's last frame pooling with itself.  The
-//     operand is post-ReLU (>= 0), so the bf16 maximum is the unsigned 16-bit maximum
-//     (v_pk_max_u16), the same trick conv_kernel uses while staging;
+//     operand is post-ReLU (>= 0, either zero), so the bf16 maximum is the SIGNED 16-bit maximum
+//     (v_pk_max_i16; -0.0 orders below every other such value), the same trick conv_kernel uses while staging;
 //   * residual add and any activation in the epilogue.
 #include "vc_common.h"
 #include "vc_conv256.h"
@@ -24,7 +24,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+typedef short i16x8 __attribute__((ext_vector_type(8)));
 
 // rows per block = 64 * WM (WM row groups of waves); the activation slab holds 8 more rows: taps - 1 <= 6 and 1 pool row
 constexpr int a_rows(int wm) { return 64 * wm + 8; }
@@ -35,7 +35,7 @@ __device__ __forceinline__ void glds16(const void* g, void* l) {
 }
 
 __device__ __forceinline__ bf16x8 max_nonneg(bf16x8 x, bf16x8 y) {
-    return __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(u16x8, x), __builtin_bit_cast(u16x8, y)));
+    return __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(i16x8, x), __builtin_bit_cast(i16x8, y)));
 }
 
 __device__ __forceinline__ float act_fn(float v, int act) {

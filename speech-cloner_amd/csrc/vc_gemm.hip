@@ -125,16 +125,17 @@ __device__ __forceinline__ bf16x8 vmax(bf16x8 a, bf16x8 b) {
     for (int e = 0; e < 8; ++e) a[e] = ((float)a[e] >= (float)b[e]) ? a[e] : b[e];
     return a;
 }
-// max of NON-NEGATIVE values (post-ReLU): IEEE ordering == unsigned integer ordering of the bit
-// patterns, so bf16 pairs go through v_pk_max_u16 and f32 through v_max_u32.
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+// max of values that are >= 0 (post-ReLU), either zero included: for them IEEE ordering == SIGNED integer ordering
+// of the bit patterns (-0.0 is the most negative integer, so it loses to every other such value, where the
+// unsigned order would rank it above all of them), so bf16 pairs go through v_pk_max_i16 and f32 through v_max_i32.
+typedef short i16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ bf16x8 vmax_nonneg(bf16x8 a, bf16x8 b) {
-    const u16x8 r = __builtin_elementwise_max(__builtin_bit_cast(u16x8, a), __builtin_bit_cast(u16x8, b));
+    const i16x8 r = __builtin_elementwise_max(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b));
     return __builtin_bit_cast(bf16x8, r);
 }
 __device__ __forceinline__ f32x4 vmax_nonneg(f32x4 a, f32x4 b) {
-    const u32x4 r = __builtin_elementwise_max(__builtin_bit_cast(u32x4, a), __builtin_bit_cast(u32x4, b));
+    const i32x4 r = __builtin_elementwise_max(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b));
     return __builtin_bit_cast(f32x4, r);
 }
 

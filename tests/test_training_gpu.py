@@ -11,21 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+from conv_gemm_ref import drop_mask as _mask      # host twin of drop_keep_elem (csrc/vc_gemm.hip)
 from oracle import model_oracle as mo
 
 pytestmark = pytest.mark.gpu
-
-
-def _mask(M, ldc, ncol, seed, keep):
-    """Host twin of drop_keep_elem: keep iff (splitmix64(idx + seed*phi) >> 40) < keep * 2^24."""
-    idx = (np.arange(M, dtype=np.uint64)[:, None] * np.uint64(ldc) + np.arange(ncol, dtype=np.uint64)[None, :])
-    with np.errstate(over='ignore'):
-        x = idx + np.uint64(seed) * np.uint64(0x9E3779B97F4A7C15)
-        x ^= x >> np.uint64(30); x *= np.uint64(0xBF58476D1CE4E5B9)
-        x ^= x >> np.uint64(27); x *= np.uint64(0x94D049BB133111EB)
-        x ^= x >> np.uint64(31)
-    u = (x >> np.uint64(40)).astype(np.float32)
-    return (u < np.float32(keep) * np.float32(16777216.0)).astype(np.float64)
 
 
 def _cfg(T=40, dropout=0.1, loss_type='sum'):
