@@ -1048,6 +1048,97 @@ int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const i
                          int32_t max_a, int32_t max_b, int32_t* d_counts, float* d_per, void* d_workspace, size_t workspace_bytes,
                          void* stream);
 
+/* Speaker.  The fourth question asked of a conversion: does it sound like the target speaker, and no longer like the
+ * source?  The text-independent answer needs no parallel sentence and no pretrained model: a diagonal-covariance
+ * Gaussian mixture fitted on the cepstra of many speakers (the universal background model, UBM), the same mixture with
+ * its means MAP-adapted to one speaker, and the mean per-frame log-likelihood ratio (LLR) of an utterance between the
+ * two (Reynolds, Quatieri and Dunn 2000).  Added without a version bump.
+ *
+ * Limits (VC_ERR_UNSUPPORTED beyond them): components 1 <= M <= 256; feature width 1 <= D <= 64; batch <= 65,535;
+ * max_frames * D <= 2^30; groups <= 4,096; models of one table <= 4,097 (4,096 speakers and the UBM).  Lengths d_len int32 [batch] ON THE DEVICE, clamped to
+ * [0, max_frames]; masks uint8 [batch, max_frames] on the device or NULL (every frame); a frame is KEPT when its mask is
+ * set and it lies below the length.  float32 arithmetic unless said otherwise.
+ *
+ * vc_spk_features_f32: d_cep [batch, max_frames, n_coef] (what vc_mel_cepstra writes), n_coef <= 32; d_feat
+ * [batch, max_frames, D], D = n_coef * (1 + deltas).  Columns 0 .. n_coef-1 are the cepstra; with deltas = 1 columns
+ * n_coef .. 2 n_coef - 1 are
+ *     delta[t] = ((c[t+1] - c[t-1]) + 2 (c[t+2] - c[t-2])) / 10,  indices clamped to [0, len-1]
+ * (two rounded differences, one fused multiply-add, one correctly rounded division; over ALL frames below len, masked or
+ * not).  With cmn = 1 the mean of every column over the kept frames is subtracted from all rows below len: the sum is
+ * float64 in a fixed order -- lane r of four adds the kept frames r, r + 4, ... ascending, the four partial sums are added
+ * in the order ((0 + 1) + 2) + 3 --, the quotient is rounded to float32 once.  Without a kept frame nothing is
+ * subtracted.  Rows from len on are zeros.  One workgroup per utterance.
+ *
+ * The model.  d_w [M], d_mu [n_models, M, D], d_var [M, D]: weights and variances are shared by all models (MAP adaptation
+ * here moves means only; model 0 is by convention the UBM).  vc_gmm_prepare_f32 writes the table the other launches
+ * read, vc_gmm_table_floats(n_models, M, D) = (n_models + 1) M D + M floats: the means transposed to [model][d][m],
+ * 1 / var [d][m] (the float64 quotient of the widened variance, rounded once) and
+ *     c_m = log w_m - 0.5 * sum_d log(2 pi var_md)         (float64, d ascending, rounded once).
+ *
+ * vc_gmm_loglik_f32: per frame x of utterance b, with the means of model d_model[b] (clamped to [0, n_models)):
+ *     l_m = c_m - 0.5 * sum_d (x_d - mu_md)^2 * (1 / var_md)    the DIRECT form: the expanded x^2 a - 2 x b product
+ *                                                              cancels for narrow components.  d ascending; per term one
+ *                                                              rounded difference, one rounded square, one fused
+ *                                                              multiply-add
+ *     ll  = max_m l_m + log sum_m exp(l_m - max)               the sum: lane l of 64 adds components l, l + 64, ...
+ *                                                              ascending, the lanes are added in a butterfly
+ * d_ll [batch, max_frames], 0 from len on.  d_model_b / d_ll_b: the same for a second model per utterance, or both NULL;
+ * the two passes share one read of the features.  One workgroup per (utterance, tile of vc_gmm_tile_frames() = 32
+ * frames).  A frame's ll is a function of the frame and its model alone.
+ *
+ * vc_gmm_score_f32: d_n_frames [batch] int32 = the kept frames; d_values [batch, 3] float32 = ll_a, ll_b (the means of
+ * d_ll_a, d_ll_b over the kept frames) and llr = ll_a - ll_b (the difference of the two float64 means, rounded once).
+ * Lane t of 256 adds the kept frames t, t + 256, ... in that order in float64, the 256 partial sums are added in a fixed
+ * tree (lane t adds lane t + 128, then t + 64, ... t + 1), each figure is rounded once.  No kept frame: n_frames = 0 and
+ * NaN figures.  d_ll_b NULL: ll_b and llr are NaN.
+ *
+ * vc_gmm_accumulate_f32: the fused E-step.  d_group [batch] int32 in [0, n_groups), or any other value to leave the
+ * utterance out.  d_ll is vc_gmm_loglik_f32's output for model `model` of the table.  In FLOAT64:
+ *     N [n_groups, M], S1, S2 [n_groups, M, D] = the sums of gamma, gamma x, gamma x^2 over the kept frames of the group's
+ *     utterances, gamma = exp(l_m - ll) (float32, l_m as above);  L [n_groups] = the sum of ll over the same frames.
+ * gamma is formed and folded into the sums; no [frames, M] array exists.  Grid = (chunks of 64 components) x
+ * (P = vc_gmm_partitions(n_groups) = max(1, 128 / n_groups) frame partitions) x n_groups: constants and arguments, never
+ * a property of the device.  Tile k of utterance b goes to partition (b + k) mod P; a partition walks its utterances
+ * and tiles ascending and adds frame by frame; the P partial sums of an element meet in the order 0 .. P - 1 in a
+ * second launch: bit-identical from run to run and under graph replay.  Every output element is written once (zeros
+ * for a group without utterances).  Workspace: vc_gmm_workspace_bytes(n_groups, M, D) =
+ *     n_groups * P * ceil(M / 64) * (64 (1 + 2 D) + 1) * 8 bytes rounded up to 256, and 0 when P = 1 (n_groups > 64: the
+ *     workgroups write the outputs themselves);
+ * independent of the number of frames, 33,820,672 bytes at most (n_groups = 1, M = 256, D = 64).  Too small:
+ * VC_ERR_WORKSPACE.
+ *
+ * vc_gmm_update_f32: one launch, elementwise, float64 arithmetic on the float64 statistics, each output rounded once.
+ *   mode 0 (EM, n_groups = 1): w_m = max(N_m / sum_k N_k, 2^-40) -- NOT renormalised after the floor (the sum over k
+ *     ascending; 2^-40 when there is no frame at all); mu = S1 / N; var = max(S2 / N - mu^2, d_var_floor[d]) with the
+ *     unrounded mu.  A component with N_m < min_count keeps d_mu_in and d_var_in (its weight is still updated).
+ *   mode 1 (MAP): alpha = N_gm / (N_gm + relevance); mu_g = alpha * (S1_gm / N_gm) + (1 - alpha) * mu_in, d_mu_in [M, D] the
+ *     UBM's means, d_mu_out [n_groups, M, D].  N_gm = 0 gives mu_in exactly: a group without utterances returns the UBM's
+ *     means bit for bit.  d_S2, d_var_in, d_var_floor, d_w_out, d_var_out are not read and may be NULL.
+ *
+ * The score figures of an utterance are a function of that utterance and its model alone: bit-identical alone and in any
+ * batch.  No atomics, no memset, no host synchronisation, no allocation; every launch is capturable; arguments are
+ * checked before any HIP call. */
+int vc_gmm_tile_frames(void);
+int vc_gmm_partitions(int32_t n_groups);
+size_t vc_gmm_table_floats(int32_t n_models, int32_t M, int32_t D);
+size_t vc_gmm_workspace_bytes(int32_t n_groups, int32_t M, int32_t D);
+int vc_spk_features_f32(const float* d_cep, const int32_t* d_len, const uint8_t* d_mask, int32_t batch, int32_t max_frames,
+                        int32_t n_coef, int32_t deltas, int32_t cmn, float* d_feat, void* stream);
+int vc_gmm_prepare_f32(const float* d_w, const float* d_mu, const float* d_var, int32_t n_models, int32_t M, int32_t D, float* d_table,
+                       void* stream);
+int vc_gmm_loglik_f32(const float* d_feat, const int32_t* d_len, int32_t batch, int32_t max_frames, int32_t D, const float* d_table,
+                      int32_t n_models, int32_t M, const int32_t* d_model, float* d_ll, const int32_t* d_model_b, float* d_ll_b,
+                      void* stream);
+int vc_gmm_score_f32(const float* d_ll_a, const float* d_ll_b, const int32_t* d_len, const uint8_t* d_mask, int32_t batch,
+                     int32_t max_frames, int32_t* d_n_frames, float* d_values, void* stream);
+int vc_gmm_accumulate_f32(const float* d_feat, const float* d_ll, const int32_t* d_len, const uint8_t* d_mask, const int32_t* d_group,
+                          int32_t batch, int32_t max_frames, int32_t D, const float* d_table, int32_t n_models, int32_t M, int32_t model,
+                          int32_t n_groups, double* d_N, double* d_S1, double* d_S2, double* d_L, void* d_workspace,
+                          size_t workspace_bytes, void* stream);
+int vc_gmm_update_f32(int32_t mode, const double* d_N, const double* d_S1, const double* d_S2, int32_t n_groups, int32_t M, int32_t D,
+                      const float* d_mu_in, const float* d_var_in, const float* d_var_floor, float min_count, float relevance,
+                      float* d_w_out, float* d_mu_out, float* d_var_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

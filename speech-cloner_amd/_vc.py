@@ -256,6 +256,19 @@ _SIGS = {
     'vc_edit_distance_rows': (C.c_int, []),
     'vc_edit_distance_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
     'vc_edit_distance_i32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    # speaker similarity (csrc/vc_gmm.hip)
+    'vc_gmm_tile_frames': (C.c_int, []),
+    'vc_gmm_partitions': (C.c_int, [C.c_int32]),
+    'vc_gmm_table_floats': (C.c_size_t, [C.c_int32] * 3),
+    'vc_gmm_workspace_bytes': (C.c_size_t, [C.c_int32] * 3),
+    'vc_spk_features_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'vc_gmm_prepare_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    'vc_gmm_loglik_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    'vc_gmm_score_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    'vc_gmm_accumulate_f32': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    'vc_gmm_update_f32': (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P,
+                                    _P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -291,7 +304,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches): a build older than this binding
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
                               '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None

@@ -33,7 +33,7 @@ Definitions (include/vc_hip.h, "Evaluation"):
 Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
 the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip, csrc/vc_f0.hip (the pitch tracker
 and its figures), csrc/vc_activity.hip (the masks) and csrc/vc_content.hip (the content scores,
-DESIGN.md section 17); there is no CPU path.
+DESIGN.md section 17); there is no CPU path.  Speaker similarity (GMM-UBM, log-likelihood ratios) lives in speaker.py.
 """
 from collections import namedtuple
 
