@@ -664,7 +664,8 @@ int vc_highway_chain(const void* d_X, int32_t M, int32_t H, int32_t ldx, int32_t
  * (hp/encoder_cfg_d.json: 80 features, prenet 80 -> 40, 6 banks x 128 filters, GRU of 40 units; bf16
  * weights, inference).  vc_cbhg_front_supported() says whether a shape takes this path; callers run
  * the per-layer entry points (vc_conv_gemm, vc_highway_chain) otherwise -- same results within bf16
- * rounding (different float32 summation order).
+ * rounding (different float32 summation order).  The pool between the banks and conv1d_1 orders either zero
+ * below every positive value (the signed integer maximum of the post-ReLU values, as vc_conv_gemm's pro_pool = 2).
  *
  * Weights are handed over in MFMA fragment order, built with vc_mfma_pack from row-major bf16
  * matrices W [rows, K] (row = output channel, K contiguous):

@@ -23,8 +23,10 @@
 // lanes of a ds_read_b128 group hit 16 different bank groups.  SAME-padding zeros depend on
 // (output frame, tap) and are a per-lane select on the A fragment.
 #include <cstdlib>
-#include "vc_common.h"
+#include "vc_device.h"
 #include "vc_bank256.h"
+
+using vc::f32x16, vc::f32x4, vc::bf16x8, vc::bf16x4, vc::u32x4;
 
 namespace {
 
@@ -36,9 +38,6 @@ namespace {
 #define ABL(mask) false
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int NT = 512;
 constexpr int BM = 256;
 constexpr int A_ROWS = 288;                        // 256 + 32 halo rows
@@ -46,11 +45,6 @@ constexpr int A_BYTES = A_ROWS * 128;
 constexpr int B_BYTES = 256 * 128;
 constexpr int COEF_OFF = 2 * A_BYTES + 2 * B_BYTES;    // 139,264: scale[256] | shift[256] of the pair (f32)
 constexpr int LDS_BYTES = COEF_OFF + 2 * 256 * 4;
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(uintptr_t)g,
-                                     (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)l, 16, 0, 0);
-}
 
 __global__ void __launch_bounds__(NT, 1)
 bank256_kernel(Bank256Args a) {
@@ -127,7 +121,7 @@ bank256_kernel(Bank256Args a) {
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
             const int rb = q * 8 + wid;
-            if (rb * 8 < a_rows_needed && rb < A_ROWS / 8) glds16(a_src[q] + cs * 64, dst + q * 8192);
+            if (rb * 8 < a_rows_needed && rb < A_ROWS / 8) vc::glds16(a_src[q] + cs * 64, dst + q * 8192);
         }
     };
     auto stageB = [&](int n, int buf) {
@@ -141,7 +135,7 @@ bank256_kernel(Bank256Args a) {
         char* dst = Bs + buf * B_BYTES + wid * 1024;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (q >= 2 || j < pr.taps0) glds16(b_src[q] + (q < 2 ? koffL : koffR), dst + q * 8192);
+            if (q >= 2 || j < pr.taps0) vc::glds16(b_src[q] + (q < 2 ? koffL : koffR), dst + q * 8192);
     };
 
     // ---------------- MFMA roles
@@ -155,23 +149,12 @@ bank256_kernel(Bank256Args a) {
     for (int s = 0; s < 4; ++s) b_off[s] = (wc * 64 + li) * 128 + (((2 * s + lh) ^ xb) << 4);
     int jlo[4], jhi[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = min(m0 + wr * 128 + i * 32 + li, a.M - 1);
-        const int t = m % a.T;
-        jlo[i] = max(0, pad_l - t);
-        jhi[i] = a.T - t + pad_l;
-    }
+    for (int i = 0; i < 4; ++i) vc::same_tap_range(min(m0 + wr * 128 + i * 32 + li, a.M - 1), a.T, pad_l, jlo[i], jhi[i]);
     const bool left_wave = wc < 2;
     // taps [J_lo, J_hi) need no select anywhere in this wave (wave-uniform: scalar branch per tile)
     int J_lo = max(max(jlo[0], jlo[1]), max(jlo[2], jlo[3]));
     int J_hi = min(min(jhi[0], jhi[1]), min(jhi[2], jhi[3]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        J_lo = max(J_lo, __shfl_xor(J_lo, o, 64));
-        J_hi = min(J_hi, __shfl_xor(J_hi, o, 64));
-    }
-    J_lo = __builtin_amdgcn_readfirstlane(J_lo);
-    J_hi = __builtin_amdgcn_readfirstlane(J_hi);
+    vc::wave_tap_range(J_lo, J_hi);
     if (left_wave) J_hi = min(J_hi, pr.taps0);
 
     f32x16 acc[4][2];
@@ -359,8 +342,6 @@ bank256_kernel(Bank256Args a) {
         // for nobody, so the exchange cannot deadlock whatever the residency; with two splits the sum a + b does not
         // depend on who was last (cdna_hip_programming.md Guideline 16, form R1).
         typedef __attribute__((address_space(1))) unsigned gu32;
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         gu32* const tk = (gu32*)(uintptr_t)(a.tick + 2 * rt);
         int* const tsh = reinterpret_cast<int*>(smem);
         if (tid == 0) tsh[0] = (int)__hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -427,7 +408,6 @@ bank256_kernel(Bank256Args a) {
                 const float svv[4] = {sv.x, sv.y, sv.z, sv.w}, bvv[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                     bf16x4 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -457,10 +437,8 @@ bank256_kernel(Bank256Args a) {
             if (a.pool && row < BM - 1) {
                 // max_pooling1d(2, 1, 'same') of the post-ReLU result: signed 16-bit order == bf16 order for x >= 0
                 // (a -0.0 from fmaxf(-0.0f, 0.0f) orders below everything else); the window's last frame pools with itself
-                typedef short i16x8 __attribute__((ext_vector_type(8)));
                 const bf16x8 nx = *reinterpret_cast<const bf16x8*>(src + EP);
-                const bf16x8 mx = __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(i16x8, vv),
-                                                                                      __builtin_bit_cast(i16x8, nx)));
+                const bf16x8 mx = vc::max_nonneg(vv, nx);
                 vv = (min(gm, a.M - 1) % a.T == a.T - 1) ? vv : mx;
             }
             // streaming store: the 210 MB output must not displace the weight tiles from L2
@@ -479,7 +457,7 @@ int vc_bank256_ksplit(int M, int nslab) {
     return (2 * ntm <= 256 && nslab >= 8) ? 2 : 1;
 }
 
-static size_t tick_bytes(int ntm) { return ((size_t)ntm * 8 + 255) & ~(size_t)255; }
+static size_t tick_bytes(int ntm) { return vc::align256((size_t)ntm * 8); }
 
 size_t vc_bank256_ws_bytes(int M, int ksplit) {
     if (ksplit <= 1) return 0;
@@ -488,12 +466,7 @@ size_t vc_bank256_ws_bytes(int M, int ksplit) {
 }
 
 int vc_launch_bank256(const Bank256Args& a, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bank256_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<bank256_kernel>(LDS_BYTES)) return rc;
     const int stride = a.pool ? BM - 1 : BM;
     const int ntm = (a.M + stride - 1) / stride;
     Bank256Args b = a;

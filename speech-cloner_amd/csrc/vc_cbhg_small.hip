@@ -25,14 +25,16 @@
 //    GEMM over K = 40 k (zero-padded weights to a multiple of 16; the over-read hits the next row x 0).
 //  * Bank + first projection: wave w owns bank channels [32w, 32w+32) of every filter width.  Its
 //    slice of the bank output goes through a wave-private LDS tile (norm + relu applied, frames outside
-//    the window zeroed), comes back max-pooled (v_pk_max_u16 of rows r, r+1: post-ReLU bf16 orders like
-//    u16) at row shifts -1, 0, +1 and feeds the k = 3 projection's partial sum over those 32 channels --
+//    the window zeroed), comes back max-pooled (vc::max_nonneg of rows r, r+1: post-ReLU bf16 orders like
+//    i16) at row shifts -1, 0, +1 and feeds the k = 3 projection's partial sum over those 32 channels --
 //    so the 768-channel bank output never exists, the 4 partial sums are added once through LDS in a
 //    fixed order (deterministic), and the heavy weights are streamed once per block.
 // TF's SAME padding: prenet / projection outputs of frames outside the window are stored as zeros;
 // pooled frame -1 is forced to zero on the fragment (max(0, bank[0]) would leak into it).
-#include "vc_common.h"
+#include "vc_device.h"
 #include <cstdlib>
+
+using vc::f32x16, vc::f32x4, vc::bf16x8, vc::bf16x4;
 
 namespace {
 
@@ -42,12 +44,6 @@ namespace {
 #else
 #define ABL(mask) false
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int CS_C = 40;                 // CBHG width (embed_size / 2)
 constexpr int CS_PITCH = 2 * CS_C;       // bytes per LDS row: dense, see above
@@ -84,9 +80,6 @@ __device__ __forceinline__ bf16x8 chain(const bf16x4 (&v)[NT][4], int s) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi[e]; }
     return o;
-}
-__device__ __forceinline__ bf16x8 max_nonneg(bf16x8 a, bf16x8 b) {
-    return __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(u16x8, a), __builtin_bit_cast(u16x8, b)));
 }
 // same-wave LDS hand-off (a wave's LDS instructions execute in order; this only stops the compiler)
 __device__ __forceinline__ void wave_lds_fence() {
@@ -296,7 +289,7 @@ cbhg_small_kernel(CbhgSmallArgs a) {
                 for (int d = 0; d < 4; ++d) f[d] = *reinterpret_cast<const bf16x8*>(br + d * CS_PITCH);
 #pragma unroll
                 for (int tap = 0; tap < 3; ++tap) {
-                    bf16x8 pl = max_nonneg(f[tap], f[tap + 1]);
+                    bf16x8 pl = vc::max_nonneg(f[tap], f[tap + 1]);
                     pl = m1[mi][tap] ? zero8 : pl;
 #pragma unroll
                     for (int nt = 0; nt < NTC; ++nt) acc1[nt][mi] = mfma(wq[tap][s][nt], pl, acc1[nt][mi]);
@@ -555,11 +548,6 @@ prenet_chain_kernel(PrenetArgs a) {
 // drops from 4 x 0.34 MB to 0.34 MB; the kernel above is bound by exactly that stream (42 us for 4 us of MFMA work).
 // Biases sit in LDS so that the only vector-memory operations in flight inside the loops are the chunk loads: the
 // counted wait "all but my newest 4" then means "chunk c has landed, c + 1 may still fly".
-__device__ __forceinline__ void pn_glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(uintptr_t)g,
-                                     (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)l, 16, 0, 0);
-}
-
 template <int CINP, int U1, int U2>
 __global__ void __launch_bounds__(256, U1 <= 256 ? 2 : 1)
 prenet_chain_lds_kernel(PrenetArgs a) {
@@ -583,7 +571,7 @@ prenet_chain_lds_kernel(PrenetArgs a) {
         const bf16x8* src = (c < C1 ? a.pk1 + (size_t)c * CH * 64 : a.pk2 + (size_t)(c - C1) * CH * 64) + lane;
         char* dst = wbuf + (c % 3) * CH * 1024 + w * 4096;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) pn_glds16(src + (w * 4 + u) * 64, dst + u * 1024);
+        for (int u = 0; u < 4; ++u) vc::glds16(src + (w * 4 + u) * 64, dst + u * 1024);
     };
 
     bf16x8 xb[KS1];
@@ -667,14 +655,8 @@ prenet_chain_lds_kernel(PrenetArgs a) {
 template <int CINP, int U1, int U2> int launch_prenet_chain(const PrenetArgs& a, hipStream_t st) {
     constexpr int LDS = 4 * 32 * (U2 * 2 + 16);
     constexpr int LDS_SHARED = LDS + 3 * 16 * 1024 + (U1 + U2) * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(prenet_chain_kernel<CINP, U1, U2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(prenet_chain_lds_kernel<CINP, U1, U2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_SHARED));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<prenet_chain_kernel<CINP, U1, U2>>(LDS)) return rc;
+    if (int rc = vc::allow_dynamic_lds<prenet_chain_lds_kernel<CINP, U1, U2>>(LDS_SHARED)) return rc;
     const dim3 grid((unsigned)((a.M + 127) / 128));
     if (vc::opt(vc::OPT_PRENET_LDS) != 0)
         hipLaunchKernelGGL((prenet_chain_lds_kernel<CINP, U1, U2>), grid, dim3(256), LDS_SHARED, st, a);
@@ -702,12 +684,7 @@ mfma_pack_kernel(const __bf16* W, int rows, int K, int ldw, int chained, int nti
 constexpr int cbhg_small_lds(int mi) { return cbhg_small_lds_tiles(mi) + CO_TOTAL * 4; }
 
 template <int MI> int launch_cbhg_small(const CbhgSmallArgs& a, int n_windows, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(cbhg_small_kernel<6, 80, 80, MI>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, cbhg_small_lds(MI)));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<cbhg_small_kernel<6, 80, 80, MI>>(cbhg_small_lds(MI))) return rc;
     hipLaunchKernelGGL((cbhg_small_kernel<6, 80, 80, MI>), dim3((unsigned)(n_windows * a.tiles_per_win)), dim3(256),
                        cbhg_small_lds(MI), st, a);
     VC_HIP_CHECK(hipGetLastError());

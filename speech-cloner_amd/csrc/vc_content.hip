@@ -35,7 +35,7 @@
 //
 // Every result is a function of its own pair or utterance alone: fixed geometry, fixed orders, no atomics.
 #include <cmath>
-#include "vc_common.h"
+#include "vc_device.h"
 
 namespace {
 
@@ -230,7 +230,6 @@ __device__ inline ECell shfl_cell(const ECell& c, int src) {
     return ECell{__shfl(c.E, src, 64), __shfl(c.m, src, 64), __shfl(c.s, src, 64), __shfl(c.d, src, 64)};
 }
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool ed_shape_ok(int batch, int max_a, int max_b) {
     return batch >= 1 && batch <= 65535 && max_a >= 1 && max_a <= ED_MAX && max_b >= 1 && max_b <= ED_MAX;
 }
@@ -366,7 +365,7 @@ int vc_edit_distance_rows(void) { return ED_ROWS; }
 
 size_t vc_edit_distance_workspace_bytes(int32_t batch, int32_t max_a, int32_t max_b) {
     if (!ed_shape_ok(batch, max_a, max_b)) return 0;
-    return align256((size_t)batch * 2 * max_b * sizeof(ECell));
+    return vc::align256((size_t)batch * 2 * max_b * sizeof(ECell));
 }
 
 int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const int32_t* d_n_a, const int32_t* d_n_b, int32_t batch,

@@ -13,39 +13,18 @@
 //   * POOL: tf.layers.max_pooling1d(pool_size=2, strides=1, padding='same') of the operand is taken
 //     on the fragments: max(row, row + 1) with the window's last frame pooling with itself.  The
 //     operand is post-ReLU (>= 0, either zero), so the bf16 maximum is the SIGNED 16-bit maximum
-//     (v_pk_max_i16; -0.0 orders below every other such value), the same trick conv_kernel uses while staging;
+//     (vc::max_nonneg, vc_device.h), which conv_kernel takes while staging;
 //   * residual add and any activation in the epilogue.
-#include "vc_common.h"
+#include "vc_device.h"
 #include "vc_conv256.h"
 #include <cstdlib>
 
-namespace {
+using vc::f32x16, vc::bf16x8, vc::bf16x4;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short i16x8 __attribute__((ext_vector_type(8)));
+namespace {
 
 // rows per block = 64 * WM (WM row groups of waves); the activation slab holds 8 more rows: taps - 1 <= 6 and 1 pool row
 constexpr int a_rows(int wm) { return 64 * wm + 8; }
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(uintptr_t)g,
-                                     (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)l, 16, 0, 0);
-}
-
-__device__ __forceinline__ bf16x8 max_nonneg(bf16x8 x, bf16x8 y) {
-    return __builtin_bit_cast(bf16x8, __builtin_elementwise_max(__builtin_bit_cast(i16x8, x), __builtin_bit_cast(i16x8, y)));
-}
-
-__device__ __forceinline__ float act_fn(float v, int act) {
-    switch (act) {
-        case VC_ACT_RELU: return fmaxf(v, 0.0f);
-        case VC_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        case VC_ACT_TANH: return tanhf(v);
-        default: return v;
-    }
-}
 
 // counted wait: everything but the newest `n` LDS-direct loads of this wave has landed
 __device__ __forceinline__ void wait_loads_but(int n) {
@@ -99,7 +78,7 @@ conv256_kernel(Conv256Args a) {
 #pragma unroll
         for (int q = 0; q < AQ; ++q) {
             const int rb = q * NWAVE + wid;
-            if (rb * 8 < a_rows_needed && rb < A_ROWS / 8) glds16(a_src[q] + cs * 64, dst + q * NWAVE * 1024);
+            if (rb * 8 < a_rows_needed && rb < A_ROWS / 8) vc::glds16(a_src[q] + cs * 64, dst + q * NWAVE * 1024);
         }
     };
     auto stageB = [&](int n, int buf) {
@@ -107,7 +86,7 @@ conv256_kernel(Conv256Args a) {
         const int koff = j * a.Cin + cs * 64;
         char* dst = Bs + buf * B_BYTES + wid * 1024;
 #pragma unroll
-        for (int q = 0; q < BQ; ++q) glds16(b_src[q] + koff, dst + q * NWAVE * 1024);
+        for (int q = 0; q < BQ; ++q) vc::glds16(b_src[q] + koff, dst + q * NWAVE * 1024);
     };
 
     // ---------------- MFMA roles
@@ -117,16 +96,12 @@ conv256_kernel(Conv256Args a) {
     int b_off[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) b_off[s] = (wc * 64 + li) * 128 + (((2 * s + lh) ^ xb) << 4);
-    int jlo[2], jhi[2];
+    int jlo[2], jhi[2];                                // taps [jlo, jhi) read a real frame, and taps < jhi - 1 a real NEXT frame (pool partner)
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int m = min(m0 + wr * 64 + i * 32 + li, a.M - 1);
-        const int t = m % a.T;
-        jlo[i] = max(0, pad_l - t);                    // taps [jlo, jhi) read a real frame
-        jhi[i] = a.T - t + pad_l;                      // ... and taps < jhi - 1 a real NEXT frame (pool partner)
-    }
+    for (int i = 0; i < 2; ++i) vc::same_tap_range(min(m0 + wr * 64 + i * 32 + li, a.M - 1), a.T, pad_l, jlo[i], jhi[i]);
     int J_lo = max(jlo[0], jlo[1]);
     int J_hi = min(jhi[0], jhi[1]) - (POOL ? 1 : 0);
+    // vc::wave_tap_range spelled out: through the helper the compiler orders this kernel's prologue differently
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         J_lo = max(J_lo, __shfl_xor(J_lo, o, 64));
@@ -242,7 +217,7 @@ conv256_kernel(Conv256Args a) {
             bf16x8 av[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                if constexpr (POOL) av[i] = max_nonneg(fa[cur][i], fp[cur][i]);
+                if constexpr (POOL) av[i] = vc::max_nonneg(fa[cur][i], fp[cur][i]);
                 else av[i] = fa[cur][i];
             }
             if (need_mask) {
@@ -298,7 +273,7 @@ conv256_kernel(Conv256Args a) {
                     bf16x4 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float val = act_fn(acc[i][c][4 * q + e] * svv[e] + bvv[e], a.act);
+                        float val = vc::act_fn(acc[i][c][4 * q + e] * svv[e] + bvv[e], a.act);
                         if (a.R) val += (float)rr[e];
                         o[e] = (__bf16)val;
                     }
@@ -326,12 +301,7 @@ template <int WN, bool POOL, int WM> int launch(const Conv256Args& a, hipStream_
     constexpr int BM = 64 * WM;
     constexpr int LDS = 2 * a_rows(WM) * 128 + NBUF * 64 * WN * 128;
     static_assert(LDS <= 160 * 1024 && BM * (64 * WN * 2 + 16) <= LDS, "LDS budget (K loop, epilogue tile)");
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv256_kernel<WN, POOL, NBUF, WM>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<conv256_kernel<WN, POOL, NBUF, WM>>(LDS)) return rc;
     hipLaunchKernelGGL((conv256_kernel<WN, POOL, NBUF, WM>), dim3((a.M + BM - 1) / BM, a.N / (64 * WN)), dim3(64 * WM * WN), LDS, st, a);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;

@@ -32,7 +32,7 @@
 // summation order per distance (d = 0 .. n_coef-1, fused multiply-adds), no atomics.
 #include <cmath>
 #include <mutex>
-#include "vc_common.h"
+#include "vc_device.h"
 
 namespace {
 
@@ -49,8 +49,7 @@ struct Cell {                           // accumulated cost and path length of o
     int32_t L;
 };
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline size_t boundary_bytes(int batch, int max_b) { return align256((size_t)batch * 2 * max_b * sizeof(Cell)); }
+inline size_t boundary_bytes(int batch, int max_b) { return vc::align256((size_t)batch * 2 * max_b * sizeof(Cell)); }
 inline int words_per_row(int max_b) { return (max_b + 15) >> 4; }
 
 template <int NC>
@@ -320,7 +319,7 @@ size_t vc_dtw_workspace_size(int32_t batch, int32_t max_a, int32_t max_b, int32_
     size_t need = boundary_bytes(batch, max_b);
     if (want_path) {
         if (code_bytes(batch, max_a, max_b) > MAX_CODE_BYTES) return 0;
-        need += align256((size_t)code_bytes(batch, max_a, max_b));
+        need += vc::align256((size_t)code_bytes(batch, max_a, max_b));
     }
     return need;
 }

@@ -18,9 +18,11 @@
 #include <cstring>
 #include <vector>
 
-#include "vc_common.h"
+#include "vc_device.h"
 #include "fe_dft400.h"
 #include "vc_frontend400.h"
+
+using vc::f32x4;
 
 namespace {
 
@@ -515,26 +517,25 @@ fe_finalize_kernel(FeArgs a, int g2) {
         }
     }
     // DCT-II (audio_lib.py:176-179) + first-coefficient shift + scale (:220-224)
-    typedef float f4 __attribute__((ext_vector_type(4)));
     for (int i = tid; i < (G + 2) * NC; i += FE_THREADS) {
         const int r = i / NC, c = i - r * NC;
-        const f4* d = reinterpret_cast<const f4*>(D + c * DS);
-        const f4* m = reinterpret_cast<const f4*>(Mc + r * NM4);
+        const f32x4* d = reinterpret_cast<const f32x4*>(D + c * DS);
+        const f32x4* m = reinterpret_cast<const f32x4*>(Mc + r * NM4);
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;      // float4 LDS reads, 4 independent chains
 #pragma unroll 4
         for (int j = 0; j < NM4 / 4; ++j) {
-            const f4 dv = d[j], mv = m[j];
+            const f32x4 dv = d[j], mv = m[j];
             a0 = fmaf(dv[0], mv[0], a0); a1 = fmaf(dv[1], mv[1], a1);
             a2 = fmaf(dv[2], mv[2], a2); a3 = fmaf(dv[3], mv[3], a3);
         }
         float acc = (a0 + a1) + (a2 + a3);
         if (c == 0 && a.first_mfcc) {
             // identical summation order on frame 0 => frame 0's own coefficient cancels to exactly 0
-            const f4* m0 = reinterpret_cast<const f4*>(M0);
+            const f32x4* m0 = reinterpret_cast<const f32x4*>(M0);
             float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
 #pragma unroll 4
             for (int j = 0; j < NM4 / 4; ++j) {
-                const f4 dv = d[j], mv = m0[j];
+                const f32x4 dv = d[j], mv = m0[j];
                 b0 = fmaf(dv[0], mv[0], b0); b1 = fmaf(dv[1], mv[1], b1);
                 b2 = fmaf(dv[2], mv[2], b2); b3 = fmaf(dv[3], mv[3], b3);
             }
@@ -757,8 +758,6 @@ int vc_frontend_get_dct(const vc_frontend_plan* plan, double* h_out) {
     return VC_OK;
 }
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // Workspace: [fast400: the one-launch form's arrival counters, batch x 256 B at offset 0, zeroed before each of its
 // launches] | |x| partials | statistics | mel, each 256-byte aligned.
 static void ws_layout(const vc_frontend_plan* p, int32_t batch, int32_t max_samples, size_t* o_partial,
@@ -766,10 +765,10 @@ static void ws_layout(const vc_frontend_plan* p, int32_t batch, int32_t max_samp
     const int mf = 1 + max_samples / p->cfg.hop_length;
     const int g = p->fft400 ? FE_G400 : FE_GGEN;
     const int nt = (mf + g - 1) / g;
-    size_t o = p->fast400 ? align256((size_t)vc_fe400_fused_count_bytes(batch)) : 0;
-    *o_partial = o; o = align256(o + (size_t)batch * FE_NPART * 4);
-    *o_stats = o;   o = align256(o + (size_t)batch * nt * 8 * 4);
-    *o_mel = o;     o = align256(o + (size_t)batch * mf * p->cfg.n_mels * 4);
+    size_t o = p->fast400 ? vc::align256((size_t)vc_fe400_fused_count_bytes(batch)) : 0;
+    *o_partial = o; o = vc::align256(o + (size_t)batch * FE_NPART * 4);
+    *o_stats = o;   o = vc::align256(o + (size_t)batch * nt * 8 * 4);
+    *o_mel = o;     o = vc::align256(o + (size_t)batch * mf * p->cfg.n_mels * 4);
     *total = o; *ntiles = nt; *max_frames = mf;
 }
 
@@ -813,7 +812,7 @@ int vc_frontend_stages_f32(const vc_frontend_plan* plan, const float* d_wav, con
         f.nt1 = ntiles;
         // one-launch form: tile records in the mel slot (batch x max_frames x 80 floats, of which this path uses only frame
         // 0's rows): [mel0 | records]; arrival counters in the workspace's first block (ws_layout)
-        const size_t o_rec = align256((size_t)batch * c.n_mels * 4);
+        const size_t o_rec = vc::align256((size_t)batch * c.n_mels * 4);
         f.fstride = vc_fe400_fused_stride(max_frames);
         f.fstats = reinterpret_cast<float*>(wsb + o_mel + o_rec);
         f.fcount = reinterpret_cast<unsigned*>(wsb);

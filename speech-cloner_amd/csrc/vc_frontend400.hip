@@ -18,9 +18,11 @@
 // Recomputing the transform is the cheaper side of that trade: the kernels are issue- and latency-bound, not
 // byte-bound, and the transform is ~40 % of a pass's instructions.
 #include <hip/hip_runtime.h>
-#include "vc_common.h"
+#include "vc_device.h"
 #include "fe_dft400.h"
 #include "vc_frontend400.h"
+
+using vc::f32x4;
 
 namespace {
 
@@ -37,8 +39,6 @@ constexpr int IM_W = 48 * RP;                       // 960 floats of imaginary p
 constexpr int PP = RE_W / 4;                        // 260: pitch of a power-tile row (4 rows per wave region, 59 floats of slack each)
 constexpr float NEG_INF = -3.402823466e38f, POS_INF = 3.402823466e38f;
 constexpr float DB10 = 3.0102999566398120f;         // 10 log10(x) = DB10 * log2(x)
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // In-kernel phase stamps (s_memtime), -DVC_ABLATE builds only (tools/fe_phase_stamps.py reads them back): wave 0 of
 // every block writes the shader clock at each phase boundary into an unused part of the workspace.  The shipped
@@ -305,8 +305,8 @@ fe400_kernel(Fe400Args a) {
         const int ri = has_im ? g3l * 12 + k13 - 1 : 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const f4 vr = *reinterpret_cast<const f4*>(are_w + r * RP + 4 * q);
-            const f4 vi = *reinterpret_cast<const f4*>(aim_w + ri * RP + 4 * q);
+            const f32x4 vr = *reinterpret_cast<const f32x4*>(are_w + r * RP + 4 * q);
+            const f32x4 vi = *reinterpret_cast<const f32x4*>(aim_w + ri * RP + 4 * q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) { zr[4 * q + e] = vr[e]; zi[4 * q + e] = has_im ? vi[e] : 0.0f; }
         }
@@ -322,7 +322,7 @@ fe400_kernel(Fe400Args a) {
         if (tid < 240) {
 #pragma unroll
             for (int j = 0; j < NH; j += 4) {
-                const f4 d = *reinterpret_cast<const f4*>(a.dct_half + ci * NH + j);
+                const f32x4 d = *reinterpret_cast<const f32x4*>(a.dct_half + ci * NH + j);
                 drow[j] = d[0]; drow[j + 1] = d[1]; drow[j + 2] = d[2]; drow[j + 3] = d[3];
             }
         }
@@ -425,9 +425,9 @@ fe400_kernel(Fe400Args a) {
         // ---------------- M_dB out (float4 rows) and the sum / difference halves for the DCT
         {
             const bool clip = a.clip != 0;
-            f4* o = reinterpret_cast<f4*>(a.mel_db + (row0 + fo) * NM);
+            f32x4* o = reinterpret_cast<f32x4*>(a.mel_db + (row0 + fo) * NM);
             for (int i = tid; i < nrows * (NM / 4); i += NT) {
-                f4 v = *reinterpret_cast<const f4*>(Mc + NM + 4 * i);
+                f32x4 v = *reinterpret_cast<const f32x4*>(Mc + NM + 4 * i);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float w = mS * (v[e] - mM);
@@ -449,11 +449,11 @@ fe400_kernel(Fe400Args a) {
         if (tid < 240) {
             const float norm = a.mfcc_norm;
             for (int gg = cf; gg < G; gg += 6) {
-                const f4* sd = reinterpret_cast<const f4*>(SD + gg * NM + (ci & 1) * NH);
+                const f32x4* sd = reinterpret_cast<const f32x4*>(SD + gg * NM + (ci & 1) * NH);
                 float acc4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int j = 0; j < NH / 4; ++j) {
-                    const f4 s = sd[j];
+                    const f32x4 s = sd[j];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc4[e] = fmaf(drow[4 * j + e], s[e], acc4[e]);
                 }
@@ -469,18 +469,18 @@ fe400_kernel(Fe400Args a) {
         {
             const bool clip = a.clip != 0;
             const int mw = a.deriv ? 2 * NC : NC;
-            f4* o = reinterpret_cast<f4*>(a.mfcc + (row0 + fo) * mw);
+            f32x4* o = reinterpret_cast<f32x4*>(a.mfcc + (row0 + fo) * mw);
             const int per_row = mw / 4;
             for (int i = tid; i < nrows * per_row; i += NT) {
                 const int gg = i / per_row, c = 4 * (i - gg * per_row);
                 const int f = fo + gg;
-                f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+                f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (f < F) {
                     if (c < NC) {
-                        v = *reinterpret_cast<const f4*>(Mf + (gg + 1) * NC + c);
+                        v = *reinterpret_cast<const f32x4*>(Mf + (gg + 1) * NC + c);
                     } else if (f >= 1 && f <= F - 2) {
-                        const f4 nx = *reinterpret_cast<const f4*>(Mf + (gg + 2) * NC + (c - NC));
-                        const f4 pv = *reinterpret_cast<const f4*>(Mf + gg * NC + (c - NC));
+                        const f32x4 nx = *reinterpret_cast<const f32x4*>(Mf + (gg + 2) * NC + (c - NC));
+                        const f32x4 pv = *reinterpret_cast<const f32x4*>(Mf + gg * NC + (c - NC));
                         v = 2.0f * (nx - pv);
                     }
                     if (clip) {
@@ -677,8 +677,8 @@ fe400_fused_kernel(Fe400Args a) {
                 const int ri = has_im ? g3l * 12 + k13 - 1 : 0;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const f4 vr = *reinterpret_cast<const f4*>(are_w + r * RP + 4 * q);
-                    const f4 vi = *reinterpret_cast<const f4*>(aim_w + ri * RP + 4 * q);
+                    const f32x4 vr = *reinterpret_cast<const f32x4*>(are_w + r * RP + 4 * q);
+                    const f32x4 vi = *reinterpret_cast<const f32x4*>(aim_w + ri * RP + 4 * q);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { zr[4 * q + e] = vr[e]; zi[4 * q + e] = has_im ? vi[e] : 0.0f; }
                 }
@@ -857,7 +857,7 @@ fe400_fused_kernel(Fe400Args a) {
     if (tid_c < 240) {
 #pragma unroll
         for (int j = 0; j < NH; j += 4) {
-            const f4 d = *reinterpret_cast<const f4*>(a.dct_half + ci * NH + j);
+            const f32x4 d = *reinterpret_cast<const f32x4*>(a.dct_half + ci * NH + j);
             drow[j] = d[0]; drow[j + 1] = d[1]; drow[j + 2] = d[2]; drow[j + 3] = d[3];
         }
     }
@@ -890,9 +890,9 @@ fe400_fused_kernel(Fe400Args a) {
     // ---------------- M_dB out (float4 rows) and the sum / difference halves for the DCT
     {
         const bool clip = a.clip != 0;
-        f4* o = reinterpret_cast<f4*>(a.mel_db + (row0 + fo) * NM);
+        f32x4* o = reinterpret_cast<f32x4*>(a.mel_db + (row0 + fo) * NM);
         for (int i = tid_c; i < nrows * (NM / 4); i += NT) {
-            f4 v = *reinterpret_cast<const f4*>(Mc + NM + 4 * i);
+            f32x4 v = *reinterpret_cast<const f32x4*>(Mc + NM + 4 * i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float w = mS * (v[e] - mM);
@@ -914,11 +914,11 @@ fe400_fused_kernel(Fe400Args a) {
     if (tid_c < 240) {
         const float norm = a.mfcc_norm;
         for (int gg = cf; gg < G; gg += 6) {
-            const f4* sd = reinterpret_cast<const f4*>(SD + gg * NM + (ci & 1) * NH);
+            const f32x4* sd = reinterpret_cast<const f32x4*>(SD + gg * NM + (ci & 1) * NH);
             float acc4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int j = 0; j < NH / 4; ++j) {
-                const f4 sv = sd[j];
+                const f32x4 sv = sd[j];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc4[e] = fmaf(drow[4 * j + e], sv[e], acc4[e]);
             }
@@ -933,18 +933,18 @@ fe400_fused_kernel(Fe400Args a) {
     // ---------------- [MFCC | delta] out
     {
         const bool clip = a.clip != 0;
-        f4* o = reinterpret_cast<f4*>(a.mfcc + (row0 + fo) * mw);
+        f32x4* o = reinterpret_cast<f32x4*>(a.mfcc + (row0 + fo) * mw);
         const int per_row = mw / 4;
         for (int i = tid_c; i < nrows * per_row; i += NT) {
             const int gg = i / per_row, c = 4 * (i - gg * per_row);
             const int f = fo + gg;
-            f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
             if (f < F) {
                 if (c < NC) {
-                    v = *reinterpret_cast<const f4*>(Mf + (gg + 1) * NC + c);
+                    v = *reinterpret_cast<const f32x4*>(Mf + (gg + 1) * NC + c);
                 } else if (f >= 1 && f <= F - 2) {
-                    const f4 nx = *reinterpret_cast<const f4*>(Mf + (gg + 2) * NC + (c - NC));
-                    const f4 pv = *reinterpret_cast<const f4*>(Mf + gg * NC + (c - NC));
+                    const f32x4 nx = *reinterpret_cast<const f32x4*>(Mf + (gg + 2) * NC + (c - NC));
+                    const f32x4 pv = *reinterpret_cast<const f32x4*>(Mf + gg * NC + (c - NC));
                     v = 2.0f * (nx - pv);
                 }
                 if (clip) {

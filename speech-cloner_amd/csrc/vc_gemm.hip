@@ -18,15 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
-#include "vc_common.h"
+#include "vc_device.h"
 #include "vc_bank256.h"
 #include "vc_conv256.h"
 
-namespace {
+using vc::f32x16, vc::f32x4, vc::bf16x8;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+namespace {
 
 constexpr int BN = 128;                        // block tile: (64*MI) x 128, MI = 1 or 2
 constexpr int ROWB = 144;                      // LDS row pitch in bytes (128 data + 16 pad)
@@ -77,15 +75,6 @@ __device__ __forceinline__ bool drop_keep_elem(unsigned long long idx, unsigned 
     return (float)(unsigned)(x >> 40) < keep * 16777216.0f;
 }
 
-__device__ __forceinline__ float act_fn(float v, int act) {
-    switch (act) {
-        case VC_ACT_RELU: return fmaxf(v, 0.0f);
-        case VC_ACT_SIGMOID: return 1.0f / (1.0f + __expf(-v));
-        case VC_ACT_TANH: return tanhf(v);
-        default: return v;
-    }
-}
-
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(__bf16 v) { return (float)v; }
 
@@ -124,19 +113,6 @@ __device__ __forceinline__ bf16x8 vmax(bf16x8 a, bf16x8 b) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) a[e] = ((float)a[e] >= (float)b[e]) ? a[e] : b[e];
     return a;
-}
-// max of values that are >= 0 (post-ReLU), either zero included: for them IEEE ordering == SIGNED integer ordering
-// of the bit patterns (-0.0 is the most negative integer, so it loses to every other such value, where the
-// unsigned order would rank it above all of them), so bf16 pairs go through v_pk_max_i16 and f32 through v_max_i32.
-typedef short i16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 vmax_nonneg(bf16x8 a, bf16x8 b) {
-    const i16x8 r = __builtin_elementwise_max(__builtin_bit_cast(i16x8, a), __builtin_bit_cast(i16x8, b));
-    return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ f32x4 vmax_nonneg(f32x4 a, f32x4 b) {
-    const i32x4 r = __builtin_elementwise_max(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b));
-    return __builtin_bit_cast(f32x4, r);
 }
 
 template <typename T, int MI> struct Mma;
@@ -227,7 +203,7 @@ __device__ __forceinline__ void epilogue_tile(const KArgs& a, const KGroup& grp,
             for (int r = 0; r < 16; ++r) {
                 const int lrow = row_w + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 const int gm = min(m0 + lrow, a.M - 1);
-                float v = act_fn(acc[mi][ni][r] * s + b, a.act);
+                float v = vc::act_fn(acc[mi][ni][r] * s + b, a.act);
                 if (a.drop_keep > 0.0f)
                     v = drop_keep_elem((unsigned long long)gm * a.ldc + oc, a.drop_seed, a.drop_keep) ? v / a.drop_keep : 0.0f;
                 if (a.R) v += to_f32(reinterpret_cast<const T*>(a.R)[(size_t)gm * a.ldr + gn]);
@@ -357,7 +333,7 @@ gemm_kernel(KArgs a) {
             if (PRO >= 1) {
                 vec_t v2 = ra2[p];
                 if (PRO == 2) v2 = pro_apply(v2, a.pro_scale, a.pro_shift, st_c, a.pro_relu);
-                if (pool) v = nonneg ? vmax_nonneg(v, v2) : vmax(v, v2);
+                if (pool) v = nonneg ? vc::max_nonneg(v, v2) : vmax(v, v2);
             }
             *reinterpret_cast<vec_t*>(As + (sr + 32 * p) * ROWB + sc * 16) = ((okbits >> p) & 1u) ? v : zero;
         }
@@ -527,7 +503,7 @@ conv_kernel(KArgs a) {
             if (PRO >= 1) {
                 vec_t v2 = ra2[p];
                 if (PRO == 2) v2 = pro_apply(v2, a.pro_scale, a.pro_shift, c, a.pro_relu);
-                if (pool) v = nonneg ? vmax_nonneg(v, v2) : vmax(v, v2);
+                if (pool) v = nonneg ? vc::max_nonneg(v, v2) : vmax(v, v2);
             }
             if (a_in[p]) *reinterpret_cast<vec_t*>(As + swz(sr + 32 * p, sc)) = v;
         }
@@ -645,12 +621,7 @@ conv_kernel(KArgs a) {
 
 template <typename T, int PRO> int launch_conv(const vc_gemm_desc* d, const KArgs& ka, hipStream_t st) {
     const int ntm = (d->M + 127) / 128, ntn = (d->N + BN - 1) / BN;
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_kernel<T, PRO>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, conv_lds_bytes()));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<conv_kernel<T, PRO>>(conv_lds_bytes())) return rc;
     hipLaunchKernelGGL((conv_kernel<T, PRO>), dim3(ntm * ntn, d->sum_groups ? d->sum_groups : d->n_groups), dim3(GEMM_THREADS), conv_lds_bytes(), st, ka);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
@@ -821,12 +792,7 @@ template <typename T, int MODE, int MI, int PRO> int launch_one(const vc_gemm_de
     constexpr int BM = 64 * MI;
     const int ntm = (d->M + BM - 1) / BM, ntn = (d->N + BN - 1) / BN;
     dim3 grid(ntm * ntn, d->n_groups), block(GEMM_THREADS);
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<T, MODE, MI, PRO>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(MI)));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<gemm_kernel<T, MODE, MI, PRO>>(lds_bytes(MI))) return rc;
     hipLaunchKernelGGL((gemm_kernel<T, MODE, MI, PRO>), grid, block, lds_bytes(MI), st, ka);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
@@ -1051,12 +1017,7 @@ extern "C" int vc_conv_wgrad(const vc_wgrad_desc* d, void* stream) {
         const int tiles = ((gg.taps * d->Cin + 127) / 128) * ((gg.N + BN - 1) / BN);
         if (tiles > max_tiles) max_tiles = tiles;
     }
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes(2)));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<wgrad_kernel>(lds_bytes(2))) return rc;
     // Small grids (dense / highway / GRU filters) would run hundreds of K slabs serially on a few
     // CUs: split the frame range over gridDim.z until ~2 blocks per CU exist.  The caller zeroes dW
     // when it passes splits_allowed (atomic accumulation); the summation order is then not fixed.

@@ -20,14 +20,11 @@
 //   * K split over up to 8 workgroups per row tile for single-pair launches (every workgroup publishes its accumulators
 //     write-through, then takes a ticket; the last one adds the slabs in split order -- bit-identical run to run).
 #include <cstdlib>
-#include "vc_common.h"
+#include "vc_device.h"
+
+using vc::f32x16, vc::f32x4, vc::f16x8, vc::f16x4, vc::u32x4;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 512;
 constexpr int BM = 256;
@@ -67,11 +64,6 @@ struct G16Args {
     unsigned* tick;       // [row tiles] arrival counters, zeroed by the launcher before every launch
     G16Pair p[16];
 };
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(uintptr_t)g,
-                                     (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)l, 16, 0, 0);
-}
 
 // Position of the K walk (all wave-uniform): K slab cs = plane * nsl + cr, tap j of the slab's `taps`, left padding `pad`.
 struct Walk { int cs, cr, plane, j, taps, pad; };
@@ -183,7 +175,7 @@ gemm16_kernel(G16Args a) {
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
             const int rb = q * 8 + wid;
-            if (rb * 8 < a_rows_needed && rb < A_ROWS / 8) glds16(a_src[q] + xo, dst + q * 8192);
+            if (rb * 8 < a_rows_needed && rb < A_ROWS / 8) vc::glds16(a_src[q] + xo, dst + q * 8192);
         }
     };
     auto stageB = [&](const Walk& w, int buf) {
@@ -199,7 +191,7 @@ gemm16_kernel(G16Args a) {
         char* dst = Bs + buf * B_BYTES + wid * 1024;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (q >= 2 ? !half_only : w.j < narrow) glds16(b_src[q] + (q < 2 ? koffL : koffR), dst + q * 8192);
+            if (q >= 2 ? !half_only : w.j < narrow) vc::glds16(b_src[q] + (q < 2 ? koffL : koffR), dst + q * 8192);
     };
 
     // ---------------- MFMA roles
@@ -220,13 +212,7 @@ gemm16_kernel(G16Args a) {
     }
     int S_lo = max(max(slo[0], slo[1]), max(slo[2], slo[3]));
     int S_hi = min(min(shi[0], shi[1]), min(shi[2], shi[3]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        S_lo = max(S_lo, __shfl_xor(S_lo, o, 64));
-        S_hi = min(S_hi, __shfl_xor(S_hi, o, 64));
-    }
-    S_lo = __builtin_amdgcn_readfirstlane(S_lo);
-    S_hi = __builtin_amdgcn_readfirstlane(S_hi);
+    vc::wave_tap_range(S_lo, S_hi);
     const bool left_wave = wc < 2;
 
     f32x16 acc[4][2];
@@ -364,7 +350,6 @@ gemm16_kernel(G16Args a) {
         // one finds every slab of the row tile published, acquires, and sums them in split order -- its own included, so
         // the result does not depend on who was last.  Nobody waits for anybody (cdna_hip_programming.md Guideline 16).
         typedef __attribute__((address_space(1))) unsigned gu32;
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         gu32* const tk = (gu32*)(uintptr_t)(a.tick + rt);
         int* const tsh = reinterpret_cast<int*>(smem);
         const int voff = (wid * 32 * 64 + lane) * 16;              // + ((i*2 + c)*4 + q) * 1024
@@ -380,7 +365,7 @@ gemm16_kernel(G16Args a) {
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const f32x4v v = {acc[i][c][4 * q], acc[i][c][4 * q + 1], acc[i][c][4 * q + 2], acc[i][c][4 * q + 3]};
+                        const f32x4 v = {acc[i][c][4 * q], acc[i][c][4 * q + 1], acc[i][c][4 * q + 2], acc[i][c][4 * q + 3]};
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs,
                                                                voff + ((i * 2 + c) * 4 + q) * 1024, 0, 16);     // aux 16 = sc1
                     }
@@ -401,7 +386,7 @@ gemm16_kernel(G16Args a) {
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const f32x4v v = *reinterpret_cast<const __attribute__((address_space(1))) f32x4v*>(sp + ((i * 2 + c) * 4 + q) * 1024);
+                        const f32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>(sp + ((i * 2 + c) * 4 + q) * 1024);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) acc[i][c][4 * q + e] = sl == 0 ? v[e] : acc[i][c][4 * q + e] + v[e];
                     }
@@ -428,7 +413,7 @@ gemm16_kernel(G16Args a) {
                     const float4 bv = *reinterpret_cast<const float4*>(smem + COEF_OFF + 1024 + chp * 4);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        f32x4v o;
+                        f32x4 o;
                         o[0] = fmaf(acc[i][c][4 * q + 0] * rsc[i], sv.x, bv.x);
                         o[1] = fmaf(acc[i][c][4 * q + 1] * rsc[i], sv.y, bv.y);
                         o[2] = fmaf(acc[i][c][4 * q + 2] * rsc[i], sv.z, bv.z);
@@ -437,7 +422,7 @@ gemm16_kernel(G16Args a) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.0f);
                         }
-                        *reinterpret_cast<f32x4v*>(smem + (i * 32 + li) * EP + chp * 4) = o;
+                        *reinterpret_cast<f32x4*>(smem + (i * 32 + li) * EP + chp * 4) = o;
                     }
                 }
             }
@@ -461,11 +446,11 @@ gemm16_kernel(G16Args a) {
                 const int h = it * 16 + hr;                    // half-row index: row = h >> 1, half = h & 1
                 const int row = h >> 1, half = h & 1;
                 const int lm = rt * BM + pass * 128 + row;     // output row, counted from the pair's row0
-                f32x4v vv = *reinterpret_cast<const f32x4v*>(smem + row * EP + half * 512 + l32 * 16);
+                f32x4 vv = *reinterpret_cast<const f32x4*>(smem + row * EP + half * 512 + l32 * 16);
                 if (lm < (half ? pr.nrows1 : pr.nrows0)) {
-                    f32x4v* dst = reinterpret_cast<f32x4v*>(a.Cout + (size_t)lm * a.ldc + (half ? pr.c_off1 : pr.c_off0) + l32 * 4);
+                    f32x4* dst = reinterpret_cast<f32x4*>(a.Cout + (size_t)lm * a.ldc + (half ? pr.c_off1 : pr.c_off0) + l32 * 4);
                     if (a.accumulate) {
-                        const f32x4v old = *dst;
+                        const f32x4 old = *dst;
                         vv += old;
                         *dst = vv;
                     } else {
@@ -756,7 +741,7 @@ transpose_split16_kernel(const float* __restrict__ X, int M, int C, int ldx, int
     }
 }
 
-static size_t tick_bytes(int ntm) { return ((size_t)ntm * 4 + 255) & ~(size_t)255; }
+static size_t tick_bytes(int ntm) { return vc::align256((size_t)ntm * 4); }
 
 // K slabs of one plane product walk; how many ways a single-pair launch splits them
 static int choose_ksplit(int M, int n_pairs, int kslabs) {
@@ -844,12 +829,7 @@ int vc_gemm16(const vc_gemm16_desc* d, void* stream) {
     VC_REQUIRE(d->atomic_splits >= 0 && d->atomic_splits <= MAX_SPLIT && !(atomic && (d->d_col_shift || d->ragged)),
                "vc_gemm16: atomic_splits 0..8, without col_shift / ragged");
     VC_REQUIRE((reinterpret_cast<uintptr_t>(d->d_X16) & 15) == 0 && (reinterpret_cast<uintptr_t>(d->d_C) & 15) == 0, "vc_gemm16: unaligned");
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<gemm16_kernel>(LDS_BYTES)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     G16Args a{};
     a.X = d->d_X16; a.row_scale = d->d_row_scale; a.M = d->M; a.T = d->T; a.C = d->C; a.ldx = d->ldx;

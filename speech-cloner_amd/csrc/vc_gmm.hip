@@ -36,7 +36,7 @@
 // No atomics, no memset, no hand-off between workgroups; fixed geometry and fixed orders: every output is bit-identical
 // from run to run and under graph replay, and the score figures of an utterance do not depend on its batch.
 #include <cmath>
-#include "vc_common.h"
+#include "vc_device.h"
 
 namespace {
 
@@ -51,7 +51,6 @@ constexpr int CHUNK = 64;               // components per accumulate workgroup
 constexpr int PARTS = 128;              // frame partitions of one group when G = 1
 constexpr int DQ = MAX_D / 4;           // dimensions per lane of the accumulate kernel
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int n_parts(int G) { return G >= PARTS ? 1 : PARTS / G; }
 __host__ __device__ inline size_t blk_doubles(int D) { return (size_t)CHUNK * (1 + 2 * D) + 1; }
 
@@ -435,7 +434,7 @@ size_t vc_gmm_workspace_bytes(int32_t n_groups, int32_t M, int32_t D) {
     if (n_groups < 1 || n_groups > MAX_S || M < 1 || D < 1 || !gmm_shape_ok(n_groups, M, D)) return 0;
     const int P = n_parts(n_groups);
     if (P == 1) return 0;
-    return align256((size_t)n_groups * P * ((M + CHUNK - 1) / CHUNK) * blk_doubles(D) * sizeof(double));
+    return vc::align256((size_t)n_groups * P * ((M + CHUNK - 1) / CHUNK) * blk_doubles(D) * sizeof(double));
 }
 
 int vc_spk_features_f32(const float* d_cep, const int32_t* d_len, const uint8_t* d_mask, int32_t batch, int32_t max_frames,

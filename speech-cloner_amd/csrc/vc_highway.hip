@@ -17,14 +17,11 @@
 // 4-deep register ring ahead of the MFMAs) -- LDS holds nothing but the activation tile.
 // LDS image: rows of H bf16; the 16-byte slot s of row r sits at slot s ^ (r & 15), so the 16 rows
 // of a ds_read_b128 lane group hit 16 different bank groups.
-#include "vc_common.h"
+#include "vc_device.h"
+
+using vc::f32x16, vc::f32x4, vc::bf16x8, vc::bf16x4;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4h __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HW_BM = 128;
 constexpr int HW_MAX_LAYERS = 8;
@@ -153,11 +150,11 @@ highway_chain_kernel(HwChainArgs a) {
 #endif
         HW_T(1);
         // ---- gate (lane-local) -> next activation tile
-        f32x4h bH[4], bT[4];
+        f32x4 bH[4], bT[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            bH[q] = *reinterpret_cast<const f32x4h*>(bias_s + layer * 2 * H + w * 64 + 8 * q + 4 * lh);
-            bT[q] = *reinterpret_cast<const f32x4h*>(bias_s + layer * 2 * H + w * 64 + 32 + 8 * q + 4 * lh);
+            bH[q] = *reinterpret_cast<const f32x4*>(bias_s + layer * 2 * H + w * 64 + 8 * q + 4 * lh);
+            bT[q] = *reinterpret_cast<const f32x4*>(bias_s + layer * 2 * H + w * 64 + 32 + 8 * q + 4 * lh);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -205,7 +202,7 @@ highway_chain_kernel(HwChainArgs a) {
             for (int c = 0; c < 2; ++c)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const f32x4h bb = *reinterpret_cast<const f32x4h*>(a.Pbias + grp * 64 + c * 32 + 8 * q + 4 * lh);
+                    const f32x4 bb = *reinterpret_cast<const f32x4*>(a.Pbias + grp * 64 + c * 32 + 8 * q + 4 * lh);
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -217,17 +214,17 @@ highway_chain_kernel(HwChainArgs a) {
                 for (int c = 0; c < 2; ++c)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        f32x4h o;
+                        f32x4 o;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = acc[i][c][4 * q + e];
-                        *reinterpret_cast<f32x4h*>(stg + li * 256 + (((c * 8 + 2 * q + lh) ^ x15) << 4)) = o;
+                        *reinterpret_cast<f32x4*>(stg + li * 256 + (((c * 8 + 2 * q + lh) ^ x15) << 4)) = o;
                     }
 #pragma unroll 2
                 for (int j = 0; j < 8; ++j) {
                     const int row = j * 4 + (lane >> 4), ch = lane & 15;
-                    const f32x4h v = *reinterpret_cast<const f32x4h*>(stg + row * 256 + ((ch ^ (row & 15)) << 4));
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(stg + row * 256 + ((ch ^ (row & 15)) << 4));
                     const int gm = m0 + i * 32 + row;
-                    if (gm < a.M) *reinterpret_cast<f32x4h*>(a.P + (size_t)gm * a.ldp + grp * 64 + ch * 4) = v;
+                    if (gm < a.M) *reinterpret_cast<f32x4*>(a.P + (size_t)gm * a.ldp + grp * 64 + ch * 4) = v;
                 }
             }
         }
@@ -252,12 +249,7 @@ highway_chain_kernel(HwChainArgs a) {
 
 template <int H> int launch_chain(const HwChainArgs& a, hipStream_t st) {
     constexpr int LDS = 2 * HW_BM * 2 * H + HW_MAX_LAYERS * 2 * H * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(highway_chain_kernel<H>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<highway_chain_kernel<H>>(LDS)) return rc;
     hipLaunchKernelGGL(highway_chain_kernel<H>, dim3((a.M + HW_BM - 1) / HW_BM), dim3(2 * H), LDS, st, a);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;

@@ -23,13 +23,12 @@
 // k = 32 + 16h .. 32 + 16h + 15 in bytes 16..31; its scale byte is that of K block h (k = 32h .. 32h + 31) of row r.
 #include <algorithm>
 #include <cstdlib>
-#include "vc_common.h"
+#include "vc_device.h"
 #include "vc_mx8.h"
 
-namespace {
+using vc::f32x16, vc::i32x8;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
+namespace {
 
 constexpr int NT = 256;
 constexpr int TILE = 128;            // frames per workgroup

@@ -12,15 +12,14 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
-#include "vc_common.h"
+#include "vc_device.h"
+
+using vc::f32x4, vc::bf16x8, vc::bf16x4, vc::bf16x2;
 
 namespace {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ float ld_w(const float* p) { return *p; }
 __device__ __forceinline__ float ld_w(const __bf16* p) { return (float)*p; }
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 // bf16 recurrences: v_exp_f32 + v_rcp_f32 (1 ulp each) instead of libm tanhf / IEEE division --
 // the gate arithmetic of 16 sequences lands on one CU in the MFMA kernel, so it must be cheap.
 __device__ __forceinline__ float fast_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
@@ -86,7 +85,7 @@ gru_generic_kernel(GruArgs a) {
         }
         for (int o = KS1 >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
         if (act1 && ks1 == 0) {
-            const float g = sigmoidf_(acc + xg);
+            const float g = vc::sigmoidf_(acc + xg);
             if (col1 < H) rh[col1] = g * h[col1];       // r first (GRUCell split order)
             else u[col1 - H] = g;
         }
@@ -162,8 +161,8 @@ lstm_generic_kernel(LstmArgs a) {
         }
         __syncthreads();
         if (tid < H) {
-            const float gi = sigmoidf_(z[tid]), gj = tanhf(z[H + tid]);
-            const float gf = sigmoidf_(z[2 * H + tid] + 1.0f), go = sigmoidf_(z[3 * H + tid]);
+            const float gi = vc::sigmoidf_(z[tid]), gj = tanhf(z[H + tid]);
+            const float gf = vc::sigmoidf_(z[2 * H + tid] + 1.0f), go = vc::sigmoidf_(z[3 * H + tid]);
             c = gf * c + gi * gj;
             const float hn = go * tanhf(c);
             h[tid] = hn;
@@ -184,8 +183,6 @@ lstm_generic_kernel(LstmArgs a) {
 //            columns), KS1 = NT / 2H adjacent lanes are summed with DPP-style shuffles;
 //   phase 2: thread (col2 = tid / KS2, ks2) the same for the H candidate columns, KS2 = NT / H.
 // Two barriers per step; h_old of a column lives in the owning thread's register.
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // Weights arrive PRE-PACKED by gru_pack_kernel in the exact register order:
 //   packed[dir][chunk c][thread tid][EPC elements]  (one 16-byte chunk per lane => coalesced)
@@ -195,9 +192,9 @@ template <typename WT> struct Res;
 template <> struct Res<__bf16> {
     static constexpr int EPC = 8;                            // elements per 16-byte chunk
     typedef __bf16 hstore_t;
-    typedef bf16x8v chunk_t;
+    typedef bf16x8 chunk_t;
     static __device__ __forceinline__ void dot(const chunk_t& w, const __bf16* hs, float& a0, float& a1) {
-        const bf16x8v hv = *reinterpret_cast<const bf16x8v*>(hs);
+        const bf16x8 hv = *reinterpret_cast<const bf16x8*>(hs);
         const bf16x2 w0 = {w[0], w[1]}, w1 = {w[2], w[3]}, w2 = {w[4], w[5]}, w3 = {w[6], w[7]};
         const bf16x2 h0 = {hv[0], hv[1]}, h1 = {hv[2], hv[3]}, h2 = {hv[4], hv[5]}, h3 = {hv[6], hv[7]};
         a0 = __builtin_amdgcn_fdot2_f32_bf16(w0, h0, a0, false);
@@ -209,9 +206,9 @@ template <> struct Res<__bf16> {
 template <> struct Res<float> {
     static constexpr int EPC = 4;
     typedef float hstore_t;
-    typedef f32x4v chunk_t;
+    typedef f32x4 chunk_t;
     static __device__ __forceinline__ void dot(const chunk_t& w, const float* hs, float& a0, float& a1) {
-        const f32x4v hv = *reinterpret_cast<const f32x4v*>(hs);
+        const f32x4 hv = *reinterpret_cast<const f32x4*>(hs);
         a0 = fmaf(w[0], hv[0], a0);
         a1 = fmaf(w[1], hv[1], a1);
         a0 = fmaf(w[2], hv[2], a0);
@@ -307,7 +304,7 @@ gru_resident_kernel(GruArgs a, const WT* packed) {
 #pragma unroll
         for (int o = KS1 >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
         if (ks1 == 0) {
-            const float g = (sizeof(WT) == 2) ? fast_sigmoid(acc + xg) : sigmoidf_(acc + xg);
+            const float g = (sizeof(WT) == 2) ? fast_sigmoid(acc + xg) : vc::sigmoidf_(acc + xg);
             if (col1 < H) {
                 const int s = col1 / KL2, off = col1 - s * KL2;
                 rhb[s * (KL2 + P) + off] = (hs_t)(g * hf[col1]);
@@ -363,7 +360,6 @@ int launch_resident(const GruArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
 // pair live in the same lane and register, so the whole gate arithmetic is lane-local; only r*h
 // and h cross waves (LDS, two barriers per step).  The matrix work of a step costs 3H^2*16 MAC
 // at 2048 MAC/clk/CU = 0.64 us (H = 256), independent of how many of the 16 slots are used.
-typedef float f32x4m __attribute__((ext_vector_type(4)));
 
 template <int H> struct MfGeom {
     static constexpr int NW = 8, UW = H / NW, TPW = UW / 16, KSN = H / 32;
@@ -420,19 +416,19 @@ gru_mfma_kernel(GruArgs a, const __bf16* packed) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __bf16* hb = reinterpret_cast<__bf16*>(smem);                 // [16][PITCH]
     __bf16* rhb = hb + 16 * PITCH;                                // [16][PITCH]
-    bf16x8v* candL = reinterpret_cast<bf16x8v*>(rhb + 16 * PITCH);   // [NW][NF_C][64] when CAND_LDS
+    bf16x8* candL = reinterpret_cast<bf16x8*>(rhb + 16 * PITCH);   // [NW][NF_C][64] when CAND_LDS
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int dir = blockIdx.y, seq0 = blockIdx.x * 16;
     const int n = lane & 15, q = lane >> 4;
     const int seq = min(seq0 + n, a.n_seq - 1);
     const bool seq_ok = (seq0 + n) < a.n_seq;
-    const bf16x8v* pk = reinterpret_cast<const bf16x8v*>(packed) + ((size_t)(dir * G::NW + wave) * G::NF) * 64 + lane;
+    const bf16x8* pk = reinterpret_cast<const bf16x8*>(packed) + ((size_t)(dir * G::NW + wave) * G::NF) * 64 + lane;
 
-    bf16x8v wg[G::NF_G];
+    bf16x8 wg[G::NF_G];
 #pragma unroll
     for (int f = 0; f < G::NF_G; ++f) wg[f] = pk[(size_t)f * 64];
-    bf16x8v wc[G::CAND_LDS ? 1 : G::NF_C];
+    bf16x8 wc[G::CAND_LDS ? 1 : G::NF_C];
     if (G::CAND_LDS) {
 #pragma unroll
         for (int f = 0; f < G::NF_C; ++f) candL[(wave * G::NF_C + f) * 64 + lane] = pk[(size_t)(G::NF_G + f) * 64];
@@ -453,13 +449,13 @@ gru_mfma_kernel(GruArgs a, const __bf16* packed) {
     const float* xbase = a.xproj + (size_t)seq * a.T * xrow + (size_t)dir * H3 + ucol;
     int t = dir ? a.T - 1 : 0;
     const int dt = dir ? -1 : 1;
-    f32x4m xr[TPW], xu[TPW], xc[TPW];
+    f32x4 xr[TPW], xu[TPW], xc[TPW];
 #pragma unroll
     for (int tl = 0; tl < TPW; ++tl) {
         const float* xp = xbase + (size_t)t * xrow + tl * 16;
-        xr[tl] = *reinterpret_cast<const f32x4m*>(xp);
-        xu[tl] = *reinterpret_cast<const f32x4m*>(xp + H);
-        xc[tl] = *reinterpret_cast<const f32x4m*>(xp + 2 * H);
+        xr[tl] = *reinterpret_cast<const f32x4*>(xp);
+        xu[tl] = *reinterpret_cast<const f32x4*>(xp + H);
+        xc[tl] = *reinterpret_cast<const f32x4*>(xp + 2 * H);
     }
     __syncthreads();
 
@@ -474,16 +470,16 @@ gru_mfma_kernel(GruArgs a, const __bf16* packed) {
         const float* xn = xbase + (size_t)(more ? t + dt : t) * xrow;
         // ---- phase 1: r and u pre-activations.  All h fragments are fetched up front so the MFMA
         // chain never waits on an LDS read it has just issued.
-        bf16x8v bfr[KSN];
+        bf16x8 bfr[KSN];
 #pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8v*>(hrow + ks * 32);
-        f32x4m ar[TPW], au[TPW];
+        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(hrow + ks * 32);
+        f32x4 ar[TPW], au[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
             ar[tl] = xr[tl];
             au[tl] = xu[tl];
-            xr[tl] = *reinterpret_cast<const f32x4m*>(xn + tl * 16);          // next step's, in place
-            xu[tl] = *reinterpret_cast<const f32x4m*>(xn + tl * 16 + H);
+            xr[tl] = *reinterpret_cast<const f32x4*>(xn + tl * 16);          // next step's, in place
+            xu[tl] = *reinterpret_cast<const f32x4*>(xn + tl * 16 + H);
         }
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks) {
@@ -497,42 +493,40 @@ gru_mfma_kernel(GruArgs a, const __bf16* packed) {
         float uu[TPW][4];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
-            typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-            bf16x4v o;
+            bf16x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float r = fast_sigmoid(ar[tl][e]);
                 uu[tl][e] = fast_sigmoid(au[tl][e]);
                 o[e] = (__bf16)(r * hreg[tl][e]);
             }
-            *reinterpret_cast<bf16x4v*>(rhb + n * PITCH + ucol + tl * 16) = o;
+            *reinterpret_cast<bf16x4*>(rhb + n * PITCH + ucol + tl * 16) = o;
         }
         GRU_T(1);                                                    // MFMA results waited for, sigmoids, r*h stored
         GRU_LDS_BARRIER();
         GRU_T(2);                                                    // barrier A
         // ---- phase 2: candidate, state update
 #pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8v*>(rrow + ks * 32);
-        f32x4m ac[TPW];
+        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(rrow + ks * 32);
+        f32x4 ac[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
             ac[tl] = xc[tl];
-            xc[tl] = *reinterpret_cast<const f32x4m*>(xn + tl * 16 + 2 * H);
+            xc[tl] = *reinterpret_cast<const f32x4*>(xn + tl * 16 + 2 * H);
         }
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks) {
 #pragma unroll
             for (int tl = 0; tl < TPW; ++tl) {
-                const bf16x8v w = G::CAND_LDS ? candL[(wave * G::NF_C + tl * KSN + ks) * 64 + lane] : wc[G::CAND_LDS ? 0 : tl * KSN + ks];
+                const bf16x8 w = G::CAND_LDS ? candL[(wave * G::NF_C + tl * KSN + ks) * 64 + lane] : wc[G::CAND_LDS ? 0 : tl * KSN + ks];
                 ac[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, bfr[ks], ac[tl], 0, 0, 0);
             }
         }
         GRU_T(3);                                                    // r*h fragments read, 16 candidate MFMAs issued
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
-            typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-            bf16x4v o;
-            f32x4m hv;
+            bf16x4 o;
+            f32x4 hv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float c = fast_tanh(ac[tl][e]);
@@ -541,11 +535,11 @@ gru_mfma_kernel(GruArgs a, const __bf16* packed) {
                 hv[e] = hn;
                 o[e] = (__bf16)hn;
             }
-            *reinterpret_cast<bf16x4v*>(hb + n * PITCH + ucol + tl * 16) = o;
+            *reinterpret_cast<bf16x4*>(hb + n * PITCH + ucol + tl * 16) = o;
             if (seq_ok) {
                 const size_t oi = ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + ucol + tl * 16;
-                if (a.out_bf16) *reinterpret_cast<bf16x4v*>(reinterpret_cast<__bf16*>(a.out) + oi) = o;
-                else *reinterpret_cast<f32x4m*>(reinterpret_cast<float*>(a.out) + oi) = hv;
+                if (a.out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.out) + oi) = o;
+                else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + oi) = hv;
             }
         }
         GRU_T(4);                                                    // MFMA results waited for, tanh, update, stores issued
@@ -570,12 +564,7 @@ int launch_mfma(const GruArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     hipLaunchKernelGGL((gru_mfma_pack_kernel<H>), dim3(256), dim3(256), 0, st, static_cast<const __bf16*>(a.Wh[0]),
                        static_cast<const __bf16*>(a.Wh[1]), packed);
     const size_t lds = 2 * 16 * (size_t)G::PITCH * 2 + (G::CAND_LDS ? (size_t)G::NW * G::NF_C * 64 * 16 : 0);
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_mfma_kernel<H>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<gru_mfma_kernel<H>>((int)lds)) return rc;
     hipLaunchKernelGGL((gru_mfma_kernel<H>), dim3((a.n_seq + 15) / 16, 2), dim3(512), lds, st, a,
                        static_cast<const __bf16*>(packed));
     VC_HIP_CHECK(hipGetLastError());
@@ -639,11 +628,10 @@ __global__ void __launch_bounds__(256, 1)
 gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
     typedef Mf4Geom<H> G;
     constexpr int TPW = G::TPW, KSN = G::KSN, PITCH = G::PITCH, UW = G::UW, KL = G::KL, KR = G::KR;
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __bf16* hb = reinterpret_cast<__bf16*>(smem);                 // [16][PITCH]
     __bf16* rhb = hb + 16 * PITCH;                                // [16][PITCH]
-    bf16x8v* candL = reinterpret_cast<bf16x8v*>(rhb + 16 * PITCH);   // [NW][TPW][KL][64]
+    bf16x8* candL = reinterpret_cast<bf16x8*>(rhb + 16 * PITCH);   // [NW][TPW][KL][64]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -651,16 +639,16 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
     const int n = lane & 15, q = lane >> 4;
     const int seq = min(seq0 + n, a.n_seq - 1);
     const bool seq_ok = (seq0 + n) < a.n_seq;
-    const bf16x8v* pk = reinterpret_cast<const bf16x8v*>(packed) + ((size_t)(dir * G::NW + wave) * G::NF) * 64 + lane;
+    const bf16x8* pk = reinterpret_cast<const bf16x8*>(packed) + ((size_t)(dir * G::NW + wave) * G::NF) * 64 + lane;
 
-    bf16x8v wr[TPW][KSN], wu[TPW][KSN], wc[TPW][KR];
+    bf16x8 wr[TPW][KSN], wu[TPW][KSN], wc[TPW][KR];
 #pragma unroll
     for (int tl = 0; tl < TPW; ++tl)
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks) {
             wr[tl][ks] = pk[(size_t)((0 * TPW + tl) * KSN + ks) * 64];
             wu[tl][ks] = pk[(size_t)((1 * TPW + tl) * KSN + ks) * 64];
-            const bf16x8v c = pk[(size_t)(G::NF_G + tl * KSN + ks) * 64];
+            const bf16x8 c = pk[(size_t)(G::NF_G + tl * KSN + ks) * 64];
             if (ks < KR) wc[tl][ks < KR ? ks : 0] = c;
             else candL[((wave * TPW + tl) * KL + (ks - KR)) * 64 + lane] = c;
         }
@@ -677,13 +665,13 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
     const float* xbase = a.xproj + (size_t)seq * a.T * xrow + (size_t)dir * H3 + ucol;
     int t = dir ? a.T - 1 : 0;
     const int dt = dir ? -1 : 1;
-    f32x4m xr[TPW], xu[TPW], xc[TPW];
+    f32x4 xr[TPW], xu[TPW], xc[TPW];
 #pragma unroll
     for (int tl = 0; tl < TPW; ++tl) {
         const float* xp = xbase + (size_t)t * xrow + tl * 16;
-        xr[tl] = *reinterpret_cast<const f32x4m*>(xp);
-        xu[tl] = *reinterpret_cast<const f32x4m*>(xp + H);
-        xc[tl] = *reinterpret_cast<const f32x4m*>(xp + 2 * H);
+        xr[tl] = *reinterpret_cast<const f32x4*>(xp);
+        xu[tl] = *reinterpret_cast<const f32x4*>(xp + H);
+        xc[tl] = *reinterpret_cast<const f32x4*>(xp + 2 * H);
     }
     __syncthreads();
 
@@ -708,16 +696,16 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
     for (int step = 0; step < a.T; ++step, t += dt) {
         const float* xn = xbase + (size_t)(step + 1 < a.T ? t + dt : t) * xrow;
         // ---- phase 1: r, then u with r's sigmoids in its gaps
-        bf16x8v bfr[KSN];
+        bf16x8 bfr[KSN];
 #pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8v*>(hrow + ks * 32);
-        f32x4m ar[TPW], au[TPW];
+        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(hrow + ks * 32);
+        f32x4 ar[TPW], au[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
             ar[tl] = xr[tl];
             au[tl] = xu[tl];
-            xr[tl] = *reinterpret_cast<const f32x4m*>(xn + tl * 16);          // next step's, in place
-            xu[tl] = *reinterpret_cast<const f32x4m*>(xn + tl * 16 + H);
+            xr[tl] = *reinterpret_cast<const f32x4*>(xn + tl * 16);          // next step's, in place
+            xu[tl] = *reinterpret_cast<const f32x4*>(xn + tl * 16 + H);
         }
         GRU_T(0);                                                    // requests of the next step's projections issued
 #pragma unroll
@@ -746,10 +734,10 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
         GRU_T(1);                                                    // fragments read, r and u products issued, r's sigmoids
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
-            bf16x4v o;
+            bf16x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (__bf16)rhf[tl][e];
-            *reinterpret_cast<bf16x4v*>(rhb + n * PITCH + ucol + tl * 16) = o;
+            *reinterpret_cast<bf16x4*>(rhb + n * PITCH + ucol + tl * 16) = o;
         }
         GRU_T(2);                                                    // r*h stored
         GRU4_BARRIER();                                              // barrier A: r*h complete
@@ -758,18 +746,18 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
         for (int tl = 0; tl < TPW; ++tl) asm volatile("" : "+v"(au[tl]));      // u's readers: behind the barrier
         // ---- phase 2: candidate (u's sigmoids between its products), state update
 #pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8v*>(rrow + ks * 32);
-        f32x4m ac[TPW];
+        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(rrow + ks * 32);
+        f32x4 ac[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
             ac[tl] = xc[tl];
-            xc[tl] = *reinterpret_cast<const f32x4m*>(xn + tl * 16 + 2 * H);
+            xc[tl] = *reinterpret_cast<const f32x4*>(xn + tl * 16 + 2 * H);
         }
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks)
 #pragma unroll
             for (int tl = 0; tl < TPW; ++tl) {
-                const bf16x8v w = ks < KR ? wc[tl][ks < KR ? ks : 0] : candL[((wave * TPW + tl) * KL + (ks < KR ? 0 : ks - KR)) * 64 + lane];
+                const bf16x8 w = ks < KR ? wc[tl][ks < KR ? ks : 0] : candL[((wave * TPW + tl) * KL + (ks < KR ? 0 : ks - KR)) * 64 + lane];
                 ac[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, bfr[ks], ac[tl], 0, 0, 0);
             }
         float uu[TPW][4];
@@ -777,8 +765,8 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
         for (int tl = 0; tl < TPW; ++tl)
 #pragma unroll
             for (int e = 0; e < 4; ++e) uu[tl][e] = fast_sigmoid(au[tl][e]);
-        bf16x4v ob[TPW];
-        f32x4m hv[TPW];
+        bf16x4 ob[TPW];
+        f32x4 hv[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
 #pragma unroll
@@ -789,18 +777,18 @@ gru_mfma4_kernel(GruArgs a, const __bf16* packed) {
                 hv[tl][e] = hn;
                 ob[tl][e] = (__bf16)hn;
             }
-            *reinterpret_cast<bf16x4v*>(hb + n * PITCH + ucol + tl * 16) = ob[tl];
+            *reinterpret_cast<bf16x4*>(hb + n * PITCH + ucol + tl * 16) = ob[tl];
         }
         GRU_T(4);                                                    // candidate products, u's sigmoids, tanh, update, h stored
         if (seq_ok) {
             if (a.out_bf16) {
 #pragma unroll
                 for (int tl = 0; tl < TPW; ++tl)
-                    *reinterpret_cast<bf16x4v*>(reinterpret_cast<__bf16*>(a.out) + ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + ucol + tl * 16) = ob[tl];
+                    *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.out) + ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + ucol + tl * 16) = ob[tl];
             } else {
 #pragma unroll
                 for (int tl = 0; tl < TPW; ++tl)
-                    *reinterpret_cast<f32x4m*>(reinterpret_cast<float*>(a.out) + ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + ucol + tl * 16) = hv[tl];
+                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + ucol + tl * 16) = hv[tl];
             }
         }
         GRU_T(5);                                                    // output stores issued
@@ -826,12 +814,7 @@ int launch_mfma4(const GruArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     __bf16* packed = static_cast<__bf16*>(ws);
     hipLaunchKernelGGL((gru_mfma4_pack_kernel<H>), dim3(256), dim3(256), 0, st, static_cast<const __bf16*>(a.Wh[0]),
                        static_cast<const __bf16*>(a.Wh[1]), packed);
-    static bool attr_done = false;
-    if (!attr_done) {
-        VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_mfma4_kernel<H>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<gru_mfma4_kernel<H>>((int)G::LDS)) return rc;
     hipLaunchKernelGGL((gru_mfma4_kernel<H>), dim3((a.n_seq + 15) / 16, 2), dim3(256), G::LDS, st, a,
                        static_cast<const __bf16*>(packed));
     VC_HIP_CHECK(hipGetLastError());
@@ -885,7 +868,6 @@ __global__ void __launch_bounds__(64 * MfsGeom<H>::WPB)
 gru_mfma_small_kernel(GruArgs a, const __bf16* packed) {
     typedef MfsGeom<H> G;
     constexpr int TPW = G::TPW, KSN = G::KSN, PITCH = G::PITCH;
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -896,8 +878,8 @@ gru_mfma_small_kernel(GruArgs a, const __bf16* packed) {
     const int n = lane & 15, q = lane >> 4;
     const int seq = min(seq0 + n, a.n_seq - 1);
     const bool seq_ok = (seq0 + n) < a.n_seq;
-    const bf16x8v* pk = reinterpret_cast<const bf16x8v*>(packed) + (size_t)dir * G::NF * 64 + lane;
-    bf16x8v w[3][TPW][KSN];
+    const bf16x8* pk = reinterpret_cast<const bf16x8*>(packed) + (size_t)dir * G::NF * 64 + lane;
+    bf16x8 w[3][TPW][KSN];
 #pragma unroll
     for (int g = 0; g < 3; ++g)
 #pragma unroll
@@ -919,29 +901,29 @@ gru_mfma_small_kernel(GruArgs a, const __bf16* packed) {
     for (int tl = 0; tl < TPW; ++tl) uok[tl] = tl * 16 + q * 4 < H;
     int t = dir ? a.T - 1 : 0;
     const int dt = dir ? -1 : 1;
-    const f32x4m zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-    f32x4m xr[TPW], xu[TPW], xc[TPW];
+    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 xr[TPW], xu[TPW], xc[TPW];
 #pragma unroll
     for (int tl = 0; tl < TPW; ++tl) {
         const float* xp = xbase + (size_t)t * xrow + tl * 16;
-        xr[tl] = uok[tl] ? *reinterpret_cast<const f32x4m*>(xp) : zero4;
-        xu[tl] = uok[tl] ? *reinterpret_cast<const f32x4m*>(xp + H) : zero4;
-        xc[tl] = uok[tl] ? *reinterpret_cast<const f32x4m*>(xp + 2 * H) : zero4;
+        xr[tl] = uok[tl] ? *reinterpret_cast<const f32x4*>(xp) : zero4;
+        xu[tl] = uok[tl] ? *reinterpret_cast<const f32x4*>(xp + H) : zero4;
+        xc[tl] = uok[tl] ? *reinterpret_cast<const f32x4*>(xp + 2 * H) : zero4;
     }
     const __bf16* hrow = hb + n * PITCH + 8 * q;
     const __bf16* rrow = rhb + n * PITCH + 8 * q;
     for (int step = 0; step < a.T; ++step, t += dt) {
         const float* xn = xbase + (size_t)(step + 1 < a.T ? t + dt : t) * xrow;
-        bf16x8v bfr[KSN];
+        bf16x8 bfr[KSN];
 #pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8v*>(hrow + ks * 32);
-        f32x4m ar[TPW], au[TPW];
+        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(hrow + ks * 32);
+        f32x4 ar[TPW], au[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
             ar[tl] = xr[tl];
             au[tl] = xu[tl];
-            xr[tl] = uok[tl] ? *reinterpret_cast<const f32x4m*>(xn + tl * 16) : zero4;
-            xu[tl] = uok[tl] ? *reinterpret_cast<const f32x4m*>(xn + tl * 16 + H) : zero4;
+            xr[tl] = uok[tl] ? *reinterpret_cast<const f32x4*>(xn + tl * 16) : zero4;
+            xu[tl] = uok[tl] ? *reinterpret_cast<const f32x4*>(xn + tl * 16 + H) : zero4;
         }
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks)
@@ -952,19 +934,19 @@ gru_mfma_small_kernel(GruArgs a, const __bf16* packed) {
             }
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
-            bf16x4v o;
+            bf16x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (__bf16)(fast_sigmoid(ar[tl][e]) * hreg[tl][e]);
-            if (uok[tl]) *reinterpret_cast<bf16x4v*>(rhb + n * PITCH + tl * 16 + q * 4) = o;
+            if (uok[tl]) *reinterpret_cast<bf16x4*>(rhb + n * PITCH + tl * 16 + q * 4) = o;
         }
         // (same wave: the LDS writes above are ordered before the reads below)
 #pragma unroll
-        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8v*>(rrow + ks * 32);
-        f32x4m ac[TPW];
+        for (int ks = 0; ks < KSN; ++ks) bfr[ks] = *reinterpret_cast<const bf16x8*>(rrow + ks * 32);
+        f32x4 ac[TPW];
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
             ac[tl] = xc[tl];
-            xc[tl] = uok[tl] ? *reinterpret_cast<const f32x4m*>(xn + tl * 16 + 2 * H) : zero4;
+            xc[tl] = uok[tl] ? *reinterpret_cast<const f32x4*>(xn + tl * 16 + 2 * H) : zero4;
         }
 #pragma unroll
         for (int ks = 0; ks < KSN; ++ks)
@@ -973,8 +955,8 @@ gru_mfma_small_kernel(GruArgs a, const __bf16* packed) {
                 ac[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2][tl][ks], bfr[ks], ac[tl], 0, 0, 0);
 #pragma unroll
         for (int tl = 0; tl < TPW; ++tl) {
-            bf16x4v o;
-            f32x4m hv;
+            bf16x4 o;
+            f32x4 hv;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float u = fast_sigmoid(au[tl][e]);
@@ -985,11 +967,11 @@ gru_mfma_small_kernel(GruArgs a, const __bf16* packed) {
                 o[e] = (__bf16)hn;
             }
             if (uok[tl]) {
-                *reinterpret_cast<bf16x4v*>(hb + n * PITCH + tl * 16 + q * 4) = o;
+                *reinterpret_cast<bf16x4*>(hb + n * PITCH + tl * 16 + q * 4) = o;
                 if (seq_ok) {
                     const size_t oi = ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + tl * 16 + q * 4;
-                    if (a.out_bf16) *reinterpret_cast<bf16x4v*>(reinterpret_cast<__bf16*>(a.out) + oi) = o;
-                    else *reinterpret_cast<f32x4m*>(reinterpret_cast<float*>(a.out) + oi) = hv;
+                    if (a.out_bf16) *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.out) + oi) = o;
+                    else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.out) + oi) = hv;
                 }
             }
         }
@@ -1064,8 +1046,8 @@ gru_wave_kernel(GruArgs a) {
             au1 = fmaf(h1, wu[k + 1], au1);
         }
         constexpr bool FAST = sizeof(WT) == 2;            // bf16 model: v_exp/v_rcp gate functions
-        const float r = FAST ? fast_sigmoid(ar0 + ar1) : sigmoidf_(ar0 + ar1);
-        const float u = FAST ? fast_sigmoid(au0 + au1) : sigmoidf_(au0 + au1);
+        const float r = FAST ? fast_sigmoid(ar0 + ar1) : vc::sigmoidf_(ar0 + ar1);
+        const float u = FAST ? fast_sigmoid(au0 + au1) : vc::sigmoidf_(au0 + au1);
         const float rh = r * h;
         float ac0 = xc, ac1 = 0.0f, ac2 = 0.0f, ac3 = 0.0f;
 #pragma unroll

@@ -7,7 +7,9 @@
 // Activations here are float32 (the reference trains in float32).
 #include <hip/hip_runtime.h>
 
-#include "vc_common.h"
+#include "vc_device.h"
+
+using vc::f32x4;
 
 namespace {
 
@@ -15,8 +17,6 @@ constexpr int TB = 256;
 // rows summed by one block of the column-statistics kernels: 64 (was 256) gives the 12,800 x 4,096 bank tensors 3,200
 // blocks instead of 800 -- these loops are load-latency bound, more waves hide more of it
 constexpr int BN_ROWS = 64;
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
 // ---------------------------------------------------------------------------- column statistics
 // X [M, C] (row stride ld) -> partial sums over row blocks: part[blk][2][C].  Deterministic:
@@ -257,7 +257,7 @@ highway_bwd_kernel(const float* pre, int NP, const float* X, const float* dO, in
         const int j = (int)(i - r * H);
         const int ch = 64 * (j >> 5) + (j & 31), ct = ch + 32;
         const float ph = pre[r * NP + ch], pt = pre[r * NP + ct];
-        const float h = fmaxf(ph, 0.0f), t = sigmoidf_(pt);
+        const float h = fmaxf(ph, 0.0f), t = vc::sigmoidf_(pt);
         const float g = dO[i], x = X[i];
         dpre[r * NP + ch] = ph > 0.0f ? g * t : 0.0f;
         dpre[r * NP + ct] = g * (h - x) * t * (1.0f - t);
@@ -444,7 +444,7 @@ gru_train_fwd_kernel(GruTrainArgs a) {
         for (int col = tid; col < 2 * H; col += NT) {
             float acc = xbase[(size_t)t * xrow + col];
             for (int k = 0; k < H; ++k) acc = fmaf(h[k], W[(size_t)k * H3 + col], acc);
-            const float g = sigmoidf_(acc);
+            const float g = vc::sigmoidf_(acc);
             gates[row * H3 + col] = g;
             if (col < H) { const float v = g * h[col]; rhs[col] = v; rhg[row * H + col] = v; }
             else us[col - H] = g;
@@ -557,7 +557,6 @@ __device__ int g_gru_train_ablate;                  // -DVC_ABLATE builds only: 
 template <int S>
 __device__ __forceinline__ void ms_matvec(const float* __restrict__ w, size_t stride, const float* vec, int vstride, int n,
                                           float (&acc)[S]) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
     int k = 0;
     for (; k + 16 <= n; k += 16) {
         float wv[16];
@@ -573,7 +572,7 @@ __device__ __forceinline__ void ms_matvec(const float* __restrict__ w, size_t st
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                const f4 v = *reinterpret_cast<const f4*>(vec + s * vstride + k + 4 * q);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(vec + s * vstride + k + 4 * q);
                 acc[s] = fmaf(v[0], wv[4 * q], acc[s]); acc[s] = fmaf(v[1], wv[4 * q + 1], acc[s]);
                 acc[s] = fmaf(v[2], wv[4 * q + 2], acc[s]); acc[s] = fmaf(v[3], wv[4 * q + 3], acc[s]);
             }
@@ -582,7 +581,7 @@ __device__ __forceinline__ void ms_matvec(const float* __restrict__ w, size_t st
         const float w0 = w[(size_t)k * stride], w1 = w[(size_t)(k + 1) * stride], w2 = w[(size_t)(k + 2) * stride], w3 = w[(size_t)(k + 3) * stride];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const f4 v = *reinterpret_cast<const f4*>(vec + s * vstride + k);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(vec + s * vstride + k);
             acc[s] = fmaf(v[0], w0, acc[s]); acc[s] = fmaf(v[1], w1, acc[s]);
             acc[s] = fmaf(v[2], w2, acc[s]); acc[s] = fmaf(v[3], w3, acc[s]);
         }
@@ -607,7 +606,6 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 template <int H, int KRG, int KRC>
 __global__ void __launch_bounds__(512, 1)
 gru_train_fwd_res_kernel(GruTrainArgs a) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
     constexpr int NT = 512, H3 = 3 * H, TG = NT / (2 * H), KG = H / TG, TC = NT / H, KC = H / TC;
     static_assert(TG >= 1 && TC >= 1 && KRG <= KG && KRC <= KC && KRG % 4 == 0 && KRC % 4 == 0 && (KG - KRG) % 16 == 0 && (KC - KRC) % 16 == 0, "slices");
     __shared__ __attribute__((aligned(16))) float h[H];
@@ -647,7 +645,7 @@ gru_train_fwd_res_kernel(GruTrainArgs a) {
             const float* hv = h + sg * KG;
 #pragma unroll
             for (int q = 0; q < KRG / 4; ++q) {
-                const f4 v = *reinterpret_cast<const f4*>(hv + 4 * q);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(hv + 4 * q);
                 acc = fmaf(v[0], wg[4 * q], acc); acc = fmaf(v[1], wg[4 * q + 1], acc);
                 acc = fmaf(v[2], wg[4 * q + 2], acc); acc = fmaf(v[3], wg[4 * q + 3], acc);
             }
@@ -658,7 +656,7 @@ gru_train_fwd_res_kernel(GruTrainArgs a) {
                 for (int u = 0; u < 16; ++u) wv[u] = wgp[(size_t)(k + u) * H3];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const f4 v = *reinterpret_cast<const f4*>(hv + k + 4 * q);
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(hv + k + 4 * q);
                     acc = fmaf(v[0], wv[4 * q], acc); acc = fmaf(v[1], wv[4 * q + 1], acc);
                     acc = fmaf(v[2], wv[4 * q + 2], acc); acc = fmaf(v[3], wv[4 * q + 3], acc);
                 }
@@ -667,7 +665,7 @@ gru_train_fwd_res_kernel(GruTrainArgs a) {
 #pragma unroll
         for (int o = 1; o < TG; o <<= 1) acc += __shfl_xor(acc, o, 64);
         {
-            const float g = sigmoidf_(acc);
+            const float g = vc::sigmoidf_(acc);
             if (sg == 0) {
                 gates[row * H3 + cg] = g;
                 if (cg < H) { const float v = g * h[cg]; rhs[cg] = v; rhg[row * H + cg] = v; }
@@ -681,7 +679,7 @@ gru_train_fwd_res_kernel(GruTrainArgs a) {
             const float* rv = rhs + sc * KC;
 #pragma unroll
             for (int q = 0; q < KRC / 4; ++q) {
-                const f4 v = *reinterpret_cast<const f4*>(rv + 4 * q);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(rv + 4 * q);
                 ac = fmaf(v[0], wc[4 * q], ac); ac = fmaf(v[1], wc[4 * q + 1], ac);
                 ac = fmaf(v[2], wc[4 * q + 2], ac); ac = fmaf(v[3], wc[4 * q + 3], ac);
             }
@@ -692,7 +690,7 @@ gru_train_fwd_res_kernel(GruTrainArgs a) {
                 for (int u = 0; u < 16; ++u) wv[u] = wcp[(size_t)(k + u) * H3];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const f4 v = *reinterpret_cast<const f4*>(rv + k + 4 * q);
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(rv + k + 4 * q);
                     ac = fmaf(v[0], wv[4 * q], ac); ac = fmaf(v[1], wv[4 * q + 1], ac);
                     ac = fmaf(v[2], wv[4 * q + 2], ac); ac = fmaf(v[3], wv[4 * q + 3], ac);
                 }
@@ -752,7 +750,7 @@ gru_train_fwd_ms_kernel(GruTrainArgs a) {
             ms_matvec<GS>(W + col, (size_t)H3, h, H, H, acc);
 #pragma unroll
             for (int s = 0; s < GS; ++s) {
-                const float g = sigmoidf_(acc[s]);
+                const float g = vc::sigmoidf_(acc[s]);
                 const size_t row = (size_t)sq[s] * a.T + t;
                 if (seq0 + s < a.n_seq) gates[row * H3 + col] = g;
                 if (col < H) {
@@ -853,8 +851,8 @@ lstm_train_fwd_kernel(LstmTrainArgs a) {
         }
         __syncthreads();
         if (tid < H) {
-            const float gi = sigmoidf_(z[tid]), gj = tanhf(z[H + tid]);
-            const float gf = sigmoidf_(z[2 * H + tid] + 1.0f), go = sigmoidf_(z[3 * H + tid]);
+            const float gi = vc::sigmoidf_(z[tid]), gj = tanhf(z[H + tid]);
+            const float gf = vc::sigmoidf_(z[2 * H + tid] + 1.0f), go = vc::sigmoidf_(z[3 * H + tid]);
             c = gf * c + gi * gj;
             const float hn = go * tanhf(c);
             h[tid] = hn;
@@ -1050,7 +1048,6 @@ gru_bwd_ms_kernel(GruBwdMsArgs aa) {
 template <int H>
 __global__ void __launch_bounds__(512, 1)
 gru_bwd_res_kernel(GruBwdMsArgs aa) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
     const GruBwdArgs& a = aa.b;
     constexpr int NT = 512, H3 = 3 * H, TP = NT / H, N1 = H / TP, N2 = 2 * H / TP;
     static_assert(TP == 4 && N1 % 4 == 0 && N2 % 4 == 0, "H = 128");
@@ -1102,7 +1099,7 @@ gru_bwd_res_kernel(GruBwdMsArgs aa) {
             const float* v = dcp + sl * N1;
 #pragma unroll
             for (int q = 0; q < N1 / 4; ++q) {
-                const f4 x = *reinterpret_cast<const f4*>(v + 4 * q);
+                const f32x4 x = *reinterpret_cast<const f32x4*>(v + 4 * q);
                 acc = fmaf(x[0], w1[4 * q], acc); acc = fmaf(x[1], w1[4 * q + 1], acc);
                 acc = fmaf(x[2], w1[4 * q + 2], acc); acc = fmaf(x[3], w1[4 * q + 3], acc);
             }
@@ -1124,7 +1121,7 @@ gru_bwd_res_kernel(GruBwdMsArgs aa) {
             const float* v = dgp + sl * N2;
 #pragma unroll
             for (int q = 0; q < N2 / 4; ++q) {
-                const f4 x = *reinterpret_cast<const f4*>(v + 4 * q);
+                const f32x4 x = *reinterpret_cast<const f32x4*>(v + 4 * q);
                 acc = fmaf(x[0], w2[4 * q], acc); acc = fmaf(x[1], w2[4 * q + 1], acc);
                 acc = fmaf(x[2], w2[4 * q + 2], acc); acc = fmaf(x[3], w2[4 * q + 3], acc);
             }

@@ -24,7 +24,7 @@
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include "vc_common.h"
+#include "vc_device.h"
 #include "fe_dft400.h"
 
 namespace {
@@ -475,21 +475,14 @@ static int griffin_lim_run(const char* fn, const vc_vocoder_plan* p, const float
     a.beta = (float)((double)momentum / (1.0 + (double)momentum));
     const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
     const size_t smem = fast ? p->smem400 : p->smem_gen;
-    static bool attr_done = false;
-    if (!attr_done) {
-        const void* kernels[] = {
-            reinterpret_cast<const void*>(gl_iter_generic_kernel<true, MOM_OFF>),
-            reinterpret_cast<const void*>(gl_iter_generic_kernel<false, MOM_OFF>),
-            reinterpret_cast<const void*>(gl_iter_generic_kernel<false, MOM_FIRST>),
-            reinterpret_cast<const void*>(gl_iter_generic_kernel<false, MOM_ON>),
-            reinterpret_cast<const void*>(gl_iter400_kernel<true, MOM_OFF>),
-            reinterpret_cast<const void*>(gl_iter400_kernel<false, MOM_OFF>),
-            reinterpret_cast<const void*>(gl_iter400_kernel<false, MOM_FIRST>),
-            reinterpret_cast<const void*>(gl_iter400_kernel<false, MOM_ON>)};
-        for (const void* k : kernels)
-            VC_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
+    if (int rc = vc::allow_dynamic_lds<gl_iter_generic_kernel<true, MOM_OFF>,
+                                       gl_iter_generic_kernel<false, MOM_OFF>,
+                                       gl_iter_generic_kernel<false, MOM_FIRST>,
+                                       gl_iter_generic_kernel<false, MOM_ON>,
+                                       gl_iter400_kernel<true, MOM_OFF>,
+                                       gl_iter400_kernel<false, MOM_OFF>,
+                                       gl_iter400_kernel<false, MOM_FIRST>,
+                                       gl_iter400_kernel<false, MOM_ON>>(160 * 1024)) return rc;
     const dim3 ogrid(((unsigned)wav_stride + VT - 1) / VT, (unsigned)batch);
     const dim3 sgrid(((unsigned)L + VT - 1) / VT, (unsigned)batch);
     const size_t osmem = (size_t)p->N * sizeof(float);

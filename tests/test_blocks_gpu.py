@@ -512,6 +512,62 @@ def test_encoder_front_single_launch(N, T, L, f32_in, mi):
     _close(y, ref, TOL['bfloat16'], 'fused encoder front T=%d L=%d' % (T, L))
 
 
+@pytest.mark.parametrize('mi', [2, 4])
+def test_cbhg_front_pool_orders_signed_zeros(mi):
+    """The pool between vc_cbhg_front's filter bank and conv1d_1 orders -0.0 below every positive value, as the
+    per-layer path does (vc_conv_gemm pro_pool = 2 / the pooled bank epilogue).  One window of 8 frames (the smallest
+    shape vc_cbhg_front_supported accepts).  Frames Z have zero features and, with zero prenet biases, a prenet output
+    of exactly +0.0; frames P are random.  The k = 1 filter's 128 channels have a folded batch norm of scale -1 and
+    weights of one sign, so that after the ReLU
+      channels   0..63  (weights -1, shift -0.0): Z -> fmaf(+0, -1, -0.0) = -0.0,  P -> a positive value of ~5,
+      channels  64..95  (weights +1, shift -0.0): Z -> -0.0,                       P -> +0.0,
+      channels  96..127 (weights -1, shift +0.0): Z -> +0.0,                       P -> positive.
+    Frames Z P Z Z P P Z P: -0.0 meets a positive value and a +0.0 on either side, zeros meet zeros, positive meets
+    positive, and a positive value sits on the window's last frame (which pools with itself).  An unsigned integer
+    maximum returns the -0.0 for five of the eight frames of channels 0..63 and loses 64 inputs of ~5 to conv1d_1."""
+    import modules
+    rng = np.random.RandomState(11)
+    T, L = 8, 1
+    st = _store('bfloat16')
+    x = (0.5 * rng.standard_normal((1, T, 80))).astype(np.float32)
+    x[0, [0, 2, 3, 6], :] = 0.0
+    x = torch.from_numpy(x).cuda()
+    args = dict(embed_size=80, num_conv_banks=6, num_highwaynet_blocks=L, dropout_rate=0.4, is_training=False)
+    with modules.variable_store(st), modules.variable_scope('e'):
+        modules.OPTIONS['cbhg_front'] = False
+        modules.prenet_CBHG(x, **args)                                     # creates the variables
+        for n, v in list(st.vars.items()):                                   # as test_encoder_front_single_launch, but
+            if n.startswith('e/prenet/'):                                    # the prenet biases stay 0
+                continue
+            if n.endswith('gamma') or n.endswith('moving_variance'):
+                st.assign(n, rng.uniform(0.5, 1.5, tuple(v.shape)).astype(np.float32))
+            elif n.endswith('beta') or n.endswith('moving_mean') or n.endswith('bias'):
+                st.assign(n, rng.uniform(-0.3, 0.3, tuple(v.shape)).astype(np.float32))
+        bank = 'e/CBHG/conv1d_banks/'
+        k1 = np.full((1, 40, 128), -1.0, np.float32)
+        k1[:, :, 64:96] = 1.0
+        st.assign(bank + 'conv1d/conv1d/kernel', k1)
+        bn = {k: st.vars[bank + 'bn/' + k].cpu().numpy() for k in ('gamma', 'moving_variance', 'moving_mean', 'beta')}
+        bn['gamma'][:128], bn['moving_variance'][:128] = -1.0, 1.0 - modules.BN_EPS
+        bn['moving_mean'][:128] = -0.0                                       # -0.0 * scale = +0.0, and beta - (+0.0) keeps beta's sign
+        bn['beta'][:96], bn['beta'][96:128] = -0.0, 0.0
+        for k, v in bn.items():
+            st.assign(bank + 'bn/' + k, v)
+        scale, shift = (t.cpu().numpy() for t in modules._prep_bn(st, bank + 'bn', 768))
+        assert (scale[:128] < 0).all() and (shift[:128] == 0).all()
+        assert np.signbit(shift[:96]).all() and not np.signbit(shift[96:128]).any()
+        y_ref = modules.prenet_CBHG(x, **args)
+        modules.OPTIONS['cbhg_front'] = True
+        _vc.set_option('cbhg_front_mi', mi)
+        assert modules._vc.lib().vc_cbhg_front_supported(80, 80, 40, 6, 128, L, 40, T)
+        y = modules.prenet_CBHG(x, **args)
+    torch.cuda.synchronize()
+    assert y.shape == (1, T, 80) and not torch.isnan(y.float()).any()
+    d = (y.float() - y_ref.float()).abs()
+    print('fused against per-layer: max %.3e, mean %.3e' % (d.max().item(), d.mean().item()))
+    assert d.max().item() < 2e-2 and d.mean().item() < 2e-4, (d.max().item(), d.mean().item())
+
+
 @pytest.mark.parametrize('N,T,cin,E', [(2, 400, 61, 256), (3, 77, 80, 512), (1, 1, 61, 256), (64, 400, 80, 512)])
 def test_prenet_single_launch(N, T, cin, E):
     """The decoder stages' prenet as one launch (vc_prenet_chain: intermediate in registers) against the two
