@@ -66,9 +66,6 @@ const char* vc_target_arch(void);
  *                    (every frame transformed once; blocks wait for the summary of their own utterance)
  *   "fe_fused_spin"  polls a block of the one-launch front-end waits for the other tiles of its utterance before it
  *                    computes their records itself (default 4000, ~4 ms); 0 = never wait (tests of that path)
- *   "gru_small_mfma" 1 = the encoder's H = 40 bf16 recurrence with 16 sequences per wave on MFMA instead of one wave per
- *                    sequence (measured slower; default: off)
- *   "gru_mfma4"      1 = the four-wave MFMA recurrence with all weights in registers (bit-identical, measured slower)
  *   "prenet_lds"     0 = every wave of the fused prenet streams the weights from L2 itself (default: one stream per
  *                    block, shared through LDS)
  *   "gru_train_resident" 0 = the float32 training recurrences stream all their weights from L2 every step (default:
@@ -80,6 +77,9 @@ const char* vc_target_arch(void);
  *                    training forward kernel, which keeps half of the 786 KB of weights resident: 15.8 -> 3.0 ms at 64 windows)
  *   "gemm16_split"   vc_gemm16, single-pair launches: ways K is split over workgroups (1..8) + 16 * block map (0 = the splits
  *                    of a row tile on one XCD, 1 = one K range per XCD: ways must divide 8); default: chosen from the shape
+ * Any other name is an unknown option and returns VC_ERR_INVALID.  That includes the two names that used to select the
+ * four-wave MFMA recurrence and the encoder's 16-sequences-per-wave MFMA recurrence: both kernels were measured slower
+ * and removed together with their options.
  * All alternatives compute the same function (tests compare them).  Three more names, "ablate_bank256",
  * "ablate_bank256_only" and "ablate_cbhg_front", skip parts of a kernel for timing and give WRONG results: they
  * exist only in a library built with -DVC_ABLATE (tools/build_ablate.sh; vc_ablate_build() returns 1 there) and
