@@ -294,7 +294,10 @@ int vc_lstm_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw
 
 /* softmax + argmax over the last axis (encoder.py:110-111): logits float32 [M, ldl >= N] ->
  * probabilities (dtype out_dtype, row stride ldp, columns [N, ldp) zero-filled so the
- * decoder's first dense can read 16-byte rows) and int32 class ids (first maximum). */
+ * decoder's first dense can read 16-byte rows) and int32 class ids (first maximum).  The class id lies in [0, N) for
+ * every input: a row in which no logit exceeds the lowest finite float (all -inf, all -FLT_MAX, all NaN) gets class 0,
+ * as tf.argmax gives on an all-equal row; NaN logits never win against a number.  The probabilities of such a row are
+ * NaN (all -inf, all NaN) or 1 / N (all -FLT_MAX); every other row is unaffected.  d_class may be NULL. */
 int vc_softmax_argmax(const float* d_logits, int32_t M, int32_t N, int32_t ldl,
                       void* d_prob, int32_t ldp, int32_t out_dtype, int32_t* d_class, void* stream);
 /* Same, writing the probabilities twice in one launch: float32 (the API's y_pred) and a zero-padded bf16 copy (the
@@ -310,7 +313,8 @@ int vc_softmax_argmax_dual(const float* d_logits, int32_t M, int32_t N, int32_t 
  *   d_Wh[dir]: recurrent weights [H, 3H] = [Wg_h | Wc_h] (rows = h index), dtype w_dtype.
  *   d_out [n_seq*T, 2H] (dtype out_dtype): fw in columns [0,H), bw in [H,2H).
  *   d_workspace: scratch of vc_gru_workspace_bytes(H, w_dtype) bytes (the register-resident
- *   kernels re-pack the weights into their per-lane order there on every call). */
+ *   kernels re-pack the weights into their per-lane order there on every call; they return VC_ERR_WORKSPACE and
+ *   launch nothing when it is NULL or smaller).  1 <= H <= 1024; w_dtype and out_dtype are independent. */
 size_t vc_gru_workspace_bytes(int32_t H, int32_t w_dtype);
 int vc_gru_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw, int32_t w_dtype,
                  int32_t n_seq, int32_t T, int32_t H, void* d_out, int32_t out_dtype,

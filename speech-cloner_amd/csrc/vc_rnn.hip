@@ -37,10 +37,14 @@ template <typename T> __device__ __forceinline__ void st_out(void* o, size_t i, 
     else reinterpret_cast<float*>(o)[i] = v;
 }
 
-// Generic recurrence: any H.  Thread (col, ks): column `col` of the phase's weight block, K-slice
-// ks of KS (KS a power of two <= 64, lanes of one column adjacent => shuffle reduction).
+// Generic recurrence: any H <= 1024.  Thread group (col, ks): column `col` of the phase's weight block, K-slice
+// ks of KS (KS a power of two <= 64, lanes of one column adjacent => shuffle reduction).  NT / KS groups exist; a group
+// takes columns col, col + NT / KS, ...: one column per group up to H = 256 (2H <= NT = 512), up to GEN_C1 gate and
+// GEN_C2 candidate columns per thread beyond (KS = 1 there).
+constexpr int GEN_NT_MAX = 512, GEN_H_MAX = 1024;
+constexpr int GEN_C1 = 2 * GEN_H_MAX / GEN_NT_MAX, GEN_C2 = GEN_H_MAX / GEN_NT_MAX;
 template <typename WT>
-__global__ void __launch_bounds__(512)
+__global__ void __launch_bounds__(GEN_NT_MAX)
 gru_generic_kernel(GruArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int H = a.H, H3 = 3 * H, NT = blockDim.x, tid = threadIdx.x;
@@ -59,58 +63,86 @@ gru_generic_kernel(GruArgs a) {
     int KS1 = 1, KS2 = 1;
     while (KS1 * 2 <= 64 && KS1 * 2 * 2 * H <= NT) KS1 *= 2;
     while (KS2 * 2 <= 64 && KS2 * 2 * H <= NT) KS2 *= 2;
-    const int col1 = tid / KS1, ks1 = tid % KS1;      // gate column in [0, 2H)
-    const int col2 = tid / KS2, ks2 = tid % KS2;      // candidate column in [0, H)
-    const bool act1 = col1 < 2 * H, act2 = col2 < H;
+    const int col1 = tid / KS1, ks1 = tid % KS1, cs1 = NT / KS1;      // gate columns col1 + i cs1 in [0, 2H)
+    const int col2 = tid / KS2, ks2 = tid % KS2, cs2 = NT / KS2;      // candidate columns col2 + i cs2 in [0, H)
     const size_t xrow = 6 * (size_t)H;
     const float* xbase = a.xproj + (size_t)seq * a.T * xrow + (size_t)dir * H3;
     __syncthreads();
 
     int t = dir ? a.T - 1 : 0;
     const int dt = dir ? -1 : 1;
-    float xg = (act1 && ks1 == 0) ? xbase[(size_t)t * xrow + col1] : 0.0f;
-    float xc = (act2 && ks2 == 0) ? xbase[(size_t)t * xrow + 2 * H + col2] : 0.0f;
+    float xg[GEN_C1], xc[GEN_C2];
+#pragma unroll
+    for (int i = 0; i < GEN_C1; ++i) {
+        const int col = col1 + i * cs1;
+        xg[i] = (col < 2 * H && ks1 == 0) ? xbase[(size_t)t * xrow + col] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < GEN_C2; ++i) {
+        const int col = col2 + i * cs2;
+        xc[i] = (col < H && ks2 == 0) ? xbase[(size_t)t * xrow + 2 * H + col] : 0.0f;
+    }
     for (int step = 0; step < a.T; ++step, t += dt) {
         // prefetch next step's input projections
-        float xg_n = 0.0f, xc_n = 0.0f;
-        if (step + 1 < a.T) {
-            if (act1 && ks1 == 0) xg_n = xbase[(size_t)(t + dt) * xrow + col1];
-            if (act2 && ks2 == 0) xc_n = xbase[(size_t)(t + dt) * xrow + 2 * H + col2];
+        float xg_n[GEN_C1], xc_n[GEN_C2];
+        const bool more = step + 1 < a.T;
+#pragma unroll
+        for (int i = 0; i < GEN_C1; ++i) {
+            const int col = col1 + i * cs1;
+            xg_n[i] = (more && col < 2 * H && ks1 == 0) ? xbase[(size_t)(t + dt) * xrow + col] : 0.0f;
         }
-        // phase 1: gates
-        float acc = 0.0f;
-        if (act1) {
-            const WT* w = Wg + col1;
+#pragma unroll
+        for (int i = 0; i < GEN_C2; ++i) {
+            const int col = col2 + i * cs2;
+            xc_n[i] = (more && col < H && ks2 == 0) ? xbase[(size_t)(t + dt) * xrow + 2 * H + col] : 0.0f;
+        }
+        // phase 1: gates (a column's KS1 lanes take the branch together)
+#pragma unroll
+        for (int i = 0; i < GEN_C1; ++i) {
+            const int col = col1 + i * cs1;
+            if (col >= 2 * H) break;
+            float acc = 0.0f;
+            const WT* w = Wg + col;
             for (int k = ks1; k < H; k += KS1) acc = fmaf(h[k], ld_w(w + (size_t)k * H3), acc);
-        }
-        for (int o = KS1 >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        if (act1 && ks1 == 0) {
-            const float g = vc::sigmoidf_(acc + xg);
-            if (col1 < H) rh[col1] = g * h[col1];       // r first (GRUCell split order)
-            else u[col1 - H] = g;
+            for (int o = KS1 >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+            if (ks1 == 0) {
+                const float g = vc::sigmoidf_(acc + xg[i]);
+                if (col < H) rh[col] = g * h[col];          // r first (GRUCell split order)
+                else u[col - H] = g;
+            }
         }
         __syncthreads();
         // phase 2: candidate
-        float acc2 = 0.0f;
-        if (act2) {
-            const WT* w = Wg + 2 * H + col2;
+        float hn[GEN_C2];
+#pragma unroll
+        for (int i = 0; i < GEN_C2; ++i) {
+            const int col = col2 + i * cs2;
+            hn[i] = 0.0f;
+            if (col >= H) break;
+            float acc2 = 0.0f;
+            const WT* w = Wg + 2 * H + col;
             for (int k = ks2; k < H; k += KS2) acc2 = fmaf(rh[k], ld_w(w + (size_t)k * H3), acc2);
-        }
-        for (int o = KS2 >> 1; o > 0; o >>= 1) acc2 += __shfl_xor(acc2, o, 64);
-        float hn = 0.0f;
-        if (act2 && ks2 == 0) {
-            const float c = tanhf(acc2 + xc);
-            const float uu = u[col2];
-            hn = uu * h[col2] + (1.0f - uu) * c;
+            for (int o = KS2 >> 1; o > 0; o >>= 1) acc2 += __shfl_xor(acc2, o, 64);
+            if (ks2 == 0) {
+                const float c = tanhf(acc2 + xc[i]);
+                const float uu = u[col];
+                hn[i] = uu * h[col] + (1.0f - uu) * c;
+            }
         }
         __syncthreads();                                // everyone done reading h / rh
-        if (act2 && ks2 == 0) {
-            h[col2] = hn;
-            st_out<WT>(a.out, ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + col2, hn, a.out_bf16);
+#pragma unroll
+        for (int i = 0; i < GEN_C2; ++i) {
+            const int col = col2 + i * cs2;
+            if (col < H && ks2 == 0) {
+                h[col] = hn[i];
+                st_out<WT>(a.out, ((size_t)seq * a.T + t) * 2 * H + (size_t)dir * H + col, hn[i], a.out_bf16);
+            }
         }
         __syncthreads();
-        xg = xg_n;
-        xc = xc_n;
+#pragma unroll
+        for (int i = 0; i < GEN_C1; ++i) xg[i] = xg_n[i];
+#pragma unroll
+        for (int i = 0; i < GEN_C2; ++i) xc[i] = xc_n[i];
     }
 }
 
@@ -679,7 +711,7 @@ softmax_argmax_kernel(const float* logits, int M, int N, int ldl, void* prob, in
         }
         if (prob2 && c < ldp2) prob2[(size_t)row * ldp2 + c] = (__bf16)p;      // second, zero-padded bf16 copy
     }
-    if (cls && lane == 0) cls[row] = mi;
+    if (cls && lane == 0) cls[row] = mi < N ? mi : 0;       // no logit above -FLT_MAX (all -inf / lowest / NaN): class 0
 }
 
 __global__ void __launch_bounds__(256)
@@ -707,7 +739,7 @@ int vc_gru_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw,
                  int32_t T, int32_t H, void* d_out, int32_t out_dtype, void* d_workspace, size_t workspace_bytes,
                  void* stream) {
     VC_REQUIRE(d_xproj && d_Wh_fw && d_Wh_bw && d_out, "NULL argument");
-    VC_REQUIRE(n_seq > 0 && T > 0 && H > 0 && H <= 1024, "bad shape n_seq=%d T=%d H=%d", n_seq, T, H);
+    VC_REQUIRE(n_seq > 0 && T > 0 && H > 0 && H <= GEN_H_MAX, "bad shape n_seq=%d T=%d H=%d", n_seq, T, H);
     VC_REQUIRE(w_dtype == VC_F32 || w_dtype == VC_BF16, "bad w_dtype %d", w_dtype);
     VC_REQUIRE(out_dtype == VC_F32 || out_dtype == VC_BF16, "bad out_dtype %d", out_dtype);
     GruArgs a;
@@ -718,7 +750,7 @@ int vc_gru_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw,
     a.w_in_lds = (base + wbytes <= 150 * 1024);
     const size_t lds = base + (a.w_in_lds ? wbytes : 0);
     int nt = 256;
-    while (nt < 512 && nt < 2 * H) nt *= 2;
+    while (nt < GEN_NT_MAX && nt < 2 * H) nt *= 2;
     hipStream_t st = static_cast<hipStream_t>(stream);
     dim3 grid(n_seq, 2);
     // register-resident kernels for the decoder's sizes
