@@ -37,7 +37,8 @@ extern "C" {
 
 /* 2: vc_frontend_f32 / vc_frontend_stages_f32 take out_rows, vc_transpose_pad takes slack_row, vc_gemm_desc has
  *    sum_groups.  Bump on EVERY change of an exported signature or struct layout: the Python binding (_vc.py) refuses
- *    to load a library whose vc_version() differs from its own constant.
+ *    to load a library whose vc_version() differs from its own constant.  An export that is only added or removed
+ *    (vc_ablate_build was the last one removed) does not bump it: the binding resolves every export by name at load.
  * 3: vc_gemm_desc ends with d_workspace / workspace_bytes (vc_conv_gemm_workspace_bytes); vc_bn_post_routing added.
  * 4: vc_split16 / vc_weights16 / vc_gemm16 (training convolutions on split-float16 operands).
  * 5: vc_mx8_quantize / vc_mx8_conv / vc_mx8_conv_workspace_bytes and vc_mx8_conv_desc (MX-FP8 inference).
@@ -79,16 +80,14 @@ const char* vc_target_arch(void);
  *                    of a row tile on one XCD, 1 = one K range per XCD: ways must divide 8); default: chosen from the shape
  * Any other name is an unknown option and returns VC_ERR_INVALID.  That includes the two names that used to select the
  * four-wave MFMA recurrence and the encoder's 16-sequences-per-wave MFMA recurrence: both kernels were measured slower
- * and removed together with their options.
- * All alternatives compute the same function (tests compare them).  Three more names, "ablate_bank256",
- * "ablate_bank256_only" and "ablate_cbhg_front", skip parts of a kernel for timing and give WRONG results: they
- * exist only in a library built with -DVC_ABLATE (tools/build_ablate.sh; vc_ablate_build() returns 1 there) and
- * are rejected with VC_ERR_INVALID by the shipped build.  Options are process-global; set them between launches.
+ * and removed together with their options.  It also includes "ablate_bank256",
+ * "ablate_bank256_only" and "ablate_cbhg_front", which skipped parts of a kernel for timing in a separate build of the
+ * library: that build and every path it compiled in are gone, its measurements are in DESIGN.md sections 6 and 8.
+ * All alternatives compute the same function (tests compare them).  Options are process-global; set them between launches.
  * They are read when a launch call is made, so a captured graph keeps the values of its capture: setting an option
  * afterwards does not change what the graph replays. */
 int vc_set_option(const char* name, int value);
 int vc_get_option(const char* name, int* value);
-int vc_ablate_build(void);
 
 /* ------------------------------------------------------------------------------------------
  * Signal front-end: audio_lib.calc_MFCC_input  (/root/reference/audio_lib.py:89-244)

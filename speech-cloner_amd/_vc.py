@@ -149,7 +149,6 @@ _SIGS = {
     'vc_target_arch': (C.c_char_p, []),
     'vc_set_option': (C.c_int, [C.c_char_p, C.c_int]),
     'vc_get_option': (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
-    'vc_ablate_build': (C.c_int, []),
     'vc_frontend_host_tables': (C.c_int, [C.POINTER(FrontendCfg), _P, _P]),
     'vc_frontend_plan_create': (C.c_int, [C.POINTER(FrontendCfg), _P, C.POINTER(_P)]),
     'vc_frontend_plan_destroy': (None, [_P]),

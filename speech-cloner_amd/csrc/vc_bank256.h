@@ -28,7 +28,7 @@ struct Bank256Args {
     int32_t ksplit;       // 1 = off
     float* ws;            // [row tiles][ksplit - 1][256 * 256] float32 partial accumulators (register order)
     unsigned* tick;       // [row tiles][2] {arrival ticket, slabs published}; zeroed by the launcher before every launch
-    int32_t dbg;          // -DVC_ABLATE builds only (option ablate_bank256): 1 = skip the K loop, 2 = skip the stores, 4 = no loads inside the K loop, 8 = no barrier (timing only, wrong results); ignored by the shipped build
+    int32_t pad_;         // never read: keeps p[] at byte 296 (sizeof 936), the kernel-argument offsets bank256_kernel was tuned and measured with
     Bank256Pair p[16];
 };
 

@@ -30,14 +30,6 @@ using vc::f32x16, vc::f32x4, vc::bf16x8, vc::bf16x4, vc::u32x4;
 
 namespace {
 
-// Timing-only ablations (wrong results) are compiled in with -DVC_ABLATE alone (tools/build_ablate.sh); the shipped
-// library has no such path: ABL() is the constant false.
-#ifdef VC_ABLATE
-#define ABL(mask) ((a.dbg & (mask)) != 0)
-#else
-#define ABL(mask) false
-#endif
-
 constexpr int NT = 512;
 constexpr int BM = 256;
 constexpr int A_ROWS = 288;                        // 256 + 32 halo rows
@@ -234,13 +226,13 @@ bank256_kernel(Bank256Args a) {
             if (s == 3) {
                 // every read of tile n has been issued; retire them, publish tile n+1, recycle tile n's buffer
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                if (!ABL(8)) __syncthreads();
-                if (n + 2 < ntiles && !ABL(4)) stageB(n + 2, n & 1);
+                __syncthreads();
+                if (n + 2 < ntiles) stageB(n + 2, n & 1);
                 have_next = n + 1 < ntiles;
                 if (have_next) {
                     const int cs1 = (n + 1) / ntap;
                     // first tile of a slab: bring in the slab after it (its buffer was last read a slab ago)
-                    if ((n + 1) - cs1 * ntap == 0 && cs1 + 1 < nslab && !ABL(4)) stageA(cs1 + 1, (cs1 + 1) & 1);
+                    if ((n + 1) - cs1 * ntap == 0 && cs1 + 1 < nslab) stageA(cs1 + 1, (cs1 + 1) & 1);
                     jn = tap_setup(n + 1);
                 }
                 nb = (n + 1) & 1;
@@ -325,8 +317,7 @@ bank256_kernel(Bank256Args a) {
         }
         j = jn;
     };
-    const int nrun = ABL(1) ? 0 : ntiles;
-    for (int n = 0; n < nrun; ++n) {
+    for (int n = 0; n < ntiles; ++n) {
         tile(n, !(j >= J_lo && j < J_hi));
     }
 
@@ -442,7 +433,7 @@ bank256_kernel(Bank256Args a) {
                 vv = (min(gm, a.M - 1) % a.T == a.T - 1) ? vv : mx;
             }
             // streaming store: the 210 MB output must not displace the weight tiles from L2
-            if (gm < a.M && row < nrows && !ABL(2))
+            if (gm < a.M && row < nrows)
                 __builtin_nontemporal_store(vv, reinterpret_cast<bf16x8*>(C + (size_t)gm * a.ldc + (half ? pr.c_off1 : pr.c_off0) + l16 * 8));
         }
     }

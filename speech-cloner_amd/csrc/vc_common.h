@@ -27,8 +27,7 @@ constexpr int WAVE = 64;
 
 // Kernel-selection options (vc_set_option / vc_get_option, include/vc_hip.h).  -1 = the library's own choice.
 // They pick between HIP kernels that compute the SAME function (A/B measurements, regression tests); nothing in
-// the library reads the process environment.  The result-corrupting ablation switches exist only in builds made
-// with -DVC_ABLATE (tools/build_ablate.sh), never in the shipped libvc_hip.so.
+// the library reads the process environment, and no option changes what a kernel computes.
 enum Option {
     OPT_BANK256 = 0,      // 0: filter banks on conv_kernel instead of bank256_kernel
     OPT_BANK256_XCD,      // 0: plain 2-D grid, 1: whole pairs per XCD, 2: pairs split over two XCDs (default)
@@ -47,9 +46,6 @@ enum Option {
     OPT_GRU_F32_WIDE,     // 0: float32 inference recurrences of more than 128 units stay on gru_generic_kernel (default: the training forward kernel)
     OPT_F32_F16X3,        // 0: float32 inference convolutions stay on the f32-input MFMA kernels (default: vc_gemm16)
     OPT_GEMM16_SPLIT,     // vc_gemm16 single-pair launches: K split ways (1..8) + 16 * block map (0: a row tile's splits on one XCD, 1: a K range per XCD); default: automatic
-    OPT_ABLATE_BANK256,   // -DVC_ABLATE only: bit mask, see vc_bank256.h
-    OPT_ABLATE_BANK256_ONLY,   // -DVC_ABLATE only: launch one pair alone
-    OPT_ABLATE_CBHG_FRONT,     // -DVC_ABLATE only: bit mask, see vc_cbhg_small.hip
     OPT_COUNT
 };
 int opt(Option o);        // current value, -1 if unset

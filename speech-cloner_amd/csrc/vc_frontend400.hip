@@ -40,20 +40,6 @@ constexpr int PP = RE_W / 4;                        // 260: pitch of a power-til
 constexpr float NEG_INF = -3.402823466e38f, POS_INF = 3.402823466e38f;
 constexpr float DB10 = 3.0102999566398120f;         // 10 log10(x) = DB10 * log2(x)
 
-// In-kernel phase stamps (s_memtime), -DVC_ABLATE builds only (tools/fe_phase_stamps.py reads them back): wave 0 of
-// every block writes the shader clock at each phase boundary into an unused part of the workspace.  The shipped
-// library contains none of this.
-#ifdef VC_ABLATE
-#define FE_STAMP(i)                                                                                         \
-    do {                                                                                                    \
-        if (threadIdx.x == 0)                                                                               \
-            reinterpret_cast<unsigned long long*>(a.mel0 + 65536)[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = \
-                __builtin_amdgcn_s_memtime();                                                               \
-    } while (0)
-#else
-#define FE_STAMP(i) do { } while (0)
-#endif
-
 // LDS carve (floats): A_re [4 waves][52 rows] | A_im [4 waves][48 rows] | scalars.
 // Everything up to the power tile is WAVE-LOCAL: a wave loads the 640 samples under its own 4 frames (into its own
 // imaginary-row region, which it overwrites only after reading them: LDS operations of one wave execute in order), runs
@@ -88,7 +74,7 @@ __device__ __forceinline__ float pow_db_clipped(float v, float offp, float pfloo
 
 // One filter of the sparse mel matrix on one frame: 14 reads issued together (reads past the filter's own count meet
 // zero weights; past the tile's last row they meet the zero pad), then one FMA chain.  A per-term `if (j < count)`
-// here serialised every LDS round trip behind a branch: 10,280 of a block's 20,810 cycles (s_memtime stamps).
+// here serialised every LDS round trip behind a branch: 10,280 of a block's 20,810 cycles.
 __device__ __forceinline__ float mel_dot(const float* p, const float (&w)[14]) {
     float v[14];
 #pragma unroll
@@ -138,7 +124,6 @@ fe400_kernel(Fe400Args a) {
         return;
     }
 
-    FE_STAMP(0);
     // ---------------- tables this thread needs in registers (L2 hits; issued before anything waits)
     const int n2 = tid & 15;
     float wreg[25];
@@ -258,7 +243,6 @@ fe400_kernel(Fe400Args a) {
             }
         }
     }
-    FE_STAMP(1);
 
     float mw_[14];
 #pragma unroll
@@ -291,7 +275,6 @@ fe400_kernel(Fe400Args a) {
             aim_w[(i0 + k1) * RP + n2] = ai[k1];
         }
     }
-    FE_STAMP(2);
 
     // ---------------- step 3: lane = row (g3l, k13) of the wave's 52: complex 16-point DFT over n2 -> |Y|^2
     const int g3l = lane / 13, k13 = lane - g3l * 13;
@@ -327,7 +310,6 @@ fe400_kernel(Fe400Args a) {
             }
         }
     }
-    FE_STAMP(3);
     // (no barrier: the wave's power rows go over its OWN real rows, all of which are in its registers by now)
     // power tile: bin k1 + 25 k2 directly for k2 <= 7 (and 200 = 0 + 25 * 8); the bins with residue 13..24 are the
     // mirror images 400 - k of the outputs with k2 >= 8 (hermitian symmetry, fe_dft400.h bin_of)
@@ -360,9 +342,7 @@ fe400_kernel(Fe400Args a) {
     for (int j = 0; j < 14; ++j) mw_[j] = j < mcnt ? mw_[j] : 0.0f;
     if constexpr (STATS) {
         float mmax = NEG_INF, mmin = POS_INF;
-        FE_STAMP(4);
         __syncthreads();                                // power tile complete
-        FE_STAMP(5);
         if (mg < 3) {
             for (int gg = mg; gg < G; gg += 3) {
                 const float acc = mel_dot(Pt + gg * PP + ms, mw_);
@@ -386,15 +366,12 @@ fe400_kernel(Fe400Args a) {
             float* s = a.stats + ((size_t)b * a.nt1 + blockIdx.x) * 8;
             s[0] = pmax; s[1] = pmin; s[2] = mmax; s[3] = mmin; s[4] = asum;
         }
-        FE_STAMP(6);
         return;
     } else {
         float* const Mc = Aim + G * NC + G * NM;        // [G][80]  clipped mel dB
         float* const Mf = Aim;                          // [G][40]  scaled cepstra
         float* const SD = Aim + G * NC;                 // [G][80]  j < 40: m[j] + m[79-j], j >= 40: m[j-40] - m[119-j]
-        FE_STAMP(4);
         __syncthreads();                                // power tile + constants
-        FE_STAMP(5);
         const float offp = sc[0], pfloor = sc[1], pS = sc[2], pM = sc[8], offm = sc[3], mfloor = sc[4], mS = sc[5], mM = sc[6],
                     c00 = sc[7];
         const int nvalid = min(GO, F - fo);             // output frames that exist
@@ -413,7 +390,6 @@ fe400_kernel(Fe400Args a) {
                 if (gg < nrows) o[gg * NB] = gg < nvalid ? w : 0.0f;
             }
         }
-        FE_STAMP(6);
         // ---------------- mel power -> dB of the "amplitude" (quirk) -> top_db clip: all 16 frames (DCT halo)
         if (mg < 3) {
             for (int gg = mg; gg < G; gg += 3) {
@@ -421,7 +397,6 @@ fe400_kernel(Fe400Args a) {
             }
         }
         __syncthreads();
-        FE_STAMP(7);
         // ---------------- M_dB out (float4 rows) and the sum / difference halves for the DCT
         {
             const bool clip = a.clip != 0;
@@ -444,7 +419,6 @@ fe400_kernel(Fe400Args a) {
             }
         }
         __syncthreads();
-        FE_STAMP(8);
         // ---------------- DCT-II: coefficient ci (even: sums, odd: differences), frames cf, cf + 6, cf + 12
         if (tid < 240) {
             const float norm = a.mfcc_norm;
@@ -464,7 +438,6 @@ fe400_kernel(Fe400Args a) {
             }
         }
         __syncthreads();
-        FE_STAMP(9);
         // ---------------- [MFCC | delta] out (audio_lib.py:226-228, 238): delta = 2 (M[t+1] - M[t-1]), 0 at both ends
         {
             const bool clip = a.clip != 0;
@@ -491,7 +464,6 @@ fe400_kernel(Fe400Args a) {
                 o[i] = v;
             }
         }
-        FE_STAMP(10);
     }
 }
 
@@ -523,7 +495,7 @@ fe400_kernel(Fe400Args a) {
 constexpr unsigned FUSED_SPIN_LIMIT = 4000;          // x (s_sleep 24 + one L2 round trip) ~ 4 ms
 // One counter per 256 bytes: with the 32 counters of a batch in ONE cache line every arrival and every poll of ~1,000
 // resident blocks went through one L2 channel (a word serves ~88 requests per microsecond): blocks waited a median of
-// 69,000 cycles for their utterance and the launch took 103 us (tools/fe_phase_stamps.py fused; profiles/r03).
+// 69,000 cycles for their utterance and the launch took 103 us (profiles/r03).
 constexpr int FCOUNT_PITCH = 64;                     // unsigned words
 
 __device__ __forceinline__ float ld_sc1(const float* p) {
@@ -574,7 +546,6 @@ fe400_fused_kernel(Fe400Args a) {
 
     // mode 0: own tile (publish, wait); 1: walking the utterance's tiles after a poll ran out; 2: own tile again
     int mode = 0, cur = own;
-    FE_STAMP(0);
     for (;;) {
         const int fo = GO * cur, f0 = fo - 1;
         // Every per-thread index of the transform is derived INSIDE the loop from an opaque copy of the thread index: the
@@ -636,7 +607,6 @@ fe400_fused_kernel(Fe400Args a) {
                 if (idx >= alo && idx < ahi) asum += fabsf(curv[u]);
             }
         }
-        if (mode == 0) FE_STAMP(1);                     // samples in LDS
         // ---------------- 25-point stage + twiddle
         float mw_[14];
 #pragma unroll
@@ -665,7 +635,6 @@ fe400_fused_kernel(Fe400Args a) {
                 aim_w[(i0 + k1) * RP + n2] = ai[k1];
             }
         }
-        if (mode == 0) FE_STAMP(2);                     // 25-point stage
         // ---------------- 16-point stage -> |Y|^2 -> the wave's four power rows (over its own real rows)
         float pmax = NEG_INF, pmin = POS_INF;
         {
@@ -707,9 +676,7 @@ fe400_fused_kernel(Fe400Args a) {
                 }
             }
         }
-        if (mode == 0) FE_STAMP(3);                     // 16-point stage, power rows
         __syncthreads();                                // power tile complete; every wave is past its imaginary rows
-        if (mode == 0) FE_STAMP(4);
         // ---------------- mel power of all 16 frames -> LDS; extremes; frame 0's row
 #pragma unroll
         for (int j = 0; j < 14; ++j) mw_[j] = j < mcnt ? mw_[j] : 0.0f;
@@ -728,7 +695,6 @@ fe400_fused_kernel(Fe400Args a) {
         if (lane == 0) { sc[16 + wv * 5 + 0] = pmax; sc[16 + wv * 5 + 1] = pmin; sc[16 + wv * 5 + 2] = mmax; sc[16 + wv * 5 + 3] = mmin; sc[16 + wv * 5 + 4] = asum; }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (frame 0's mel row: every storing wave drains)
         __syncthreads();
-        if (mode == 0) FE_STAMP(5);                     // mel power, reductions, barrier
         if (mode == 2) break;                           // own tiles restored; the records are all in memory
         if (tid == 0) {
 #pragma unroll
@@ -789,7 +755,6 @@ fe400_fused_kernel(Fe400Args a) {
         }
     }
 
-    FE_STAMP(6);                                        // record published, the utterance's tiles waited for
     // ---------------- the utterance's constants (wave 0), from the published records: sc1 loads only
     const int fo = fo_own;
     // (everything below is addressed from an opaque copy of the thread index: left to itself the compiler computes the
@@ -862,7 +827,6 @@ fe400_fused_kernel(Fe400Args a) {
         }
     }
     __syncthreads();                                    // constants
-    FE_STAMP(7);
     const float offp = sc[0], pfloor = sc[1], pS = sc[2], pM = sc[8], offm = sc[3], mfloor = sc[4], mS = sc[5], mM = sc[6],
                 c00 = sc[7];
     const int nvalid = min(GO, F - fo);
@@ -880,13 +844,11 @@ fe400_fused_kernel(Fe400Args a) {
             if (gg < nrows) o[gg * NB] = gg < nvalid ? w : 0.0f;
         }
     }
-    FE_STAMP(8);                                        // P_dB out
     // ---------------- mel power -> clipped dB, in place (each thread the elements it wrote)
     if (mg_c < 3) {
         for (int gg = mg_c; gg < G; gg += 3) Mc[gg * NM + mm_c] = mel_db_clipped(Mc[gg * NM + mm_c], offm, mfloor);
     }
     __syncthreads();
-    FE_STAMP(9);                                        // mel dB + barrier
     // ---------------- M_dB out (float4 rows) and the sum / difference halves for the DCT
     {
         const bool clip = a.clip != 0;
@@ -909,7 +871,6 @@ fe400_fused_kernel(Fe400Args a) {
         }
     }
     __syncthreads();
-    FE_STAMP(10);                                       // M_dB out, sum / difference, barrier
     // ---------------- DCT-II
     if (tid_c < 240) {
         const float norm = a.mfcc_norm;
@@ -929,7 +890,6 @@ fe400_fused_kernel(Fe400Args a) {
         }
     }
     __syncthreads();
-    FE_STAMP(11);                                       // DCT + barrier
     // ---------------- [MFCC | delta] out
     {
         const bool clip = a.clip != 0;
@@ -955,7 +915,6 @@ fe400_fused_kernel(Fe400Args a) {
             o[i] = v;
         }
     }
-    FE_STAMP(12);
 }
 
 }  // namespace

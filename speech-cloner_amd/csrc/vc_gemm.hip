@@ -836,11 +836,6 @@ int launch_bank256(const vc_gemm_desc* d, hipStream_t st) {
         p.c_off0 = d->groups[g].c_off; p.c_off1 = d->groups[g + 1].c_off;
         p.extra = 1;
     }
-    b.dbg = 0;
-#ifdef VC_ABLATE
-    b.dbg = vc::opt(vc::OPT_ABLATE_BANK256) > 0 ? vc::opt(vc::OPT_ABLATE_BANK256) : 0;
-    if (const int p = vc::opt(vc::OPT_ABLATE_BANK256_ONLY); p >= 0 && p < b.n_pairs) { b.p[0] = b.p[p]; b.n_pairs = 1; }
-#endif
     return vc_launch_bank256(b, st);
 }
 
@@ -891,7 +886,7 @@ int launch_proj256(const vc_gemm_desc* d, hipStream_t st) {
     }
     b.X = d->d_X; b.M = d->M; b.T = d->T; b.Cin = d->Cin; b.ldx = d->ldx;
     b.epi_scale = d->d_epi_scale; b.epi_shift = d->d_epi_shift; b.act = d->act;
-    b.C = d->d_C; b.ldc = d->ldc; b.n_pairs = 1; b.pool = 0; b.dbg = 0;
+    b.C = d->d_C; b.ldc = d->ldc; b.n_pairs = 1; b.pool = 0;
     Bank256Pair& p = b.p[0];
     p.Bt0 = g.d_Bt;
     p.Bt1 = static_cast<const char*>(g.d_Bt) + (size_t)128 * g.K * 2;      // rows 128.. of the [256, K] bf16 matrix

@@ -84,15 +84,6 @@ __device__ __forceinline__ void hw_tile(const bf16x8* pw, const bf16x8* next, co
     }
 }
 
-// -DVC_ABLATE builds only: cycle sums per phase (s_memtime, thread 0 of workgroup 7), read back with
-// vc_ablate_read_highway_stamps (tools/highway_phase_stamps.py).  The shipped library contains none of this.
-#ifdef VC_ABLATE
-__device__ unsigned long long g_hw_stamps[8];
-#define HW_T(i) do { if (stamp) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc_t[i] += t_ - t_prev; t_prev = t_; } } while (0)
-#else
-#define HW_T(i) do { } while (0)
-#endif
-
 template <int H>
 __global__ void __launch_bounds__(2 * H, H == 256 ? 1 : 2)
 highway_chain_kernel(HwChainArgs a) {
@@ -102,10 +93,6 @@ highway_chain_kernel(HwChainArgs a) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5, x15 = li & 15;
     const int m0 = blockIdx.x * HW_BM;
-#ifdef VC_ABLATE
-    const bool stamp = blockIdx.x == 7 && tid == 0;
-    unsigned long long acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = __builtin_amdgcn_s_memtime();
-#endif
 
     // ---- activation tile -> LDS buffer 0
     for (int idx = tid; idx < HW_BM * NS; idx += NT) {
@@ -136,7 +123,6 @@ highway_chain_kernel(HwChainArgs a) {
         }
     }
     __syncthreads();
-    HW_T(0);
 
     for (int layer = 0; layer < a.n_layers; ++layer) {
         const char* cur = smem + (layer & 1) * (HW_BM * RB);
@@ -145,10 +131,6 @@ highway_chain_kernel(HwChainArgs a) {
         f32x16 acc[4][2];
         const bf16x8* nextw = more ? wptr(layer + 1, 0) : (a.PW ? reinterpret_cast<const bf16x8*>(a.PW) + ((size_t)w * KS * 2) * 64 + lane : nullptr);
         hw_tile<H>(wptr(layer, 0), nextw, cur + li * RB, lh, x15, wr, acc);
-#ifdef VC_ABLATE
-        if (stamp) asm volatile("" :: "v"(acc[3][1][15]));     // the stamp waits for the last accumulator
-#endif
-        HW_T(1);
         // ---- gate (lane-local) -> next activation tile
         f32x4 bH[4], bT[4];
 #pragma unroll
@@ -170,9 +152,7 @@ highway_chain_kernel(HwChainArgs a) {
                 *reinterpret_cast<bf16x4*>(nxt + off) = o;
             }
         }
-        HW_T(2);
         __syncthreads();
-        HW_T(3);
     }
 
     const char* fin = smem + (a.n_layers & 1) * (HW_BM * RB);
@@ -229,13 +209,6 @@ highway_chain_kernel(HwChainArgs a) {
             }
         }
     }
-    HW_T(4);
-#ifdef VC_ABLATE
-    if (stamp) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g_hw_stamps[i] = acc_t[i];
-    }
-#endif
     if (a.Y == nullptr) return;
     // ---- final tile -> global
     for (int idx = tid; idx < HW_BM * NS; idx += NT) {
@@ -282,14 +255,6 @@ int vc_highway_pack(const void* d_Bt, int32_t n_cols, int32_t H, void* d_packed,
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }
-
-#ifdef VC_ABLATE
-int vc_ablate_read_highway_stamps(unsigned long long* h_out) {
-    VC_HIP_CHECK(hipDeviceSynchronize());
-    VC_HIP_CHECK(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_hw_stamps), sizeof(unsigned long long) * 8));
-    return VC_OK;
-}
-#endif
 
 int vc_highway_chain(const void* d_X, int32_t M, int32_t H, int32_t ldx, int32_t n_layers, const void* const* d_packed,
                      const float* const* d_bias, void* d_Y, int32_t ldy, const void* d_proj_packed,

@@ -551,21 +551,12 @@ gru_bwd_kernel(GruBwdArgs a) {
 // acc[s] += sum_k vec[s][k] * w[k * stride]  for k in [0, n): the weight column is read in batches
 // of 16 independent loads (a 4-load batch per iteration left each wave waiting on L2 64-128 times
 // per phase and step: the recurrences were latency-bound).  n must be a multiple of 4.
-#ifdef VC_ABLATE
-__device__ int g_gru_train_ablate;                  // -DVC_ABLATE builds only: set by vc_ablate_set_gru_train
-#endif
 template <int S>
 __device__ __forceinline__ void ms_matvec(const float* __restrict__ w, size_t stride, const float* vec, int vstride, int n,
                                           float (&acc)[S]) {
     int k = 0;
     for (; k + 16 <= n; k += 16) {
         float wv[16];
-#ifdef VC_ABLATE
-        if (g_gru_train_ablate) {                            // timing only: no weight stream (tools/ab_gru_train.py --floor)
-#pragma unroll
-            for (int u = 0; u < 16; ++u) wv[u] = 0.001f * (float)(k + u);
-        } else
-#endif
 #pragma unroll
         for (int u = 0; u < 16; ++u) wv[u] = w[(size_t)(k + u) * stride];
 #pragma unroll
@@ -1418,7 +1409,7 @@ int vc_gru_train_forward(const float* d_xproj, const float* d_Wh_fw, const float
         hipStream_t st = static_cast<hipStream_t>(stream);
         // H = 128: all 196 KB of weights in registers and the step's input projections requested a step ahead: 1.38 -> 0.53 ms
         // per launch at 32 windows.  H = 256: half of the 786 KB resident (192 registers per thread): 3.14 -> 2.95 ms -- the
-        // step there is mostly NOT the weight stream (2.5 ms remain with the loads removed: tools/ab_gru_train.py --floor).
+        // step there is mostly NOT the weight stream (2.5 ms remain with the loads removed: DESIGN.md section 6, round 2).
         const bool resident = gs == 1 && vc::opt(vc::OPT_GRU_TRAIN_RESIDENT) != 0;
         if (resident && H == 128) hipLaunchKernelGGL((gru_train_fwd_res_kernel<128, 64, 32>), grid, dim3(512), 0, st, a);
         else if (resident && H == 256) hipLaunchKernelGGL((gru_train_fwd_res_kernel<256, 128, 64>), grid, dim3(512), 0, st, a);
@@ -1431,13 +1422,6 @@ int vc_gru_train_forward(const float* d_xproj, const float* d_Wh_fw, const float
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }
-
-#ifdef VC_ABLATE
-int vc_ablate_set_gru_train(int32_t v) {
-    VC_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_gru_train_ablate), &v, sizeof(int)));
-    return VC_OK;
-}
-#endif
 
 int vc_gru_backward(const float* d_dout, const float* d_out, const float* d_gates, const float* d_Wh_fw,
                     const float* d_Wh_bw, const float* d_WhT_fw, const float* d_WhT_bw, int32_t n_seq, int32_t T,

@@ -145,11 +145,19 @@ def test_fused_launch_shape_queries_and_validation_without_gpu():
 
 def test_kernel_options_are_explicit_and_ablations_are_not_shipped():
     """Kernel selection goes through vc_set_option only: the library does not import getenv, unknown names are
-    errors, and the result-corrupting ablation switches are rejected by the shipped (non -DVC_ABLATE) build."""
+    errors, and nothing of the former ablation build is left: its three switches are unknown options like any other,
+    the library exports no symbol of it and no source of the library names its macro."""
+    import glob
     import subprocess
     import _vc
-    lib = _vc.lib()
-    assert lib.vc_ablate_build() == 0
+    _vc.lib()
+    defined = subprocess.run(['nm', '-D', '--defined-only', _vc.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert 'vc_set_option' in defined                                         # nm did list the exports
+    assert [ln for ln in defined.splitlines() if 'ablate' in ln.lower()] == []
+    csrc = os.path.join(ROOT, 'speech-cloner_amd', 'csrc')
+    sources = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.h')) + [os.path.join(ROOT, 'include', 'vc_hip.h')]
+    assert len(sources) > 20
+    assert [f for f in sources if 'VC_ABLATE' in open(f).read()] == []
     assert _vc.get_option('gru_mfma') == -1
     _vc.set_option('gru_mfma', 1)
     assert _vc.get_option('gru_mfma') == 1
@@ -160,7 +168,7 @@ def test_kernel_options_are_explicit_and_ablations_are_not_shipped():
     with pytest.raises(_vc.VCError, match='unknown option'):
         _vc.set_option('no_such_switch', 1)
     for name in ('ablate_bank256', 'ablate_bank256_only', 'ablate_cbhg_front'):
-        with pytest.raises(_vc.VCError, match='VC_ABLATE'):
+        with pytest.raises(_vc.VCError, match='unknown option'):
             _vc.set_option(name, 1)
     und = subprocess.run(['nm', '-D', '--undefined-only', _vc.LIB_PATH], capture_output=True, text=True).stdout
     assert 'getenv' not in und
