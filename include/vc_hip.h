@@ -652,7 +652,8 @@ int vc_inv_preemphasis_normalize(const vc_vocoder_plan* plan, float* d_wav, cons
  * vc_highway_chain: d_packed / d_bias are HOST arrays of n_layers (0..8) device pointers (bias:
  * float32 [2H], paired order).  d_Y [M, ldy] bf16 receives the last layer's output (NULL: not
  * stored; may equal d_X).  d_proj_packed (NULL: no tail) / d_proj_bias [n_proj] / d_P [M, ldp]
- * float32.  Bit-identical to n_layers launches of vc_conv_gemm(VC_GEMM_HIGHWAY) + one dense launch. */
+ * float32; any n_proj that is a multiple of 64 is served, also one below the 64 columns per wave of a pass (a wave without
+ * a column group loads nothing).  Bit-identical to n_layers launches of vc_conv_gemm(VC_GEMM_HIGHWAY) + one dense launch. */
 int vc_highway_pack(const void* d_Bt, int32_t n_cols, int32_t H, void* d_packed, void* stream);
 int vc_highway_chain(const void* d_X, int32_t M, int32_t H, int32_t ldx, int32_t n_layers,
                      const void* const* d_packed, const float* const* d_bias, void* d_Y, int32_t ldy,
@@ -689,7 +690,8 @@ int vc_highway_chain(const void* d_X, int32_t M, int32_t H, int32_t ldx, int32_t
  *   norm of the 768 bank channels) | [2208, 2272) conv1d_1 scale | [2272, 2336) shift | [2336, 2400) conv1d_2 scale |
  *   [2400, 2464) shift | [2464, 2720) GRU bias (240) | [2720 + 128 l, +128) highway layer l biases, paired order.
  * d_x [n_windows * T, ldx] float32 (x_f32 = 1) or bf16; d_xproj [n_windows * T, ldp] float32 receives
- * columns [0, 240). */
+ * columns [0, 240).  A window whose features are NaN comes out as NaN (the ReLUs of this launch keep a NaN) and does not
+ * reach its neighbours. */
 #define VC_CBHG_FRONT_MAX_HIGHWAY 4
 typedef struct vc_cbhg_front_desc {
     const void* d_x;
@@ -714,7 +716,8 @@ int vc_cbhg_front(const vc_cbhg_front_desc* desc, void* stream);
  * launches): the intermediate stays in registers.  d_pk1 = vc_mfma_pack(W1^T [units1, cin_padded], chained = 0),
  * d_pk2 = vc_mfma_pack(W2^T [units2, units1], chained = 1); d_b1 [units1], d_b2 [units2] float32;
  * d_X [M, ldx] bf16, or float32 with x_f32 = 1 (converted on load: y_mel of the previous stage), padding columns zero; d_Y [M, ldy] bf16.  Same bf16 rounding points as the two launches,
- * float32 sums in the same K order (bit-identical in practice, tested to 1e-2). */
+ * float32 sums in the same K order: bit-identical to the two launches on the device (tests/test_chain_kernels_gpu.py asserts
+ * equality at M = 1 .. 257 for both shapes and both kernel forms). */
 int vc_prenet_chain_supported(int32_t cin_padded, int32_t units1, int32_t units2);
 int vc_prenet_chain(const void* d_X, int32_t x_f32, int32_t M, int32_t ldx, int32_t cin_padded, int32_t units1, int32_t units2,
                     const void* d_pk1, const float* d_b1, const void* d_pk2, const float* d_b2, void* d_Y, int32_t ldy,

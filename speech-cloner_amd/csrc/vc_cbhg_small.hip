@@ -64,6 +64,12 @@ __device__ __forceinline__ f32x16 zero16() {
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
+// relu that keeps a NaN (fmaxf returns its other operand): a window of NaN features must come out as NaN, as it does from
+// the float64 definition, not as finite numbers; every other value, signed zeros included, is fmaxf's
+__device__ __forceinline__ float relu_nan(float v) {
+    const float r = fmaxf(v, 0.0f);
+    return v != v ? v : r;
+}
 // second operand of the next (chained-K) layer, k-step s, from result tiles v[tile][16] held as bf16
 template <int NT>
 __device__ __forceinline__ bf16x8 chain(const bf16x4 (&v)[NT][4], int s) {
@@ -182,7 +188,7 @@ cbhg_small_kernel(CbhgSmallArgs a) {
             for (int q = 0; q < 4; ++q) {
                 const f32x4 bb = *reinterpret_cast<const f32x4*>(co + CO_B1 + 32 * tl + 8 * q + 4 * lh);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) y1[tl][q][e] = (__bf16)fmaxf(acc[4 * q + e] + bb[e], 0.0f);
+                for (int e = 0; e < 4; ++e) y1[tl][q][e] = (__bf16)relu_nan(acc[4 * q + e] + bb[e]);
             }
         }
 #pragma unroll
@@ -194,7 +200,7 @@ cbhg_small_kernel(CbhgSmallArgs a) {
             for (int q = 0; q < 4; ++q) {
                 const f32x4 bb = *reinterpret_cast<const f32x4*>(co + CO_B2 + 32 * tl + 8 * q + 4 * lh);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) pres[tl][q][e] = (__bf16)(inw ? fmaxf(acc[4 * q + e] + bb[e], 0.0f) : 0.0f);
+                for (int e = 0; e < 4; ++e) pres[tl][q][e] = (__bf16)(inw ? relu_nan(acc[4 * q + e] + bb[e]) : 0.0f);
             }
         }
     }
@@ -262,7 +268,7 @@ cbhg_small_kernel(CbhgSmallArgs a) {
             for (int mi = 0; mi < MI; ++mi) {
                 bf16x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (__bf16)(inr[mi] ? fmaxf(fmaf(bacc[mi][4 * q + e], sc[e], sh[e]), 0.0f) : 0.0f);
+                for (int e = 0; e < 4; ++e) o[e] = (__bf16)(inr[mi] ? relu_nan(fmaf(bacc[mi][4 * q + e], sc[e], sh[e])) : 0.0f);
                 *reinterpret_cast<bf16x4*>(Bw + (32 * mi + li) * CS_PITCH + (8 * q + 4 * lh) * 2) = o;
             }
         }
@@ -330,7 +336,7 @@ cbhg_small_kernel(CbhgSmallArgs a) {
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(co + CO_P1S + c0), sh = *reinterpret_cast<const f32x4*>(co + CO_P1B + c0);
                 bf16x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (__bf16)(inw ? fmaxf(fmaf(v[e], sc[e], sh[e]), 0.0f) : 0.0f);
+                for (int e = 0; e < 4; ++e) o[e] = (__bf16)(inw ? relu_nan(fmaf(v[e], sc[e], sh[e])) : 0.0f);
                 *reinterpret_cast<bf16x4*>(Qt + rw * CS_PITCH + c0 * 2) = o;
             }
         }

@@ -129,7 +129,8 @@ highway_chain_kernel(HwChainArgs a) {
         char* nxt = smem + ((layer & 1) ^ 1) * (HW_BM * RB);
         const bool more = layer + 1 < a.n_layers;
         f32x16 acc[4][2];
-        const bf16x8* nextw = more ? wptr(layer + 1, 0) : (a.PW ? reinterpret_cast<const bf16x8*>(a.PW) + ((size_t)w * KS * 2) * 64 + lane : nullptr);
+        // the tail's column group w exists only for w < NP / 64 (wave-uniform): no prefetch past the packed array
+        const bf16x8* nextw = more ? wptr(layer + 1, 0) : (a.PW && w < a.NP / 64 ? reinterpret_cast<const bf16x8*>(a.PW) + ((size_t)w * KS * 2) * 64 + lane : nullptr);
         hw_tile<H>(wptr(layer, 0), nextw, cur + li * RB, lh, x15, wr, acc);
         // ---- gate (lane-local) -> next activation tile
         f32x4 bH[4], bT[4];
@@ -164,7 +165,7 @@ highway_chain_kernel(HwChainArgs a) {
         const char* xrow = fin + li * RB;
         char* const stg = smem + ((a.n_layers & 1) ^ 1) * (HW_BM * RB) + w * 8192;    // the other activation buffer is idle
         static_assert((2 * H / 64) * 8192 <= HW_BM * 2 * H, "a 32 x 64 float32 sub-tile per wave fits the idle buffer");
-        if (a.n_layers == 0) {
+        if (a.n_layers == 0 && w < ngroups) {
             const bf16x8* p0 = reinterpret_cast<const bf16x8*>(a.PW) + ((size_t)w * KS * 2) * 64 + lane;
 #pragma unroll
             for (int s = 0; s < HW_RING; ++s) { wr[s][0] = p0[s * 128]; wr[s][1] = p0[s * 128 + 64]; }
