@@ -883,7 +883,8 @@ int vc_frame_mcd_f32(const float* d_ca, const float* d_cb, const int32_t* d_len_
  *   Refine      a parabola through d'(tau - 1), d'(tau), d'(tau + 1): offset = 0.5 (y0 - y2) / (y0 - 2 y1 + y2) when the
  *               denominator is positive, else 0, clamped to [-0.5, 0.5]; f0 = sample_rate / (tau + offset).
  *   Aperiodicity  min over tau_min <= tau <= tau_max of d'(tau), for every frame, voiced or not.
- * No smoothing, no octave correction (pYIN and its kin are not built).  Samples are expected to be finite.
+ * No smoothing, no octave correction in this launch ("Pitch tracking" below decodes a path through several candidates
+ * per frame).  Samples are expected to be finite.
  *
  * vc_f0_yin_f32: d_wav [batch] rows of max_len samples, row stride ld >= max_len; d_lens int32 [batch] ON THE DEVICE
  * (NULL = max_len), clamped to [0, max_len]; d_f0, d_aperiodicity [batch, max_frames] float32, max_frames >=
@@ -913,6 +914,62 @@ int vc_f0_yin_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int3
 int vc_f0_metrics_f32(const float* d_f0_a, const float* d_f0_b, const int32_t* d_len_a, const int32_t* d_len_b, int32_t batch,
                       int32_t max_a, int32_t max_b, const int32_t* d_path, const int32_t* d_path_len, int32_t max_path,
                       int32_t* d_counts, float* d_values, void* stream);
+
+/* Pitch tracking.  vc_f0_yin_f32 decides every frame alone and takes the FIRST dip of d' below the threshold; where the
+ * fundamental is weak the dip at half the period slips under the threshold and the frame is reported an octave high.
+ * These two launches keep several candidates per frame and choose among them along the utterance (Viterbi decoding, as
+ * in pYIN's second stage, on YIN's own d').  Added without a version bump.
+ *
+ * Candidates.  Frames, d(tau) and d'(tau) are exactly those of vc_f0_yin_f32 (the same frame count and placement, the
+ * direct-form difference, the same order of the running sum: the kernels share that code).  A lag tau in
+ * [tau_min, tau_max] is a candidate when d'(tau) < d'(tau - 1) (the left neighbour counts as +inf at tau = tau_min),
+ * d'(tau) <= d'(tau + 1) (the right neighbour as +inf at tau = tau_max) and d'(tau) < ceiling; so some lag holding the
+ * range minimum is a candidate whenever that minimum is below the ceiling.  The n_cand candidates of lowest d' are kept
+ * (on a tie in d' the smaller lag) and stored in ascending lag, each with f0 = sample_rate / (tau + offset) (YIN's
+ * clamped parabola, the same arithmetic), pitch = log2(f0) and cost = d'(tau).  Per frame also n, the number of
+ * candidates kept, and aperiodicity, the minimum of d' over the range, bit-identical to vc_f0_yin_f32's.  From an
+ * utterance's frame count on n = 0 and aperiodicity = 1; slots from n on hold f0 = 0, pitch = 0, cost = 1.  Digital
+ * silence (d' = 1 everywhere) gives n = 0 for any ceiling <= 1.
+ *
+ * vc_f0_candidates_f32: d_wav, d_lens, max_len, ld, sample_rate, hop, frame_length, tau_min, tau_max, max_frames as
+ * vc_f0_yin_f32; d_f0, d_pitch, d_cost [batch, max_frames, n_cand] float32; d_n [batch, max_frames] int32;
+ * d_aperiodicity [batch, max_frames] float32.  vc_f0_yin_f32's tiling; after d' is in LDS each lane flags a local
+ * minimum, and the n_cand lowest are taken by repeated arg-min over (d', lag) in a fixed order (no atomics).  Every
+ * output element is written exactly once.  Limits: those of vc_f0_yin_f32 and 1 <= n_cand <= 15; ceiling finite and > 0.
+ *
+ * Decoding.  S = n_cand + 1 states per frame: state 0 is unvoiced with local cost unvoiced_cost, state k >= 1 is
+ * candidate k - 1 with local cost cost[k - 1]; a state beyond n[f] is absent (cost +inf).  Transition t(i, j): 0 between
+ * unvoiced and unvoiced, switch_cost between unvoiced and voiced either way, jump_cost * |pitch_i - pitch_j| between two
+ * voiced states.  In float32, in this association order, nothing fused:
+ *     delta_0(j) = c_0(j);    delta_f(j) = min_i (delta_{f-1}(i) + t(i, j)) + c_f(j),  the lowest i among equals;
+ * after every frame m_f = min_j delta_f(j) is subtracted from every state and added into a float64 total (delta stays at
+ * the size of the transition costs however long the utterance is).  The last state is the lowest j of minimal delta;
+ * the path is read back from the stored predecessors.  With jump_cost = switch_cost = 0 and unvoiced_cost = threshold a
+ * frame is voiced exactly when its aperiodicity is below the threshold: YIN's decision.
+ *
+ * vc_f0_viterbi_f32: d_pitch, d_cost [batch, max_frames, n_cand] float32 and d_n [batch, max_frames] int32 (clamped to
+ * [0, n_cand]) as vc_f0_candidates_f32 writes them; d_frames int32 [batch] ON THE DEVICE, the frame counts (NULL =
+ * max_frames), clamped to [0, max_frames].  d_state [batch, max_frames] int32: 0 unvoiced, k candidate k - 1, -1 from
+ * the frame count on; d_total [batch] float32, the float64 total rounded once (0 without a frame); with d_cand_f0
+ * [batch, max_frames, n_cand] also d_f0 [batch, max_frames] = the chosen candidate's f0, 0 where unvoiced or beyond the
+ * frame count (pass both or NULL for both).  One wave per utterance; the lattice is staged through LDS in tiles of
+ * vc_f0_viterbi_tile() frames, two buffers; the predecessors are 4 bits per state, 8 bytes per frame, in d_workspace
+ * (8-byte aligned, vc_f0_viterbi_workspace_size bytes: host arithmetic only, 0 for a shape the launch would refuse).
+ * Every output element is written exactly once; no atomics, no memset.  The three costs must be finite and not negative
+ * (VC_ERR_INVALID).  Limits (VC_ERR_UNSUPPORTED): batch <= 65,535, max_frames <= 2^30 + 1, n_cand <= 15.
+ *
+ * Both are functions of their own utterance alone, bit-identical alone, in any batch, from run to run and under graph
+ * replay; capturable from the first call; arguments are checked before any HIP call. */
+int vc_f0_candidates_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, float sample_rate,
+                         int32_t hop, int32_t frame_length, int32_t tau_min, int32_t tau_max, float ceiling, int32_t n_cand,
+                         float* d_f0, float* d_pitch, float* d_cost, int32_t* d_n, float* d_aperiodicity, int32_t max_frames,
+                         void* stream);
+int32_t vc_f0_viterbi_tile(void);
+size_t vc_f0_viterbi_workspace_size(int32_t batch, int32_t max_frames, int32_t n_cand);
+int vc_f0_viterbi_f32(const float* d_pitch, const float* d_cost, const int32_t* d_n, const int32_t* d_frames, int32_t batch,
+                      int32_t max_frames, int32_t n_cand, float unvoiced_cost, float jump_cost, float switch_cost,
+                      const float* d_cand_f0, int32_t* d_state, float* d_f0, float* d_total, void* d_workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* Speech activity.  The scores above run over every frame, silence included; these five launches answer "where is the
  * speech" on the device, so that the DTW, the MCD and the F0 figures can be taken over speech frames only.  Added without

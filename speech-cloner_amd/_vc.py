@@ -268,6 +268,13 @@ _SIGS = {
                                         C.c_int32, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     'vc_gmm_update_f32': (C.c_int, [C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, C.c_float, _P, _P,
                                     _P, _P]),
+    # pitch tracking (csrc/vc_f0.hip, csrc/vc_f0_track.hip); the two older pitch rows still close the table
+    'vc_f0_candidates_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_float, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    'vc_f0_viterbi_tile': (C.c_int32, []),
+    'vc_f0_viterbi_workspace_size': (C.c_size_t, [C.c_int32] * 3),
+    'vc_f0_viterbi_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, _P, _P, _P, _P,
+                                    _P, C.c_size_t, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -303,7 +310,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*): a build older than this binding
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
                               '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None

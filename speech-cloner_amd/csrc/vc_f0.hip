@@ -15,6 +15,9 @@
 // d' goes to LDS; the first lag below the threshold and the minimum are reductions (exact, whatever their order); lane 0
 // walks to the bottom of the dip and fits the parabola.
 //
+// f0_candidates_kernel: the same tiling and the same d' (yin_stage, yin_dprime and yin_refine are the one text both kernels
+// use), then every local minimum of d' below a ceiling instead of the first dip below a threshold; see the kernel.
+//
 // A frame's result depends on that utterance's samples alone and on nothing that varies from run to run: no atomics, no
 // hand-off between workgroups, and G (chosen from the LDS budget) changes which workgroup computes a frame, not how.
 //
@@ -33,10 +36,65 @@ constexpr int MAX_SAMPLES = 1 << 30;    // f * hop and every sample index stay i
 constexpr int MAX_CELLS = 1 << 30;
 constexpr int LDS_BUDGET = 64 * 1024;   // the default limit: no function attribute, capturable from the first call
 constexpr int NT_M = 256;               // lanes of the metrics kernel
+constexpr int MAX_CAND = 15;            // candidates per frame: with the unvoiced state, 16 states (csrc/vc_f0_track.hip)
 
 inline int yin_lanes(int tau_max) { return (tau_max + 2 + 63) & ~63; }
 inline size_t yin_lds_bytes(int W, int tau_max, int hop, int G) {
     return ((size_t)W + tau_max + 1 + (size_t)(G - 1) * hop + yin_lanes(tau_max) + 64) * sizeof(float);
+}
+inline size_t cand_lds_bytes(int W, int tau_max, int hop, int G) { return yin_lds_bytes(W, tau_max, hop, G) + 64 * sizeof(float); }
+
+// The tile's samples, zeros outside [0, len): xs[e] = x[s0 + e], e < n_stage.
+__device__ __forceinline__ void yin_stage(float* xs, const float* __restrict__ x, int s0, int n_stage, int len, int t, int NT) {
+    for (int e = t; e < n_stage; e += NT) {
+        const int i = s0 + e;
+        xs[e] = (i >= 0 && i < len) ? x[i] : 0.0f;
+    }
+}
+
+// d'(t) of the frame at `a`, also left in dp[t]: the difference, the scan and the normalisation, shared by f0_yin_kernel
+// and f0_candidates_kernel (one text, so both see the same d' bit for bit).  Holds one __syncthreads().
+__device__ __forceinline__ float yin_dprime(const float* a, int W, int n_lags, int t, int lane, int wave, float* dp, float* wtot) {
+    // lanes beyond the last lag repeat it (their reads stay inside the stage) and are left out below
+    const float* c = a + min(t, n_lags - 1);
+    float acc = 0.0f;
+    int j = 0;
+    for (; j + 8 <= W; j += 8) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float df = a[j + u] - c[j + u];
+            acc = fmaf(df, df, acc);
+        }
+    }
+    for (; j < W; ++j) {
+        const float df = a[j] - c[j];
+        acc = fmaf(df, df, acc);
+    }
+    const float d = t < n_lags ? acc : 0.0f;
+    float v = d;                                                    // inclusive scan over lags; d(0) is exactly zero
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const float u = __shfl_up(v, s, 64);
+        if (lane >= s) v += u;
+    }
+    if (lane == 63) wtot[wave] = v;
+    __syncthreads();
+    float off = 0.0f;
+    for (int w = 0; w < wave; ++w) off += wtot[w];
+    const float S = wave == 0 ? v : v + off;
+    float q = 1.0f;
+    if (t > 0 && S > 0.0f) q = (d * (float)t) / S;
+    dp[t] = q;
+    return q;
+}
+
+// f0 of the dip at lag tau: the clamped parabola through d'(tau - 1 .. tau + 1)
+__device__ __forceinline__ float yin_refine(const float* dp, int tau, float sr) {
+    const float y0 = dp[tau - 1], y1 = dp[tau], y2 = dp[tau + 1];
+    const float den = (y0 - 2.0f * y1) + y2;
+    float o = den > 0.0f ? 0.5f * (y0 - y2) / den : 0.0f;
+    o = fminf(fmaxf(o, -0.5f), 0.5f);
+    return sr / ((float)tau + o);
 }
 
 __global__ void __launch_bounds__(MAX_LAGS)
@@ -66,49 +124,14 @@ f0_yin_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lens, i
         for (int f = g0 + t; f < g_end; f += NT) { out_f[f] = 0.0f; out_a[f] = 1.0f; }
         return;
     }
-    const float* __restrict__ x = wav + (size_t)b * ld;
-    const int s0 = g0 * hop - (W + tau_max) / 2;
-    for (int e = t; e < n_stage; e += NT) {
-        const int i = s0 + e;
-        xs[e] = (i >= 0 && i < len) ? x[i] : 0.0f;
-    }
+    yin_stage(xs, wav + (size_t)b * ld, g0 * hop - (W + tau_max) / 2, n_stage, len, t, NT);
     __syncthreads();
     for (int f = g0; f < g_end; ++f) {
         if (f >= n_fr) {                                            // uniform over the workgroup
             if (t == 0) { out_f[f] = 0.0f; out_a[f] = 1.0f; }
             continue;
         }
-        const float* a = xs + (f - g0) * hop;
-        // lanes beyond the last lag repeat it (their reads stay inside the stage) and are left out below
-        const float* c = a + min(t, n_lags - 1);
-        float acc = 0.0f;
-        int j = 0;
-        for (; j + 8 <= W; j += 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float df = a[j + u] - c[j + u];
-                acc = fmaf(df, df, acc);
-            }
-        }
-        for (; j < W; ++j) {
-            const float df = a[j] - c[j];
-            acc = fmaf(df, df, acc);
-        }
-        const float d = t < n_lags ? acc : 0.0f;
-        float v = d;                                                // inclusive scan over lags; d(0) is exactly zero
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const float u = __shfl_up(v, s, 64);
-            if (lane >= s) v += u;
-        }
-        if (lane == 63) wtot[wave] = v;
-        __syncthreads();
-        float off = 0.0f;
-        for (int w = 0; w < wave; ++w) off += wtot[w];
-        const float S = wave == 0 ? v : v + off;
-        float q = 1.0f;
-        if (t > 0 && S > 0.0f) q = (d * (float)t) / S;
-        dp[t] = q;
+        const float q = yin_dprime(xs + (f - g0) * hop, W, n_lags, t, lane, wave, dp, wtot);
         const bool in_range = t >= tau_min && t <= tau_max;
         float m = in_range ? q : __builtin_inff();
         int first = (in_range && q < threshold) ? t : 0x7fffffff;
@@ -125,16 +148,110 @@ f0_yin_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lens, i
             if (first <= tau_max) {
                 int tau = first;
                 while (tau + 1 <= tau_max && dp[tau + 1] < dp[tau]) ++tau;
-                const float y0 = dp[tau - 1], y1 = dp[tau], y2 = dp[tau + 1];
-                const float den = (y0 - 2.0f * y1) + y2;
-                float o = den > 0.0f ? 0.5f * (y0 - y2) / den : 0.0f;
-                o = fminf(fmaxf(o, -0.5f), 0.5f);
-                hz = sr / ((float)tau + o);
+                hz = yin_refine(dp, tau, sr);
             }
             out_f[f] = hz;
             out_a[f] = m;
         }
         __syncthreads();                                            // dp, wtot, wmin and wfirst are written again by the next frame
+    }
+}
+
+// The candidates of every frame (include/vc_hip.h, "Pitch tracking"): f0_yin_kernel's tiling, staging and d', then the
+// local minima of d' below the ceiling, the n_cand lowest of them by repeated arg-min over (d', lag), written in
+// ascending lag.  A round of the selection: each wave's minimum on DPP, the lowest lane that holds it from a ballot (lags
+// ascend with lanes, so that is the smallest lag), the waves' pairs through LDS (two buffers in turn: one barrier a
+// round), every lane scanning them in wave order with a strict compare, so the smaller lag wins a tie.  The chosen
+// lanes then count the chosen lanes below them (a ballot and the waves' counts), refine their own lag and store it.
+__global__ void __launch_bounds__(MAX_LAGS)
+f0_candidates_kernel(const float* __restrict__ wav, const int32_t* __restrict__ lens, int max_len, int ld, float sr, int hop, int W,
+                     int tau_min, int tau_max, float ceiling, int n_cand, int G, float* __restrict__ c_f0,
+                     float* __restrict__ c_pitch, float* __restrict__ c_cost, int32_t* __restrict__ c_n, float* __restrict__ aper,
+                     int max_frames) {
+    extern __shared__ __align__(16) float lds[];
+    const int t = threadIdx.x;
+    const int NT = blockDim.x;
+    const int lane = t & 63, wave = t >> 6, n_waves = NT >> 6;
+    const int n_lags = tau_max + 2;
+    const int n_stage = W + tau_max + 1 + (G - 1) * hop;
+    float* xs = lds;                                                // [n_stage]
+    float* dp = xs + n_stage;                                       // [NT]
+    float* wtot = dp + NT;                                          // [16]
+    float* wmin = wtot + 16;                                        // [16]
+    float* wkq = wmin + 16;                                         // [2][16] the waves' lowest d' of a round
+    int* wkt = reinterpret_cast<int*>(wkq + 32);                    // [2][16] and its lag
+    int* wcnt = wkt + 32;                                           // [16] chosen lanes per wave
+    const float NONE = 3.402823466e38f;                             // vc::wave_min's identity; no candidate holds it (d' < ceiling)
+    const int b = blockIdx.y;
+    const int g0 = blockIdx.x * G;
+    const int len = lens ? min(max(lens[b], 0), max_len) : max_len;
+    const int n_fr = 1 + len / hop;
+    const size_t row = (size_t)b * max_frames;
+    const int g_end = min(g0 + G, max_frames);
+    if (g0 >= n_fr) {                                               // the whole tile lies beyond the utterance
+        for (int f = g0 + t; f < g_end; f += NT) { c_n[row + f] = 0; aper[row + f] = 1.0f; }
+        const size_t e0 = (row + g0) * n_cand, e1 = (row + g_end) * n_cand;
+        for (size_t e = e0 + t; e < e1; e += NT) { c_f0[e] = 0.0f; c_pitch[e] = 0.0f; c_cost[e] = 1.0f; }
+        return;
+    }
+    yin_stage(xs, wav + (size_t)b * ld, g0 * hop - (W + tau_max) / 2, n_stage, len, t, NT);
+    __syncthreads();
+    for (int f = g0; f < g_end; ++f) {
+        const size_t o = (row + f) * n_cand;
+        if (f >= n_fr) {                                            // uniform over the workgroup
+            if (t < n_cand) { c_f0[o + t] = 0.0f; c_pitch[o + t] = 0.0f; c_cost[o + t] = 1.0f; }
+            if (t == 0) { c_n[row + f] = 0; aper[row + f] = 1.0f; }
+            continue;
+        }
+        const float q = yin_dprime(xs + (f - g0) * hop, W, n_lags, t, lane, wave, dp, wtot);
+        const bool in_range = t >= tau_min && t <= tau_max;
+        float m = in_range ? q : __builtin_inff();
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) m = fminf(m, __shfl_xor(m, s, 64));
+        if (lane == 0) wmin[wave] = m;
+        __syncthreads();                                            // every d' is in dp
+        const bool flag = in_range && q < ceiling && (t == tau_min || q < dp[t - 1]) && (t == tau_max || q <= dp[t + 1]);
+        float key = flag ? q : NONE;
+        bool taken = false;
+        for (int k = 0; k < n_cand; ++k) {
+            const float wm = vc::wave_min(key);
+            const unsigned long long held = __ballot(key == wm);
+            if (lane == 0) {
+                wkq[(k & 1) * 16 + wave] = wm;
+                wkt[(k & 1) * 16 + wave] = wm < NONE ? (wave << 6) + __ffsll((long long)held) - 1 : 0x7fffffff;
+            }
+            __syncthreads();
+            float bq = NONE;
+            int bt = 0x7fffffff;
+            for (int w = 0; w < n_waves; ++w) {
+                const float wq = wkq[(k & 1) * 16 + w];
+                if (wq < bq) { bq = wq; bt = wkt[(k & 1) * 16 + w]; }
+            }
+            if (bt == 0x7fffffff) break;                            // uniform: no local minimum is left
+            if (t == bt) { taken = true; key = NONE; }
+        }
+        const unsigned long long chosen = __ballot(taken);
+        if (lane == 0) wcnt[wave] = __popcll(chosen);
+        __syncthreads();
+        int below = __popcll(chosen & ((1ull << lane) - 1ull)), n = 0;
+        for (int w = 0; w < n_waves; ++w) {
+            const int c = wcnt[w];
+            if (w < wave) below += c;
+            n += c;
+        }
+        if (taken) {
+            const float hz = yin_refine(dp, t, sr);
+            c_f0[o + below] = hz;
+            c_pitch[o + below] = log2f(hz);
+            c_cost[o + below] = q;
+        }
+        if (t >= n && t < n_cand) { c_f0[o + t] = 0.0f; c_pitch[o + t] = 0.0f; c_cost[o + t] = 1.0f; }
+        if (t == 0) {
+            for (int w = 1; w < n_waves; ++w) m = fminf(m, wmin[w]);
+            c_n[row + f] = n;
+            aper[row + f] = m;
+        }
+        __syncthreads();                                            // dp and the waves' words are written again by the next frame
     }
 }
 
@@ -272,6 +389,37 @@ int vc_f0_yin_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int3
     hipLaunchKernelGGL(f0_yin_kernel, grid, dim3(yin_lanes(tau_max)), yin_lds_bytes(frame_length, tau_max, hop, G),
                        static_cast<hipStream_t>(stream), d_wav, d_lens, max_len, ld, sample_rate, hop, frame_length, tau_min, tau_max,
                        threshold, G, d_f0, d_aperiodicity, max_frames);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+int vc_f0_candidates_f32(const float* d_wav, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, float sample_rate,
+                         int32_t hop, int32_t frame_length, int32_t tau_min, int32_t tau_max, float ceiling, int32_t n_cand,
+                         float* d_f0, float* d_pitch, float* d_cost, int32_t* d_n, float* d_aperiodicity, int32_t max_frames,
+                         void* stream) {
+    VC_REQUIRE(d_wav && d_f0 && d_pitch && d_cost && d_n && d_aperiodicity, "vc_f0_candidates_f32: NULL argument");
+    VC_REQUIRE(batch >= 1 && max_len >= 1 && ld >= max_len && hop >= 1 && frame_length >= 1 && n_cand >= 1,
+               "vc_f0_candidates_f32: bad shape (batch %d, max_len %d, ld %d, hop %d, frame_length %d, n_cand %d; need all >= 1 and "
+               "ld >= max_len)", batch, max_len, ld, hop, frame_length, n_cand);
+    VC_REQUIRE(tau_min >= 1 && tau_max >= tau_min, "vc_f0_candidates_f32: need 1 <= tau_min <= tau_max (got %d, %d)", tau_min, tau_max);
+    VC_REQUIRE(std::isfinite(sample_rate) && sample_rate > 0.0f && std::isfinite(ceiling) && ceiling > 0.0f,
+               "vc_f0_candidates_f32: need a finite sample_rate > 0 and a finite ceiling > 0 (got %g, %g)", (double)sample_rate,
+               (double)ceiling);
+    VC_REQUIRE(max_frames >= 1, "vc_f0_candidates_f32: max_frames must be at least 1 (got %d)", max_frames);
+    if (batch > 65535 || max_len > MAX_SAMPLES || frame_length > MAX_W || tau_max + 2 > MAX_LAGS || hop > MAX_HOP ||
+        max_frames > MAX_SAMPLES + 1 || n_cand > MAX_CAND)
+        return vc::set_error(VC_ERR_UNSUPPORTED, "vc_f0_candidates_f32: limits are batch <= 65535, max_len <= %d, frame_length <= %d, "
+                             "tau_max <= %d (one lane per lag), hop <= %d, max_frames <= %d, n_cand <= %d; got batch %d, max_len %d, "
+                             "frame_length %d, tau_max %d, hop %d, max_frames %d, n_cand %d", MAX_SAMPLES, MAX_W, MAX_LAGS - 2, MAX_HOP,
+                             MAX_SAMPLES + 1, MAX_CAND, batch, max_len, frame_length, tau_max, hop, max_frames, n_cand);
+    VC_REQUIRE(max_frames >= 1 + max_len / hop, "vc_f0_candidates_f32: max_frames %d is less than 1 + max_len / hop = %d", max_frames,
+               1 + max_len / hop);
+    int G = 16;
+    while (G > 1 && cand_lds_bytes(frame_length, tau_max, hop, G) > (size_t)LDS_BUDGET) G >>= 1;
+    const dim3 grid((unsigned)((max_frames + G - 1) / G), (unsigned)batch);
+    hipLaunchKernelGGL(f0_candidates_kernel, grid, dim3(yin_lanes(tau_max)), cand_lds_bytes(frame_length, tau_max, hop, G),
+                       static_cast<hipStream_t>(stream), d_wav, d_lens, max_len, ld, sample_rate, hop, frame_length, tau_min, tau_max,
+                       ceiling, n_cand, G, d_f0, d_pitch, d_cost, d_n, d_aperiodicity, max_frames);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }

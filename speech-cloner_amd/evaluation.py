@@ -12,6 +12,9 @@ two.  The same number, frame by frame (``align='frame'``), compares two conversi
   mcd_batch(mel_a, mel_b, len_a, len_b, cfg_d, ...)             the two above in one; mel as convert_batch returns it
   mcd_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)       resampler and front-end on both sides first
   f0_batch(wav, lens, sr, hop_length, ...)                      -> (f0 [B, F] Hz, 0 = unvoiced; aperiodicity; n_frames): YIN
+  f0_candidates_batch(wav, lens, sr, hop_length, ..., n_cand, ceiling)   -> up to n_cand F0 candidates per frame (f0, pitch, cost, n)
+  f0_viterbi_batch(pitch, cost, n, lens, unvoiced_cost, jump_cost, switch_cost, f0)   -> the cheapest path through them (state, total, f0)
+  f0_track_batch(wav, lens, sr, hop_length, ..., jump_cost, switch_cost, n_cand)      the two above in one; drops in for f0_batch
   f0_metrics_batch(f0_a, f0_b, len_a, len_b, path, path_len)    voicing error, F0 RMSE (cents, Hz), log-F0 correlation
   score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, ...)     MCD and the F0 figures along one DTW path in one call
   activity_batch(wav, lens, hop_length, frame_length, mode, ...) -> speech-activity mask, frame list, intervals, frame energy
@@ -32,7 +35,7 @@ Definitions (include/vc_hip.h, "Evaluation"):
 
 Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
 the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip, csrc/vc_f0.hip (the pitch tracker
-and its figures), csrc/vc_activity.hip (the masks) and csrc/vc_content.hip (the content scores,
+and its figures), csrc/vc_f0_track.hip (the Viterbi decoding of F0 candidates, section 19), csrc/vc_activity.hip (the masks) and csrc/vc_content.hip (the content scores,
 DESIGN.md section 17); there is no CPU path.  Speaker similarity (GMM-UBM, log-likelihood ratios) lives in speaker.py.
 """
 from collections import namedtuple
@@ -51,6 +54,11 @@ F0_MAX_SAMPLES = 2 ** 30
 
 _RESULT = namedtuple('mcd', 'total path_len mcd path')
 _F0 = namedtuple('f0', 'f0 aperiodicity n_frames')
+_F0_CAND = namedtuple('f0_candidates', 'f0 pitch cost n aperiodicity frames')
+_F0_PATH = namedtuple('f0_viterbi', 'state total f0')
+_F0_TRACK = namedtuple('f0_track', 'f0 aperiodicity n_frames state total')
+F0_MAX_CAND = 15            # vc_f0_candidates_f32, vc_f0_viterbi_f32: with the unvoiced state, 16 states
+F0_METHODS = ('yin', 'viterbi')
 _F0_FIELDS = 'n_cells n_both_voiced n_vuv_mismatch vuv_error f0_rmse_cents f0_rmse_hz logf0_corr'
 _F0_METRICS = namedtuple('f0_metrics', _F0_FIELDS)
 _SCORE = namedtuple('score', 'mcd total path_len path ' + _F0_FIELDS + ' f0_a f0_b n_active_a n_active_b mask_a mask_b')
@@ -461,6 +469,157 @@ def f0_batch(wav, lens=None, sr=16000, hop_length=80, frame_length=512, fmin=60.
     return _F0(f0, ap, [1 + int(n) // args[1] for n in h])
 
 
+def _track_args(n_cand, ceiling, what):
+    if isinstance(n_cand, bool) or not isinstance(n_cand, (int, np.integer)) or not 1 <= n_cand <= F0_MAX_CAND:
+        raise ValueError(' - ERROR, {}: n_cand must be an integer in [1, {}], got {!r}'.format(what, F0_MAX_CAND, n_cand))
+    ceiling = float(ceiling)
+    if not (np.isfinite(ceiling) and ceiling > 0.0):
+        raise ValueError(' - ERROR, {}: ceiling must be finite and positive, got {!r}'.format(what, ceiling))
+    return int(n_cand), ceiling
+
+
+def _viterbi_costs(unvoiced_cost, jump_cost, switch_cost, what):
+    out = []
+    for v, name in ((unvoiced_cost, 'unvoiced_cost'), (jump_cost, 'jump_cost'), (switch_cost, 'switch_cost')):
+        v = float(v)
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(' - ERROR, {}: {} must be finite and not negative, got {!r}'.format(what, name, v))
+        out.append(v)
+    return tuple(out)
+
+
+def _f0_candidates_launch(wav, d_len, args, n_cand, ceiling):
+    """wav: cuda, contiguous float32 [B, Lmax]; d_len: device int32 [B] or None.  No host check in here."""
+    import torch
+    sr, hop, W, tau_min, tau_max, _ = args
+    B, Lmax = wav.shape
+    Fmax = 1 + Lmax // hop
+    f0, pitch, cost = (torch.empty((B, Fmax, n_cand), dtype=torch.float32, device=wav.device) for _ in range(3))
+    n = torch.empty((B, Fmax), dtype=torch.int32, device=wav.device)
+    ap = torch.empty((B, Fmax), dtype=torch.float32, device=wav.device)
+    _vc.check(_vc.lib().vc_f0_candidates_f32(_vc.ptr(wav), _vc.ptr(d_len), B, Lmax, Lmax, float(sr), hop, W, tau_min, tau_max, ceiling,
+                                             n_cand, _vc.ptr(f0), _vc.ptr(pitch), _vc.ptr(cost), _vc.ptr(n), _vc.ptr(ap), Fmax,
+                                             _vc.current_stream()))
+    return f0, pitch, cost, n, ap
+
+
+def _f0_viterbi_launch(pitch, cost, n, d_frames, costs, cand_f0):
+    """pitch, cost (and cand_f0 or None): cuda, contiguous float32 [B, F, n_cand]; n int32 [B, F]; d_frames device int32
+    [B] or None.  No host check in here."""
+    import torch
+    lib = _vc.lib()
+    B, F, n_cand = pitch.shape
+    dev = pitch.device
+    need = lib.vc_f0_viterbi_workspace_size(B, F, n_cand)
+    if need == 0:
+        raise _vc.VCError('vc_f0_viterbi_workspace_size refused {} utterances of {} frames with {} candidates'.format(B, F, n_cand))
+    ws = torch.empty((need // 8,), dtype=torch.int64, device=dev)
+    state = torch.empty((B, F), dtype=torch.int32, device=dev)
+    total = torch.empty((B,), dtype=torch.float32, device=dev)
+    f0 = None if cand_f0 is None else torch.empty((B, F), dtype=torch.float32, device=dev)
+    _vc.check(lib.vc_f0_viterbi_f32(_vc.ptr(pitch), _vc.ptr(cost), _vc.ptr(n), _vc.ptr(d_frames), B, F, n_cand, costs[0], costs[1],
+                                    costs[2], _vc.ptr(cand_f0), _vc.ptr(state), _vc.ptr(f0), _vc.ptr(total), _vc.ptr(ws), need,
+                                    _vc.current_stream()))
+    return state, total, f0
+
+
+def _f0_track_launch(wav, d_len, d_frames, args, n_cand, ceiling, costs):
+    """Both launches of the Viterbi tracker: (f0 [B, Fmax], aperiodicity, state, total).  No host check in here."""
+    f0c, pitch, cost, n, ap = _f0_candidates_launch(wav, d_len, args, n_cand, ceiling)
+    state, total, f0 = _f0_viterbi_launch(pitch, cost, n, d_frames, costs, f0c)
+    return f0, ap, state, total
+
+
+def _check_wav(wav, what):
+    import torch
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    if torch.is_tensor(wav) and wav.dtype != torch.float32:
+        raise ValueError(' - ERROR, {}: wav must be float32, got {}'.format(what, wav.dtype))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    if B > 65535 or Lmax > F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of at most {} samples (got {} of {})'.format(what, F0_MAX_SAMPLES, B, Lmax))
+    return B, Lmax
+
+
+def f0_candidates_batch(wav, lens=None, sr=16000, hop_length=80, frame_length=512, fmin=60.0, fmax=400.0, n_cand=8, ceiling=1.0):
+    """Up to n_cand F0 candidates per frame (vc_f0_candidates_f32; the definition is in include/vc_hip.h, "Pitch
+    tracking"): the local minima of YIN's d' below ``ceiling``, the n_cand lowest of them, in ascending lag.
+
+    wav, lens, sr, hop_length, frame_length, fmin, fmax as in f0_batch: the frames and d' are f0_batch's.  Returns a
+    namedtuple: f0, pitch (= log2 f0), cost (= d' at the lag), each float32 [B, Fmax, n_cand]; n int32 [B, Fmax], the
+    number of candidates of a frame (slots from n on hold 0, 0, 1; n = 0 beyond a row's frames and in digital silence);
+    aperiodicity [B, Fmax], bit-identical to f0_batch's; frames, the list of frame counts (f0_batch's n_frames)."""
+    import torch
+    B, Lmax = _check_wav(wav, 'f0_candidates_batch')
+    args = _f0_args(sr, hop_length, frame_length, fmin, fmax, 0.5, 'f0_candidates_batch')
+    n_cand, ceiling = _track_args(n_cand, ceiling, 'f0_candidates_batch')
+    h = np.full((B,), Lmax, dtype=np.int64) if lens is None else _check_lens(lens, B, Lmax, 'f0_candidates_batch: lens')
+    _need_gpu('f0_candidates_batch')
+    d_len, = _upload_lens(h)
+    out = _f0_candidates_launch(_to_device(wav, torch.float32), d_len, args, n_cand, ceiling)
+    return _F0_CAND(*out, [1 + int(v) // args[1] for v in h])
+
+
+def f0_viterbi_batch(pitch, cost, n, lens, unvoiced_cost=0.15, jump_cost=0.5, switch_cost=0.1, f0=None):
+    """The cheapest path through a lattice of candidates with an unvoiced state (vc_f0_viterbi_f32).
+
+    pitch, cost float32 [B, F, n_cand] and n int32 [B, F] as f0_candidates_batch returns them (any lattice will do: pitch
+    in octaves, cost >= 0, n candidates per frame); lens: host integers in [1, F], the frame counts.  State 0 (unvoiced)
+    costs unvoiced_cost per frame, a candidate its cost; moving between unvoiced and voiced costs switch_cost, between
+    two candidates jump_cost per octave.  Returns a namedtuple: state int32 [B, F] (0 unvoiced, k candidate k - 1, -1
+    beyond a row's frames), total float32 [B] (the path's cost), and f0 [B, F] (0 where unvoiced) when given the
+    candidates' f0 [B, F, n_cand], else None."""
+    import torch
+    for t, name in ((pitch, 'pitch'), (cost, 'cost')) + (((f0, 'f0'),) if f0 is not None else ()):
+        if getattr(t, 'ndim', 0) != 3 or min(t.shape) < 1 or tuple(t.shape) != tuple(pitch.shape):
+            raise ValueError(' - ERROR, f0_viterbi_batch: {} must be [B, F, n_cand], the same for pitch, cost and f0'.format(name))
+        if torch.is_tensor(t) and t.dtype != torch.float32:
+            raise ValueError(' - ERROR, f0_viterbi_batch: {} must be float32, got {}'.format(name, t.dtype))
+    B, F, n_cand = (int(v) for v in pitch.shape)
+    if getattr(n, 'ndim', 0) != 2 or tuple(n.shape) != (B, F):
+        raise ValueError(' - ERROR, f0_viterbi_batch: n must be [B, F] = {}'.format((B, F)))
+    if (n.dtype != torch.int32) if torch.is_tensor(n) else (np.asarray(n).dtype.kind not in 'iu'):
+        raise ValueError(' - ERROR, f0_viterbi_batch: n must be an int32 tensor or an integer array, got {}'.format(n.dtype))
+    _track_args(n_cand, 1.0, 'f0_viterbi_batch')
+    costs = _viterbi_costs(unvoiced_cost, jump_cost, switch_cost, 'f0_viterbi_batch')
+    h = _check_lens(lens, B, F, 'f0_viterbi_batch: lens')
+    if B > 65535 or F > F0_MAX_SAMPLES + 1:
+        raise ValueError(' - ERROR, f0_viterbi_batch: at most 65535 utterances of at most {} frames'.format(F0_MAX_SAMPLES + 1))
+    _need_gpu('f0_viterbi_batch')
+    d_frames, = _upload_lens(h)
+    if not torch.is_tensor(n):
+        n = torch.from_numpy(np.ascontiguousarray(n, dtype=np.int32))
+    n = n.to('cuda').contiguous()
+    out = _f0_viterbi_launch(_to_device(pitch, torch.float32), _to_device(cost, torch.float32), n, d_frames, costs,
+                             None if f0 is None else _to_device(f0, torch.float32))
+    return _F0_PATH(*out)
+
+
+def f0_track_batch(wav, lens=None, sr=16000, hop_length=80, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5,
+                   switch_cost=0.1, n_cand=8, ceiling=1.0):
+    """F0 of B utterances by Viterbi decoding over YIN's candidates: f0_candidates_batch, then f0_viterbi_batch with
+    unvoiced_cost = threshold.  Where f0_batch takes the first dip of d' below the threshold, frame by frame (and reports
+    the octave above when the dip at half the period slips under it), this takes the path of least cost through up to
+    n_cand dips per frame.  With jump_cost = switch_cost = 0 its voicing is f0_batch's on every frame.
+
+    Arguments as f0_batch, plus the path's costs.  Returns a namedtuple with f0_batch's fields in f0_batch's shapes and
+    dtypes -- f0 [B, Fmax] (0 = unvoiced), aperiodicity [B, Fmax] (bit-identical to f0_batch's), n_frames -- so it goes
+    wherever f0_batch's result goes, plus state int32 [B, Fmax] and total float32 [B] as in f0_viterbi_batch.  The
+    defaults 0.5 and 0.1 come from synthetic signals with a weak fundamental, not from speech."""
+    import torch
+    B, Lmax = _check_wav(wav, 'f0_track_batch')
+    args = _f0_args(sr, hop_length, frame_length, fmin, fmax, threshold, 'f0_track_batch')
+    n_cand, ceiling = _track_args(n_cand, ceiling, 'f0_track_batch')
+    costs = _viterbi_costs(args[5], jump_cost, switch_cost, 'f0_track_batch')
+    h = np.full((B,), Lmax, dtype=np.int64) if lens is None else _check_lens(lens, B, Lmax, 'f0_track_batch: lens')
+    _need_gpu('f0_track_batch')
+    frames = [1 + int(v) // args[1] for v in h]
+    d_len, d_frames = _upload_lens(h, frames)
+    f0, ap, state, total = _f0_track_launch(_to_device(wav, torch.float32), d_len, d_frames, args, n_cand, ceiling, costs)
+    return _F0_TRACK(f0, ap, frames, state, total)
+
+
 def _check_track(t, what):
     import torch
     if getattr(t, 'ndim', 0) != 2 or min(t.shape) < 1:
@@ -505,7 +664,7 @@ def f0_metrics_batch(f0_a, f0_b, len_a, len_b, path=None, path_len=None):
 
 def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best', scale=None,
                     n_coef=24, align='dtw', band=None, first_coef=1, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15,
-                    mask=None, top_db=40.0, max_gap=20, min_run=0):
+                    mask=None, top_db=40.0, max_gap=20, min_run=0, f0_method='yin', jump_cost=0.5, switch_cost=0.1, n_cand=8):
     """The three figures of a pair of utterances in one call -- MCD, F0 error, voiced / unvoiced error -- along ONE path.
 
     Arguments as mcd_wav_batch (the path is always made with align='dtw'), plus the tracker's frame_length, fmin, fmax,
@@ -518,10 +677,16 @@ def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b
     mask, top_db, max_gap, min_run as in mcd_wav_batch; the voiced modes reuse the tracks computed anyway.  With a mask
     mcd, total and path_len come from the DTW over the kept frames, path is in original frame numbers and the F0 figures
     are taken along it on the original tracks (align='frame': over the frames set in both masks).  n_active == 0 marks
-    a side that kept all its frames because none was active."""
+    a side that kept all its frames because none was active.
+
+    f0_method='viterbi' takes both tracks from f0_track_batch's launches (jump_cost, switch_cost, n_cand; unvoiced_cost =
+    threshold) instead of f0_batch's; everything that does not read a track (mcd, total, path_len, path without a voiced
+    mask) is bit-identical either way."""
     import audio_lib
     if cfg_d is None:
         raise ValueError(' - ERROR, score_wav_batch: cfg_d (the data-set configuration) is required')
+    if f0_method not in F0_METHODS:
+        raise ValueError(' - ERROR, score_wav_batch: f0_method must be one of {}, got {!r}'.format(F0_METHODS, f0_method))
     audio_lib._res_params(res_type)
     a = _wav_side(wav_a, lens_a, cfg_d, wav_sr_a, 'wav_a')
     b = _wav_side(wav_b, lens_b, cfg_d, wav_sr_b, 'wav_b')
@@ -534,6 +699,12 @@ def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b
     elif a['B'] > 65535:
         raise ValueError(' - ERROR, score_wav_batch: at most 65535 pairs')
     args = _f0_args(cfg_d['sample_rate'], cfg_d['hop_length'], frame_length, fmin, fmax, threshold, 'score_wav_batch')
+    if f0_method == 'viterbi':
+        n_cand, _ = _track_args(n_cand, 1.0, 'score_wav_batch')
+        costs = _viterbi_costs(args[5], jump_cost, switch_cost, 'score_wav_batch')
+        track = lambda x, d_len, d_fr: _f0_track_launch(x, d_len, d_fr, args, n_cand, 1.0, costs)[0]
+    else:
+        track = lambda x, d_len, d_fr: _f0_launch(x, d_len, args)[0]
     if mask is not None:
         act = _activity_args(mask, top_db, max_gap, min_run, 'score_wav_batch')
         _check_energy(cfg_d['hop_length'], cfg_d['win_length'], max(a['Fmax'], b['Fmax']), 'score_wav_batch')
@@ -543,7 +714,7 @@ def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b
     x_b = _wav_at_rate(wav_b, b, d_in_b, cfg_d, res_type)
     if mask is not None:
         x_a, x_b = x_a.contiguous(), x_b.contiguous()
-        f0_a, f0_b = _f0_launch(x_a, d_len_a, args)[0], _f0_launch(x_b, d_len_b, args)[0]
+        f0_a, f0_b = track(x_a, d_len_a, d_fa), track(x_b, d_len_b, d_fb)
         ma = _wav_mask(x_a, d_len_a, d_fa, cfg_d, act, f0_a)
         mb = _wav_mask(x_b, d_len_b, d_fb, cfg_d, act, f0_b)
         ia, ib = _compact_launch(ma, d_fa), _compact_launch(mb, d_fb)
@@ -559,7 +730,7 @@ def score_wav_batch(wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b
         return _SCORE(r.mcd, r.total, r.path_len, r.path, *m, f0_a, f0_b, ia.n_active, ib.n_active, ma, mb)
     ca = _cepstra_launch(_mel_launch(x_a, d_len_a, cfg_d), n_coef, first_coef)
     cb = _cepstra_launch(_mel_launch(x_b, d_len_b, cfg_d), n_coef, first_coef)
-    f0_a, f0_b = _f0_launch(x_a.contiguous(), d_len_a, args)[0], _f0_launch(x_b.contiguous(), d_len_b, args)[0]
+    f0_a, f0_b = track(x_a.contiguous(), d_len_a, d_fa), track(x_b.contiguous(), d_len_b, d_fb)
     r = _frame_launch(ca, cb, d_fa, d_fb, scale) if align == 'frame' else _dtw_launch(ca, cb, d_fa, d_fb, scale, band, True)
     m = _f0_metrics_launch(f0_a, f0_b, d_fa, d_fb, r.path, r.path_len if r.path is not None else None)
     return _SCORE(r.mcd, r.total, r.path_len, r.path, *m, f0_a, f0_b, None, None, None, None)
