@@ -784,6 +784,44 @@ int vc_compound_stitch(const void* d_src, int32_t src_dtype, const int32_t* d_ut
 int vc_phase_init(const int32_t* d_n_frames, const int32_t* d_utt_id, int32_t batch, int32_t max_frames, int32_t n_bins,
                   int64_t seed, float* d_phase, void* stream);
 
+/* vc_phase_spsi: a deterministic initial phase for Griffin-Lim computed from the magnitudes alone -- single-pass
+ * spectrogram inversion (Beauregard, Harish & Wyse 2015): pick every frame's spectral peaks, interpolate each peak's
+ * frequency, advance its phase by hop * frequency, lock the neighbouring bins to their peak.  No seed, no utterance id,
+ * no generator state: an utterance's phase does not depend on its place in the batch, on max_frames or on the other
+ * utterances.  Added without a version bump (a new export; no existing signature moved).
+ *
+ * d_amp [batch, max_frames, n_bins] float32, frame-major (the layout vc_griffin_lim_f32 takes), n_bins = 1 + n_fft/2;
+ * d_n_frames int32 [batch], NULL = max_frames; d_phase like d_amp.  The definition is exact: phase is kept as an unsigned
+ * 32-bit fraction of a turn (addition wraps mod 2^32 = one turn), and per frame t, from m = amp[u, t, :] only:
+ *   peak   bin k in 1 .. n_bins-2 with m[k] > m[k-1] and m[k] > m[k+1] (strict float32 comparisons);
+ *   owner  a peak owns itself; a non-peak bin b in 1 .. n_bins-2 is owned by the peak k > b if m[j] < m[j+1] for all
+ *          b <= j < k, by the peak k < b if m[j] < m[j-1] for all k < j <= b, and by the higher-frequency one if both
+ *          hold (a valley); bins 0 and n_bins-1 and every bin no peak reaches (plateaus, all-equal frames, monotone
+ *          ramps) are unowned;
+ *   inc(k) = uint32((uint64((hop*k) % n_fft) << 32) / n_fft) + uint32(llrint((double)p * ((double)hop * 2^32 / n_fft))),
+ *          p = 0.5f * (a - d) / ((a - 2.0f*c) + d) in float32 (this association, IEEE division) with
+ *          (a, c, d) = m[k-1], m[k], m[k+1];
+ *   v(t, b) = v(t-1, k) + inc(k) + (((b - k) & 1) << 31) if b is owned by k, v(t-1, b) otherwise, v(-1, .) = 0 -- the
+ *          half turn on every odd neighbour is the phase slope of a window centred at n_fft/2 in a frame that starts at
+ *          sample 0, which is what the vocoder's STFT uses;
+ *   phase[u, t, b] = float32(int32(v)) * float32(pi / 2^31) for t < n_frames[u], 0.0f beyond.
+ * Expected magnitudes are finite and non-negative; for them |p| <= 1/2 up to rounding.  No index is ever computed from a
+ * magnitude's value, only from comparisons, so any input bits (NaN, inf, negative) give some phase and never an
+ * out-of-range access; a p that is not finite or exceeds 1 in magnitude (only such inputs produce one) counts as 0.
+ *
+ * Three launches on `stream`, 32 frames per chunk: per (utterance, chunk) the composed map of the chunk's frames
+ * (source bin uint16, offset uint32 per bin), per utterance the state at every chunk's start, per (utterance, chunk) the
+ * replay that writes the phases.  No workgroup waits for another, no atomics, no memset, no host synchronisation:
+ * hipGraph-capturable; every element of d_phase is written exactly once and d_amp is only read.  d_workspace:
+ * vc_phase_spsi_workspace_bytes bytes (10 bytes per bin and chunk), 4-byte aligned, contents irrelevant before and after.
+ * VC_ERR_INVALID before any launch for a NULL pointer, batch outside [1, 65535], max_frames < 1, n_fft < 4,
+ * n_bins != 1 + n_fft/2, n_bins > 65535, hop outside [1, 65535], a short workspace, and for n_bins > 2978: the
+ * kernels keep a fill's magnitudes and tables in 64 KiB of LDS at 22 bytes per bin (n_fft up to 5955; the vocoder
+ * itself stops at n_fft 4096). */
+size_t vc_phase_spsi_workspace_bytes(int32_t batch, int32_t max_frames, int32_t n_bins);
+int vc_phase_spsi(const float* d_amp, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t n_bins,
+                  int32_t n_fft, int32_t hop, float* d_phase, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Resampling: what librosa.load(path, cfg['sample_rate']) does to a file of another rate before the reference sees it
  * (test.py:472, ARCTIC_reader.py:233, TIMIT_reader.py:308, TARGET_spk_reader.py:108), for a ragged batch on the device.

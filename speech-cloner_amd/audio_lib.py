@@ -19,6 +19,9 @@ cases of them):
   phase_init(n_frames, Fmax, n_bins, seed, utt_ids) -> torch.cuda tensor [B, Fmax, bins], Griffin-Lim's initial
                               phase drawn on the device (Philox4x32-10; include/vc_hip.h vc_phase_init);
                               the batched vocoder calls take it as ``phase0='device'``
+  phase_spsi(amp, n_frames)  -> torch.cuda tensor [B, Fmax, bins], a deterministic initial phase computed from the
+                             magnitudes (single-pass spectrogram inversion; include/vc_hip.h vc_phase_spsi);
+                             the batched vocoder calls take it as ``phase0='spsi'``
 
 The Griffin-Lim entry points take ``momentum`` (default 0.0, the reference's algorithm): fast
 Griffin-Lim as in librosa.griffinlim / torchaudio GriffinLim, see include/vc_hip.h
@@ -253,6 +256,10 @@ class _VocPlan:
         size = lib.vc_vocoder_workspace_bytes_momentum if momentum else lib.vc_vocoder_workspace_bytes
         return torch.empty(size(self.handle, batch, max_frames, int(trace)), dtype=torch.uint8, device=device)
 
+    def spsi_workspace(self, batch, max_frames, device):
+        """Scratch for ONE vc_phase_spsi call at this plan's bins, like workspace()."""
+        return _spsi_workspace(batch, max_frames, self.n_bins, device)
+
 
 def check_momentum(momentum):
     """Fast Griffin-Lim momentum as a float; ValueError unless finite and in [0, 1) (torchaudio's rule)."""
@@ -335,6 +342,63 @@ def phase_init(n_frames, Fmax, n_bins, seed=0, utt_ids=None, out=None):
     return out
 
 
+SPSI_CHUNK_FRAMES = 32          # frames per chunk of vc_phase_spsi's scan (csrc/vc_spsi.hip SPSI_CHUNK)
+
+
+def _spsi_workspace(batch, max_frames, n_bins, device):
+    """Scratch for ONE vc_phase_spsi call, from the caching allocator of the current stream (see _Plan.workspace)."""
+    import torch
+    return torch.empty(_vc.lib().vc_phase_spsi_workspace_bytes(batch, max_frames, n_bins), dtype=torch.uint8, device=device)
+
+
+def _phase_spsi_launch(amp, d_nf, n_fft, hop_length, out=None, plan=None):
+    """The launches of phase_spsi on validated device tensors (amp [B, Fmax, 1 + n_fft//2] float32 contiguous, d_nf int32
+    [B] or None): no host check, copy or wait in here.  plan: the vocoder plan that hands out the scratch (the vocoder
+    calls pass theirs; phase_spsi on its own needs none, so it also takes sizes a vocoder plan does not)."""
+    import torch
+    B, Fmax, nb = amp.shape
+    if out is None:
+        out = torch.empty_like(amp)
+    ws = plan.spsi_workspace(B, Fmax, amp.device) if plan is not None else _spsi_workspace(B, Fmax, nb, amp.device)
+    _vc.check(_vc.lib().vc_phase_spsi(_vc.ptr(amp), _vc.ptr(d_nf), B, Fmax, nb, int(n_fft), int(hop_length), _vc.ptr(out),
+                                      _vc.ptr(ws), ws.numel(), _vc.current_stream()))
+    return out
+
+
+def phase_spsi(amp, n_frames=None, hop_length=80, n_fft=400, out=None):
+    """A deterministic initial phase for Griffin-Lim from the magnitudes alone (vc_phase_spsi, include/vc_hip.h): float32
+    [B, Fmax, bins] cuda.  Single-pass spectrogram inversion: every frame's spectral peaks advance by hop_length times
+    their interpolated frequency and lock their neighbouring bins; rows beyond n_frames are 0.  amp: float32
+    [B, Fmax, 1 + n_fft//2] magnitudes, frame-major (numpy or tensor; expected finite and non-negative).  n_frames: [B]
+    host ints or int32 cuda tensor (None = all Fmax).  No seed and no utt_ids: an utterance's phase depends on its own
+    magnitudes only, not on its place in the batch, on Fmax or on the other utterances."""
+    import torch
+    n_fft, hop_length = int(n_fft), int(hop_length)
+    if not torch.is_tensor(amp):
+        amp = torch.from_numpy(np.ascontiguousarray(amp, dtype=np.float32))
+    if amp.dim() != 3 or amp.shape[0] == 0 or amp.shape[1] == 0 or amp.shape[2] != 1 + n_fft // 2:
+        raise ValueError(' - ERROR, phase_spsi: amp must be [B, F, {}]'.format(1 + n_fft // 2))
+    B, Fmax, nb = (int(v) for v in amp.shape)
+    if n_frames is not None:
+        if (int(n_frames.shape[0]) if torch.is_tensor(n_frames) else len(n_frames)) != B:
+            raise ValueError(' - ERROR, phase_spsi: n_frames must have one entry per utterance ({})'.format(B))
+        if not torch.is_tensor(n_frames) and (max(n_frames) > Fmax or min(n_frames) < 0):
+            raise ValueError(' - ERROR, phase_spsi: n_frames must be [B] with values in [0, {}]'.format(Fmax))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('phase_spsi needs a GPU (no CPU fallback)')
+    amp = amp.to(device='cuda', dtype=torch.float32).contiguous()
+    d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
+    if out is not None and (tuple(out.shape) != (B, Fmax, nb) or out.dtype != torch.float32 or not out.is_contiguous()
+                            or not out.is_cuda):
+        raise ValueError(' - ERROR, phase_spsi: out must be contiguous cuda float32 [B, Fmax, bins]')
+    return _phase_spsi_launch(amp, d_nf, n_fft, hop_length, out)
+
+
+def _check_phase0_name(phase0):
+    if isinstance(phase0, str) and phase0 not in ('device', 'spsi'):
+        raise ValueError(" - ERROR, griffin_lim_batch: phase0 must be None, 'device', 'spsi' or an array, got {!r}".format(phase0))
+
+
 def _griffin_lim_launch(plan, amp, phase0, d_nf, num_iters, trace, momentum):
     """The launches of griffin_lim_batch on validated device tensors (amp, phase0 [B, Fmax, bins] float32 contiguous,
     d_nf int32 [B] or None): no host check, copy or wait in here."""
@@ -360,12 +424,14 @@ def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_ite
     """Batched Griffin-Lim on the GPU.  amp: float32 [B, Fmax, bins] magnitudes (frame-major, the
     decoder's y_stft layout); phase0: same shape, radians (default: pi * np.random.rand drawn per
     utterance in the reference's [bins, F] order, audio_lib.py:255), or 'device': drawn by
-    phase_init(n_frames, Fmax, bins, seed, utt_ids) without touching the host generator.  momentum: fast Griffin-Lim
+    phase_init(n_frames, Fmax, bins, seed, utt_ids) without touching the host generator, or 'spsi': computed from amp by
+    phase_spsi (deterministic; seed and utt_ids are not used).  momentum: fast Griffin-Lim
     (0 <= momentum < 1; 0 = the reference's algorithm, 0.99 = librosa's default).
     Returns wav [B, hop*(Fmax-1)] cuda float32 (zero beyond an utterance's hop*(frames-1) samples)
     and, with ``trace``, the per-iteration sum of squared waveform changes [num_iters, B]."""
     import torch
     momentum = check_momentum(momentum)
+    _check_phase0_name(phase0)
     if not torch.cuda.is_available():
         raise _vc.VCError('griffin_lim needs a GPU (no CPU fallback)')
     plan = _get_voc_plan(win_length, hop_length, n_fft)
@@ -377,9 +443,10 @@ def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_ite
     B, Fmax, nb = amp.shape
     d_nf, h_nf = _frames_arg(n_frames, B, Fmax, plan)
     if isinstance(phase0, str):
-        if phase0 != 'device':
-            raise ValueError(" - ERROR, griffin_lim_batch: phase0 must be None, 'device' or an array, got {!r}".format(phase0))
-        phase0 = phase_init(h_nf if d_nf is None else d_nf, Fmax, nb, seed, utt_ids)
+        if phase0 == 'spsi':
+            phase0 = _phase_spsi_launch(amp, d_nf, plan.n_fft, plan.hop_length, plan=plan)
+        else:
+            phase0 = phase_init(h_nf if d_nf is None else d_nf, Fmax, nb, seed, utt_ids)
     elif phase0 is None:
         ph = np.zeros((B, Fmax, nb), dtype=np.float32)
         for b in range(B):
@@ -426,6 +493,7 @@ def from_power_to_wav_batch(P, n_frames=None, P_dB_norm_factor=0.01, pre_emphasi
     momentum: fast Griffin-Lim; phase0 / seed / utt_ids: see griffin_lim_batch."""
     import torch
     momentum = check_momentum(momentum)
+    _check_phase0_name(phase0)
     if not torch.cuda.is_available():
         raise _vc.VCError('from_power_to_wav needs a GPU (no CPU fallback)')
     plan = _get_voc_plan(win_length, hop_length, n_fft)

@@ -251,8 +251,10 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     configuration of test.py (sample_rate, hop_length, win_length, n_fft, n_timesteps, the front-end's settings).
     phase: 'device' (vc_phase_init from ``seed`` and ``utt_ids``, default 0 .. B-1; the true and the predicted
     spectrum start from the same phase), 'numpy' (the reference's draws from the global generator, in the order of a
-    loop of conversion2 calls) or a [B, Fout, bins] array.  window_batch: windows per decoder chunk (utterances and
-    passes mixed), issued round-robin on the decoder's streams.  vocode=False stops after the stitch.
+    loop of conversion2 calls), 'spsi' (audio_lib.phase_spsi: computed from the magnitudes, so the true and the predicted
+    spectrum each get the start of their own; ``seed`` and ``utt_ids`` are ignored) or a [B, Fout, bins] array.
+    window_batch: windows per decoder chunk (utterances and passes mixed), issued round-robin on the decoder's streams.
+    vocode=False stops after the stitch.
     encoder: only for a decoder built WITHOUT one (an MX-FP8 decoder owns its store and takes posteriors): the
     encoder whose posteriors feed it, chunk by chunk on the same streams.
     wav_sr: the sample rate of ``wav`` (None = cfg_d['sample_rate']); another rate is resampled on the device first
@@ -270,8 +272,8 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     seed = audio_lib.check_seed(seed)
     if cfg_d is None:
         raise ValueError(' - ERROR, convert_batch: cfg_d (the data-set configuration) is required')
-    if isinstance(phase, str) and phase not in ('device', 'numpy'):
-        raise ValueError(" - ERROR, convert_batch: phase must be 'device', 'numpy' or a [B, Fout, bins] array, got {!r}".format(phase))
+    if isinstance(phase, str) and phase not in ('device', 'numpy', 'spsi'):
+        raise ValueError(" - ERROR, convert_batch: phase must be 'device', 'numpy', 'spsi' or a [B, Fout, bins] array, got {!r}".format(phase))
     if getattr(wav, 'ndim', 0) != 2:
         raise ValueError(' - ERROR, convert_batch: wav must be [B, Lmax]')
     B, Lmax = int(wav.shape[0]), int(wav.shape[1])
@@ -383,6 +385,8 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     lib = _vc.lib()
     if isinstance(phase, str) and phase == 'device':
         ph_true = ph_pred = audio_lib.phase_init(d_nout, Fout, n_bins, seed, d_ids)
+    elif isinstance(phase, str) and phase == 'spsi':
+        ph_true = ph_pred = None                                   # from each spectrum's own magnitudes, in to_wav
 
     def power_to_amp(P, rl):
         amp = torch.empty_like(P)
@@ -391,6 +395,8 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
         return amp
 
     def to_wav(amp, ph):
+        if ph is None:
+            ph = audio_lib._phase_spsi_launch(amp, d_nout, vplan.n_fft, vplan.hop_length, plan=vplan)
         w = audio_lib._griffin_lim_launch(vplan, amp, ph, d_nout, n_iter, False, momentum)
         _vc.check(lib.vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(w), _vc.ptr(d_nout), B, Fout, w.shape[1],
                                                    float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
