@@ -625,7 +625,7 @@ struct vc_frontend_plan {
     vc_frontend_cfg cfg;
     int n_bins, mfcc_width, nnz;
     bool fft400;
-    bool fast400;                 // shipped configuration: the two-launch path of vc_frontend400.hip
+    bool fast400;                 // shipped configuration: the one- or two-launch path of vc_frontend400.hip
     std::vector<double> mel, dct;
     void* d_blob;
     FeDev dev;

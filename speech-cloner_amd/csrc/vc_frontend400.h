@@ -1,5 +1,5 @@
-// Internal interface between vc_frontend.hip (plan, validation, dispatch) and vc_frontend400.hip (the two-launch
-// front-end of the shipped configuration).
+// Internal interface between vc_frontend.hip (plan, validation, dispatch) and vc_frontend400.hip (the front-end
+// of the shipped configuration: one launch, or a statistics pass and a feature pass built from the same device code).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

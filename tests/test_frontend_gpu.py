@@ -60,17 +60,32 @@ def test_single_utterance_api_matches_oracle():
             _cmp(d, r, TOL[name], '%s L=%d' % (name, L))
 
 
+# The shipped configuration's forms (library options): the default (one launch), the two-launch form (statistics pass +
+# feature pass), and the one-launch form with nobody waiting (every block walks its utterance).
+FORMS = ({}, {'fe_fused': 0})
+FORMS_AND_NO_WAIT = FORMS + ({'fe_fused_spin': 0},)
+# unit normalisation factors: the fast path with the minimum shift, the scale and the amplitude offset all skipped
+FE_KW_UNIT = dict(FE_KW, mfcc_norm_factor=1.0, M_dB_norm_factor=1.0, P_dB_norm_factor=1.0, mean_abs_amp_norm=1.0,
+                  clip_output=False)
+
+
 def test_noise_and_flag_variants():
+    import _vc
     import audio_lib
     rng = np.random.RandomState(5)
     wav = rng.standard_normal(12345).astype(np.float32)
+    other_path = dict(FE_KW, hop_length=40, n_mels=128)         # not the shipped sizes: the general path, no forms
     for kw in (dict(FE_KW), dict(FE_KW, calc_mfcc_derivate=False), dict(FE_KW, clip_output=False),
                dict(FE_KW, mfcc_normaleze_first_mfcc=False, pre_emphasis=0.0),
-               dict(FE_KW, hop_length=40, n_mels=128), dict(FE_KW, window='hamming')):
-        dev = audio_lib.calc_MFCC_input(wav, **kw)
+               other_path, dict(FE_KW, window='hamming'), FE_KW_UNIT):
+        # unit norm factors: values are raw dB (|x| ~ 100) -> scale the tolerance by 100
+        scale = 100 if kw is FE_KW_UNIT else 1
         ref = fo.calc_MFCC_input(wav, **kw)
-        for name, d, r in zip(('mfcc', 'mel', 'pdb'), dev, ref):
-            _cmp(d, r, TOL[name], '%s %s' % (name, sorted(kw.items())[:0]))
+        for form in (({},) if kw is other_path else FORMS_AND_NO_WAIT):
+            with _vc.options(**form):
+                dev = audio_lib.calc_MFCC_input(wav, **kw)
+            for name, d, r in zip(('mfcc', 'mel', 'pdb'), dev, ref):
+                _cmp(d, r, scale * TOL[name], '%s %s %s' % (name, form, sorted(kw.items())[:0]))
 
 
 def test_config2_full_size_properties():
@@ -101,11 +116,12 @@ def test_config2_full_size_properties():
 
 
 def test_ragged_tile_edges_and_narrow_dynamic_range():
-    """The two-launch path of the shipped configuration at its seams: utterances whose frame counts sit on and around
+    """Both forms of the shipped configuration at their seams: utterances whose frame counts sit on and around
     the 14-frame feature tiles and the 16-frame statistics tiles (F = 3, 14, 15, 16, 17, 29), the shortest legal one, and
     white noise -- whose spectrum spans far less than top_db = 80 dB, so the min shift acts on the TRUE minimum (not the
     floor) and must still map it to exactly 0, as `x - x.min()` does in the reference (audio_lib.py:230-235)."""
     import torch
+    import _vc
     import audio_lib
     rng = np.random.RandomState(11)
     lens = [201, 1119, 1120, 1279, 1280, 2319, 8000]
@@ -113,11 +129,18 @@ def test_ragged_tile_edges_and_narrow_dynamic_range():
     wav = np.zeros((len(lens), L), np.float32)
     for b, n in enumerate(lens):
         wav[b, :n] = rng.standard_normal(n).astype(np.float32) * (0.01 + 0.3 * b)
-    mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(torch.from_numpy(wav).cuda(), lens, **FE_KW)
-    Fmax = 1 + L // 80
+    refs = [fo.calc_MFCC_input(wav[b, :n], **FE_KW) for b, n in enumerate(lens)]
+    for form in FORMS:
+        with _vc.options(**form):
+            mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(torch.from_numpy(wav).cuda(), lens, **FE_KW)
+        _ragged_checks(wav, lens, refs, mfcc, mel, pdb)
+
+
+def _ragged_checks(wav, lens, refs, mfcc, mel, pdb):
+    Fmax = 1 + max(lens) // 80
     for b, n in enumerate(lens):
         F = 1 + n // 80
-        ref = fo.calc_MFCC_input(wav[b, :n], **FE_KW)
+        ref = refs[b]
         for name, t, r in zip(('mfcc', 'mel', 'pdb'), (mfcc, mel, pdb), ref):
             _cmp(t[b, :F].cpu().numpy(), r, TOL[name], '%s len %d' % (name, n))
             if F < Fmax:
@@ -142,6 +165,15 @@ def test_stored_rows_can_be_fewer_than_the_frames():
         wav[b, :n] = rng.standard_normal(n).astype(np.float32) * 0.05 * (b + 1)
     wav[1, 63960:] *= 40.0                      # utterance 1's maximum sits in frame 800, which R = 800 does not store
     d = torch.from_numpy(wav).cuda()
+    for form in FORMS:
+        with _vc.options(**form):
+            _stored_rows_checks(d, lens)
+
+
+def _stored_rows_checks(d, lens):
+    import torch
+    import _vc
+    import audio_lib
     full = audio_lib.calc_MFCC_input_batch(d, lens, **FE_KW)
     assert full[0].shape[1] == 801
     for R in (800, 795, 14, 1):
