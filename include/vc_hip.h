@@ -1241,6 +1241,60 @@ int vc_gmm_update_f32(int32_t mode, const double* d_N, const double* d_S1, const
                       const float* d_mu_in, const float* d_var_in, const float* d_var_floor, float min_count, float relevance,
                       float* d_w_out, float* d_mu_out, float* d_var_out, void* stream);
 
+/* Alignment.  "Content" reads a phoneme sequence OFF the posteriors; forced alignment goes the other way: the sequence is
+ * KNOWN (a transcript) and the question is where each of its states lies in the frames.  An exact dynamic programme over
+ * the given states, left to right, with three moves: stay, advance, and skip one state that is marked optional (the
+ * silence between two words).  Added without a version bump.
+ *
+ * Inputs, per utterance b, all on the device: d_score [batch, max_frames, C] float32, the emission score of class c at
+ * frame t (callers pass log-posteriors; finite or -inf); d_seq [batch, max_seq] int32, the expected classes; d_opt
+ * [batch, max_seq] uint8 or NULL (no state optional), non-zero = the state may be skipped; d_n_frames, d_n_seq int32
+ * [batch], clamped to [0, max]: F and S.
+ *
+ *   Emission    e(t, s) = score[b, t, seq[s]], and -inf when seq[s] lies outside [0, C).  No address is formed from an
+ *               unchecked data value.
+ *   Recurrence  float32; every operation is one IEEE addition or a compare-select.
+ *               D(0, s) = e(0, s) for s = 0, and for s = 1 iff opt[0]; -inf for every other s.
+ *               D(t, s) = e(t, s) + best, where best starts as D(t-1, s) (stay, code 0), is replaced by D(t-1, s-1)
+ *               (advance, code 1) iff that is strictly greater, and is then replaced by D(t-1, s-2) (skip, code 2) iff
+ *               opt[s-1] is set and that is strictly greater.  The strict > in exactly this order is the tie rule (stay
+ *               before advance before skip) and the NaN rule (a comparison with a NaN is false).
+ *   End         final = S-1; final = S-2 instead iff S >= 2, opt[S-1] is set and D(F-1, S-2) > D(F-1, S-1).
+ *               total = D(F-1, final).  The utterance is INFEASIBLE when F == 0, S == 0 or total == -inf.
+ *   Path        read back from the codes, mechanically, from (F-1, final): at frame t >= 1 in state s the state of frame
+ *               t-1 is s - code(t, s).  (On finite and -inf scores a feasible path ends in a state D(0, .) admits; with a
+ *               NaN among the scores the walk is still carried out as written and may end elsewhere.)
+ *
+ * Outputs, every element written exactly once per call (no memset, no atomics):
+ *   d_frame_state [batch, max_frames] int32   the state of every frame; -1 from F on and when infeasible
+ *   d_start, d_end [batch, max_seq] int32     first frame and one past the last frame of every visited state; -1 for a
+ *                                             skipped state, from S on and when infeasible
+ *   d_seg_score [batch, max_seq] float32      the mean of e(t, s) over the state's own frames: the emissions widened to
+ *                                             float64, added in frame order, divided by the count (float64), rounded once
+ *                                             to float32; NaN where start is -1
+ *   d_total [batch] float32                   -inf when infeasible
+ *   d_n_visited [batch] int32                 the number of states with start >= 0
+ * There is no multiplication anywhere, so nothing can be contracted; additions, the float64 division and the conversions
+ * are correctly rounded: the device equals the float32 restatement of tests/align_ref.py BIT FOR BIT in every output, with
+ * one exception that is named here: a NaN is a NaN -- the sign and payload bits of a NaN result (possible only when the
+ * scores hold a NaN or +inf) are not specified.
+ *
+ * Two launches on the caller's stream.  Forward: one workgroup of one wave per utterance; a lane owns K = 1, 2, 4, 8 or 16
+ * consecutive states (the least such K with 64 K >= max_seq) with their D in registers; the two values a lane needs from
+ * its left neighbour come by shuffles; no LDS, no barrier; the emissions are gathered four frames ahead; the two-bit
+ * codes of 16 frames make one 32-bit word per state.  Back-track: one workgroup per utterance; one lane walks the codes,
+ * then one lane per state writes that state's frames, boundaries and mean.  d_workspace (4-byte aligned):
+ *     vc_align_workspace_bytes = align256(4 batch) + align256(batch * ceil(max_frames / 16) * max_seq * 4)
+ * (host arithmetic only; 0 for a shape the launch would refuse; too small: VC_ERR_WORKSPACE).  Limits (VC_ERR_UNSUPPORTED
+ * beyond them): max_seq <= 1,024; batch <= 65,535; C <= 65,535; max_frames such that the workspace stays below 2^31 bytes.
+ * A function of its own utterance alone: bit-identical alone, in any batch, from run to run and under graph replay;
+ * lengths are read on the device; capturable from the first call; arguments are checked before any HIP call. */
+size_t vc_align_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_seq);
+int vc_align_f32(const float* d_score, const int32_t* d_seq, const uint8_t* d_opt, const int32_t* d_n_frames, const int32_t* d_n_seq,
+                 int32_t batch, int32_t max_frames, int32_t max_seq, int32_t n_classes, int32_t* d_frame_state, int32_t* d_start,
+                 int32_t* d_end, float* d_seg_score, float* d_total, int32_t* d_n_visited, void* d_workspace, size_t workspace_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

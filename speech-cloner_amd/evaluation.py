@@ -1337,3 +1337,241 @@ def content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=Non
         path, path_len = r.path, r.path_len
     c = _content_launch(p_a, p_b, d_la, d_lb, path, path_len, _cmap_device(cmap), min_run, ma, mb)
     return _CONTENT_WAV(*c, p_a, p_b, d_la, d_lb, path, path_len, ma, mb)
+
+
+ALIGN_MAX_SEQ = 1024        # vc_align_f32
+ALIGN_MAX_CLASSES = 65535
+_ALIGN_FIELDS = 'frame_state start end seg_score total n_visited labels'
+_ALIGN = namedtuple('alignment', _ALIGN_FIELDS)
+_ALIGN_WAV = namedtuple('alignment_wav', _ALIGN_FIELDS + ' ppg n_frames')
+
+
+def _check_align_ppg(x, what):
+    import torch
+    if getattr(x, 'ndim', 0) != 3 or min(x.shape) < 1:
+        raise ValueError(' - ERROR, {} must be [B, F, C]'.format(what))
+    dt = x.dtype if torch.is_tensor(x) else np.asarray(x).dtype
+    if dt not in (torch.float32, np.dtype(np.float32)):
+        raise ValueError(' - ERROR, {} must be float32, got {}'.format(what, dt))
+    B, F, C = (int(v) for v in x.shape)
+    if B > 65535 or C > ALIGN_MAX_CLASSES:
+        raise ValueError(' - ERROR, {}: at most 65535 rows of at most {} classes (got {} of {})'.format(what, ALIGN_MAX_CLASSES, B, C))
+    return B, F, C
+
+
+def _check_align_seq(seq, n_seq, optional, B, C, what):
+    """seq [B, S] int32 and optional None or [B, S] uint8 / bool, each a host array or a device tensor; n_seq as
+    _check_counts.  A host seq has its values below the row's count checked against [0, C) (every value of the row
+    when the counts live on the device); a device seq is taken as it is: the launch gives a class outside [0, C) the
+    score -inf.  Returns (seq, (host counts | None, device counts | None), optional) with host arrays converted."""
+    import torch
+    if getattr(seq, 'ndim', 0) != 2 or min(seq.shape) < 1 or int(seq.shape[0]) != B:
+        raise ValueError(' - ERROR, {}: seq must be [{}, S]'.format(what, B))
+    dt = seq.dtype if torch.is_tensor(seq) else np.asarray(seq).dtype
+    if dt not in (torch.int32, np.dtype(np.int32)):
+        raise ValueError(' - ERROR, {}: seq must be int32, got {}'.format(what, dt))
+    S = int(seq.shape[1])
+    if S > ALIGN_MAX_SEQ:
+        raise ValueError(' - ERROR, {}: at most {} states per utterance (got {})'.format(what, ALIGN_MAX_SEQ, S))
+    n = _check_counts(n_seq, B, 0, S, '{}: n_seq'.format(what))
+    if not (torch.is_tensor(seq) and seq.is_cuda):
+        h = np.ascontiguousarray(seq.cpu().numpy() if torch.is_tensor(seq) else seq)
+        used = np.arange(S)[None, :] < (n[0][:, None] if n[0] is not None else S)
+        if used.any() and (h[used].min() < 0 or h[used].max() >= C):
+            raise ValueError(' - ERROR, {}: seq must hold classes in [0, {})'.format(what, C))
+        seq = h
+    if optional is not None:
+        if getattr(optional, 'ndim', 0) != 2 or tuple(int(v) for v in optional.shape) != (B, S):
+            raise ValueError(' - ERROR, {}: optional must be [{}, {}], as seq'.format(what, B, S))
+        dt = optional.dtype if torch.is_tensor(optional) else np.asarray(optional).dtype
+        if dt not in (torch.uint8, torch.bool, np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise ValueError(' - ERROR, {}: optional must be uint8 or bool, got {}'.format(what, dt))
+        if not (torch.is_tensor(optional) and optional.is_cuda):
+            optional = np.ascontiguousarray((optional.cpu().numpy() if torch.is_tensor(optional) else np.asarray(optional)) != 0, dtype=np.uint8)
+    return seq, n, optional
+
+
+def _check_align_size(B, F, S, what):
+    a256 = lambda v: (v + 255) // 256 * 256                         # vc_align_workspace_bytes
+    if a256(B * 4) + a256(B * ((F + 15) // 16) * S * 4) >= 2 ** 31:
+        raise ValueError(' - ERROR, {}: the moves of {} utterances of {} frames x {} states need 2 GiB or more; align fewer '
+                         'utterances per call'.format(what, B, F, S))
+
+
+def _align_kind(kind, floor, what):
+    if kind not in ('prob', 'log'):
+        raise ValueError(" - ERROR, {}: kind must be 'prob' or 'log', got {!r}".format(what, kind))
+    fl = float(floor)
+    if not (np.isfinite(fl) and fl > 0.0):
+        raise ValueError(' - ERROR, {}: floor must be finite and positive, got {!r}'.format(what, floor))
+    return fl
+
+
+def _pinned_up(h):
+    import torch
+    return torch.from_numpy(h).pin_memory().to('cuda', non_blocking=True)
+
+
+def _align_launch(score, seq, opt, d_frames, d_nseq):
+    """score: cuda, contiguous float32 [B, F, C]; seq int32 [B, S], opt uint8 [B, S] or None, counts: all on the device.
+    The two launches of vc_align_f32 and labels = seq[frame_state].  No host check in here, nothing waited for."""
+    import torch
+    lib = _vc.lib()
+    B, F, C = score.shape
+    S = seq.shape[1]
+    dev = score.device
+    frame_state = torch.empty((B, F), dtype=torch.int32, device=dev)
+    bounds = torch.empty((2, B, S), dtype=torch.int32, device=dev)
+    n_visited = torch.empty((B,), dtype=torch.int32, device=dev)
+    seg_score = torch.empty((B, S), dtype=torch.float32, device=dev)
+    total = torch.empty((B,), dtype=torch.float32, device=dev)
+    need = lib.vc_align_workspace_bytes(B, F, S)
+    if need == 0:
+        raise _vc.VCError('vc_align_workspace_bytes refused {} utterances of {} frames x {} states'.format(B, F, S))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _vc.check(lib.vc_align_f32(_vc.ptr(score), _vc.ptr(seq), _vc.ptr(opt), _vc.ptr(d_frames), _vc.ptr(d_nseq), B, F, S, C,
+                               _vc.ptr(frame_state), _vc.ptr(bounds[0]), _vc.ptr(bounds[1]), _vc.ptr(seg_score), _vc.ptr(total),
+                               _vc.ptr(n_visited), _vc.ptr(ws), need, _vc.current_stream()))
+    labels = torch.where(frame_state >= 0, torch.gather(seq, 1, frame_state.clamp_min(0).long()), frame_state)
+    return _ALIGN(frame_state, bounds[0], bounds[1], seg_score, total, n_visited, labels)
+
+
+def _align_device(seq, n, optional):
+    """Uploads (pinned, no wait) whatever of seq / counts / optional is still on the host."""
+    import torch
+    seq = seq.contiguous() if torch.is_tensor(seq) else _pinned_up(seq)
+    if optional is not None:
+        optional = (optional.to(torch.uint8).contiguous() if torch.is_tensor(optional) else _pinned_up(optional))
+    return seq, optional, _upload_mixed(*n)
+
+
+def align_batch(ppg, lens, seq, n_seq, optional=None, kind='prob', floor=1e-10):
+    """Forced alignment of B utterances (vc_align_f32; the definition is in include/vc_hip.h, "Alignment"): where does each
+    phoneme of a KNOWN sequence lie in the frames?  ppg [B, F_max, C] float32 (cuda tensor or numpy array): posteriors
+    (kind='prob': the scores are torch.log(ppg.clamp_min(floor)), taken on the device) or ready scores such as
+    log-posteriors (kind='log': passed through; finite or -inf).  lens: the frame counts, host integers in [0, F_max] or an
+    int32 [B] device tensor.  seq [B, S_max] int32: the expected classes (host array: checked against [0, C); device
+    tensor: a class outside gets the score -inf); n_seq: their counts, host integers in [0, S_max] or int32 [B] on the
+    device.  optional: None or [B, S_max] uint8 / bool, 1 = the state may be skipped (the silence between two words).
+    S_max <= 1,024, B <= 65,535, C <= 65,535, and B * ceil(F_max / 16) * S_max * 4 bytes of moves below 2 GiB.
+    Nothing is copied back and the host waits for nothing.  Returns a namedtuple of device tensors: frame_state
+    [B, F_max] int32 (the state of every frame, -1 from the count on and for an utterance that cannot be aligned), start,
+    end [B, S_max] int32 (first frame, one past the last; -1 for a skipped state), seg_score [B, S_max] float32 (the mean
+    score of the state's class over its frames -- with log-posteriors the "goodness of pronunciation"; NaN where start is
+    -1), total [B] float32 (-inf: cannot be aligned), n_visited [B] int32, and labels [B, F_max] int32 =
+    seq[frame_state] (-1 where frame_state is -1)."""
+    import torch
+    B, F, C = _check_align_ppg(ppg, 'align_batch: ppg')
+    fl = _align_kind(kind, floor, 'align_batch')
+    nf = _check_counts(lens, B, 0, F, 'align_batch: lens')
+    seq, ns, optional = _check_align_seq(seq, n_seq, optional, B, C, 'align_batch')
+    _check_align_size(B, F, int(seq.shape[1]), 'align_batch')
+    _need_gpu('align_batch')
+    d_seq, d_opt, (d_frames, d_nseq) = _align_device(seq, (nf, ns), optional)
+    score = _to_device(ppg, torch.float32)
+    if kind == 'prob':
+        score = torch.log(score.clamp_min(fl))
+    return _align_launch(score, d_seq, d_opt, d_frames, d_nseq)
+
+
+def align_wav_batch(encoder, wav, lens, seq, n_seq, cfg_d, wav_sr=None, res_type='kaiser_best', optional=None, window_batch=64,
+                    ppg=None):
+    """Forced alignment of B WAVEFORMS against their transcripts.  encoder: the phoneme recogniser
+    (encoder.encoder_spec_phn).  The posteriors are those of content_wav_batch (its _content_side: the resampler for
+    wav_sr, the front-end, convert_batch's window tables with t_s = 0, t_e = 60 and two passes, the encoder in chunks of
+    window_batch windows, the stitch), i.e. exactly convert_batch's phn_pred; ppg: such posteriors [B, Fout, n_phn] that
+    are already there, instead of running the encoder.  Only frames that come from the waveform are aligned:
+    min(n_out, min(n_src, n_e) - n_s) per utterance.  seq, n_seq, optional as in align_batch, which this ends in
+    (kind='prob').  Returns align_batch's fields, then ppg [B, Fout, n_phn] and n_frames (int32 [B]), on the device."""
+    import torch
+    import audio_lib
+    import conversion
+    if cfg_d is None:
+        raise ValueError(' - ERROR, align_wav_batch: cfg_d (the data-set configuration) is required')
+    audio_lib._res_params(res_type)
+    a = _wav_side(wav, lens, cfg_d, wav_sr, 'wav')
+    B = a['B']
+    window_batch = int(window_batch)
+    if window_batch <= 0:
+        raise ValueError(' - ERROR, align_wav_batch: window_batch must be positive')
+    plan = conversion.convert_plan(a['h'], cfg_d, 0, 60, True)
+    C = int(encoder.cfg_d['n_output'])
+    if B > 65535 or C > ALIGN_MAX_CLASSES:
+        raise ValueError(' - ERROR, align_wav_batch: at most 65535 utterances and {} classes (got {} and {})'.format(ALIGN_MAX_CLASSES, B, C))
+    if ppg is not None:
+        if _check_align_ppg(ppg, 'align_wav_batch: ppg') != (B, plan.Fout, C):
+            raise ValueError(' - ERROR, align_wav_batch: ppg must be [{}, {}, {}], as convert_batch returns phn_pred for wav'
+                             .format(B, plan.Fout, C))
+    seq, ns, optional = _check_align_seq(seq, n_seq, optional, B, C, 'align_wav_batch')
+    _check_align_size(B, plan.Fout, int(seq.shape[1]), 'align_wav_batch')
+    h_l = np.minimum(plan.n_out, plan.n_clip - plan.n_s)
+    if h_l.min() < 1:
+        raise ValueError(' - ERROR, align_wav_batch: every utterance needs at least one frame of its own')
+    _need_gpu('align_wav_batch')
+    d_in, d_len, d_clip, d_win, d_utt, d_true, d_l = _upload_lens(a['h_in'], a['h'], plan.n_clip, plan.win_tab, plan.utt_tab,
+                                                                  plan.true_tab, h_l)
+    d_seq, d_opt, (d_nseq,) = _align_device(seq, (ns,), optional)
+    if ppg is not None:
+        ppg = _to_device(ppg, torch.float32)
+    _, _, ppg = _content_side(encoder, wav, a, plan, (d_in, d_len, d_clip, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)),
+                              cfg_d, res_type, window_batch, ppg)
+    r = _align_launch(torch.log(ppg.clamp_min(1e-10)), d_seq, d_opt, d_l, d_nseq)
+    return _ALIGN_WAV(*r, ppg, d_l)
+
+
+def alignment_min_frames(hop_length, win_length):
+    """L of phn_v_from_alignment: the number of frames per segment from which its round trip holds, W/2 // hop + 1."""
+    return (int(win_length) // 2) // int(hop_length) + 1
+
+
+def phn_v_from_alignment(start, end, seq, names, hop_length, n_samples):
+    """One utterance's alignment as the (start_sample, end_sample, phn) list that audio_lib.calc_PHN_target consumes.
+    start, end: the utterance's rows of align_batch's result, downloaded (host integers, -1 = the state was skipped: it
+    is left out); seq: its expected classes; names[c]: the phoneme name of class c; n_samples: the samples of the
+    waveform (the aligned frame count must be the front-end's F = 1 + n_samples // hop_length).
+
+    Where the sample boundaries go.  calc_PHN_target gives frame i the window [i hop - H, i hop + H) (H = win_length / 2,
+    win_length even), takes as "current" the first segment that ends after the window's start, and picks the NEXT segment
+    instead iff the window overlaps that one strictly more -- it compares these two only.  For a window that straddles
+    one boundary b, with both neighbours reaching beyond the window, the overlaps are b - (i hop - H) and (i hop + H) - b:
+    the next segment wins iff b < i hop.  A state whose frames are [st, en) must keep frame en - 1 and lose frame en, so
+    (en - 1) hop <= b < en hop.  This helper puts b = en hop - h2, h2 = ceil(hop / 2): the middle of that range.  The
+    first segment starts at sample 0 and the last one ends at n_samples: the list labels the waveform, nothing outside.
+
+    How long segments must be.  Number the visited segments k = 0 .. n-1, b_k the end of k, frames [st_k, en_k), len_k
+    frames.  Frame i of segment k is labelled k when
+    (1) "current" is k - 1 or k, i.e. segment k - 2 ends at or before the window's start even for i = st_k:
+        b_{k-2} = st_{k-1} hop - h2 <= st_k hop - H, i.e. len_{k-1} hop >= H - h2;
+    (2) with "current" = k the comparison keeps k.  If the window ends inside k the next overlap is not positive.  Else
+        k overlaps by b_k - (i hop - H) and k + 1 by at most (i hop + H) - b_k, and b_k >= i hop holds for i <= en_k - 1.
+        Only the FIRST segment can start after the window's start (sample 0 against a negative i hop - H): then its
+        overlap is b_0 = len_0 hop - h2 against at most i hop + H - b_0, largest at i = len_0 - 1, which asks
+        len_0 hop >= H + 2 h2 - hop;
+    (3) with "current" = k - 1 the comparison moves on to k.  The overlap of k - 1 is at most b_{k-1} - (i hop - H)
+        <= H - h2 (largest at i = st_k).  If k reaches beyond the window its overlap is (i hop + H) - b_{k-1} >= H + h2.
+        Otherwise it is the whole of k, which must be STRICTLY more than H - h2: len_k hop >= H - h2 + 1 for an inner
+        segment; the LAST segment ends at n_samples >= (F - 1) hop, so it holds at least (len_k - 1) hop + h2 samples,
+        which asks len_k hop >= H + hop - 2 h2 + 1.
+    hop - 2 h2 is 0 or -1, so all of these hold when len_k hop >= H + 1 for every visited segment: the round trip
+        calc_PHN_target(y, phn_v_from_alignment(...), name -> class, hop, W) == seq[frame_state]
+    holds when every visited segment lasts at least L = H // hop + 1 frames (alignment_min_frames; 3 for hop 80, W 400).
+    The edges set L: inner segments get by with (3)'s H - h2 + 1 samples.  At L - 1 it fails: (L - 1) hop <= H, and with
+    n_samples = (F - 1) hop the last segment holds (L - 2) hop + h2 <= H - h2 samples for an even hop -- no longer
+    strictly more than its left neighbour's overlap, so its first frame keeps the neighbour's label
+    (tests/test_align_cpu.py runs the case)."""
+    start, end, seq = (np.asarray(v).reshape(-1) for v in (start, end, seq))
+    hop, n_samples = int(hop_length), int(n_samples)
+    if hop < 1 or n_samples < 1:
+        raise ValueError(' - ERROR, phn_v_from_alignment: hop_length and n_samples must be positive')
+    if not len(start) == len(end) == len(seq):
+        raise ValueError(' - ERROR, phn_v_from_alignment: start, end and seq must have one entry per state')
+    vis = [s for s in range(len(seq)) if start[s] >= 0]
+    if not vis:
+        return []
+    h2 = (hop + 1) // 2
+    out = []
+    for n, s in enumerate(vis):
+        a = 0 if n == 0 else int(start[s]) * hop - h2
+        b = n_samples if n == len(vis) - 1 else int(end[s]) * hop - h2
+        out.append((a, b, names[int(seq[s])]))
+    return out
