@@ -62,7 +62,8 @@ const char* vc_target_arch(void);
  *   "proj256"        0 = the 256-channel k = 3 projection on conv256_kernel instead of the bank tiles
  *   "proj256_split"  0 = never split that projection's K over two workgroups per row tile (see d_workspace)
  *   "wgrad_xcd"      0 = weight-gradient tiles dealt round-robin to the XCDs
- *   "gru_mfma"       0 = VALU recurrence always, 1 = MFMA recurrence always (default: from 32 sequences up)
+ *   "gru_mfma"       0 = VALU (register-resident) recurrence always, 1 = MFMA recurrence always (default: vc_gru_bidir takes
+ *                    the MFMA form from 32 sequences up; vc_gru_form at 256 units takes it when the resident grid exceeds one round of CUs)
  *   "fe_fused"       0 = the shipped front-end configuration as two launches (statistics pass, feature pass) instead of ONE
  *                    (every frame transformed once; blocks wait for the summary of their own utterance)
  *   "fe_fused_spin"  polls a block of the one-launch front-end waits for the other tiles of its utterance before it
@@ -318,6 +319,32 @@ size_t vc_gru_workspace_bytes(int32_t H, int32_t w_dtype);
 int vc_gru_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw, int32_t w_dtype,
                  int32_t n_seq, int32_t T, int32_t H, void* d_out, int32_t out_dtype,
                  void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* The same recurrence on weights packed ONCE (bf16, H = 128 or 256: the two kernels that keep the weights on chip and read
+ * them in a per-lane order of their own).  A model's recurrent weights do not change between inference calls, so the
+ * caller packs when it loads them and again only when they change:
+ *   vc_gru_form           which form a call of n_seq sequences takes.  H = 256: VC_GRU_FORM_RESIDENT (one sequence per
+ *                         workgroup, 2 n_seq workgroups) when those fit ONE round of n_cu compute units, VC_GRU_FORM_MFMA (16
+ *                         sequences per workgroup) beyond.  H = 128, where the two forms take the same time at 64 sequences:
+ *                         resident below 32 sequences, MFMA from 32 up, whatever n_cu.  Option "gru_mfma" 0 / 1 forces
+ *                         either.  n_cu <= 0: the current device's count (asked once per device).  VC_GRU_FORM_NONE for any
+ *                         other H / dtype (no packed form: call vc_gru_bidir); -1 when the device cannot be asked
+ *                         (vc_last_error).  Pure host code for n_cu > 0, for H = 128 and with the option set.
+ *   vc_gru_packed_bytes   size of a form's image (0: no such form for H / w_dtype).
+ *   vc_gru_pack           writes the image of d_Wh_fw / d_Wh_bw ([H, 3H] each, as vc_gru_bidir takes them) to d_packed
+ *                         (16-byte aligned, vc_gru_packed_bytes long; VC_ERR_WORKSPACE and no launch when shorter).
+ *   vc_gru_bidir_packed   vc_gru_bidir on an image; `form` must be the form the image was packed for (the two layouts
+ *                         differ and carry no tag: an image of the other form gives wrong numbers, not an error).
+ * Results are bit-identical to vc_gru_bidir with the same form forced. */
+#define VC_GRU_FORM_NONE 0
+#define VC_GRU_FORM_RESIDENT 1
+#define VC_GRU_FORM_MFMA 2
+int32_t vc_gru_form(int32_t H, int32_t w_dtype, int32_t n_seq, int32_t n_cu);
+size_t vc_gru_packed_bytes(int32_t form, int32_t H, int32_t w_dtype);
+int vc_gru_pack(int32_t form, const void* d_Wh_fw, const void* d_Wh_bw, int32_t w_dtype, int32_t H, void* d_packed,
+                size_t packed_bytes, void* stream);
+int vc_gru_bidir_packed(int32_t form, const float* d_xproj, const void* d_packed, size_t packed_bytes, int32_t w_dtype,
+                        int32_t n_seq, int32_t T, int32_t H, void* d_out, int32_t out_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training step of decoder_specs (/root/reference/decoder.py:185-263, 327-345), float32.

@@ -40,6 +40,7 @@ VC_F32, VC_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 GEMM_PLAIN, GEMM_HIGHWAY = 0, 1
 GEMM_MAX_GROUPS = 32
+GRU_FORM_NONE, GRU_FORM_RESIDENT, GRU_FORM_MFMA = 0, 1, 2       # include/vc_hip.h: VC_GRU_FORM_*
 
 
 class GemmGroup(C.Structure):
@@ -169,6 +170,10 @@ _SIGS = {
     'vc_gru_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'vc_gru_bidir': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P,
                                C.c_size_t, _P]),
+    'vc_gru_form': (C.c_int32, [C.c_int32] * 4),
+    'vc_gru_packed_bytes': (C.c_size_t, [C.c_int32] * 3),
+    'vc_gru_pack': (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P]),
+    'vc_gru_bidir_packed': (C.c_int, [C.c_int32, _P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     'vc_lstm_bidir': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     'vc_convert': (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_size_t, _P]),
     'vc_conv_wgrad': (C.c_int, [C.POINTER(WgradDesc), _P]),
@@ -316,7 +321,8 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*): a build older than this binding
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then the
+                # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '
                               '(make -C speech-cloner_amd/csrc)' % (LIB_PATH, name)) from None
@@ -350,18 +356,23 @@ def options(**kw):
             set_option(k, v)
 
 
-# Two kernels fill an otherwise idle chip at the price of extra workgroup time: the k = 3 projection's K split over two
-# workgroups per row tile (-43 % for that launch alone, +0.8 % per step when ten batches are in flight) and the
+# Three kernels fill an otherwise idle chip at the price of extra workgroup time: the k = 3 projection's K split over two
+# workgroups per row tile (-43 % for that launch alone, +0.8 % per step when ten batches are in flight), the
 # front-end's one-launch form, whose blocks WAIT for their utterance (-14 % alone, +5.5 % per pipelined step: a waiting
-# block keeps its CU from the register-filling MFMA launches of the other streams).  The library's defaults serve a
-# caller with one batch at a time (the reference's test.py); a caller that keeps several batches in flight on several
-# streams runs its loop under this context (bench.py's throughput loop does).
+# block keeps its CU from the register-filling MFMA launches of the other streams), and the register-resident
+# recurrence, which takes one CU per sequence and direction for all 400 steps where the MFMA form packs sixteen sequences
+# on one (the MFMA form is worth +7.7 % frames/s with ten batches of 64 windows in flight).  The library's defaults
+# serve a caller with one batch at a time (the reference's test.py); a caller that keeps several batches in flight on
+# several streams runs its loop under this context (bench.py's throughput loop does).
 THROUGHPUT_OPTIONS = {'proj256_split': 0, 'fe_fused': 0}
+# ... and the kernel form such a caller pins where the default would choose by the makespan of one call
+# (tests/test_abi.py holds THROUGHPUT_OPTIONS to the two switched-off kernels above, so the forced form has its own table).
+THROUGHPUT_FORMS = {'gru_mfma': 1}
 
 
 def throughput_mode():
     """with _vc.throughput_mode(): ...  -- the option set for callers that keep several batches in flight."""
-    return options(**THROUGHPUT_OPTIONS)
+    return options(**THROUGHPUT_OPTIONS, **THROUGHPUT_FORMS)
 
 
 def check(rc):

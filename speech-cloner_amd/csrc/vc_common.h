@@ -37,7 +37,7 @@ enum Option {
     OPT_PROJ256,          // 0: 256-channel long-K projection on conv256_kernel instead of the bank tiles
     OPT_PROJ256_SPLIT,    // 0: never split that projection's K over two workgroups per row tile
     OPT_WGRAD_XCD,        // 0: weight-gradient tiles dealt round-robin instead of group-per-XCD
-    OPT_GRU_MFMA,         // 0: VALU recurrence always, 1: MFMA recurrence always (default: from 32 sequences up)
+    OPT_GRU_MFMA,         // 0: VALU recurrence always, 1: MFMA recurrence always (default: vc_gru_bidir from 32 sequences up, vc_gru_form by makespan)
     OPT_FE_FUSED,         // 0: the shipped front-end configuration as two launches (statistics pass + feature pass) instead of one
     OPT_FE_FUSED_SPIN,    // polls a block of the one-launch front-end waits for its utterance's tiles (default 4000 ~ 4 ms); 0: never wait
     OPT_PRENET_LDS,       // 0: every wave of prenet_chain streams the weights itself (default: shared through LDS)

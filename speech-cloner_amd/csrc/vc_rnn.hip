@@ -10,6 +10,8 @@
 // step -- that costs >= 1 us on this chip (MI355X_MICROARCH.md, hand-off price list), more than a
 // whole step.
 #include <hip/hip_runtime.h>
+#include <atomic>
+#include <cstdint>
 #include <cstdlib>
 
 #include "vc_device.h"
@@ -367,18 +369,30 @@ gru_resident_kernel(GruArgs a, const WT* packed) {
     }
 }
 
+// Packing and running are separate launches: the packed image depends on the weights alone, so a caller whose weights
+// stay put packs once (vc_gru_pack) and runs on the image (vc_gru_bidir_packed); vc_gru_bidir packs into its workspace
+// on every call.
+template <int H, typename WT, int NT>
+void pack_resident(const void* Wfw, const void* Wbw, void* packed, hipStream_t st) {
+    hipLaunchKernelGGL((gru_pack_kernel<H, WT, NT>), dim3(256), dim3(256), 0, st, static_cast<const WT*>(Wfw),
+                       static_cast<const WT*>(Wbw), static_cast<WT*>(packed));
+}
+
+template <int H, typename WT, int NT>
+int run_resident(const GruArgs& a, const void* packed, hipStream_t st) {
+    hipLaunchKernelGGL((gru_resident_kernel<H, WT, NT>), dim3(a.n_seq, 2), dim3(NT), 0, st, a,
+                       static_cast<const WT*>(packed));
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
 template <int H, typename WT, int NT>
 int launch_resident(const GruArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
     const size_t need = 2 * (size_t)3 * H * H * sizeof(WT);
     if (ws == nullptr || ws_bytes < need)
         return vc::set_error(VC_ERR_WORKSPACE, "vc_gru_bidir: workspace too small (%zu < %zu)", ws_bytes, need);
-    WT* packed = static_cast<WT*>(ws);
-    hipLaunchKernelGGL((gru_pack_kernel<H, WT, NT>), dim3(256), dim3(256), 0, st,
-                       static_cast<const WT*>(a.Wh[0]), static_cast<const WT*>(a.Wh[1]), packed);
-    hipLaunchKernelGGL((gru_resident_kernel<H, WT, NT>), dim3(a.n_seq, 2), dim3(NT), 0, st, a,
-                       static_cast<const WT*>(packed));
-    VC_HIP_CHECK(hipGetLastError());
-    return VC_OK;
+    pack_resident<H, WT, NT>(a.Wh[0], a.Wh[1], ws, st);
+    return run_resident<H, WT, NT>(a, ws, st);
 }
 
 
@@ -562,20 +576,29 @@ gru_mfma_kernel(GruArgs a, const __bf16* packed) {
 }
 
 template <int H>
-int launch_mfma(const GruArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+void pack_mfma(const void* Wfw, const void* Wbw, void* packed, hipStream_t st) {
+    hipLaunchKernelGGL((gru_mfma_pack_kernel<H>), dim3(256), dim3(256), 0, st, static_cast<const __bf16*>(Wfw),
+                       static_cast<const __bf16*>(Wbw), static_cast<__bf16*>(packed));
+}
+
+template <int H>
+int run_mfma(const GruArgs& a, const void* packed, hipStream_t st) {
     typedef MfGeom<H> G;
-    const size_t need = 2 * (size_t)3 * H * H * sizeof(__bf16);
-    if (ws == nullptr || ws_bytes < need)
-        return vc::set_error(VC_ERR_WORKSPACE, "vc_gru_bidir: workspace too small (%zu < %zu)", ws_bytes, need);
-    __bf16* packed = static_cast<__bf16*>(ws);
-    hipLaunchKernelGGL((gru_mfma_pack_kernel<H>), dim3(256), dim3(256), 0, st, static_cast<const __bf16*>(a.Wh[0]),
-                       static_cast<const __bf16*>(a.Wh[1]), packed);
     const size_t lds = 2 * 16 * (size_t)G::PITCH * 2 + (G::CAND_LDS ? (size_t)G::NW * G::NF_C * 64 * 16 : 0);
     if (int rc = vc::allow_dynamic_lds<gru_mfma_kernel<H>>((int)lds)) return rc;
     hipLaunchKernelGGL((gru_mfma_kernel<H>), dim3((a.n_seq + 15) / 16, 2), dim3(512), lds, st, a,
                        static_cast<const __bf16*>(packed));
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
+}
+
+template <int H>
+int launch_mfma(const GruArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
+    const size_t need = 2 * (size_t)3 * H * H * sizeof(__bf16);
+    if (ws == nullptr || ws_bytes < need)
+        return vc::set_error(VC_ERR_WORKSPACE, "vc_gru_bidir: workspace too small (%zu < %zu)", ws_bytes, need);
+    pack_mfma<H>(a.Wh[0], a.Wh[1], ws, st);
+    return run_mfma<H>(a, ws, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -701,6 +724,48 @@ convert_kernel(const void* src, int sdt, void* dst, int ddt, size_t n) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Which of the two bf16 forms (H = 128 / 256) a packed-weights call takes.  Measured alone on an MI355X (256 CUs) at 64
+// windows x 400 steps, weights packed beforehand (profiles/gru_modes/README.md):
+//   resident (one sequence per workgroup, weights in VGPRs, 2 * n_seq workgroups): H = 256 1.45 us/step, H = 128 0.92;
+//   MFMA (16 sequences per workgroup, 2 * ceil(n_seq / 16) workgroups):             H = 256 1.86 us/step, H = 128 0.92.
+// A resident workgroup of H = 256 fills its CU's register file, so the form keeps its per-step figure only while every
+// workgroup has a CU to itself: the makespan of one call is smallest with the resident form when its 2 * n_seq
+// workgroups fit ONE round of the device's CUs, and with the MFMA form beyond (a second round doubles the resident
+// time).  That is the rule at H = 256.  At H = 128 the two forms tie at 64 windows (the step is barrier-bound either
+// way), so that size keeps the rule it had: resident below 32 sequences, MFMA -- sixteen times fewer CUs for the same
+// time -- from 32 up.  These are the library's defaults, which serve a caller with one batch in flight.  A caller that
+// keeps several batches in flight wants the CUs for the MFMA-bound launches of its other streams and forces the MFMA
+// form (gru_mfma = 1, part of _vc.throughput_mode(): +7.7 % frames/s at 64 windows with ten steps in flight);
+// gru_mfma = 0 forces the resident form.
+int gru_pick_form(int H, int w_dtype, int n_seq, int n_cu, int gm) {
+    if (w_dtype != VC_BF16 || (H != 128 && H != 256) || n_seq <= 0) return VC_GRU_FORM_NONE;
+    if (gm >= 0) return gm == 1 ? VC_GRU_FORM_MFMA : VC_GRU_FORM_RESIDENT;
+    if (H == 128) return n_seq < 32 ? VC_GRU_FORM_RESIDENT : VC_GRU_FORM_MFMA;
+    return 2 * (long long)n_seq <= n_cu ? VC_GRU_FORM_RESIDENT : VC_GRU_FORM_MFMA;
+}
+
+// CU count of the current device, asked once per device.
+int device_cu_count(int* n_cu) {
+    constexpr int MAX_DEV = 64;
+    static std::atomic<int> cached[MAX_DEV];
+    int dev = 0;
+    VC_HIP_CHECK(hipGetDevice(&dev));
+    if (dev >= 0 && dev < MAX_DEV) {
+        const int c = cached[dev].load(std::memory_order_relaxed);
+        if (c > 0) { *n_cu = c; return VC_OK; }
+    }
+    int c = 0;
+    VC_HIP_CHECK(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
+    if (dev >= 0 && dev < MAX_DEV) cached[dev].store(c, std::memory_order_relaxed);
+    *n_cu = c;
+    return VC_OK;
+}
+
+bool gru_form_ok(int form, int H, int w_dtype) {
+    return (form == VC_GRU_FORM_RESIDENT || form == VC_GRU_FORM_MFMA) && w_dtype == VC_BF16 && (H == 128 || H == 256);
+}
+
 }  // namespace
 
 extern "C" {
@@ -728,12 +793,10 @@ int vc_gru_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw,
     while (nt < GEN_NT_MAX && nt < 2 * H) nt *= 2;
     hipStream_t st = static_cast<hipStream_t>(stream);
     dim3 grid(n_seq, 2);
-    // register-resident kernels for the decoder's sizes
-    // bf16, one sequence per workgroup, weights in VGPRs: 1.5 us/step at H = 256 on 2 * n_seq CUs.
-    // bf16, 16 sequences per workgroup on MFMA: 3.3 us/step but 16x fewer CUs.  A batch that would
-    // occupy a quarter of the chip or more with the first form takes the second, which leaves the
-    // CUs to the MFMA-bound launches of the other streams (full path: +7.7 % frames/s at 64
-    // windows); small batches keep the low-latency form.  vc_set_option("gru_mfma", 0 / 1) forces either.
+    // The decoder's sizes in bf16 have two forms (figures and the reasoning: gru_pick_form above).  This entry point packs
+    // the weights into the workspace on every call and keeps the rule its callers know: the resident form below 32
+    // sequences, the MFMA form from 32 up; vc_set_option("gru_mfma", 0 / 1) forces either.  The packed-weights entry
+    // point (vc_gru_bidir_packed with the form vc_gru_form names) chooses by makespan from the device's CU count.
     const int gm = vc::opt(vc::OPT_GRU_MFMA);
     const bool use_valu = gm >= 0 ? (gm != 1) : (n_seq < 32);
     if (w_dtype == VC_BF16 && H == 256) return use_valu ? launch_resident<256, __bf16, 512>(a, d_workspace, workspace_bytes, st)
@@ -760,6 +823,55 @@ int vc_gru_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw,
     }
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
+}
+
+int32_t vc_gru_form(int32_t H, int32_t w_dtype, int32_t n_seq, int32_t n_cu) {
+    const int gm = vc::opt(vc::OPT_GRU_MFMA);
+    if (n_cu <= 0 && gm < 0 && H == 256 && w_dtype == VC_BF16 && device_cu_count(&n_cu) != VC_OK) return -1;
+    return gru_pick_form(H, w_dtype, n_seq, n_cu, gm);
+}
+
+size_t vc_gru_packed_bytes(int32_t form, int32_t H, int32_t w_dtype) {
+    return gru_form_ok(form, H, w_dtype) ? 2 * (size_t)3 * H * H * 2 : 0;
+}
+
+int vc_gru_pack(int32_t form, const void* d_Wh_fw, const void* d_Wh_bw, int32_t w_dtype, int32_t H, void* d_packed,
+                size_t packed_bytes, void* stream) {
+    VC_REQUIRE(d_Wh_fw && d_Wh_bw && d_packed, "vc_gru_pack: NULL argument");
+    VC_REQUIRE(reinterpret_cast<uintptr_t>(d_packed) % 16 == 0, "vc_gru_pack: d_packed is not 16-byte aligned");
+    VC_REQUIRE(gru_form_ok(form, H, w_dtype), "vc_gru_pack: no packed form %d for H=%d w_dtype=%d", form, H, w_dtype);
+    const size_t need = vc_gru_packed_bytes(form, H, w_dtype);
+    if (packed_bytes < need)
+        return vc::set_error(VC_ERR_WORKSPACE, "vc_gru_pack: image buffer too small (%zu < %zu)", packed_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (form == VC_GRU_FORM_RESIDENT) {
+        if (H == 256) pack_resident<256, __bf16, 512>(d_Wh_fw, d_Wh_bw, d_packed, st);
+        else pack_resident<128, __bf16, 256>(d_Wh_fw, d_Wh_bw, d_packed, st);
+    } else {
+        if (H == 256) pack_mfma<256>(d_Wh_fw, d_Wh_bw, d_packed, st);
+        else pack_mfma<128>(d_Wh_fw, d_Wh_bw, d_packed, st);
+    }
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+int vc_gru_bidir_packed(int32_t form, const float* d_xproj, const void* d_packed, size_t packed_bytes, int32_t w_dtype,
+                        int32_t n_seq, int32_t T, int32_t H, void* d_out, int32_t out_dtype, void* stream) {
+    VC_REQUIRE(d_xproj && d_packed && d_out, "vc_gru_bidir_packed: NULL argument");
+    VC_REQUIRE(reinterpret_cast<uintptr_t>(d_packed) % 16 == 0, "vc_gru_bidir_packed: d_packed is not 16-byte aligned");
+    VC_REQUIRE(n_seq > 0 && T > 0, "vc_gru_bidir_packed: bad shape n_seq=%d T=%d", n_seq, T);
+    VC_REQUIRE(gru_form_ok(form, H, w_dtype), "vc_gru_bidir_packed: no packed form %d for H=%d w_dtype=%d", form, H, w_dtype);
+    VC_REQUIRE(out_dtype == VC_F32 || out_dtype == VC_BF16, "bad out_dtype %d", out_dtype);
+    const size_t need = vc_gru_packed_bytes(form, H, w_dtype);
+    if (packed_bytes < need)
+        return vc::set_error(VC_ERR_WORKSPACE, "vc_gru_bidir_packed: image too small (%zu < %zu)", packed_bytes, need);
+    GruArgs a;
+    a.xproj = d_xproj; a.Wh[0] = a.Wh[1] = nullptr; a.out = d_out;             // the packed kernels never read Wh
+    a.n_seq = n_seq; a.T = T; a.H = H; a.out_bf16 = out_dtype == VC_BF16; a.w_in_lds = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (form == VC_GRU_FORM_RESIDENT)
+        return H == 256 ? run_resident<256, __bf16, 512>(a, d_packed, st) : run_resident<128, __bf16, 256>(a, d_packed, st);
+    return H == 256 ? run_mfma<256>(a, d_packed, st) : run_mfma<128>(a, d_packed, st);
 }
 
 int vc_lstm_bidir(const float* d_xproj, const void* d_Wh_fw, const void* d_Wh_bw, int32_t w_dtype, int32_t n_seq, int32_t T,

@@ -594,19 +594,23 @@ def gru(inputs, num_units=None, bidirection=False, scope="gru", use_Cudnn=False,
         xproj = torch.empty((N_ * T_, 6 * H), dtype=torch.float32, device=x.device)
         gemm_launch(x, N_ * T_, T_, Cin, Cin, 6 * H, [(btx, Cin, 1, 0, 0)], xproj, 6 * H, store.vc_dtype,
                     epi_shift=bx, out_f32=True)
-        return _gru_recurrence(xproj, N_, T_, H, wh, wh)[:, :, :H].contiguous()
+        return _gru_recurrence(xproj, N_, T_, H, wh, wh, scope=_scope(scope) + '/rnn')[:, :, :H].contiguous()
     btx, bx, wh_fw, wh_bw = _prep_gru(store, _scope(scope), Cin, H)
     xproj = torch.empty((N_ * T_, 6 * H), dtype=torch.float32, device=x.device)
     gemm_launch(x, N_ * T_, T_, Cin, Cin, 6 * H, [(btx, Cin, 1, 0, 0)], xproj, 6 * H, store.vc_dtype,
                 epi_shift=bx, out_f32=True)
-    return _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw)
+    return _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw, scope=_scope(scope))
 
 
-def _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw):
-    """The recurrent half of gru(): xproj [N*T, 6H] float32 = input projections of both directions."""
+def _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw, scope=None):
+    """The recurrent half of gru(): xproj [N*T, 6H] float32 = input projections of both directions.
+    scope: the GRU's variable scope.  With it the kernels that read the recurrent weights in a layout of their own (bf16,
+    128 / 256 units) get an image packed once per (scope, form) and kept like every other layout copy (store.cached:
+    dropped by store.invalidate()); without it, and for every other size, the library packs on every call."""
     torch = _torch()
     store = _store()
     x = xproj
+    lib = _vc.lib()
     out = torch.empty((N_, T_, 2 * H), dtype=store.dtype, device=x.device)
     if store.dtype == torch.float32 and 128 < H <= 1024 and _vc.get_option('gru_f32_wide') != 0:
         # float32 weights of more than 128 units do not fit a CU's registers: the inference kernels stream all 786 KB of
@@ -615,14 +619,31 @@ def _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw):
         # backward pass goes to scratch.
         gates = torch.empty((2, N_ * T_, 3 * H), dtype=torch.float32, device=x.device)
         rh = torch.empty((2, N_ * T_, H), dtype=torch.float32, device=x.device)
-        _vc.check(_vc.lib().vc_gru_train_forward(xproj.data_ptr(), wh_fw.data_ptr(), wh_bw.data_ptr(), N_, T_, H,
-                                                 out.data_ptr(), gates.data_ptr(), rh.data_ptr(), _vc.current_stream()))
+        _vc.check(lib.vc_gru_train_forward(xproj.data_ptr(), wh_fw.data_ptr(), wh_bw.data_ptr(), N_, T_, H,
+                                           out.data_ptr(), gates.data_ptr(), rh.data_ptr(), _vc.current_stream()))
         return out
-    nws = _vc.lib().vc_gru_workspace_bytes(H, store.vc_dtype)
+    # the form by the makespan of this call (one round of CUs: register-resident, else MFMA; option gru_mfma forces one)
+    form = lib.vc_gru_form(H, store.vc_dtype, N_, 0) if scope is not None else _vc.GRU_FORM_NONE
+    if form < 0:
+        _vc.check(form)
+    if form != _vc.GRU_FORM_NONE:
+        nbytes = lib.vc_gru_packed_bytes(form, H, store.vc_dtype)
+
+        def build():
+            pk = torch.empty((nbytes,), dtype=torch.uint8, device=store.device)
+            _vc.check(lib.vc_gru_pack(form, wh_fw.data_ptr(), wh_bw.data_ptr(), store.vc_dtype, H, pk.data_ptr(), nbytes,
+                                      _vc.current_stream()))
+            return pk
+        # the form is part of the key: the two kernels' layouts differ, and the mode may change between calls
+        pk = store.cached(('gru_rec_pk', scope, form, H, store.vc_dtype), build)
+        _vc.check(lib.vc_gru_bidir_packed(form, xproj.data_ptr(), pk.data_ptr(), nbytes, store.vc_dtype, N_, T_, H,
+                                          out.data_ptr(), store.vc_dtype, _vc.current_stream()))
+        return out
+    nws = lib.vc_gru_workspace_bytes(H, store.vc_dtype)
     ws = torch.empty((max(nws, 16),), dtype=torch.uint8, device=x.device)
-    _vc.check(_vc.lib().vc_gru_bidir(xproj.data_ptr(), wh_fw.data_ptr(), wh_bw.data_ptr(), store.vc_dtype,
-                                     N_, T_, H, out.data_ptr(), store.vc_dtype, ws.data_ptr(), nws,
-                                     _vc.current_stream()))
+    _vc.check(lib.vc_gru_bidir(xproj.data_ptr(), wh_fw.data_ptr(), wh_bw.data_ptr(), store.vc_dtype,
+                               N_, T_, H, out.data_ptr(), store.vc_dtype, ws.data_ptr(), nws,
+                               _vc.current_stream()))
     return out
 
 
@@ -774,7 +795,7 @@ def highway_chain(inputs, num_units, n_layers, scope_fmt='highwaynet_{}', gru_sc
     _vc.check(_vc.lib().vc_highway_chain(x.data_ptr(), N_ * T_, Cx, Cx, n_layers, PA, BA, None, 0,
                                          px.data_ptr(), bx.data_ptr(), 6 * H, xproj.data_ptr(), 6 * H,
                                          _vc.current_stream()))
-    return _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw)
+    return _gru_recurrence(xproj, N_, T_, H, wh_fw, wh_bw, scope=gsc)
 
 
 def CBHG(inputs, embed_size=256, num_conv_banks=16, num_highwaynet_blocks=4, dropout_rate=0.5, is_training=True,
