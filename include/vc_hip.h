@@ -1322,6 +1322,55 @@ int vc_align_f32(const float* d_score, const int32_t* d_seq, const uint8_t* d_op
                  int32_t* d_end, float* d_seg_score, float* d_total, int32_t* d_n_visited, void* d_workspace, size_t workspace_bytes,
                  void* stream);
 
+/* Full-sum alignment: the DISTRIBUTION over the paths of the same lattice, where vc_align_f32 gives the best path.  Added
+ * without a version bump.  Inputs exactly as vc_align_f32's (d_score finite or -inf; d_opt may be NULL), the lattice
+ * exactly as above: e(t, s) = score[t, seq[s]], -inf for a class outside [0, C); moves stay, advance, and skip one state
+ * s-1 iff opt[s-1]; start in state 0, or state 1 iff opt[0]; end in state S-1, or S-2 iff S >= 2 and opt[S-1].  With
+ * lse the logarithm of the sum of the exponentials (-inf terms drop out; of nothing but -inf: -inf):
+ *
+ *   la(0, s)    = e(0, s) on the admitted start states, -inf elsewhere
+ *   la(t, s)    = e(t, s) + lse(la(t-1, s), la(t-1, s-1), [opt[s-1]] la(t-1, s-2))
+ *   lb(F-1, s)  = 0 on the admitted end states, -inf elsewhere
+ *   lb(t, s)    = lse(lb(t+1, s) + e(t+1, s), lb(t+1, s+1) + e(t+1, s+1), [opt[s+1]] lb(t+1, s+2) + e(t+1, s+2))
+ *   log_z       = lse over the end states of la(F-1, .)        (the log of the sum over ALL admissible paths of the
+ *                                                               product of their frames' exp(e))
+ *   gamma(t, s) = exp(la(t, s) + lb(t, s) - log_z)             (the posterior probability of state s at frame t)
+ *   Gamma(t, c) = sum over s with seq[s] = c of gamma(t, s)    (with y the logits and e = log_softmax(y):
+ *                                                               d(-log_z)/dy = softmax(y) - Gamma)
+ *   occ(s)      = sum over t of gamma(t, s)                    (the expected number of frames of state s)
+ *
+ * The utterance is INFEASIBLE iff F == 0, S == 0 or log_z == -inf.  tests/fullsum_ref.py restates this in float64.
+ *
+ * Outputs, every element written exactly once per call (no memset):
+ *   d_log_z [batch] float32                          -inf when infeasible
+ *   d_class_post [batch, max_frames, C] float32      Gamma; all zeros from frame F on and when infeasible
+ *   d_state_post [batch, max_frames, max_seq] float32, or NULL: gamma; zeros outside the utterance (frames from F on,
+ *                                                    states from S on, infeasible)
+ *   d_occ [batch, max_seq] float32                   zeros from S on and when infeasible
+ * No output is NaN for any finite-or-(-inf) input.
+ *
+ * Arithmetic: float32 in the log domain; after each frame the row's maximum over the states is subtracted (forward: and
+ * added to a float64 sum, from which log_z is rounded once), so nothing overflows or underflows at any length and mass in
+ * states that cannot reach the end costs nothing.  gamma is normalised over the states of its frame, exp(A + B - max) /
+ * sum; Gamma is accumulated in 2^-30 fixed point with integer additions, so it is a multiple of 2^-30, independent of the
+ * order in which the states of one class arrive, and carries up to S 2^-31 of quantisation on top of gamma's error; occ
+ * adds gamma from the last frame to the first.  On scores that are 0 along one admissible path and -inf elsewhere every
+ * output is exact (log_z = 0, gamma and Gamma 0 or 1, occ the durations).
+ *
+ * Two launches on the caller's stream with vc_align_f32's geometry (one wave per utterance, K = 1, 2, 4, 8 or 16
+ * consecutive states per lane, the least K with 64 K >= max_seq; neighbours by shuffles; emissions gathered four frames
+ * ahead with a clamped frame index; no address from an unchecked class).  Forward stores the shifted rows in d_workspace
+ * (4-byte aligned):
+ *     vc_fullsum_workspace_bytes = align256(batch * max_frames * max_seq * 4)
+ * (host arithmetic only; 0 for a shape the launch would refuse; too small: VC_ERR_WORKSPACE).  Limits (VC_ERR_UNSUPPORTED
+ * beyond them): max_seq <= 1,024; batch <= 65,535; C <= 4,096 (the Gamma row lives in LDS); the workspace below 2^31
+ * bytes.  A function of its own utterance alone: bit-identical alone, in any batch, from run to run and under graph
+ * replay; lengths are read on the device; capturable from the first call; arguments are checked before any HIP call. */
+size_t vc_fullsum_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_seq);
+int vc_fullsum_f32(const float* d_score, const int32_t* d_seq, const uint8_t* d_opt, const int32_t* d_n_frames, const int32_t* d_n_seq,
+                   int32_t batch, int32_t max_frames, int32_t max_seq, int32_t n_classes, float* d_log_z, float* d_class_post,
+                   float* d_state_post, float* d_occ, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

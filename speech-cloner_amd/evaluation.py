@@ -1398,9 +1398,9 @@ def _check_align_size(B, F, S, what):
                          'utterances per call'.format(what, B, F, S))
 
 
-def _align_kind(kind, floor, what):
-    if kind not in ('prob', 'log'):
-        raise ValueError(" - ERROR, {}: kind must be 'prob' or 'log', got {!r}".format(what, kind))
+def _align_kind(kind, floor, what, kinds=('prob', 'log')):
+    if kind not in kinds:
+        raise ValueError(" - ERROR, {}: kind must be {}, got {!r}".format(what, ' or '.join((', '.join(map(repr, kinds[:-1])), repr(kinds[-1]))), kind))
     fl = float(floor)
     if not (np.isfinite(fl) and fl > 0.0):
         raise ValueError(' - ERROR, {}: floor must be finite and positive, got {!r}'.format(what, floor))
@@ -1474,6 +1474,46 @@ def align_batch(ppg, lens, seq, n_seq, optional=None, kind='prob', floor=1e-10):
     return _align_launch(score, d_seq, d_opt, d_frames, d_nseq)
 
 
+def _align_wav_front(what, encoder, wav, lens, seq, n_seq, cfg_d, wav_sr, res_type, optional, window_batch, ppg, max_classes,
+                     check_size):
+    """What align_wav_batch and align_posterior_wav_batch share: the checks, the uploads and the posteriors of
+    content_wav_batch's _content_side.  check_size(B, Fout, S, what) is the launch's own size check.  Returns
+    (ppg [B, Fout, n_phn], d_seq, d_opt, d_l, d_nseq), all on the device."""
+    import torch
+    import audio_lib
+    import conversion
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    audio_lib._res_params(res_type)
+    a = _wav_side(wav, lens, cfg_d, wav_sr, 'wav')
+    B = a['B']
+    window_batch = int(window_batch)
+    if window_batch <= 0:
+        raise ValueError(' - ERROR, {}: window_batch must be positive'.format(what))
+    plan = conversion.convert_plan(a['h'], cfg_d, 0, 60, True)
+    C = int(encoder.cfg_d['n_output'])
+    if B > 65535 or C > max_classes:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances and {} classes (got {} and {})'.format(what, max_classes, B, C))
+    if ppg is not None:
+        if _check_align_ppg(ppg, '{}: ppg'.format(what)) != (B, plan.Fout, C):
+            raise ValueError(' - ERROR, {}: ppg must be [{}, {}, {}], as convert_batch returns phn_pred for wav'
+                             .format(what, B, plan.Fout, C))
+    seq, ns, optional = _check_align_seq(seq, n_seq, optional, B, C, what)
+    check_size(B, plan.Fout, int(seq.shape[1]), what)
+    h_l = np.minimum(plan.n_out, plan.n_clip - plan.n_s)
+    if h_l.min() < 1:
+        raise ValueError(' - ERROR, {}: every utterance needs at least one frame of its own'.format(what))
+    _need_gpu(what)
+    d_in, d_len, d_clip, d_win, d_utt, d_true, d_l = _upload_lens(a['h_in'], a['h'], plan.n_clip, plan.win_tab, plan.utt_tab,
+                                                                  plan.true_tab, h_l)
+    d_seq, d_opt, (d_nseq,) = _align_device(seq, (ns,), optional)
+    if ppg is not None:
+        ppg = _to_device(ppg, torch.float32)
+    _, _, ppg = _content_side(encoder, wav, a, plan, (d_in, d_len, d_clip, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)),
+                              cfg_d, res_type, window_batch, ppg)
+    return ppg, d_seq, d_opt, d_l, d_nseq
+
+
 def align_wav_batch(encoder, wav, lens, seq, n_seq, cfg_d, wav_sr=None, res_type='kaiser_best', optional=None, window_batch=64,
                     ppg=None):
     """Forced alignment of B WAVEFORMS against their transcripts.  encoder: the phoneme recogniser
@@ -1484,39 +1524,95 @@ def align_wav_batch(encoder, wav, lens, seq, n_seq, cfg_d, wav_sr=None, res_type
     min(n_out, min(n_src, n_e) - n_s) per utterance.  seq, n_seq, optional as in align_batch, which this ends in
     (kind='prob').  Returns align_batch's fields, then ppg [B, Fout, n_phn] and n_frames (int32 [B]), on the device."""
     import torch
-    import audio_lib
-    import conversion
-    if cfg_d is None:
-        raise ValueError(' - ERROR, align_wav_batch: cfg_d (the data-set configuration) is required')
-    audio_lib._res_params(res_type)
-    a = _wav_side(wav, lens, cfg_d, wav_sr, 'wav')
-    B = a['B']
-    window_batch = int(window_batch)
-    if window_batch <= 0:
-        raise ValueError(' - ERROR, align_wav_batch: window_batch must be positive')
-    plan = conversion.convert_plan(a['h'], cfg_d, 0, 60, True)
-    C = int(encoder.cfg_d['n_output'])
-    if B > 65535 or C > ALIGN_MAX_CLASSES:
-        raise ValueError(' - ERROR, align_wav_batch: at most 65535 utterances and {} classes (got {} and {})'.format(ALIGN_MAX_CLASSES, B, C))
-    if ppg is not None:
-        if _check_align_ppg(ppg, 'align_wav_batch: ppg') != (B, plan.Fout, C):
-            raise ValueError(' - ERROR, align_wav_batch: ppg must be [{}, {}, {}], as convert_batch returns phn_pred for wav'
-                             .format(B, plan.Fout, C))
-    seq, ns, optional = _check_align_seq(seq, n_seq, optional, B, C, 'align_wav_batch')
-    _check_align_size(B, plan.Fout, int(seq.shape[1]), 'align_wav_batch')
-    h_l = np.minimum(plan.n_out, plan.n_clip - plan.n_s)
-    if h_l.min() < 1:
-        raise ValueError(' - ERROR, align_wav_batch: every utterance needs at least one frame of its own')
-    _need_gpu('align_wav_batch')
-    d_in, d_len, d_clip, d_win, d_utt, d_true, d_l = _upload_lens(a['h_in'], a['h'], plan.n_clip, plan.win_tab, plan.utt_tab,
-                                                                  plan.true_tab, h_l)
-    d_seq, d_opt, (d_nseq,) = _align_device(seq, (ns,), optional)
-    if ppg is not None:
-        ppg = _to_device(ppg, torch.float32)
-    _, _, ppg = _content_side(encoder, wav, a, plan, (d_in, d_len, d_clip, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)),
-                              cfg_d, res_type, window_batch, ppg)
+    ppg, d_seq, d_opt, d_l, d_nseq = _align_wav_front('align_wav_batch', encoder, wav, lens, seq, n_seq, cfg_d, wav_sr, res_type,
+                                                      optional, window_batch, ppg, ALIGN_MAX_CLASSES, _check_align_size)
     r = _align_launch(torch.log(ppg.clamp_min(1e-10)), d_seq, d_opt, d_l, d_nseq)
     return _ALIGN_WAV(*r, ppg, d_l)
+
+
+FULLSUM_MAX_CLASSES = 4096  # vc_fullsum_f32: the Gamma row lives in LDS
+_FULLSUM_FIELDS = 'log_z class_post state_post occupancy feasible'
+_FULLSUM = namedtuple('alignment_posterior', _FULLSUM_FIELDS)
+_FULLSUM_WAV = namedtuple('alignment_posterior_wav', _FULLSUM_FIELDS + ' ppg n_frames')
+
+
+def _check_fullsum_size(B, F, S, what):
+    if (B * F * S * 4 + 255) // 256 * 256 >= 2 ** 31:               # vc_fullsum_workspace_bytes
+        raise ValueError(' - ERROR, {}: the forward rows of {} utterances of {} frames x {} states need 2 GiB or more; pass fewer '
+                         'utterances per call'.format(what, B, F, S))
+
+
+def _check_fullsum_classes(C, what):
+    if C > FULLSUM_MAX_CLASSES:
+        raise ValueError(' - ERROR, {}: at most {} classes (got {})'.format(what, FULLSUM_MAX_CLASSES, C))
+
+
+def _fullsum_launch(score, seq, opt, d_frames, d_nseq, return_states=False):
+    """score: cuda, contiguous float32 [B, F, C]; seq int32 [B, S], opt uint8 [B, S] or None, counts: all on the device.
+    The two launches of vc_fullsum_f32 and feasible = log_z > -inf.  No host check in here, nothing waited for."""
+    import torch
+    lib = _vc.lib()
+    B, F, C = score.shape
+    S = seq.shape[1]
+    dev = score.device
+    log_z = torch.empty((B,), dtype=torch.float32, device=dev)
+    class_post = torch.empty((B, F, C), dtype=torch.float32, device=dev)
+    state_post = torch.empty((B, F, S), dtype=torch.float32, device=dev) if return_states else None
+    occ = torch.empty((B, S), dtype=torch.float32, device=dev)
+    need = lib.vc_fullsum_workspace_bytes(B, F, S)
+    if need == 0:
+        raise _vc.VCError('vc_fullsum_workspace_bytes refused {} utterances of {} frames x {} states'.format(B, F, S))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _vc.check(lib.vc_fullsum_f32(_vc.ptr(score), _vc.ptr(seq), _vc.ptr(opt), _vc.ptr(d_frames), _vc.ptr(d_nseq), B, F, S, C,
+                                 _vc.ptr(log_z), _vc.ptr(class_post), _vc.ptr(state_post), _vc.ptr(occ), _vc.ptr(ws), need,
+                                 _vc.current_stream()))
+    return _FULLSUM(log_z, class_post, state_post, occ, log_z > float('-inf'))
+
+
+def _fullsum_score(x, kind, fl):
+    import torch
+    if kind == 'prob':
+        return torch.log(x.clamp_min(fl))
+    if kind == 'logits':
+        return torch.log_softmax(x, dim=-1)
+    return x
+
+
+def align_posterior_batch(ppg, lens, seq, n_seq, optional=None, kind='prob', floor=1e-10, return_states=False):
+    """Full-sum alignment of B utterances (vc_fullsum_f32; the definition is in include/vc_hip.h, "Alignment"): not the best
+    path of the transcript through the frames, as align_batch gives it, but the distribution over ALL admissible paths.
+    ppg, lens, seq, n_seq, optional and floor as in align_batch; kind 'prob' (the scores are torch.log(ppg.clamp_min(floor))),
+    'log' (ready scores, finite or -inf, passed through) or 'logits' (the scores are torch.log_softmax over the classes).
+    S_max <= 1,024, B <= 65,535, C <= 4,096, and B * F_max * S_max * 4 bytes of forward rows below 2 GiB.  Nothing is copied
+    back and the host waits for nothing.  Returns a namedtuple of device tensors: log_z [B] float32 (the log of the sum
+    over the paths of the product of their frames' scores: the transcript's likelihood; -inf: no path), class_post
+    [B, F_max, C] float32 (Gamma: the posterior probability that the frame is in a state of the class -- with logits y,
+    softmax(y) - class_post is the gradient of -log_z; zero rows from the count on and without a path), state_post
+    [B, F_max, S_max] float32 (gamma, per state; None unless return_states), occupancy [B, S_max] float32 (the expected
+    number of frames of every state) and feasible [B] bool."""
+    import torch
+    B, F, C = _check_align_ppg(ppg, 'align_posterior_batch: ppg')
+    _check_fullsum_classes(C, 'align_posterior_batch')
+    fl = _align_kind(kind, floor, 'align_posterior_batch', ('prob', 'log', 'logits'))
+    nf = _check_counts(lens, B, 0, F, 'align_posterior_batch: lens')
+    seq, ns, optional = _check_align_seq(seq, n_seq, optional, B, C, 'align_posterior_batch')
+    _check_fullsum_size(B, F, int(seq.shape[1]), 'align_posterior_batch')
+    _need_gpu('align_posterior_batch')
+    d_seq, d_opt, (d_frames, d_nseq) = _align_device(seq, (nf, ns), optional)
+    score = _fullsum_score(_to_device(ppg, torch.float32), kind, fl)
+    return _fullsum_launch(score, d_seq, d_opt, d_frames, d_nseq, bool(return_states))
+
+
+def align_posterior_wav_batch(encoder, wav, lens, seq, n_seq, cfg_d, wav_sr=None, res_type='kaiser_best', optional=None,
+                              window_batch=64, ppg=None, return_states=False):
+    """Full-sum alignment of B WAVEFORMS against their transcripts: align_wav_batch's posteriors (the same front half, ppg
+    included) into align_posterior_batch's launch (kind='prob', floor 1e-10).  Returns align_posterior_batch's fields, then
+    ppg [B, Fout, n_phn] and n_frames (int32 [B]), on the device."""
+    import torch
+    ppg, d_seq, d_opt, d_l, d_nseq = _align_wav_front('align_posterior_wav_batch', encoder, wav, lens, seq, n_seq, cfg_d, wav_sr,
+                                                      res_type, optional, window_batch, ppg, FULLSUM_MAX_CLASSES, _check_fullsum_size)
+    r = _fullsum_launch(torch.log(ppg.clamp_min(1e-10)), d_seq, d_opt, d_l, d_nseq, bool(return_states))
+    return _FULLSUM_WAV(*r, ppg, d_l)
 
 
 def alignment_min_frames(hop_length, win_length):

@@ -947,6 +947,43 @@ class EncoderTrainer(StageTrainer):
 
     def forward_backward(self, x, target, backward=True):
         """Returns the device tensor [loss, acc, mse]."""
+        return self._forward_backward(x, lambda y: target, backward)
+
+    def forward_backward_transcript(self, x, n_frames, seq, n_seq, optional=None, backward=True):
+        """One step from recordings and a TRANSCRIPT instead of frame labels: the full-sum criterion -log Z, Z the sum over
+        all admissible paths of the transcript through the frames of the product of the frame posteriors
+        (include/vc_hip.h, "Alignment"; evaluation.align_posterior_batch).  x [N, T, Cx]: whole utterances zero-padded to T;
+        n_frames (host integers in [0, T] or int32 [N] on the device), seq [N, S] int32, n_seq, optional as in
+        evaluation.align_batch.  The same train-mode forward as forward_backward; Gamma (the posterior probability of every
+        class at every frame) is computed by vc_fullsum_f32 from log_softmax of the logits' first n_output columns; the
+        existing vc_softmax_ce call then takes Gamma as its float target, so dY = (softmax - Gamma) / M on real frames --
+        the gradient of -sum(log Z) / M -- and exactly 0 on padded ones (their target rows are zero); then the existing
+        backward.  Returns (out3, log_z [N] float32), both on the device.
+        Limits: padded frames take part in the batch-norm statistics and in the recurrences; out3's loss is the EM
+        auxiliary cross-entropy -sum(Gamma log softmax) / M, not the criterion (the criterion is -log_z); acc and mse run
+        over all M rows, padded ones included; an utterance without a path has a zero Gamma and contributes no gradient."""
+        import evaluation as ev
+        what = 'forward_backward_transcript'
+        N_, T_, _ = x.shape
+        n_out = self.cfg['n_output']
+        ev._check_fullsum_classes(n_out, what)
+        nf = ev._check_counts(n_frames, N_, 0, T_, what + ': n_frames')
+        seq, ns, optional = ev._check_align_seq(seq, n_seq, optional, N_, n_out, what)
+        ev._check_fullsum_size(N_, T_, int(seq.shape[1]), what)
+        d_seq, d_opt, (d_frames, d_nseq) = ev._align_device(seq, (nf, ns), optional)
+        got = []
+
+        def target(y):
+            score = _torch().log_softmax(y[:, :n_out], dim=-1).view(N_, T_, n_out).contiguous()
+            got.append(ev._fullsum_launch(score, d_seq, d_opt, d_frames, d_nseq))
+            return got[0].class_post
+
+        out3 = self._forward_backward(x, target, backward)
+        return out3, got[0].log_z
+
+    def _forward_backward(self, x, make_target, backward):
+        """The body of forward_backward and forward_backward_transcript.  make_target(y) -> the float target [M, n_output]
+        of the cross-entropy, given the logits; it is called between the forward and the loss, on the same stream."""
         torch = _torch()
         enc, c = self.dec, self.cfg
         self._drain_pending()
@@ -960,7 +997,9 @@ class EncoderTrainer(StageTrainer):
             y, sv = self._stage_forward(enc._scope, x, Cx, enc._embed_size, c['num_conv_banks'],
                                         c['num_highwaynet_blocks'], n_out, seed)
             self.y_logits = y
+            target = make_target(y)
             dY = torch.zeros_like(y) if backward else None
+            self.dy_logits = dY
             out3 = torch.empty(3, dtype=torch.float32, device=x.device)
             ws = torch.empty(3 * M, dtype=torch.float32, device=x.device)
             _vc.check(_lib().vc_softmax_ce(_p(y), _p(target), M, n_out, y.shape[1], _p(dY), y.shape[1], _p(out3), _p(ws), _st()))
