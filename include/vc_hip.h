@@ -1371,6 +1371,61 @@ int vc_fullsum_f32(const float* d_score, const int32_t* d_seq, const uint8_t* d_
                    int32_t batch, int32_t max_frames, int32_t max_seq, int32_t n_classes, float* d_log_z, float* d_class_post,
                    float* d_state_post, float* d_occ, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Decoding.  "Alignment" asks where the phonemes of a KNOWN sequence lie; decoding reads the sequence itself off the
+ * scores: the best path through a loop of all C classes, with a transition score between two segments and a minimum
+ * duration of M frames per segment (a phone-loop Viterbi recogniser).  Added without a version bump.
+ *
+ * Inputs, all on the device: d_score [batch, max_frames, C] float32 (log-posteriors or any additive score); d_n_frames
+ * int32 [batch], clamped to [0, max_frames]: F; d_trans [C, C] float32, shared by the batch: trans[i, j] is added when a
+ * segment of class i ends and one of class j begins (i == j is an ordinary entry: a phoneme said twice); d_init, d_final
+ * [C] float32 or NULL (zeros; nothing is added then); min_dur = M in [1, 8]; d_class_map int32 [C] or NULL (the identity),
+ * values in [-1, C) as vc_phn_segments takes it.  Every value of score, trans, init and final is finite or -inf; +inf and
+ * NaN are OUTSIDE the contract (with them -inf - -inf could form).  Within it no output is NaN except the defined fill.
+ *
+ *   States      (c, d), d = 0 .. M-1: class c in its (d+1)-th frame, or a later one when d = M-1.  e(t, c) = score[b, t, c].
+ *   Recurrence  float32; every operation is one IEEE addition or a strict compare-select; nothing is multiplied.
+ *               D(0, (c, 0)) = init[c] + e(0, c) (without init: e(0, c)); D(0, (c, d > 0)) = -inf.
+ *               X(t, c) = the maximum over i, taken in ascending order, of D(t-1, (i, M-1)) + trans[i, c], each term rounded
+ *               to float32 before the compare; a later i replaces the holder only when strictly greater, so the lowest i
+ *               wins a tie; bp(t, c) is that i.
+ *               M = 1:  D(t, (c, 0)) = e(t, c) + best; best starts as D(t-1, (c, 0)) (stay) and is replaced by X(t, c)
+ *                       (enter) iff that is strictly greater.
+ *               M > 1:  D(t, (c, 0)) = e(t, c) + X(t, c);  D(t, (c, d)) = e(t, c) + D(t-1, (c, d-1)) for 0 < d < M-1;
+ *                       D(t, (c, M-1)) = e(t, c) + best; best starts as D(t-1, (c, M-1)) (stay) and is replaced by
+ *                       D(t-1, (c, M-2)) (advance) iff that is strictly greater.
+ *   End         total = the maximum over c, ascending, of D(F-1, (c, M-1)) + final[c] (without final: the bare value), the
+ *               lowest c on a tie: the last segment lasts M frames too.  INFEASIBLE iff F == 0, F < M or total == -inf.
+ *   Path        read back from the stay / advance (enter) decisions and bp, from (F-1, (c*, M-1)) to frame 0.
+ *
+ * Outputs, every element written exactly once per call whatever the memory held (no memset, no atomics):
+ *   d_frame_class [batch, max_frames] int32   the raw class of every frame; -1 from F on and when infeasible
+ *   d_seg_label, d_seg_start, d_seg_end [batch, max_frames] int32 (end exclusive) and d_n_seg [batch] int32: the layout
+ *                                             of vc_phn_segments, -1 from the row's n_seg on.  The decoded segments have
+ *                                             their labels mapped through class_map, then equal neighbours merge, then
+ *                                             segments labelled -1 are removed ("a b a" with b -> -1 stays two "a")
+ *   d_seg_score [batch, max_frames] float32   the emissions e(t, frame_class[t]) of the segment's frames widened to
+ *                                             float64, added in frame order, divided by their count, rounded once; NaN
+ *                                             from n_seg on
+ *   d_total [batch] float32                   -inf when infeasible
+ * The device equals the float32 restatement of tests/decode_ref.py bit for bit in every output.
+ *
+ * Two launches on the caller's stream.  Forward: one workgroup per utterance, a lane per destination class with its M
+ * values of D in registers; up to 64 classes one wave with its column of trans in registers and the previous row read
+ * from the other lanes, up to 128 classes two waves with trans in LDS and one barrier per frame; the maximum over i in
+ * four chains over contiguous quarters, merged in order; emissions fetched four frames ahead with a clamped index; one
+ * byte of moves per (frame, class).  Back-track: one wave finds each segment's first frame with a ballot over 64 move
+ * bytes, then 256 lanes derive the outputs from the frames' classes.  d_workspace (4-byte aligned):
+ *     vc_decode_workspace_bytes = align256(4 batch) + align256(batch * C * ceil(max_frames / 4) * 4)
+ * (host arithmetic only; 0 for a shape the launch would refuse; too small: VC_ERR_WORKSPACE).  Limits (VC_ERR_UNSUPPORTED
+ * beyond them): C <= 128; 1 <= min_dur <= 8; batch <= 65,535; max_frames <= 16,384; the workspace below 2^31 bytes.
+ * A function of its own utterance alone: bit-identical alone, in any batch, from run to run and under graph replay;
+ * lengths are read on the device; no allocation and no host wait; arguments are checked before any HIP call. */
+size_t vc_decode_workspace_bytes(int32_t batch, int32_t max_frames, int32_t n_classes);
+int vc_decode_f32(const float* d_score, const int32_t* d_n_frames, const float* d_trans, const float* d_init, const float* d_final,
+                  const int32_t* d_class_map, int32_t batch, int32_t max_frames, int32_t n_classes, int32_t min_dur,
+                  int32_t* d_frame_class, int32_t* d_seg_label, int32_t* d_seg_start, int32_t* d_seg_end, int32_t* d_n_seg,
+                  float* d_seg_score, float* d_total, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

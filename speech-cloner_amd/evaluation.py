@@ -1177,15 +1177,17 @@ def edit_distance_batch(seq_a, seq_b, n_a, n_b):
     return _edit_launch(dev(seq_a), dev(seq_b), d_na, d_nb)
 
 
-def _content_launch(a, b, d_la, d_lb, path, path_len, cmap, min_run, ma, mb):
-    """content_batch after its checks: everything on the device.  ma, mb: uint8 masks (both or neither)."""
+def _content_launch(a, b, d_la, d_lb, path, path_len, cmap, min_run, ma, mb, dec=None):
+    """content_batch after its checks: everything on the device.  ma, mb: uint8 masks (both or neither).  dec: None (the
+    sequences are vc_phn_segments' arg-max read-outs) or _decode_args' result (they come from vc_decode_f32)."""
+    seg = (lambda x, n: _segments_launch(x, n, cmap, min_run)) if dec is None else (lambda x, n: _decode_launch(x, n, cmap, dec).seg)
     if ma is None:
         m = _ppg_metrics_launch(a, b, d_la, d_lb, path, path_len, cmap)
-        sa, sb = _segments_launch(a, d_la, cmap, min_run), _segments_launch(b, d_lb, cmap, min_run)
+        sa, sb = seg(a, d_la), seg(b, d_lb)
     else:
         ia, ib = _compact_launch(ma, d_la), _compact_launch(mb, d_lb)
-        sa = _segments_launch(_rows_launch(a, ia.index, ia.n_kept), ia.n_kept, cmap, min_run)
-        sb = _segments_launch(_rows_launch(b, ib.index, ib.n_kept), ib.n_kept, cmap, min_run)
+        sa = seg(_rows_launch(a, ia.index, ia.n_kept), ia.n_kept)
+        sb = seg(_rows_launch(b, ib.index, ib.n_kept), ib.n_kept)
         if path is None:                                            # the frames set in both masks, in original frame numbers
             ic = _compact_launch(ma, d_la, mb, d_lb)
             path, path_len = _path_map_launch(None, ic.n_kept, ic.index, ic.index, ic.index.shape[1]), ic.n_kept
@@ -1196,7 +1198,8 @@ def _content_launch(a, b, d_la, d_lb, path, path_len, cmap, min_run, ma, mb):
     return _CONTENT(*m, *e, sa, sb)
 
 
-def content_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_map=None, min_run=3, mask_a=None, mask_b=None):
+def content_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_map=None, min_run=3, mask_a=None, mask_b=None,
+                  sequence='argmax', decode=None):
     """Does the conversion still say the same thing?  The three content figures of B pairs of posteriorgrams in one call:
     ppg_metrics_batch along the cells, phn_segments_batch of both sides, and edit_distance_batch of the two phoneme
     sequences with A as the reference (per = phoneme error rate).  Arguments as in those calls; F_max <= 16,384.
@@ -1206,6 +1209,9 @@ def content_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_ma
     off, exactly as mcd_batch compacts the cepstra; start and end of the segments then count kept frames.  The frame-level
     figures run on the original posteriorgrams along ``path``, which is in original frame numbers (what the masked
     mcd_batch(return_path=True) returns visits kept frames only), or, without a path, over the frames set in both masks.
+    sequence: 'argmax' (phn_segments_batch with ``min_run``: the launches this call has always issued) or 'viterbi': the
+    two sequences come from the phone-loop decoder instead (decode_batch; ``decode`` is a dict of its keyword arguments
+    trans, penalty, init, final, min_dur, kind, floor; C <= 128), after the same mask compaction; ``min_run`` is unused then.
     Returns a namedtuple of device tensors: the four fields of ppg_metrics_batch, the six of edit_distance_batch, and
     seg_a, seg_b, the two results of phn_segments_batch."""
     import torch
@@ -1219,6 +1225,7 @@ def content_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_ma
     _check_path(path, path_len, B, 'content_batch')
     cmap = _check_class_map(class_map, C, 'content_batch')
     min_run = _check_min_run(min_run, 'content_batch')
+    dec = _content_sequence(sequence, decode, B, max(Fa, Fb), C, 'content_batch')
     masked = mask_a is not None or mask_b is not None
     if masked:
         _check_mask(mask_a, B, Fa, 'content_batch: mask_a')
@@ -1229,7 +1236,7 @@ def content_batch(ppg_a, ppg_b, len_a, len_b, path=None, path_len=None, class_ma
         path, path_len = path.to('cuda').contiguous(), path_len.to('cuda').contiguous()
     ma, mb = (_mask_to_device(mask_a, B, Fa), _mask_to_device(mask_b, B, Fb)) if masked else (None, None)
     return _content_launch(_to_device(ppg_a, torch.float32), _to_device(ppg_b, torch.float32), d_la, d_lb, path, path_len,
-                           _cmap_device(cmap), min_run, ma, mb)
+                           _cmap_device(cmap), min_run, ma, mb, _decode_upload(dec))
 
 
 def _content_side(encoder, wav, side, plan, tabs, cfg_d, res_type, window_batch, ppg):
@@ -1251,7 +1258,7 @@ def _content_side(encoder, wav, side, plan, tabs, cfg_d, res_type, window_batch,
 def content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=None, wav_sr_b=None, res_type='kaiser_best',
                       align='frame', band=None, scale=None, n_coef=24, first_coef=1, class_map=None, min_run=3, mask=None,
                       top_db=40.0, max_gap=20, mask_min_run=0, frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15,
-                      ppg_a=None, t_s=0, t_e=60, two_pass=True, window_batch=64):
+                      ppg_a=None, t_s=0, t_e=60, two_pass=True, window_batch=64, sequence='argmax', decode=None):
     """The content figures of B pairs of WAVEFORMS: typically A is the source and B is convert_batch(...).y_wav_pred; with
     align='dtw' B may be the target speaker's own recording.  encoder: the phoneme recogniser (encoder.encoder_spec_phn;
     decoder.encoder of a decoder built with one).
@@ -1267,7 +1274,8 @@ def content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=Non
     mask: None, or 'energy', 'voiced', 'energy+voiced' with top_db, max_gap, mask_min_run (activity_batch's min_run) and
     the tracker's frame_length, fmin, fmax, threshold: the masks are taken from each side's waveform as in
     score_wav_batch (energy over cfg_d['win_length'] samples) and go to content_batch and to the DTW as in
-    mcd_batch(mask_a, mask_b); the mel is the front-end's own (no speech-level gain).
+    mcd_batch(mask_a, mask_b); the mel is the front-end's own (no speech-level gain).  sequence, decode: as in
+    content_batch.
     Returns a namedtuple of device tensors: content_batch's fields, then ppg_a, ppg_b [B, Fout, n_phn], len_a, len_b (int32
     [B]), path, path_len (None with align='frame') and mask_a, mask_b (None without a mask)."""
     import torch
@@ -1300,6 +1308,7 @@ def content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=Non
             raise ValueError(' - ERROR, content_wav_batch: ppg_a must be [{}, {}, {}], as convert_batch returns phn_pred for wav_a'
                              .format(B, pa.Fout, C))
     cmap = _check_class_map(class_map, C, 'content_wav_batch')
+    dec = _content_sequence(sequence, decode, B, max(pa.Fout, pb.Fout), C, 'content_wav_batch')
     if mask is not None:
         act = _activity_args(mask, top_db, max_gap, mask_min_run, 'content_wav_batch')
         _check_energy(cfg_d['hop_length'], cfg_d['win_length'], max(a['Fmax'], b['Fmax']), 'content_wav_batch')
@@ -1335,7 +1344,7 @@ def content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, wav_sr_a=Non
         else:
             r = _dtw_launch(ca, cb, d_la, d_lb, scale, band, True)
         path, path_len = r.path, r.path_len
-    c = _content_launch(p_a, p_b, d_la, d_lb, path, path_len, _cmap_device(cmap), min_run, ma, mb)
+    c = _content_launch(p_a, p_b, d_la, d_lb, path, path_len, _cmap_device(cmap), min_run, ma, mb, _decode_upload(dec))
     return _CONTENT_WAV(*c, p_a, p_b, d_la, d_lb, path, path_len, ma, mb)
 
 
@@ -1613,6 +1622,210 @@ def align_posterior_wav_batch(encoder, wav, lens, seq, n_seq, cfg_d, wav_sr=None
                                                       res_type, optional, window_batch, ppg, FULLSUM_MAX_CLASSES, _check_fullsum_size)
     r = _fullsum_launch(torch.log(ppg.clamp_min(1e-10)), d_seq, d_opt, d_l, d_nseq, bool(return_states))
     return _FULLSUM_WAV(*r, ppg, d_l)
+
+
+# ------------------------------------------------------------------------------------- decoding (csrc/vc_decode.hip)
+DECODE_MAX_CLASSES = 128    # vc_decode_f32
+DECODE_MAX_DUR = 8
+_DECODE_FIELDS = 'frame_class labels seg seg_score total feasible'
+_DECODE = namedtuple('decoded', _DECODE_FIELDS)
+_DECODE_WAV = namedtuple('decoded_wav', _DECODE_FIELDS + ' ppg n_frames')
+_DECODE_ARGS = namedtuple('decode_args', 'trans penalty init final min_dur kind floor')
+
+
+def _check_decode_size(B, F, C, what):
+    if B > 65535 or F > EDIT_MAX or C > DECODE_MAX_CLASSES:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of at most {} frames of at most {} classes (got {} of {} of {})'
+                         .format(what, EDIT_MAX, DECODE_MAX_CLASSES, B, F, C))
+    a256 = lambda v: (v + 255) // 256 * 256                         # vc_decode_workspace_bytes
+    if a256(B * 4) + a256(B * C * ((F + 3) // 4) * 4) >= 2 ** 31:
+        raise ValueError(' - ERROR, {}: the moves of {} utterances of {} frames x {} classes need 2 GiB or more; decode fewer '
+                         'utterances per call'.format(what, B, F, C))
+
+
+def _check_decode_vec(v, shape, what):
+    """None, or a float32 array / tensor of the given shape (host: values finite or -inf; device: taken as it is)."""
+    import torch
+    if v is None:
+        return None
+    dt = v.dtype if torch.is_tensor(v) else np.asarray(v).dtype
+    if tuple(int(n) for n in getattr(v, 'shape', ())) != shape or dt not in (torch.float32, np.dtype(np.float32)):
+        raise ValueError(' - ERROR, {} must be float32 {}, got {} {}'.format(what, list(shape), dt, list(getattr(v, 'shape', ()))))
+    if torch.is_tensor(v) and v.is_cuda:
+        return v.contiguous()
+    h = np.ascontiguousarray(v.cpu().numpy() if torch.is_tensor(v) else v)
+    if np.isnan(h).any() or (h == np.inf).any():
+        raise ValueError(' - ERROR, {} must be finite or -inf'.format(what))
+    return h
+
+
+def _decode_args(trans, penalty, init, final, min_dur, kind, floor, C, what):
+    fl = _align_kind(kind, floor, what)
+    if isinstance(min_dur, bool) or not isinstance(min_dur, (int, np.integer)) or not 1 <= min_dur <= DECODE_MAX_DUR:
+        raise ValueError(' - ERROR, {}: min_dur must be an integer number of frames in [1, {}], got {!r}'.format(what, DECODE_MAX_DUR, min_dur))
+    pen = float(penalty)
+    if np.isnan(pen) or pen == np.inf:
+        raise ValueError(' - ERROR, {}: penalty must be finite or -inf, got {!r}'.format(what, penalty))
+    return _DECODE_ARGS(_check_decode_vec(trans, (C, C), '{}: trans'.format(what)), pen, _check_decode_vec(init, (C,), '{}: init'.format(what)),
+                        _check_decode_vec(final, (C,), '{}: final'.format(what)), int(min_dur), kind, fl)
+
+
+def _decode_upload(dec):
+    """The host arrays of _decode_args' result go up (pinned, no wait); None stays None."""
+    import torch
+    if dec is None:
+        return None
+    up = lambda v: v if v is None or torch.is_tensor(v) else _pinned_up(v)
+    return dec._replace(trans=up(dec.trans), init=up(dec.init), final=up(dec.final))
+
+
+def _decode_trans(dec, C, device):
+    """The [C, C] matrix the launch takes: filled with ``penalty`` without a trans, else trans + penalty in one float32 add
+    on the device (skipped for 0)."""
+    import torch
+    if dec.trans is None:
+        return torch.full((C, C), dec.penalty, dtype=torch.float32, device=device)
+    return dec.trans + dec.penalty if dec.penalty != 0.0 else dec.trans
+
+
+def _decode_launch(x, d_frames, cmap, dec):
+    """x: cuda, contiguous float32 [B, F, C] posteriors or scores (dec.kind); counts, map and dec's arrays on the device.
+    The two launches of vc_decode_f32 and labels = class_map[frame_class].  No host check in here, nothing waited for."""
+    import torch
+    lib = _vc.lib()
+    B, F, C = x.shape
+    dev = x.device
+    score = torch.log(x.clamp_min(dec.floor)) if dec.kind == 'prob' else x
+    trans = _decode_trans(dec, C, dev)
+    frame_class = torch.empty((B, F), dtype=torch.int32, device=dev)
+    out = torch.empty((3, B, F), dtype=torch.int32, device=dev)
+    n_seg = torch.empty((B,), dtype=torch.int32, device=dev)
+    seg_score = torch.empty((B, F), dtype=torch.float32, device=dev)
+    total = torch.empty((B,), dtype=torch.float32, device=dev)
+    need = lib.vc_decode_workspace_bytes(B, F, C)
+    if need == 0:
+        raise _vc.VCError('vc_decode_workspace_bytes refused {} utterances of {} frames x {} classes'.format(B, F, C))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _vc.check(lib.vc_decode_f32(_vc.ptr(score), _vc.ptr(d_frames), _vc.ptr(trans), _vc.ptr(dec.init), _vc.ptr(dec.final), _vc.ptr(cmap),
+                                B, F, C, dec.min_dur, _vc.ptr(frame_class), _vc.ptr(out[0]), _vc.ptr(out[1]), _vc.ptr(out[2]),
+                                _vc.ptr(n_seg), _vc.ptr(seg_score), _vc.ptr(total), _vc.ptr(ws), need, _vc.current_stream()))
+    labels = frame_class
+    if cmap is not None:
+        labels = torch.where(frame_class >= 0, cmap[frame_class.clamp_min(0).long()], frame_class)
+    return _DECODE(frame_class, labels, _SEG(out[0], out[1], out[2], n_seg), seg_score, total, total > float('-inf'))
+
+
+def _content_sequence(sequence, decode, B, F, C, what):
+    """None for sequence='argmax'; for 'viterbi' the checked arguments of the decoder (decode: a dict or None)."""
+    if sequence not in ('argmax', 'viterbi'):
+        raise ValueError(" - ERROR, {}: sequence must be 'argmax' or 'viterbi', got {!r}".format(what, sequence))
+    if sequence == 'argmax':
+        if decode is not None:
+            raise ValueError(" - ERROR, {}: decode is for sequence='viterbi'".format(what))
+        return None
+    kw = dict(trans=None, penalty=0.0, init=None, final=None, min_dur=3, kind='prob', floor=1e-10)
+    extra = set(decode or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: decode takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(decode or {})
+    _check_decode_size(B, F, C, what)
+    return _decode_args(C=C, what=what, **kw)
+
+
+def decode_batch(ppg, lens, trans=None, penalty=0.0, init=None, final=None, min_dur=3, class_map=None, kind='prob', floor=1e-10):
+    """Phoneme recognition of B utterances (vc_decode_f32; the definition is in include/vc_hip.h, "Decoding"): the best path
+    through a loop of all C classes, with a transition score between two phonemes and at least ``min_dur`` frames per
+    phoneme -- a path decision where phn_segments_batch takes the arg-max of every frame and cleans up afterwards.
+    ppg [B, F_max, C] float32 (cuda tensor or numpy array): posteriors (kind='prob': the scores are
+    torch.log(ppg.clamp_min(floor)), taken on the device) or ready scores (kind='log': passed through; finite or -inf).
+    lens: the frame counts, host integers in [0, F_max] or an int32 [B] device tensor.  trans [C, C] float32: trans[i, j] is
+    added where a phoneme i ends and a phoneme j begins (phn_transitions builds one from label sequences; i == j: the phoneme
+    said twice); None: a matrix filled with ``penalty``; otherwise ``penalty`` (an insertion penalty, <= 0 for fewer
+    segments) is added to it on the device.  init, final [C] float32 or None: added at the first / last frame.  class_map:
+    None or C integers in [-1, C) (evaluation.class_map).  C <= 128, min_dur in [1, 8], B <= 65,535, F_max <= 16,384.
+    Nothing is copied back and the host waits for nothing.  Returns a namedtuple of device tensors: frame_class [B, F_max]
+    int32 (the decoded class of every frame; -1 from the count on and for an utterance without a path), labels =
+    class_map[frame_class] (-1 kept), seg (labels, start, end [B, F_max] and n_seg [B], as phn_segments_batch returns
+    them, so edit_distance_batch takes them: the decoded segments mapped, equal neighbours merged, -1 dropped), seg_score
+    [B, F_max] float32 (the mean score of a segment's frames; NaN from n_seg on), total [B] float32 and feasible [B] bool."""
+    import torch
+    B, F, C = _check_align_ppg(ppg, 'decode_batch: ppg')
+    _check_decode_size(B, F, C, 'decode_batch')
+    dec = _decode_args(trans, penalty, init, final, min_dur, kind, floor, C, 'decode_batch')
+    nf = _check_counts(lens, B, 0, F, 'decode_batch: lens')
+    cmap = _check_class_map(class_map, C, 'decode_batch')
+    _need_gpu('decode_batch')
+    d_frames, = _upload_mixed(nf)
+    return _decode_launch(_to_device(ppg, torch.float32), d_frames, _cmap_device(cmap), _decode_upload(dec))
+
+
+def decode_wav_batch(encoder, wav, lens, cfg_d, wav_sr=None, res_type='kaiser_best', trans=None, penalty=0.0, init=None, final=None,
+                     min_dur=3, class_map=None, floor=1e-10, window_batch=64, ppg=None):
+    """Phoneme recognition of B WAVEFORMS.  encoder: the phoneme recogniser (encoder.encoder_spec_phn).  The posteriors are
+    those of content_wav_batch and align_wav_batch (_content_side with t_s = 0, t_e = 60 and two passes), i.e. exactly
+    convert_batch's phn_pred; ppg: such posteriors [B, Fout, n_phn] that are already there.  Only frames that come from the
+    waveform are decoded.  The other arguments as in decode_batch, which this ends in (kind='prob').  Returns decode_batch's
+    fields, then ppg [B, Fout, n_phn] and n_frames (int32 [B]), on the device."""
+    import torch
+    import audio_lib
+    import conversion
+    what = 'decode_wav_batch'
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    audio_lib._res_params(res_type)
+    a = _wav_side(wav, lens, cfg_d, wav_sr, 'wav')
+    B = a['B']
+    window_batch = int(window_batch)
+    if window_batch <= 0:
+        raise ValueError(' - ERROR, {}: window_batch must be positive'.format(what))
+    plan = conversion.convert_plan(a['h'], cfg_d, 0, 60, True)
+    C = int(encoder.cfg_d['n_output'])
+    _check_decode_size(B, plan.Fout, C, what)
+    if ppg is not None:
+        if _check_align_ppg(ppg, '{}: ppg'.format(what)) != (B, plan.Fout, C):
+            raise ValueError(' - ERROR, {}: ppg must be [{}, {}, {}], as convert_batch returns phn_pred for wav'.format(what, B, plan.Fout, C))
+    dec = _decode_args(trans, penalty, init, final, min_dur, 'prob', floor, C, what)
+    cmap = _check_class_map(class_map, C, what)
+    h_l = np.minimum(plan.n_out, plan.n_clip - plan.n_s)
+    if h_l.min() < 1:
+        raise ValueError(' - ERROR, {}: every utterance needs at least one frame of its own'.format(what))
+    _need_gpu(what)
+    d_in, d_len, d_clip, d_win, d_utt, d_true, d_l = _upload_lens(a['h_in'], a['h'], plan.n_clip, plan.win_tab, plan.utt_tab,
+                                                                  plan.true_tab, h_l)
+    if ppg is not None:
+        ppg = _to_device(ppg, torch.float32)
+    _, _, ppg = _content_side(encoder, wav, a, plan, (d_in, d_len, d_clip, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)),
+                              cfg_d, res_type, window_batch, ppg)
+    r = _decode_launch(ppg.contiguous(), d_l, _cmap_device(cmap), _decode_upload(dec))
+    return _DECODE_WAV(*r, ppg, d_l)
+
+
+def phn_transitions(seqs, n_seq, n_classes, add=1.0, scale=1.0, allow_repeat=False):
+    """A transition matrix for decode_batch from label sequences (host numpy): seqs [N, S] integers in [0, n_classes), n_seq
+    [N] their counts.  count[i, j] is the number of times j follows i; the result is
+    scale * log((count[i, j] + add) / (row_total[i] + add * C)), float32 [C, C]: with add > 0 every row of exp(result / scale)
+    sums to 1.  allow_repeat=False sets the diagonal to -inf: no phoneme follows itself, so a decoded path is determined by
+    its frames' classes."""
+    C = int(n_classes)
+    seqs, n_seq = np.asarray(seqs), np.asarray(n_seq).reshape(-1)
+    if C < 1 or seqs.ndim != 2 or seqs.dtype.kind not in 'iu' or n_seq.shape != (seqs.shape[0],) or n_seq.dtype.kind not in 'iu':
+        raise ValueError(' - ERROR, phn_transitions: seqs must be integers [N, S], n_seq integers [N] and n_classes positive')
+    if len(n_seq) and (n_seq.min() < 0 or n_seq.max() > seqs.shape[1]):
+        raise ValueError(' - ERROR, phn_transitions: n_seq must lie in [0, {}]'.format(seqs.shape[1]))
+    add, scale = float(add), float(scale)
+    if not (np.isfinite(add) and add >= 0.0 and np.isfinite(scale)):
+        raise ValueError(' - ERROR, phn_transitions: add must be finite and >= 0, scale finite')
+    pair = np.arange(seqs.shape[1] - 1)[None, :] < (n_seq[:, None] - 1) if seqs.shape[1] > 1 else np.zeros((len(seqs), 0), bool)
+    i, j = seqs[:, :-1][pair].astype(np.int64), seqs[:, 1:][pair].astype(np.int64)
+    if len(i) and (min(i.min(), j.min()) < 0 or max(i.max(), j.max()) >= C):
+        raise ValueError(' - ERROR, phn_transitions: seqs must hold classes in [0, {})'.format(C))
+    count = np.zeros((C, C), np.float64)
+    np.add.at(count, (i, j), 1.0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out = scale * np.log((count + add) / (count.sum(1, keepdims=True) + add * C))
+    if not allow_repeat:
+        out[np.arange(C), np.arange(C)] = -np.inf
+    return out.astype(np.float32)
 
 
 def alignment_min_frames(hop_length, win_length):
