@@ -5,8 +5,9 @@
 //
 // Why a second kernel: the 128 x 128 / 4-wave structure reads one ds_read_b128 per MFMA, which
 // saturates the CU's LDS port at ~41 % of the matrix peak.  Here every wave
-// owns a 128 x 64 accumulator (128 VGPRs), so 24 fragment reads feed 32 MFMAs (LDS port 75 % busy
-// at full MFMA rate), and operands reach LDS by global_load_lds (no staging registers).
+// owns a 128 x 64 accumulator (128 VGPRs), so 24 fragment reads feed a 64-channel K tile's MFMAs (32 of
+// 32x32x16 or 64 of 16x16x32: LDS port 75 % busy at full MFMA rate), and operands reach LDS by
+// global_load_lds (no staging registers).
 //
 // Work decomposition: filter widths come in pairs (2p+1, 2p+2) that share TF's SAME left padding
 // (p), so tap j of both reads the same shifted activation rows; a block computes 256 frames x
@@ -15,18 +16,31 @@
 //      buffered across slabs); tap j's fragments are the same image read j rows further down,
 //   B  per (slab, tap) a 256 x 64 weight tile (left half = narrower filter; absent at its
 //      missing last tap), double buffered, fetched one full tile ahead,
-//   one barrier per tile, placed before the LAST k-step of a tile: by then every wave has retired
+//   one barrier per tile, placed before the LAST HALF k-step of a tile: by then every wave has retired
 //      its reads of the tile (so its buffer may be refilled) and the next tile's loads, issued one
 //      tile earlier, are waited for with vmcnt(0) -- nobody waits at the tile boundary itself.
-// LDS rows are 128 B; the 16-byte slot of row r is XORed with (r >> 1) & 7, applied on the SOURCE
-// address of the LDS-direct loads (the LDS image of one wave instruction is linear), so the 16
-// lanes of a ds_read_b128 group hit 16 different bank groups.  SAME-padding zeros depend on
-// (output frame, tap) and are a per-lane select on the A fragment.
+// The matrix instruction is v_mfma_f32_16x16x32_bf16: a K tile of 64 channels is two k = 32 steps, a wave's
+// 128 x 64 tile is 8 x 4 accumulators of 16 frames x 16 channels, and lane l holds row l & 15 and the eight
+// channels of 16-byte slot (l >> 4) + 4 * step of its 128-byte row.  Per step: 8 activation + 4 weight
+// fragments (12 ds_read_b128) feed 32 MFMAs, the same LDS bytes per FLOP as on 32x32x16 (conv_kernel).
+// Only 12 fragments are live: the weights of a step are held for the step, the activations are
+// double-buffered by half steps (4 frame tiles), and within a half the channel tile is the outer loop, so
+// that weight fragment c is dead after the second half's c-th group and is refilled for the next step there.
+// LDS rows are 128 B; the 16-byte slot of row r is XORed with vc::slot_key16(r) = ((r >> 1) & 3) << 1, applied on the SOURCE
+// address of the LDS-direct loads (the LDS image of one wave instruction is linear).  A ds_read_b128 is
+// served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32); with this
+// lane map a group holds 8 rows x 2 adjacent slots, and the key (which leaves slot bit 0 alone and gives the
+// four row pairs of an aligned 8-row block four different values on slot bits 1-2) sends its 16 lanes to 16
+// different bank groups for every tap offset and both steps; the weight reads are the tap-0 case.  (By the same
+// count the key (r >> 1) & 7 of the 32-lane map is 2-way conflicted here at every tap offset that is no multiple of 4.)
+// The epilogue tile (528-byte pitch, 8-byte writes at frame l & 15, channel 4 * (l >> 4)) is conflict-free:
+// 16 rows x 4 banks apart, the lane quarters 2 banks apart.  SAME-padding zeros depend on (output frame, tap)
+// and are a per-lane select on the A fragment.
 #include <cstdlib>
 #include "vc_device.h"
 #include "vc_bank256.h"
 
-using vc::f32x16, vc::f32x4, vc::bf16x8, vc::bf16x4, vc::u32x4;
+using vc::f32x4, vc::bf16x8, vc::bf16x4, vc::u32x4;
 
 namespace {
 
@@ -93,7 +107,7 @@ bank256_kernel(Bank256Args a) {
     for (int q = 0; q < 5; ++q) {
         const int rho = (q * 8 + wid) * 8 + srow;
         const int g = min(max(m0 - pad_l + rho, 0), a.M - 1);
-        const int slot = pslot ^ ((rho >> 1) & 7);
+        const int slot = pslot ^ vc::slot_key16(rho);
         a_src[q] = X + (size_t)g * a.ldx + slot * 8 + cs0 * 64;
     }
     const int a_rows_needed = BM + ntap - 1;           // rows >= this are never read
@@ -102,7 +116,7 @@ bank256_kernel(Bank256Args a) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int n = (q * 8 + wid) * 8 + srow;
-        const int slot = pslot ^ ((n >> 1) & 7);
+        const int slot = pslot ^ vc::slot_key16(n);
         const bool left = n < 128;
         const __bf16* Bt = reinterpret_cast<const __bf16*>(left ? pr.Bt0 : pr.Bt1);
         const int K = (left ? pr.taps0 : ntap) * a.Cin;
@@ -131,50 +145,59 @@ bank256_kernel(Bank256Args a) {
     };
 
     // ---------------- MFMA roles
-    const int li = lane & 31, lh = lane >> 5;
-    // A fragment (row tile i, k-step s, tap j): LDS row rho = wr*128 + i*32 + li + j, slot (2s+lh) ^ ((rho>>1)&7)
+    const int li = lane & 15, lq = lane >> 4;
+    // A fragment (frame tile i, step s, tap j): LDS row rho = wr*128 + i*16 + li + j, slot (lq + 4s) ^ key(rho)
+    // (key = vc::slot_key16 does not depend on i)
     const int a_row0 = wr * 128 + li;
-    // B fragment (col tile c, k-step s): row n = wc*64 + c*32 + li; (n>>1)&7 = (li>>1)&7
-    const int xb = (li >> 1) & 7;
-    int b_off[4];
+    // B fragment (channel tile c, step s): row n = wc*64 + c*16 + li; key(n) = key(li)
+    const int xb = vc::slot_key16(li);
+    int b_off[2];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) b_off[s] = (wc * 64 + li) * 128 + (((2 * s + lh) ^ xb) << 4);
-    int jlo[4], jhi[4];
+    for (int s = 0; s < 2; ++s) b_off[s] = (wc * 64 + li) * 128 + (((lq + 4 * s) ^ xb) << 4);
+    // SAME padding: tap j of frame tile i reads a real frame iff 0 <= tp[i] + j < T (tp = position in the window - pad_l)
+    int tp[8];
+    int J_lo = 0, J_hi = 0x7fffffff;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) vc::same_tap_range(min(m0 + wr * 128 + i * 32 + li, a.M - 1), a.T, pad_l, jlo[i], jhi[i]);
+    for (int i = 0; i < 8; ++i) {
+        int lo, hi;
+        vc::same_tap_range(min(m0 + wr * 128 + i * 16 + li, a.M - 1), a.T, pad_l, lo, hi);
+        tp[i] = a.T - hi;
+        J_lo = max(J_lo, lo);
+        J_hi = min(J_hi, hi);
+    }
     const bool left_wave = wc < 2;
     // taps [J_lo, J_hi) need no select anywhere in this wave (wave-uniform: scalar branch per tile)
-    int J_lo = max(max(jlo[0], jlo[1]), max(jlo[2], jlo[3]));
-    int J_hi = min(min(jhi[0], jhi[1]), min(jhi[2], jhi[3]));
     vc::wave_tap_range(J_lo, J_hi);
     if (left_wave) J_hi = min(J_hi, pr.taps0);
 
-    f32x16 acc[4][2];
+    f32x4 acc[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][c][r] = 0.0f;
+            for (int r = 0; r < 4; ++r) acc[i][c][r] = 0.0f;
 
-    bf16x8 fa[2][4], fb[2][2];
-    int a_base = 0, a_o[4];                             // per-tap A addressing
+    bf16x8 fa[2][4], fb[4];                             // activations by half step, weights of the step
+    int a_base = 0, a_o[2];                             // per-tap A addressing
     auto tap_setup = [&](int n) {
         const int cs = n / ntap, j = n - cs * ntap;
         const int rho = a_row0 + j;
-        const int x = (rho >> 1) & 7;
+        const int x = vc::slot_key16(rho);
         a_base = (cs & 1) * A_BYTES + rho * 128;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) a_o[s] = ((2 * s + lh) ^ x) << 4;
+        for (int s = 0; s < 2; ++s) a_o[s] = ((lq + 4 * s) ^ x) << 4;
         return j;
     };
-    auto load_frags = [&](int set, int s, int bbuf) {
-        const char* ap = As + a_base + a_o[s];
+    // a tile's first fragments: the first half's activations and weight fragments 0..2 of step 0 (fragment 3 is read after
+    // every step's first group: the previous step's last group has released its registers by then)
+    auto load_first = [&](int bbuf) {
+        const char* ap = As + a_base + a_o[0];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fa[set][i] = *reinterpret_cast<const bf16x8*>(ap + i * 4096);
-        const char* bp = Bs + bbuf * B_BYTES + b_off[s];
-        fb[set][0] = *reinterpret_cast<const bf16x8*>(bp);
-        fb[set][1] = *reinterpret_cast<const bf16x8*>(bp + 4096);
+        for (int i = 0; i < 4; ++i) fa[0][i] = *reinterpret_cast<const bf16x8*>(ap + i * 2048);
+        const char* bp = Bs + bbuf * B_BYTES + b_off[0];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) fb[c] = *reinterpret_cast<const bf16x8*>(bp + c * 2048);
     };
 
     // ---------------- prologue
@@ -191,12 +214,9 @@ bank256_kernel(Bank256Args a) {
     if (ntiles > 1) stageB(1, 1);
     if (nslab > 1) stageA(1, 1);
     int j = tap_setup(0);
-    load_frags(0, 0, 0);
+    load_first(0);
 
-#ifndef B256_RP
-#define B256_RP 2        // fragment-read placement: 0 = ahead of the step's MFMAs, 1 = between them, 2 = pinned after 2 MFMAs
-#endif
-    // one K tile (4 k-steps of 8 MFMAs); MASK = some row of this wave sees SAME padding at this tap
+    // one K tile (2 k-steps of 32 MFMAs); MASK = some row of this wave sees SAME padding at this tap
     auto tile = [&](int n, const bool need_mask) {
         const bool active = !(left_wave && j >= pr.taps0);     // the narrower filter has no tap taps0
         if (!active) {
@@ -209,22 +229,53 @@ bank256_kernel(Bank256Args a) {
                 const int cs1 = (n + 1) / ntap;
                 if ((n + 1) - cs1 * ntap == 0 && cs1 + 1 < nslab) stageA(cs1 + 1, (cs1 + 1) & 1);
                 j = tap_setup(n + 1);
-                load_frags(0, 0, (n + 1) & 1);
+                load_first((n + 1) & 1);
             }
             return;
         }
-        bool v[4];
+        bool v[8];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = j >= jlo[i] && j < jhi[i];
+        for (int i = 0; i < 8; ++i) v[i] = (unsigned)(tp[i] + j) < (unsigned)a.T;
         const bf16x8 zero = {};
         int jn = j;
+        // group c of a half: the 4 frame tiles of the half against weight fragment c
+#define B256_GROUP(h, c)                                                                                               \
+        acc[4 * (h) + 0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[c], fa[h][0], acc[4 * (h) + 0][c], 0, 0, 0);   \
+        acc[4 * (h) + 1][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[c], fa[h][1], acc[4 * (h) + 1][c], 0, 0, 0);   \
+        acc[4 * (h) + 2][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[c], fa[h][2], acc[4 * (h) + 2][c], 0, 0, 0);   \
+        acc[4 * (h) + 3][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[c], fa[h][3], acc[4 * (h) + 3][c], 0, 0, 0)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int cur = s & 1, nxt = cur ^ 1;
+        for (int s = 0; s < 2; ++s) {
             bool have_next = true;
             int nb = n & 1;
-            if (s == 3) {
-                // every read of tile n has been issued; retire them, publish tile n+1, recycle tile n's buffer
+            // ---- first half: frame tiles 0..3; the second half's activations arrive under it
+            const char* ap = As + a_base + a_o[s] + 4 * 2048;
+            if (need_mask) {                                   // wave-uniform: scalar branch around 16 selects
+#pragma unroll
+                for (int i = 0; i < 4; ++i) fa[0][i] = v[i] ? fa[0][i] : zero;
+            }
+            __builtin_amdgcn_s_setprio(1);
+            B256_GROUP(0, 0);
+            fb[3] = *reinterpret_cast<const bf16x8*>(Bs + nb * B_BYTES + b_off[s] + 3 * 2048);
+            fa[1][0] = *reinterpret_cast<const bf16x8*>(ap);
+            fa[1][1] = *reinterpret_cast<const bf16x8*>(ap + 2048);
+            B256_GROUP(0, 1);
+            fa[1][2] = *reinterpret_cast<const bf16x8*>(ap + 2 * 2048);
+            fa[1][3] = *reinterpret_cast<const bf16x8*>(ap + 3 * 2048);
+            B256_GROUP(0, 2);
+            B256_GROUP(0, 3);
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+            __builtin_amdgcn_s_setprio(0);
+            // ---- second half: frame tiles 4..7; the next step's first-half activations and weight fragments 0..2 arrive
+            // under it, each weight fragment once its group is through
+            if (s == 1) {
+                // every read of tile n has been issued; retire them, publish tile n+1, recycle tile n's buffer.  (The
+                // barrier stands in the MIDDLE of the tile's last step: the second half's activations are read under the
+                // first half, and the slab they come from may be the one stageA refills below.)
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __syncthreads();
                 if (n + 2 < ntiles) stageB(n + 2, n & 1);
@@ -237,84 +288,39 @@ bank256_kernel(Bank256Args a) {
                 }
                 nb = (n + 1) & 1;
             }
-            const int sn = (s + 1) & 3;
-            const char* ap = As + a_base + a_o[sn];
-            const char* bp = Bs + nb * B_BYTES + b_off[sn];
-            if (need_mask) {                                   // wave-uniform: scalar branch around 16 selects
+            const int sn = s ^ 1;
+            const char* an = As + a_base + a_o[sn];
+            const char* bn = Bs + nb * B_BYTES + b_off[sn];
+            if (need_mask) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) fa[cur][i] = v[i] ? fa[cur][i] : zero;
+                for (int i = 0; i < 4; ++i) fa[1][i] = v[4 + i] ? fa[1][i] : zero;
             }
-            bf16x8* av = fa[cur];
-#if B256_RP == 0
-            if (have_next) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) fa[nxt][i] = *reinterpret_cast<const bf16x8*>(ap + i * 4096);
-                fb[nxt][0] = *reinterpret_cast<const bf16x8*>(bp);
-                fb[nxt][1] = *reinterpret_cast<const bf16x8*>(bp + 4096);
-            }
-#endif
             __builtin_amdgcn_s_setprio(1);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][0], av[0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][1], av[0], acc[0][1], 0, 0, 0);
-#if B256_RP != 0
+            B256_GROUP(1, 0);
             if (have_next) {
-                fa[nxt][0] = *reinterpret_cast<const bf16x8*>(ap);
-                fa[nxt][1] = *reinterpret_cast<const bf16x8*>(ap + 4096);
+                fa[0][0] = *reinterpret_cast<const bf16x8*>(an);
+                fa[0][1] = *reinterpret_cast<const bf16x8*>(an + 2048);
+                fb[0] = *reinterpret_cast<const bf16x8*>(bn);
             }
-#endif
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][0], av[1], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][1], av[1], acc[1][1], 0, 0, 0);
-#if B256_RP != 0
+            B256_GROUP(1, 1);
             if (have_next) {
-                fa[nxt][2] = *reinterpret_cast<const bf16x8*>(ap + 2 * 4096);
-                fa[nxt][3] = *reinterpret_cast<const bf16x8*>(ap + 3 * 4096);
+                fa[0][2] = *reinterpret_cast<const bf16x8*>(an + 2 * 2048);
+                fa[0][3] = *reinterpret_cast<const bf16x8*>(an + 3 * 2048);
+                fb[1] = *reinterpret_cast<const bf16x8*>(bn + 2048);
             }
-#endif
-            acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][0], av[2], acc[2][0], 0, 0, 0);
-            acc[2][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][1], av[2], acc[2][1], 0, 0, 0);
-#if B256_RP != 0
-            if (have_next) {
-                fb[nxt][0] = *reinterpret_cast<const bf16x8*>(bp);
-                fb[nxt][1] = *reinterpret_cast<const bf16x8*>(bp + 4096);
-            }
-#endif
-            acc[3][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][0], av[3], acc[3][0], 0, 0, 0);
-            acc[3][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][1], av[3], acc[3][1], 0, 0, 0);
-#if B256_RP == 2
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);
-#elif B256_RP == 3      // two reads per MFMA gap
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
-#elif B256_RP == 4      // reads in two groups of three
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            B256_GROUP(1, 2);
+            if (have_next) fb[2] = *reinterpret_cast<const bf16x8*>(bn + 2 * 2048);
+            B256_GROUP(1, 3);
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-#elif B256_RP == 5      // one read per gap
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#endif
+            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             __builtin_amdgcn_s_setprio(0);
         }
+#undef B256_GROUP
         j = jn;
     };
     for (int n = 0; n < ntiles; ++n) {
@@ -322,8 +328,8 @@ bank256_kernel(Bank256Args a) {
     }
 
     // ---------------- epilogue: BatchNorm scale/shift + activation -> bf16 tile in LDS -> full-row stores
-    // The weights are the MFMA's first operand, so a lane holds ONE frame (row li of the 32 x 32
-    // tile) and, per register quad q, 4 consecutive channels 8q + 4lh + {0..3}: 8-byte LDS writes.
+    // The weights are the MFMA's first operand, so a lane holds ONE frame (row li of the 16 x 16
+    // tile) and, per accumulator, 4 consecutive channels 4lq + {0..3}: 8-byte LDS writes.
     constexpr int EP = 528;                            // LDS row pitch of the [256][256] bf16 tile
     __syncthreads();                                   // all fragment reads retired; no load in flight
     if (a.ksplit > 1) {
@@ -338,7 +344,7 @@ bank256_kernel(Bank256Args a) {
         if (tid == 0) tsh[0] = (int)__hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         const int ticket = __builtin_amdgcn_readfirstlane(tsh[0]);
-        const int voff = (wid * 32 * 64 + lane) * 16;              // + ((i*2 + c)*4 + q) * 1024
+        const int voff = (wid * 32 * 64 + lane) * 16;              // + (i*4 + c) * 1024
         float* const slab0 = a.ws + (size_t)rt * (a.ksplit - 1) * 65536;
         if (ticket < a.ksplit - 1) {
             const uintptr_t base = (uintptr_t)(slab0 + (size_t)ticket * 65536);
@@ -348,15 +354,11 @@ bank256_kernel(Bank256Args a) {
             const unsigned b_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32));
             const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)b_hi << 32) | (uintptr_t)b_lo), 0, 262144, 0x00020000);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 8; ++i)
 #pragma unroll
-                for (int c = 0; c < 2; ++c)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 v = {acc[i][c][4 * q], acc[i][c][4 * q + 1], acc[i][c][4 * q + 2], acc[i][c][4 * q + 3]};
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs,
-                                                               voff + ((i * 2 + c) * 4 + q) * 1024, 0, 16);     // aux 16 = sc1
-                    }
+                for (int c = 0; c < 4; ++c)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][c]), rs,
+                                                           voff + (i * 4 + c) * 1024, 0, 16);                   // aux 16 = sc1
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // EVERY storing wave drains
             __syncthreads();
             if (tid == 0) __hip_atomic_fetch_add(tk + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -376,40 +378,34 @@ bank256_kernel(Bank256Args a) {
             const __attribute__((address_space(1))) char* sp =
                 (const __attribute__((address_space(1))) char*)(uintptr_t)(slab0 + (size_t)sl * 65536) + voff;
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 8; ++i)
 #pragma unroll
-                for (int c = 0; c < 2; ++c)
+                for (int c = 0; c < 4; ++c) {
+                    const f32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>(sp + (i * 4 + c) * 1024);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const f32x4 v = *reinterpret_cast<const __attribute__((address_space(1))) f32x4*>(sp + ((i * 2 + c) * 4 + q) * 1024);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[i][c][4 * q + e] += v[e];
-                    }
+                    for (int e = 0; e < 4; ++e) acc[i][c][e] += v[e];
+                }
         }
         __syncthreads();                               // tsh[0] was read by every wave before the tile is written over it
     }
     {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
+        for (int c = 0; c < 4; ++c) {
+            const int chp = wc * 64 + c * 16 + 4 * lq;                         // channel within the pair = column of the tile
+            const float4 sv = *reinterpret_cast<const float4*>(smem + COEF_OFF + chp * 4);
+            const float4 bv = *reinterpret_cast<const float4*>(smem + COEF_OFF + 1024 + chp * 4);
+            const float svv[4] = {sv.x, sv.y, sv.z, sv.w}, bvv[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int chp = wc * 64 + c * 32 + 8 * q + 4 * lh;             // channel within the pair
-                const float4 sv = *reinterpret_cast<const float4*>(smem + COEF_OFF + chp * 4);
-                const float4 bv = *reinterpret_cast<const float4*>(smem + COEF_OFF + 1024 + chp * 4);
-                const float svv[4] = {sv.x, sv.y, sv.z, sv.w}, bvv[4] = {bv.x, bv.y, bv.z, bv.w};
+            for (int i = 0; i < 8; ++i) {
+                bf16x4 o;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    bf16x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float val = acc[i][c][4 * q + e] * svv[e] + bvv[e];
-                        if (a.act == VC_ACT_RELU) val = fmaxf(val, 0.0f);
-                        o[e] = (__bf16)val;
-                    }
-                    const int row = wr * 128 + i * 32 + li;
-                    const int col = wc * 64 + c * 32 + 8 * q + 4 * lh;             // column of the 256-wide pair tile
-                    *reinterpret_cast<bf16x4*>(smem + row * EP + col * 2) = o;
+                for (int e = 0; e < 4; ++e) {
+                    float val = acc[i][c][e] * svv[e] + bvv[e];
+                    if (a.act == VC_ACT_RELU) val = fmaxf(val, 0.0f);
+                    o[e] = (__bf16)val;
                 }
+                const int row = wr * 128 + i * 16 + li;
+                *reinterpret_cast<bf16x4*>(smem + row * EP + chp * 2) = o;
             }
         }
     }

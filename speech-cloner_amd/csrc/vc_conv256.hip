@@ -7,7 +7,9 @@
 // tiles, activation tile (128 + taps - 1 [+1] rows of one 64-channel slab) resident across the taps
 // and double-buffered across slabs, weight tile per (slab, tap) double-buffered one tile ahead, one
 // barrier per tile before its last k-step, weights as the first MFMA operand (lane = frame), the
-// output tile through LDS into whole-row stores.  Differences:
+// output tile through LDS into whole-row stores; v_mfma_f32_16x16x32_bf16 with its lane map (row l & 15,
+// 16-byte slot (l >> 4) + 4 * step) and the conflict-free swizzle key vc::slot_key16 derived there: a K
+// tile is two k = 32 steps of 16 MFMAs, both steps' fragments double-buffered whole.  Differences:
 //   * one filter, N a multiple of 128: 2 x WN waves (WN = 2: 128 columns, 4 waves, two blocks per
 //     CU; WN = 4: 256 columns, 8 waves), 64 x 64 accumulators per wave;
 //   * POOL: tf.layers.max_pooling1d(pool_size=2, strides=1, padding='same') of the operand is taken
@@ -19,7 +21,7 @@
 #include "vc_conv256.h"
 #include <cstdlib>
 
-using vc::f32x16, vc::bf16x8, vc::bf16x4;
+using vc::f32x4, vc::bf16x8, vc::bf16x4;
 
 namespace {
 
@@ -64,14 +66,14 @@ conv256_kernel(Conv256Args a) {
     for (int q = 0; q < AQ; ++q) {
         const int rho = (q * NWAVE + wid) * 8 + srow;
         const int g = min(max(m0 - pad_l + rho, 0), a.M - 1);
-        a_src[q] = X + (size_t)g * a.ldx + (pslot ^ ((rho >> 1) & 7)) * 8;
+        a_src[q] = X + (size_t)g * a.ldx + (pslot ^ vc::slot_key16(rho)) * 8;
     }
     const int a_rows_needed = BM + ntap - 1 + (POOL ? 1 : 0);
     const __bf16* b_src[BQ];
 #pragma unroll
     for (int q = 0; q < BQ; ++q) {
         const int n = (q * NWAVE + wid) * 8 + srow;
-        b_src[q] = Bt + (size_t)min(n0 + n, a.N - 1) * a.K + (pslot ^ ((n >> 1) & 7)) * 8;
+        b_src[q] = Bt + (size_t)min(n0 + n, a.N - 1) * a.K + (pslot ^ vc::slot_key16(n)) * 8;
     }
     auto stageA = [&](int cs, int buf) {
         char* dst = As + buf * A_BYTES + wid * 1024;
@@ -90,17 +92,17 @@ conv256_kernel(Conv256Args a) {
     };
 
     // ---------------- MFMA roles
-    const int li = lane & 31, lh = lane >> 5;
+    const int li = lane & 15, lq = lane >> 4;
     const int a_row0 = wr * 64 + li;
-    const int xb = (li >> 1) & 7;
-    int b_off[4];
+    const int xb = vc::slot_key16(li);
+    int b_off[2];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) b_off[s] = (wc * 64 + li) * 128 + (((2 * s + lh) ^ xb) << 4);
-    int jlo[2], jhi[2];                                // taps [jlo, jhi) read a real frame, and taps < jhi - 1 a real NEXT frame (pool partner)
+    for (int s = 0; s < 2; ++s) b_off[s] = (wc * 64 + li) * 128 + (((lq + 4 * s) ^ xb) << 4);
+    int jlo[4], jhi[4];                                // taps [jlo, jhi) read a real frame, and taps < jhi - 1 a real NEXT frame (pool partner)
 #pragma unroll
-    for (int i = 0; i < 2; ++i) vc::same_tap_range(min(m0 + wr * 64 + i * 32 + li, a.M - 1), a.T, pad_l, jlo[i], jhi[i]);
-    int J_lo = max(jlo[0], jlo[1]);
-    int J_hi = min(jhi[0], jhi[1]) - (POOL ? 1 : 0);
+    for (int i = 0; i < 4; ++i) vc::same_tap_range(min(m0 + wr * 64 + i * 16 + li, a.M - 1), a.T, pad_l, jlo[i], jhi[i]);
+    int J_lo = max(max(jlo[0], jlo[1]), max(jlo[2], jlo[3]));
+    int J_hi = min(min(jhi[0], jhi[1]), min(jhi[2], jhi[3])) - (POOL ? 1 : 0);
     // vc::wave_tap_range spelled out: through the helper the compiler orders this kernel's prologue differently
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -110,27 +112,27 @@ conv256_kernel(Conv256Args a) {
     J_lo = __builtin_amdgcn_readfirstlane(J_lo);
     J_hi = __builtin_amdgcn_readfirstlane(J_hi);
 
-    f32x16 acc[2][2];
+    f32x4 acc[4][4];                                    // [frame tile of 16][channel tile of 16]
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][c][r] = 0.0f;
+            for (int r = 0; r < 4; ++r) acc[i][c][r] = 0.0f;
 
-    bf16x8 fa[2][2], fp[2][2], fb[2][2];
-    int a_base = 0, a_o[4], p_base = 0, p_o[4];
+    bf16x8 fa[2][4], fp[2][4], fb[2][4];
+    int a_base = 0, a_o[2], p_base = 0, p_o[2];
     int j = 0;
     auto tap_setup = [&](int n) {
         const int cs = n / ntap, jj = n - cs * ntap;
         const int rho = a_row0 + jj;
         a_base = (cs & 1) * A_BYTES + rho * 128;
         p_base = a_base + 128;
-        const int x = (rho >> 1) & 7, xp = ((rho + 1) >> 1) & 7;
+        const int x = vc::slot_key16(rho), xp = vc::slot_key16(rho + 1);
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            a_o[s] = ((2 * s + lh) ^ x) << 4;
-            p_o[s] = ((2 * s + lh) ^ xp) << 4;
+        for (int s = 0; s < 2; ++s) {
+            a_o[s] = ((lq + 4 * s) ^ x) << 4;
+            p_o[s] = ((lq + 4 * s) ^ xp) << 4;
         }
         return jj;
     };
@@ -168,34 +170,32 @@ conv256_kernel(Conv256Args a) {
     j = tap_setup(0);
     {
         const char* ap = As + a_base + a_o[0];
-        fa[0][0] = *reinterpret_cast<const bf16x8*>(ap);
-        fa[0][1] = *reinterpret_cast<const bf16x8*>(ap + 4096);
-        if constexpr (POOL) {
-            const char* pp = As + p_base + p_o[0];
-            fp[0][0] = *reinterpret_cast<const bf16x8*>(pp);
-            fp[0][1] = *reinterpret_cast<const bf16x8*>(pp + 4096);
-        }
+        const char* pp = As + p_base + p_o[0];
         const char* bp = Bs + b_off[0];
-        fb[0][0] = *reinterpret_cast<const bf16x8*>(bp);
-        fb[0][1] = *reinterpret_cast<const bf16x8*>(bp + 4096);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            fa[0][i] = *reinterpret_cast<const bf16x8*>(ap + i * 2048);
+            if constexpr (POOL) fp[0][i] = *reinterpret_cast<const bf16x8*>(pp + i * 2048);
+            fb[0][i] = *reinterpret_cast<const bf16x8*>(bp + i * 2048);
+        }
     }
 
     for (int n = 0; n < ntiles; ++n) {
         const bool need_mask = !(j >= J_lo && j < J_hi);        // wave-uniform
-        bool v[2], hn[2];
+        bool v[4], hn[4];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 4; ++i) {
             v[i] = j >= jlo[i] && j < jhi[i];
             hn[i] = j < jhi[i] - 1;
         }
         const bf16x8 zero = {};
         int jn = j;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int cur = s & 1, nxt = cur ^ 1;
+        for (int s = 0; s < 2; ++s) {
+            const int cur = s, nxt = cur ^ 1;
             bool have_next = true;
             int nb = bcur;
-            if (s == 3) {
+            if (s == 1) {
                 // every read of tile n is issued: retire them, publish tile n+1 (tiles n+2 .. n+DIST
                 // stay in flight), recycle tile n's buffer for tile n+1+DIST
                 wait_loads_but(BQ * max(0, min(keep, tail0 - n)));
@@ -210,38 +210,38 @@ conv256_kernel(Conv256Args a) {
                 if (n + 1 + DIST < ntiles) stageB(n + 1 + DIST, bcur);
                 nb = bcur + 1 == NBUF ? 0 : bcur + 1;
             }
-            const int sn = (s + 1) & 3;
+            const int sn = s ^ 1;
             const char* ap = As + a_base + a_o[sn];
             const char* pp = As + p_base + p_o[sn];
             const char* bp = Bs + nb * B_BYTES + b_off[sn];
-            bf16x8 av[2];
+            bf16x8 av[4];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < 4; ++i) {
                 if constexpr (POOL) av[i] = vc::max_nonneg(fa[cur][i], fp[cur][i]);
                 else av[i] = fa[cur][i];
             }
             if (need_mask) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
+                for (int i = 0; i < 4; ++i) {
                     if constexpr (POOL) av[i] = hn[i] ? av[i] : fa[cur][i];   // last frame pools with itself
                     av[i] = v[i] ? av[i] : zero;                               // SAME padding
                 }
             }
             __builtin_amdgcn_s_setprio(1);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][0], av[0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][1], av[0], acc[0][1], 0, 0, 0);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[cur][c], av[0], acc[0][c], 0, 0, 0);
             if (have_next) {
-                fa[nxt][0] = *reinterpret_cast<const bf16x8*>(ap);
-                fa[nxt][1] = *reinterpret_cast<const bf16x8*>(ap + 4096);
-                if constexpr (POOL) {
-                    fp[nxt][0] = *reinterpret_cast<const bf16x8*>(pp);
-                    fp[nxt][1] = *reinterpret_cast<const bf16x8*>(pp + 4096);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    fa[nxt][i] = *reinterpret_cast<const bf16x8*>(ap + i * 2048);
+                    if constexpr (POOL) fp[nxt][i] = *reinterpret_cast<const bf16x8*>(pp + i * 2048);
+                    fb[nxt][i] = *reinterpret_cast<const bf16x8*>(bp + i * 2048);
                 }
-                fb[nxt][0] = *reinterpret_cast<const bf16x8*>(bp);
-                fb[nxt][1] = *reinterpret_cast<const bf16x8*>(bp + 4096);
             }
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][0], av[1], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cur][1], av[1], acc[1][1], 0, 0, 0);
+#pragma unroll
+            for (int i = 1; i < 4; ++i)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[cur][c], av[i], acc[i][c], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
         }
         j = jn;
@@ -253,32 +253,29 @@ conv256_kernel(Conv256Args a) {
     __syncthreads();                                   // (no load is in flight any more: the last wait was vmcnt(0))
     {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
+        for (int c = 0; c < 4; ++c) {
+            const int col = wc * 64 + c * 16 + 4 * lq;                   // column of the tile
+            const int gn = min(n0 + col, a.N - 4);
+            float4 sv = make_float4(1.0f, 1.0f, 1.0f, 1.0f), bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (a.epi_scale) sv = *reinterpret_cast<const float4*>(a.epi_scale + a.c_off + gn);
+            if (a.epi_shift) bv = *reinterpret_cast<const float4*>(a.epi_shift + a.c_off + gn);
+            const float svv[4] = {sv.x, sv.y, sv.z, sv.w}, bvv[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int col = wc * 64 + c * 32 + 8 * q + 4 * lh;       // column of the tile
-                const int gn = min(n0 + col, a.N - 4);
-                float4 sv = make_float4(1.0f, 1.0f, 1.0f, 1.0f), bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (a.epi_scale) sv = *reinterpret_cast<const float4*>(a.epi_scale + a.c_off + gn);
-                if (a.epi_shift) bv = *reinterpret_cast<const float4*>(a.epi_shift + a.c_off + gn);
-                const float svv[4] = {sv.x, sv.y, sv.z, sv.w}, bvv[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int row = wr * 64 + i * 32 + li;
-                    bf16x4 rr = {};
-                    if (a.R) {
-                        const int gm = min(m0 + row, a.M - 1);
-                        rr = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(a.R) + (size_t)gm * a.ldr + gn);
-                    }
-                    bf16x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float val = vc::act_fn(acc[i][c][4 * q + e] * svv[e] + bvv[e], a.act);
-                        if (a.R) val += (float)rr[e];
-                        o[e] = (__bf16)val;
-                    }
-                    *reinterpret_cast<bf16x4*>(smem + row * EP + col * 2) = o;
+            for (int i = 0; i < 4; ++i) {
+                const int row = wr * 64 + i * 16 + li;
+                bf16x4 rr = {};
+                if (a.R) {
+                    const int gm = min(m0 + row, a.M - 1);
+                    rr = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(a.R) + (size_t)gm * a.ldr + gn);
                 }
+                bf16x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float val = vc::act_fn(acc[i][c][e] * svv[e] + bvv[e], a.act);
+                    if (a.R) val += (float)rr[e];
+                    o[e] = (__bf16)val;
+                }
+                *reinterpret_cast<bf16x4*>(smem + row * EP + col * 2) = o;
             }
         }
     }

@@ -41,6 +41,10 @@ __device__ __forceinline__ void glds16(const void* g, void* l) {
                                      (__attribute__((address_space(3))) void*)(uintptr_t)(uint32_t)(uintptr_t)l, 16, 0, 0);
 }
 
+// XOR key of the 16-byte slot of row r in a 128-byte-row LDS tile whose fragments feed v_mfma_f32_16x16x32_bf16 (lane l reads row
+// l & 15, slot (l >> 4) + 4 * step): every ds_read_b128 is conflict-free at any row offset (worked out in vc_bank256.hip).
+__device__ __forceinline__ int slot_key16(int r) { return ((r >> 1) & 3) << 1; }
+
 // max of values that are >= 0 (post-ReLU), either zero included: for them IEEE ordering == SIGNED integer ordering
 // of the bit patterns (-0.0 is the most negative integer, so it loses to every other such value, where the
 // unsigned order would rank it above all of them), so bf16 pairs go through v_pk_max_i16 and f32 through v_max_i32.
