@@ -6,7 +6,8 @@
 //     D(t, s) = e(t, s) + best,  best = D(t-1, s), then D(t-1, s-1) iff strictly greater, then D(t-1, s-2) iff opt[s-1]
 //                                and strictly greater                             (codes 0, 1, 2)
 //
-// align_forward_kernel<K>: one workgroup of ONE wave per utterance.  Lane l owns the K consecutive states l K .. l K + K - 1,
+// align_forward_kernel<K>: the geometry of vc_lattice.h (state table, gather, neighbours, end read-out are its helpers;
+// vc_fullsum.hip walks the same lattice): one workgroup of ONE wave per utterance.  Lane l owns the K consecutive states l K .. l K + K - 1,
 // their D in registers.  A frame's step takes the left neighbour's last two D of the previous row by two shuffles BEFORE
 // the lane overwrites its own, then updates its states from the highest down (D[k-1], D[k-2] are still the previous row's).
 // No LDS, no barrier.  The K emissions of a frame are gathered AL_PF = 4 frames ahead into a register ring (the frame
@@ -21,25 +22,20 @@
 // emissions in frame order divided by the count, rounded once.  The rows of frame_state from F on are filled here too.
 // Every output element is written exactly once; no atomics, no memset.
 #include <cmath>
-#include "vc_device.h"
+#include "vc_lattice.h"
 
 namespace {
 
-constexpr int AL_MAX_SEQ = 1024;
+namespace lat = vc::lattice;
+constexpr int AL_MAX_SEQ = lat::MAX_SEQ;
 constexpr int AL_MAX_CLASSES = 65535;
-constexpr int AL_PF = 4;                // frames of emissions in flight
+constexpr int AL_PF = lat::PF;          // frames of emissions in flight
 constexpr int AL_NT_B = 256;            // lanes of the back-track launch
-constexpr size_t AL_MAX_WS = (size_t)1 << 31;
 
 __host__ __device__ inline size_t al_code_words(int max_frames) { return ((size_t)max_frames + 15) / 16; }
 
 inline size_t al_ws_bytes(int batch, int max_frames, int max_seq) {
     return vc::align256((size_t)batch * sizeof(int32_t)) + vc::align256((size_t)batch * al_code_words(max_frames) * max_seq * sizeof(uint32_t));
-}
-
-inline bool al_shape_ok(int batch, int max_frames, int max_seq) {
-    if (batch < 1 || batch > 65535 || max_frames < 1 || max_seq < 1 || max_seq > AL_MAX_SEQ) return false;
-    return al_ws_bytes(batch, max_frames, max_seq) < AL_MAX_WS;
 }
 
 template <int K>
@@ -62,27 +58,15 @@ align_forward_kernel(const float* __restrict__ score, const int32_t* __restrict_
     uint32_t* __restrict__ W = codes + (size_t)b * al_code_words(max_frames) * max_seq;
     const int s0 = lane * K;
     int cls[K];                         // the checked class of each state (0 where there is none)
-    uint32_t valid = 0, skip = 0;       // bit k: state s0 + k has an emission / may be entered by a skip
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = s0 + k;
-        const int c = s < S ? Q[s] : -1;
-        const bool ok = c >= 0 && c < n_classes;
-        cls[k] = ok ? c : 0;
-        valid |= (ok ? 1u : 0u) << k;
-        skip |= ((O && s >= 2 && s < S && O[s - 1] != 0) ? 1u : 0u) << k;
-    }
+    uint32_t valid, skip;               // bit k: state s0 + k has an emission / may be entered by a skip
+    lat::state_table<K, false>(Q, O, S, s0, n_classes, cls, valid, skip);
     const bool opt0 = O && O[0] != 0;
     float D[K];
     float ring[AL_PF][K];
 #pragma unroll
     for (int k = 0; k < K; ++k) D[k] = ninf;
 #pragma unroll
-    for (int p = 0; p < AL_PF; ++p) {
-        const float* __restrict__ row = X + (size_t)min(p, F - 1) * n_classes;
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[p][k] = row[cls[k]];
-    }
+    for (int p = 0; p < AL_PF; ++p) lat::gather<K>(X, min(p, F - 1), n_classes, cls, ring[p]);
     const int n_words = (F + 15) >> 4;
     for (int w = 0; w < n_words; ++w) {
         uint32_t cw[K];
@@ -94,11 +78,7 @@ align_forward_kernel(const float* __restrict__ score, const int32_t* __restrict_
             float e[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) e[k] = (valid >> k) & 1 ? ring[j % AL_PF][k] : ninf;
-            {
-                const float* __restrict__ row = X + (size_t)min(t + AL_PF, F - 1) * n_classes;
-#pragma unroll
-                for (int k = 0; k < K; ++k) ring[j % AL_PF][k] = row[cls[k]];
-            }
+            lat::gather<K>(X, min(t + AL_PF, F - 1), n_classes, cls, ring[j % AL_PF]);
             if (t >= F) continue;                                   // (uniform; only in the last word)
             if (j == 0 && w == 0) {                                 // frame 0
 #pragma unroll
@@ -106,14 +86,11 @@ align_forward_kernel(const float* __restrict__ score, const int32_t* __restrict_
                 continue;
             }
             // the left neighbour's last two states of the previous row, before this lane overwrites its own
-            float l1 = __shfl_up(D[K - 1], 1, 64);
-            float l2 = K >= 2 ? __shfl_up(D[K >= 2 ? K - 2 : 0], 1, 64) : __shfl_up(D[0], 2, 64);
-            if (lane == 0) { l1 = ninf; l2 = ninf; }
-            if (K == 1 && lane == 1) l2 = ninf;
+            const lat::Two left = lat::left_two<K>(D, lane);
 #pragma unroll
             for (int k = K - 1; k >= 0; --k) {
-                const float p1 = k >= 1 ? D[k >= 1 ? k - 1 : 0] : l1;
-                const float p2 = k >= 2 ? D[k >= 2 ? k - 2 : 0] : (k == 1 ? l1 : l2);
+                const float p1 = k >= 1 ? D[k >= 1 ? k - 1 : 0] : left.near;
+                const float p2 = k >= 2 ? D[k >= 2 ? k - 2 : 0] : (k == 1 ? left.near : left.far);
                 float best = D[k];
                 uint32_t code = 0;
                 if (p1 > best) { best = p1; code = 1; }
@@ -126,17 +103,10 @@ align_forward_kernel(const float* __restrict__ score, const int32_t* __restrict_
         for (int k = 0; k < K; ++k)
             if (s0 + k < S) W[(size_t)w * max_seq + s0 + k] = cw[k];
     }
-    float d_last = ninf, d_prev = ninf;                             // D(F-1, S-1), D(F-1, S-2)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (s0 + k == S - 1) d_last = D[k];
-        if (s0 + k == S - 2) d_prev = D[k];
-    }
-    d_last = __shfl(d_last, (S - 1) / K, 64);
-    d_prev = __shfl(d_prev, S >= 2 ? (S - 2) / K : 0, 64);
+    const lat::Two d_end = lat::end_two<K>(D, s0, S, O);            // D(F-1, S-1); D(F-1, S-2) if a path may end there
     int fin = S - 1;
-    float tot = d_last;
-    if (S >= 2 && O && O[S - 1] != 0 && d_prev > d_last) { fin = S - 2; tot = d_prev; }
+    float tot = d_end.near;
+    if (d_end.far > d_end.near) { fin = S - 2; tot = d_end.far; }
     if (lane == 0) { total[b] = tot; final_state[b] = tot == ninf ? -1 : fin; }
 }
 
@@ -203,51 +173,31 @@ align_backtrack_kernel(const float* __restrict__ score, const int32_t* __restric
     for (int t = (feasible ? F : 0) + tid; t < max_frames; t += AL_NT_B) out_f[t] = -1;
 }
 
-template <int K>
-void al_launch_forward(int batch, hipStream_t st, const float* score, const int32_t* seq, const uint8_t* opt, const int32_t* n_frames,
-                       const int32_t* n_seq, int max_frames, int max_seq, int n_classes, float* total, int32_t* fin, uint32_t* codes) {
-    hipLaunchKernelGGL(align_forward_kernel<K>, dim3(batch), dim3(64), 0, st, score, seq, opt, n_frames, n_seq, max_frames, max_seq,
-                       n_classes, total, fin, codes);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t vc_align_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_seq) {
-    if (!al_shape_ok(batch, max_frames, max_seq)) return 0;
-    return al_ws_bytes(batch, max_frames, max_seq);
+    const size_t need = al_ws_bytes(batch, max_frames, max_seq);
+    return lat::shape_ok(batch, max_frames, max_seq, need) ? need : 0;
 }
 
 int vc_align_f32(const float* d_score, const int32_t* d_seq, const uint8_t* d_opt, const int32_t* d_n_frames, const int32_t* d_n_seq,
                  int32_t batch, int32_t max_frames, int32_t max_seq, int32_t n_classes, int32_t* d_frame_state, int32_t* d_start,
                  int32_t* d_end, float* d_seg_score, float* d_total, int32_t* d_n_visited, void* d_workspace, size_t workspace_bytes,
                  void* stream) {
-    VC_REQUIRE(d_score && d_seq && d_n_frames && d_n_seq && d_frame_state && d_start && d_end && d_seg_score && d_total &&
-               d_n_visited && d_workspace, "vc_align_f32: NULL argument");
-    VC_REQUIRE(batch >= 1 && max_frames >= 1 && max_seq >= 1 && n_classes >= 1,
-               "vc_align_f32: bad shape (batch %d, max_frames %d, max_seq %d, n_classes %d; need all >= 1)", batch, max_frames, max_seq,
-               n_classes);
-    if (n_classes > AL_MAX_CLASSES || !al_shape_ok(batch, max_frames, max_seq))
-        return vc::set_error(VC_ERR_UNSUPPORTED, "vc_align_f32: limits are batch <= 65535, max_seq <= %d, n_classes <= %d and a workspace "
-                             "below 2 GiB; got batch %d, max_frames %d, max_seq %d, n_classes %d", AL_MAX_SEQ, AL_MAX_CLASSES, batch,
-                             max_frames, max_seq, n_classes);
-    VC_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 3) == 0, "vc_align_f32: unaligned workspace");
     const size_t need = al_ws_bytes(batch, max_frames, max_seq);
-    if (workspace_bytes < need)
-        return vc::set_error(VC_ERR_WORKSPACE, "vc_align_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (int rc = lat::check_args("vc_align_f32", d_score && d_seq && d_n_frames && d_n_seq && d_frame_state && d_start && d_end &&
+                                 d_seg_score && d_total && d_n_visited && d_workspace, batch, max_frames, max_seq, n_classes,
+                                 AL_MAX_CLASSES, d_workspace, workspace_bytes, need))
+        return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int32_t* fin = static_cast<int32_t*>(d_workspace);
     uint32_t* codes = reinterpret_cast<uint32_t*>(static_cast<char*>(d_workspace) + vc::align256((size_t)batch * sizeof(int32_t)));
-    const int per_lane = (max_seq + 63) / 64;
-#define VC_AL_FWD(K) al_launch_forward<K>(batch, st, d_score, d_seq, d_opt, d_n_frames, d_n_seq, max_frames, max_seq, n_classes, \
-                                          d_total, fin, codes)
-    if (per_lane <= 1) VC_AL_FWD(1);
-    else if (per_lane <= 2) VC_AL_FWD(2);
-    else if (per_lane <= 4) VC_AL_FWD(4);
-    else if (per_lane <= 8) VC_AL_FWD(8);
-    else VC_AL_FWD(16);
-#undef VC_AL_FWD
+    lat::dispatch_per_lane(max_seq, [&](auto k) {
+        hipLaunchKernelGGL(align_forward_kernel<decltype(k)::value>, dim3(batch), dim3(64), 0, st, d_score, d_seq, d_opt, d_n_frames,
+                           d_n_seq, max_frames, max_seq, n_classes, d_total, fin, codes);
+    });
     VC_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(align_backtrack_kernel, dim3(batch), dim3(AL_NT_B), 0, st, d_score, d_seq, d_n_frames, d_n_seq, max_frames,
                        max_seq, n_classes, fin, codes, d_frame_state, d_start, d_end, d_seg_score, d_n_visited);

@@ -75,7 +75,11 @@ __device__ __forceinline__ float dpp_move(float identity, float v) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 __device__ __forceinline__ float vc_addf(float a, float b) { return a + b; }
 __device__ __forceinline__ float wave_sum(float v) { VC_WAVE_REDUCE(vc_addf, 0.0f) }
+// wave_max / wave_min are for FINITE data: a lane whose source a step disables takes the seed, +-FLT_MAX, so a wave that
+// holds nothing but -inf (+inf) comes back as the seed.  wave_max_inf seeds every step with the lane's own value and so
+// keeps an all -inf wave at -inf (the log-domain rows of vc_fullsum.hip).
 __device__ __forceinline__ float wave_max(float v) { VC_WAVE_REDUCE(fmaxf, -3.402823466e38f) }
+__device__ __forceinline__ float wave_max_inf(float v) { VC_WAVE_REDUCE(fmaxf, v) }
 // highwaynet gate (modules.py:315-319): relu(h) * t + x * (1 - t), t = sigmoid(tpre), written as
 // x + t * (relu(h) - x) with v_exp_f32 / v_rcp_f32 (1 ulp each) -- the gate arithmetic, not the
 // matrix work, bounds the fused highway chain, and an IEEE division costs ~10 instructions.
@@ -88,6 +92,17 @@ __device__ __forceinline__ float highway_gate(float hpre, float tpre, float x) {
 }
 __device__ __forceinline__ float wave_min(float v) { VC_WAVE_REDUCE(fminf, 3.402823466e38f) }
 #undef VC_WAVE_REDUCE
+// The greatest value over the wave and its index, the lowest index where several lanes hold that value; in every lane.
+struct ArgMax { float v; int idx; };
+__device__ __forceinline__ ArgMax wave_argmax_low(float v, int idx) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const float ov = __shfl_xor(v, s, 64);
+        const int oi = __shfl_xor(idx, s, 64);
+        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+    }
+    return {v, idx};
+}
 #endif
 
 }  // namespace vc

@@ -57,13 +57,7 @@ __device__ inline int wave_argmax(const float* __restrict__ row, int n_classes, 
         const float x = row[c];
         if (x > v || idx == 0x7fffffff) { v = x; idx = c; }
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const float ov = __shfl_xor(v, s, 64);
-        const int oi = __shfl_xor(idx, s, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    return idx;
+    return vc::wave_argmax_low(v, idx).idx;
 }
 
 __device__ inline double js_term(double p, double m) { return p > 0.0 ? p * log2(p / m) : 0.0; }
@@ -102,13 +96,9 @@ ppg_metrics_kernel(const float* __restrict__ ppg_a, const float* __restrict__ pp
             acc += js_term(pa, m) + js_term(pb, m);
         }
 #pragma unroll
-        for (int s = 32; s > 0; s >>= 1) {
-            acc += __shfl_xor(acc, s, 64);
-            const float oa = __shfl_xor(va, s, 64), ob = __shfl_xor(vb, s, 64);
-            const int xa = __shfl_xor(ia, s, 64), xb = __shfl_xor(ib, s, 64);
-            if (oa > va || (oa == va && xa < ia)) { va = oa; ia = xa; }
-            if (ob > vb || (ob == vb && xb < ib)) { vb = ob; ib = xb; }
-        }
+        for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
+        ia = vc::wave_argmax_low(va, ia).idx;
+        ib = vc::wave_argmax_low(vb, ib).idx;
         js_sum += 0.5 * acc;
         ++cells;
         if (class_map) { ia = class_map[ia]; ib = class_map[ib]; }

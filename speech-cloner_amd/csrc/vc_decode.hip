@@ -180,13 +180,8 @@ decode_forward_kernel(const float* __restrict__ score, const int32_t* __restrict
         const float o = R[c + 64];
         if (o > v) { v = o; vi = c + 64; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(vi, o, 64);
-        if (ov > v || (ov == v && oi < vi)) { v = ov; vi = oi; }
-    }
-    if (c == 0) { total[b] = v; fin[b] = v == ninf ? -1 : vi; }
+    const vc::ArgMax top = vc::wave_argmax_low(v, vi);
+    if (c == 0) { total[b] = top.v; fin[b] = top.v == ninf ? -1 : top.idx; }
 }
 
 __global__ void __launch_bounds__(DC_NT_B)

@@ -7,16 +7,16 @@
 //     lb(t, s) = lse(lb(t+1, s) + e(t+1, s), lb(t+1, s+1) + e(t+1, s+1), [opt[s+1]] lb(t+1, s+2) + e(t+1, s+2))
 //     gamma(t, s) = exp(la + lb - log_z),  Gamma(t, c) = sum of gamma(t, s) over seq[s] = c,  occ(s) = sum_t gamma(t, s)
 //
-// fullsum_forward_kernel<K>: the geometry of align_forward_kernel<K> -- one workgroup of ONE wave per utterance, lane l
-// owns the K consecutive states l K .. l K + K - 1, the left neighbour's last two values come by two __shfl_up before the
-// lane overwrites its own, the K emissions of a frame are gathered FS_PF = 4 frames ahead (frame index clamped to F - 1)
+// fullsum_forward_kernel<K>: the geometry of vc_lattice.h, shared with align_forward_kernel<K> -- one workgroup of ONE
+// wave per utterance, lane l owns the K consecutive states l K .. l K + K - 1, the left neighbour's last two values come by
+// two shuffles before the lane overwrites its own, the K emissions of a frame are gathered FS_PF = 4 frames ahead (frame index clamped to F - 1)
 // into a register ring, the frame loop is unrolled by FS_PF so that ring slots are compile-time.  After each frame the
 // row's maximum over the states (a wave reduction) is subtracted and added to a float64 sum; the shifted row A(t, .) goes
 // to the workspace [batch, max_frames, max_seq] (states below S only).  log_z = (sum of the shifts) + lse of the last
 // row's end states, rounded once.  A row that is all -inf is left as it is (no -inf - -inf anywhere).
 //
 // fullsum_backward_kernel<K>: the same geometry, time reversed, lb in registers, the right neighbour's first two values by
-// two __shfl_down.  The row is shifted by its maximum too (no sum is kept: nothing needs it).  gamma is formed from the
+// two shuffles.  The row is shifted by its maximum too (no sum is kept: nothing needs it).  gamma is formed from the
 // stored row and NORMALISED over the states of the frame -- exp(A + B - max) / sum, the sum one binary tree over the state
 // index, the same tree for every K -- which is the definition (the sum over s of exp(la + lb) is Z at every frame) without
 // the shifts, so neither the shifts nor log_z enter gamma.  gamma goes out when asked for, is added to the owning lane's
@@ -26,49 +26,23 @@
 // that read it.  Rows from F on, the columns from S on and an infeasible utterance (log_z = -inf, read back from the forward
 // launch) are zero-filled here; every output element is written exactly once.
 #include <cmath>
-#include "vc_device.h"
+#include "vc_lattice.h"
 
 namespace {
 
-constexpr int FS_MAX_SEQ = 1024;
+namespace lat = vc::lattice;
 constexpr int FS_MAX_CLASSES = 4096;    // the Gamma row in LDS: 16 KiB of 32-bit words
-constexpr int FS_PF = 4;                // frames of emissions (and of stored rows) in flight
-constexpr size_t FS_MAX_WS = (size_t)1 << 31;
+constexpr int FS_PF = lat::PF;          // frames of emissions (and of stored rows) in flight
 constexpr float FS_FIX = 1073741824.0f; // 2^30
 
 inline size_t fs_ws_bytes(int batch, int max_frames, int max_seq) {
     return vc::align256((size_t)batch * max_frames * max_seq * sizeof(float));
 }
 
-inline bool fs_shape_ok(int batch, int max_frames, int max_seq) {
-    if (batch < 1 || batch > 65535 || max_frames < 1 || max_seq < 1 || max_seq > FS_MAX_SEQ) return false;
-    return fs_ws_bytes(batch, max_frames, max_seq) < FS_MAX_WS;
-}
-
-// One step of a wave reduction on the DPP path (no LDS crossbar): the lane's own value and the one the control selects.
-// A lane whose source does not exist gets its own value back.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ float fs_dpp(float v) {
-    const int x = __builtin_bit_cast(int, v);
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(x, x, CTRL, ROWS, 0xf, false));
-}
-constexpr int FS_QUAD_1032 = 0xB1, FS_QUAD_2301 = 0x4E, FS_HALF_MIRROR = 0x141, FS_MIRROR = 0x140, FS_BCAST15 = 0x142, FS_BCAST31 = 0x143;
-
-// The maximum over the wave, in every lane (through lane 63 and a scalar register).
-__device__ __forceinline__ float fs_wave_max(float v) {
-    v = fmaxf(v, fs_dpp<FS_QUAD_1032, 0xf>(v));
-    v = fmaxf(v, fs_dpp<FS_QUAD_2301, 0xf>(v));
-    v = fmaxf(v, fs_dpp<FS_HALF_MIRROR, 0xf>(v));
-    v = fmaxf(v, fs_dpp<FS_MIRROR, 0xf>(v));
-    v = fmaxf(v, fs_dpp<FS_BCAST15, 0xa>(v));
-    v = fmaxf(v, fs_dpp<FS_BCAST31, 0xc>(v));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
 // The sum of a row of 64 K values, lane l holding the K consecutive ones from l K on, as ONE balanced binary tree over the
 // state index: pairs, then pairs of pairs, inside the lane and on across the lanes -- neighbours, quads (after which a
 // quad's lanes agree, so the half mirror pairs quad with quad), eights, rows of 16, then row 0 + 1 and 2 + 3, then the two
-// halves, read from lane 63.  The tree over the states of an utterance is the same for every K -- a larger K only adds
+// halves, read from lane 63 (vc::wave_sum: what it leaves in lane 63 is this tree).  The tree over the states of an utterance is the same for every K -- a larger K only adds
 // levels that add zeros -- so the sum is too.
 template <int K>
 __device__ __forceinline__ float fs_row_sum(const float (&p)[K]) {
@@ -79,14 +53,7 @@ __device__ __forceinline__ float fs_row_sum(const float (&p)[K]) {
     for (int w = 1; w < K; w <<= 1)
 #pragma unroll
         for (int k = 0; k < K; k += 2 * w) v[k] += v[k + w];
-    float r = v[0];
-    r += fs_dpp<FS_QUAD_1032, 0xf>(r);
-    r += fs_dpp<FS_QUAD_2301, 0xf>(r);
-    r += fs_dpp<FS_HALF_MIRROR, 0xf>(r);
-    r += fs_dpp<FS_MIRROR, 0xf>(r);
-    r += fs_dpp<FS_BCAST15, 0xa>(r);
-    r += fs_dpp<FS_BCAST31, 0xc>(r);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, r), 63));
+    return vc::wave_sum(v[0]);
 }
 
 // log(exp(x0) + exp(x1) + exp(x2)) for finite or -inf arguments; -inf when all three are
@@ -116,27 +83,15 @@ fullsum_forward_kernel(const float* __restrict__ score, const int32_t* __restric
     float* __restrict__ W = rows + (size_t)b * max_frames * max_seq;
     const int s0 = lane * K;
     int cls[K];                         // the checked class of each state (0 where there is none)
-    uint32_t valid = 0, skip = 0;       // bit k: state s0 + k has an emission / may be entered by a skip
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = s0 + k;
-        const int c = s < S ? Q[s] : -1;
-        const bool ok = c >= 0 && c < n_classes;
-        cls[k] = ok ? c : 0;
-        valid |= (ok ? 1u : 0u) << k;
-        skip |= ((O && s >= 2 && s < S && O[s - 1] != 0) ? 1u : 0u) << k;
-    }
+    uint32_t valid, skip;               // bit k: state s0 + k has an emission / may be entered by a skip
+    lat::state_table<K, false>(Q, O, S, s0, n_classes, cls, valid, skip);
     const bool opt0 = O && O[0] != 0;
     float A[K];
     float ring[FS_PF][K];
 #pragma unroll
     for (int k = 0; k < K; ++k) A[k] = ninf;
 #pragma unroll
-    for (int p = 0; p < FS_PF; ++p) {
-        const float* __restrict__ row = X + (size_t)min(p, F - 1) * n_classes;
-#pragma unroll
-        for (int k = 0; k < K; ++k) ring[p][k] = row[cls[k]];
-    }
+    for (int p = 0; p < FS_PF; ++p) lat::gather<K>(X, min(p, F - 1), n_classes, cls, ring[p]);
     double shift_sum = 0.0;
     for (int t0 = 0; t0 < F; t0 += FS_PF) {
 #pragma unroll
@@ -145,32 +100,25 @@ fullsum_forward_kernel(const float* __restrict__ score, const int32_t* __restric
             float e[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) e[k] = (valid >> k) & 1 ? ring[j][k] : ninf;
-            {
-                const float* __restrict__ row = X + (size_t)min(t + FS_PF, F - 1) * n_classes;
-#pragma unroll
-                for (int k = 0; k < K; ++k) ring[j][k] = row[cls[k]];
-            }
+            lat::gather<K>(X, min(t + FS_PF, F - 1), n_classes, cls, ring[j]);
             if (t >= F) continue;                                   // (uniform; only in the last group)
             if (t == 0) {
 #pragma unroll
                 for (int k = 0; k < K; ++k) A[k] = (s0 + k == 0 || (s0 + k == 1 && opt0)) ? e[k] : ninf;
             } else {
                 // the left neighbour's last two states of the previous row, before this lane overwrites its own
-                float l1 = __shfl_up(A[K - 1], 1, 64);
-                float l2 = K >= 2 ? __shfl_up(A[K >= 2 ? K - 2 : 0], 1, 64) : __shfl_up(A[0], 2, 64);
-                if (lane == 0) { l1 = ninf; l2 = ninf; }
-                if (K == 1 && lane == 1) l2 = ninf;
+                const lat::Two left = lat::left_two<K>(A, lane);
 #pragma unroll
                 for (int k = K - 1; k >= 0; --k) {
-                    const float p1 = k >= 1 ? A[k >= 1 ? k - 1 : 0] : l1;
-                    const float p2 = k >= 2 ? A[k >= 2 ? k - 2 : 0] : (k == 1 ? l1 : l2);
+                    const float p1 = k >= 1 ? A[k >= 1 ? k - 1 : 0] : left.near;
+                    const float p2 = k >= 2 ? A[k >= 2 ? k - 2 : 0] : (k == 1 ? left.near : left.far);
                     A[k] = e[k] + fs_lse3(A[k], p1, ((skip >> k) & 1) ? p2 : ninf);
                 }
             }
             float m = ninf;
 #pragma unroll
             for (int k = 0; k < K; ++k) m = fmaxf(m, A[k]);
-            m = fs_wave_max(m);
+            m = vc::wave_max_inf(m);
             if (m != ninf) {                                        // (uniform)
                 shift_sum += (double)m;
 #pragma unroll
@@ -181,16 +129,8 @@ fullsum_forward_kernel(const float* __restrict__ score, const int32_t* __restric
                 if (s0 + k < S) W[(size_t)t * max_seq + s0 + k] = A[k];
         }
     }
-    float a_last = ninf, a_prev = ninf;                             // A(F-1, S-1), A(F-1, S-2)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (s0 + k == S - 1) a_last = A[k];
-        if (s0 + k == S - 2) a_prev = A[k];
-    }
-    a_last = __shfl(a_last, (S - 1) / K, 64);
-    a_prev = __shfl(a_prev, S >= 2 ? (S - 2) / K : 0, 64);
-    const bool two = S >= 2 && O && O[S - 1] != 0;
-    const float rel = fs_lse3(a_last, two ? a_prev : ninf, ninf);
+    const lat::Two a_end = lat::end_two<K>(A, s0, S, O);            // A(F-1, S-1); A(F-1, S-2) if a path may end there
+    const float rel = fs_lse3(a_end.near, a_end.far, ninf);
     if (lane == 0) log_z[b] = rel == ninf ? ninf : (float)(shift_sum + (double)rel);
 }
 
@@ -219,20 +159,9 @@ fullsum_backward_kernel(const float* __restrict__ score, const int32_t* __restri
     for (int k = 0; k < K; ++k) acc[k] = 0.0f;
     if (F > 0) {
         int cls[K], col[K];             // the checked class / the clamped column of the stored row
-        uint32_t valid = 0, skip = 0, live = 0, last = 0;   // bit k: has an emission / may be LEFT by a skip / s < S / end state
-        const bool two = S >= 2 && O && O[S - 1] != 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int s = s0 + k;
-            const int c = s < S ? Q[s] : -1;
-            const bool ok = c >= 0 && c < n_classes;
-            cls[k] = ok ? c : 0;
-            col[k] = min(s, S - 1);
-            valid |= (ok ? 1u : 0u) << k;
-            live |= (s < S ? 1u : 0u) << k;
-            skip |= ((O && s + 2 < S && O[s + 1] != 0) ? 1u : 0u) << k;
-            last |= ((s == S - 1 || (two && s == S - 2)) ? 1u : 0u) << k;
-        }
+        uint32_t valid, skip, live, last;       // bit k: has an emission / may be LEFT by a skip / s < S / end state
+        lat::state_table<K, true>(Q, O, S, s0, n_classes, cls, valid, skip);
+        lat::state_table_ends<K>(O, S, s0, col, live, last);
         for (int c = lane; c < n_classes; c += 64) s_row[c] = 0;
         __syncthreads();
         float B[K], e1[K];              // lb of frame t + 1 (then t), shifted; the emissions of frame t + 1
@@ -241,11 +170,8 @@ fullsum_backward_kernel(const float* __restrict__ score, const int32_t* __restri
         for (int k = 0; k < K; ++k) { B[k] = ninf; e1[k] = ninf; }
 #pragma unroll
         for (int p = 0; p < FS_PF; ++p) {
-            const int tt = max(F - 1 - p, 0);
-            const float* __restrict__ row = X + (size_t)tt * n_classes;
-            const float* __restrict__ arow = W + (size_t)tt * max_seq;
-#pragma unroll
-            for (int k = 0; k < K; ++k) { ring_e[p][k] = row[cls[k]]; ring_a[p][k] = arow[col[k]]; }
+            lat::gather<K>(X, max(F - 1 - p, 0), n_classes, cls, ring_e[p]);
+            lat::gather<K>(W, max(F - 1 - p, 0), max_seq, col, ring_a[p]);
         }
         for (int i0 = 0; i0 < F; i0 += FS_PF) {
 #pragma unroll
@@ -257,13 +183,8 @@ fullsum_backward_kernel(const float* __restrict__ score, const int32_t* __restri
                     e[k] = (valid >> k) & 1 ? ring_e[j][k] : ninf;
                     a[k] = (live >> k) & 1 ? ring_a[j][k] : ninf;
                 }
-                {
-                    const int tt = max(t - FS_PF, 0);
-                    const float* __restrict__ row = X + (size_t)tt * n_classes;
-                    const float* __restrict__ arow = W + (size_t)tt * max_seq;
-#pragma unroll
-                    for (int k = 0; k < K; ++k) { ring_e[j][k] = row[cls[k]]; ring_a[j][k] = arow[col[k]]; }
-                }
+                lat::gather<K>(X, max(t - FS_PF, 0), n_classes, cls, ring_e[j]);
+                lat::gather<K>(W, max(t - FS_PF, 0), max_seq, col, ring_a[j]);
                 if (t < 0) continue;                                // (uniform; only in the last group)
                 if (t == F - 1) {
 #pragma unroll
@@ -272,21 +193,17 @@ fullsum_backward_kernel(const float* __restrict__ score, const int32_t* __restri
                     float g[K];                                     // lb(t+1, s) + e(t+1, s): -inf from S on
 #pragma unroll
                     for (int k = 0; k < K; ++k) g[k] = B[k] + e1[k];
-                    // the right neighbour's first two states
-                    float r1 = __shfl_down(g[0], 1, 64);
-                    float r2 = K >= 2 ? __shfl_down(g[K >= 2 ? 1 : 0], 1, 64) : __shfl_down(g[0], 2, 64);
-                    if (lane == 63) { r1 = ninf; r2 = ninf; }
-                    if (K == 1 && lane == 62) r2 = ninf;
+                    const lat::Two right = lat::right_two<K>(g, lane);
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
-                        const float n1 = k + 1 < K ? g[k + 1 < K ? k + 1 : 0] : r1;
-                        const float n2 = k + 2 < K ? g[k + 2 < K ? k + 2 : 0] : (k + 2 == K ? r1 : r2);
+                        const float n1 = k + 1 < K ? g[k + 1 < K ? k + 1 : 0] : right.near;
+                        const float n2 = k + 2 < K ? g[k + 2 < K ? k + 2 : 0] : (k + 2 == K ? right.near : right.far);
                         B[k] = fs_lse3(g[k], n1, ((skip >> k) & 1) ? n2 : ninf);
                     }
                     float m = ninf;
 #pragma unroll
                     for (int k = 0; k < K; ++k) m = fmaxf(m, B[k]);
-                    m = fs_wave_max(m);
+                    m = vc::wave_max_inf(m);
                     if (m != ninf) {                                // (uniform)
 #pragma unroll
                         for (int k = 0; k < K; ++k) B[k] -= m;
@@ -298,7 +215,7 @@ fullsum_backward_kernel(const float* __restrict__ score, const int32_t* __restri
                 float v[K], top = ninf;
 #pragma unroll
                 for (int k = 0; k < K; ++k) { v[k] = a[k] + B[k]; top = fmaxf(top, v[k]); }
-                top = fs_wave_max(top);
+                top = vc::wave_max_inf(top);
 #pragma unroll
                 for (int k = 0; k < K; ++k) v[k] = top != ninf ? __expf(v[k] - top) : 0.0f;
                 const float sum = fs_row_sum<K>(v);
@@ -330,52 +247,31 @@ fullsum_backward_kernel(const float* __restrict__ score, const int32_t* __restri
         if (s0 + k < max_seq) occ[(size_t)b * max_seq + s0 + k] = acc[k];
 }
 
-template <int K>
-void fs_launch(int batch, hipStream_t st, const float* score, const int32_t* seq, const uint8_t* opt, const int32_t* n_frames,
-               const int32_t* n_seq, int max_frames, int max_seq, int n_classes, float* log_z, float* class_post, float* state_post,
-               float* occ, float* rows) {
-    hipLaunchKernelGGL(fullsum_forward_kernel<K>, dim3(batch), dim3(64), 0, st, score, seq, opt, n_frames, n_seq, max_frames, max_seq,
-                       n_classes, log_z, rows);
-    hipLaunchKernelGGL(fullsum_backward_kernel<K>, dim3(batch), dim3(64), 0, st, score, seq, opt, n_frames, n_seq, max_frames, max_seq,
-                       n_classes, log_z, rows, class_post, state_post, occ);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t vc_fullsum_workspace_bytes(int32_t batch, int32_t max_frames, int32_t max_seq) {
-    if (!fs_shape_ok(batch, max_frames, max_seq)) return 0;
-    return fs_ws_bytes(batch, max_frames, max_seq);
+    const size_t need = fs_ws_bytes(batch, max_frames, max_seq);
+    return lat::shape_ok(batch, max_frames, max_seq, need) ? need : 0;
 }
 
 int vc_fullsum_f32(const float* d_score, const int32_t* d_seq, const uint8_t* d_opt, const int32_t* d_n_frames, const int32_t* d_n_seq,
                    int32_t batch, int32_t max_frames, int32_t max_seq, int32_t n_classes, float* d_log_z, float* d_class_post,
                    float* d_state_post, float* d_occ, void* d_workspace, size_t workspace_bytes, void* stream) {
-    VC_REQUIRE(d_score && d_seq && d_n_frames && d_n_seq && d_log_z && d_class_post && d_occ && d_workspace,
-               "vc_fullsum_f32: NULL argument");
-    VC_REQUIRE(batch >= 1 && max_frames >= 1 && max_seq >= 1 && n_classes >= 1,
-               "vc_fullsum_f32: bad shape (batch %d, max_frames %d, max_seq %d, n_classes %d; need all >= 1)", batch, max_frames, max_seq,
-               n_classes);
-    if (n_classes > FS_MAX_CLASSES || !fs_shape_ok(batch, max_frames, max_seq))
-        return vc::set_error(VC_ERR_UNSUPPORTED, "vc_fullsum_f32: limits are batch <= 65535, max_seq <= %d, n_classes <= %d and a "
-                             "workspace below 2 GiB; got batch %d, max_frames %d, max_seq %d, n_classes %d", FS_MAX_SEQ, FS_MAX_CLASSES,
-                             batch, max_frames, max_seq, n_classes);
-    VC_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 3) == 0, "vc_fullsum_f32: unaligned workspace");
     const size_t need = fs_ws_bytes(batch, max_frames, max_seq);
-    if (workspace_bytes < need)
-        return vc::set_error(VC_ERR_WORKSPACE, "vc_fullsum_f32: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (int rc = lat::check_args("vc_fullsum_f32", d_score && d_seq && d_n_frames && d_n_seq && d_log_z && d_class_post && d_occ &&
+                                 d_workspace, batch, max_frames, max_seq, n_classes, FS_MAX_CLASSES, d_workspace, workspace_bytes, need))
+        return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* rows = static_cast<float*>(d_workspace);
-    const int per_lane = (max_seq + 63) / 64;
-#define VC_FS_RUN(K) fs_launch<K>(batch, st, d_score, d_seq, d_opt, d_n_frames, d_n_seq, max_frames, max_seq, n_classes, d_log_z, \
-                                  d_class_post, d_state_post, d_occ, rows)
-    if (per_lane <= 1) VC_FS_RUN(1);
-    else if (per_lane <= 2) VC_FS_RUN(2);
-    else if (per_lane <= 4) VC_FS_RUN(4);
-    else if (per_lane <= 8) VC_FS_RUN(8);
-    else VC_FS_RUN(16);
-#undef VC_FS_RUN
+    lat::dispatch_per_lane(max_seq, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        hipLaunchKernelGGL(fullsum_forward_kernel<K>, dim3(batch), dim3(64), 0, st, d_score, d_seq, d_opt, d_n_frames, d_n_seq,
+                           max_frames, max_seq, n_classes, d_log_z, rows);
+        hipLaunchKernelGGL(fullsum_backward_kernel<K>, dim3(batch), dim3(64), 0, st, d_score, d_seq, d_opt, d_n_frames, d_n_seq,
+                           max_frames, max_seq, n_classes, d_log_z, rows, d_class_post, d_state_post, d_occ);
+    });
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }
