@@ -1426,6 +1426,62 @@ int vc_decode_f32(const float* d_score, const int32_t* d_n_frames, const float* 
                   int32_t* d_frame_class, int32_t* d_seg_label, int32_t* d_seg_start, int32_t* d_seg_end, int32_t* d_n_seg,
                   float* d_seg_score, float* d_total, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Duration.  Conversion keeps the source's timing: every output frame sits where its input frame sat.  These two launches
+ * move frames in time: an integer time map built from a segment table (as vc_phn_segments, vc_align_f32 and vc_decode_f32
+ * write it), and the resampling of a spectrogram along that map, before the vocoder (which rebuilds the phase, so nothing
+ * has to stay coherent).  Added without a version bump.  tests/warp_ref.py restates both; the device equals it bit for bit.
+ *
+ * vc_duration_map.  Inputs, all on the device: d_start, d_end [batch, max_seg] int32 (end exclusive) with d_n_seg [batch],
+ * clamped to [0, max_seg]; d_n_frames int32 [batch], clamped to [0, max_frames]: n.  An entry with start < 0 or
+ * end == start is ABSENT.  One of: d_out_len [batch, max_seg] int32, the output length of every present segment (>= 0); a
+ * rate table d_ratio_q int32 [n_classes], Q16 (65,536 = unchanged), every value clamped to [0, 8 * 65,536] when read, with
+ * d_label [batch, max_seg] (values in [0, n_classes)) or, without labels, n_classes == 1 and one rate for every segment;
+ * or neither (segments keep their length).  gap_q: the Q16 rate of the frames outside the segments.
+ *   Pieces   The present segments must be sorted, must not overlap and must lie in [0, n].  The frames between them,
+ *            before the first and from the last one to n are gap pieces.  Piece p has Li input frames from input offset S
+ *            and Lo output frames from output offset O (S, O: exclusive prefix sums): Lo = out_len[k], or
+ *            (Li * ratio_q[label] + 32768) >> 16 for a segment, (Li * gap_q + 32768) >> 16 for a gap.  Lo == 0 deletes it.
+ *   Map      output frame u of piece p, j = u - O:  pos = S * 65536 + ((2j + 1) * Li * 65536) / (2 * Lo) - 32768 (integer
+ *            division), clamped to [0, (n - 1) * 65536]: Q16 input frames, the centre-aligned map S + (j + 1/2) Li / Lo - 1/2
+ *            to within 2^-16, monotone across pieces, and exactly u * 65536 where every Lo == Li.
+ *   Flags    never an error.  1: the table is invalid (unsorted, overlapping, outside [0, n], end < start, a negative
+ *            out_len, a label outside the rate table); 2: the total is below min_frames; either way the utterance gets the
+ *            IDENTITY map (n frames).  4: the total exceeds out_frames and is cut there.  n == 0: n_out = 0, flags = 0.
+ * Outputs, every element written exactly once per call: d_pos [batch, out_frames] int32, -1 from n_out on; d_n_out [batch];
+ * d_out_start, d_out_end [batch, max_seg]: the present segments in output frames, clamped to n_out (a deleted segment has
+ * an empty range; under flag 2 the input table), -1 for absent entries, from n_seg on, under flag 1 and for n == 0;
+ * d_flags [batch].  One workgroup of 1,024 lanes per utterance: the table in tiles of 1,024 entries with the carried state
+ * in registers (a running maximum of the ends, a sum scan of the output lengths), then a binary search and one 64-bit
+ * division per output frame.  Everything read from the table is range-checked before use and forms no address.
+ * d_workspace (8-byte aligned): vc_duration_map_workspace_bytes = align256(batch * (max_seg + 1) * 8) (host arithmetic;
+ * 0 for a shape the launch would refuse; too small: VC_ERR_WORKSPACE).  Limits (VC_ERR_UNSUPPORTED beyond them, nothing
+ * launched): batch <= 65,535; max_seg, max_frames, out_frames <= 16,384; gap_q in [0, 8 * 65,536].
+ *
+ * vc_time_warp.  d_src [batch, max_frames, C] float32; d_pos [batch, out_frames] and d_n_out [batch] as above (n_out clamped
+ * to [0, out_frames], every pos to [0, (n - 1) * 65536] when read); d_n_frames [batch] or NULL (max_frames), clamped.
+ * VC_WARP_LINEAR: with i = pos >> 16, i1 = min(i + 1, n - 1) and w = (pos & 65535) * 2^-16 (exact),
+ * dst[u, :] = a + w * (b - a) of rows i and i1 -- three separately rounded float32 operations, no contraction; where w == 0
+ * it is row i itself and row i1 is not read.  VC_WARP_NEAREST: row min((pos + 32768) >> 16, n - 1).  Rows from n_out on
+ * (all rows when n == 0) are zero.  d_amp [batch, out_frames, C] or NULL: also the vocoder's magnitude of the warped
+ * value, exp10(0.05 * (max(0, v) / P_dB_norm_factor - 80)) (vc_compound_stitch's expression, realse == 1), 0 in the zero
+ * rows: bit-identical to vc_power_to_amp(dst, n_out).  Streaming: no LDS, no atomics, every destination element written
+ * once; 16-byte stores when out_frames * C is a multiple of 4, 16-byte reads when C is.  Limits: batch <= 65,535;
+ * max_frames, out_frames <= 16,384; frames * C < 2^30.
+ *
+ * Both are functions of their own utterance alone, bit-identical alone, in any batch, from run to run and under graph
+ * replay; lengths are read on the device; no allocation and no host wait; arguments are checked before any HIP call. */
+#define VC_WARP_LINEAR 0
+#define VC_WARP_NEAREST 1
+size_t vc_duration_map_workspace_bytes(int32_t batch, int32_t max_seg);
+int vc_duration_map(const int32_t* d_start, const int32_t* d_end, const int32_t* d_n_seg, const int32_t* d_label,
+                    const int32_t* d_out_len, const int32_t* d_ratio_q, int32_t n_classes, int32_t gap_q,
+                    const int32_t* d_n_frames, int32_t batch, int32_t max_seg, int32_t max_frames, int32_t min_frames,
+                    int32_t out_frames, int32_t* d_pos, int32_t* d_n_out, int32_t* d_out_start, int32_t* d_out_end,
+                    int32_t* d_flags, void* d_workspace, size_t workspace_bytes, void* stream);
+int vc_time_warp(const float* d_src, const int32_t* d_pos, const int32_t* d_n_out, const int32_t* d_n_frames, int32_t batch,
+                 int32_t max_frames, int32_t out_frames, int32_t C, int32_t mode, float* d_dst, float* d_amp,
+                 float P_dB_norm_factor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

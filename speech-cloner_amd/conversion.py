@@ -15,6 +15,11 @@ device: front-end -> vc_cut_windows -> encoder + decoder over window chunks -> v
 vc_phase_init -> Griffin-Lim, all tables computed on the host from the lengths before the first
 launch (``convert_plan``) and uploaded once; it returns cuda tensors.  ``wav_sr`` / ``out_sr`` put
 audio_lib's device resampler in front of and behind that chain for audio at another sample rate.
+
+``convert_duration_batch`` is ``convert_batch`` with the timing changed as well: between the stitch
+and the vocoder, ``duration_map_batch`` (vc_duration_map: an integer time map from a segment table and per-class rates or
+explicit lengths) and ``time_warp_batch`` (vc_time_warp) resample the stitched spectra; the output lengths stay on the
+device.  ``duration_stats_batch`` / ``duration_ratios`` turn two speakers' segment tables into the rate table.
 """
 from collections import namedtuple
 
@@ -242,6 +247,144 @@ def _numpy_phase(plan, n_bins, both):
     return ph
 
 
+_HOST_NT = namedtuple('convert_host', 'plan B hop n_fft n_bins h_lens h_lens_in h_nsamp utt_ids res_in res_out window_batch')
+_UP_NT = namedtuple('convert_upload', 'wav d_lens d_clip d_nout d_ids d_win d_utt d_true d_extra')
+
+
+def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
+                  res_type):
+    """The host checks and tables that convert_batch and convert_duration_batch share, before anything touches the GPU."""
+    import audio_lib
+    if getattr(wav, 'ndim', 0) != 2:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
+    h_lens = np.full((B,), Lmax, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    sr = cfg_d['sample_rate']
+    audio_lib._res_params(res_type)
+    res_in = wav_sr is not None and audio_lib._ratio(wav_sr, sr) != (1, 1)
+    res_out = vocode and out_sr is not None and audio_lib._ratio(sr, out_sr) != (1, 1)
+    h_lens_in = None
+    if res_in:
+        # lens count samples at wav_sr; everything below (checks, tables) works on the resampled lengths
+        if h_lens.shape != (B,) or h_lens.min() <= 0 or h_lens.max() > Lmax:
+            raise ValueError(' - ERROR, {}: lens must be [B] with 0 < len <= Lmax'.format(what))
+        h_lens_in, Lmax_in = h_lens, Lmax
+        h_lens, Lmax = audio_lib.resample_len(h_lens_in, wav_sr, sr), audio_lib.resample_len(Lmax_in, wav_sr, sr)
+        if h_lens.min() <= n_fft // 2:
+            raise ValueError(' - ERROR, {}: every utterance needs more than n_fft//2 = {} samples at {} Hz '
+                             '(shortest: {} after resampling from {} Hz)'.format(what, n_fft // 2, sr, int(h_lens.min()), wav_sr))
+    if h_lens.shape != (B,) or h_lens.min() <= n_fft // 2 or h_lens.max() > Lmax:
+        raise ValueError(' - ERROR, {}: lens must be [B] with n_fft//2 < len <= Lmax'.format(what))
+    if utt_ids is None:
+        utt_ids = np.arange(B)
+    utt_ids = np.asarray(utt_ids, dtype=np.int64).reshape(-1)
+    if utt_ids.shape != (B,) or utt_ids.min() < -2 ** 31 or utt_ids.max() >= 2 ** 31:
+        raise ValueError(' - ERROR, {}: utt_ids must be {} int32 values, one per utterance'.format(what, B))
+    window_batch = int(window_batch)
+    if window_batch <= 0:
+        raise ValueError(' - ERROR, {}: window_batch must be positive'.format(what))
+    if (decoder.encoder is None) == (encoder is None):
+        raise ValueError(' - ERROR, {}: pass encoder= exactly when the decoder was built without one'.format(what))
+    plan = convert_plan(h_lens, cfg_d, t_s, t_e, two_pass)
+    hop = int(cfg_d['hop_length'])
+    if vocode and hop * (int(plan.n_out.min()) - 1) <= n_fft // 2:
+        raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples'.format(what))
+    return _HOST_NT(plan, B, hop, n_fft, 1 + n_fft // 2, h_lens, h_lens_in, hop * (plan.n_out.astype(np.int64) - 1), utt_ids,
+                    res_in, res_out, window_batch)
+
+
+def _convert_upload(h, wav, extra):
+    """The waveforms if they are on the host, and one pinned table: the seven of the plan, the lengths at wav_sr when the
+    input is resampled, then ``extra`` (host int arrays); d_extra holds the device views of those last ones in that order."""
+    import torch
+    plan = h.plan
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
+    parts = [h.h_lens, plan.n_clip, plan.n_out, h.utt_ids, plan.win_tab, plan.utt_tab, plan.true_tab]
+    if h.res_in:
+        parts.append(h.h_lens_in)
+    parts += list(extra)
+    h_tab = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in parts])).pin_memory()
+    d_tab = h_tab.to('cuda', non_blocking=True)
+    offs = np.cumsum([0] + [a.size for a in parts])
+    d_lens, d_clip, d_nout, d_ids, d_win, d_utt, d_true = (d_tab[offs[i]:offs[i + 1]] for i in range(7))
+    d_extra = [d_tab[offs[i]:offs[i + 1]] for i in range(7, len(parts))]
+    return _UP_NT(wav, d_lens, d_clip, d_nout, d_ids, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2), d_extra)
+
+
+def _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type):
+    """Input resampling, front-end, windows and the model over window chunks: (mel_true, stft_true [B, Fout, C] and the
+    window batches y_mel, y_stft, y_phn [W, T, C] that compound_stitch takes)."""
+    import torch
+    import audio_lib
+    plan, hop, wav = h.plan, h.hop, up.wav
+    if h.res_in:
+        wav = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, cfg_d['sample_rate'], res_type), wav, up.d_extra[0])
+    mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(
+        wav, up.d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
+        win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
+        window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
+        mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
+        M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
+        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'], clip_output=cfg_d['clip_output'])
+    x = cut_windows(mfcc, up.d_win, up.d_clip, plan.T)
+    mel_true = cut_windows(mel, up.d_true, up.d_clip, plan.Fout)
+    stft_true = cut_windows(pdb, up.d_true, up.d_clip, plan.Fout)
+    if encoder is None:
+        outs = decoder.forward_chunks(x, h.window_batch, n_streams=2)
+    else:
+        outs = decoder.forward_chunks(x, h.window_batch, n_streams=2, width=x.shape[2],
+                                      fn=lambda xb: decoder.forward(encoder.forward(xb)['y_pred']))
+    main = torch.cuda.current_stream()
+    cols = []
+    for key in ('y_mel', 'y_stft', 'y_phn'):
+        ts = [o[key] for o in outs]
+        for t in ts:
+            t.record_stream(main)
+        cols.append(ts[0] if len(ts) == 1 else torch.cat(ts, 0))
+    return (mel_true, stft_true) + tuple(cols)
+
+
+def _vocoder_tail(cfg_d, d_nf, d_ids, n_iter, momentum, realse, seed, ph_true, ph_pred, stft_true, stft_pred, amp_pred):
+    """The vocoder behind a conversion, on frame counts that only the device needs to know (d_nf int32 [B]): the phase
+    start, the magnitudes, Griffin-Lim, de-emphasis and level.  stft_pred [B, F, bins]; amp_pred: its magnitude where a
+    kernel before this already made it (realse == 1), else None (vc_power_to_amp here); stft_true: None, or the true
+    spectrum to vocode as well.  ph_*: 'device' (one vc_phase_init from seed and d_ids, shared by both spectra), 'spsi' (from
+    each spectrum's own magnitudes) or a [B, F, bins] tensor.  Returns (y_wav_true | None, y_wav_pred) at the model's rate."""
+    import torch
+    import audio_lib
+    import _vc
+    B, F, n_bins = stft_pred.shape
+    hop = int(cfg_d['hop_length'])
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
+    lib = _vc.lib()
+    if isinstance(ph_pred, str) and ph_pred == 'device':
+        ph_true = ph_pred = audio_lib.phase_init(d_nf, F, n_bins, seed, d_ids)
+    elif isinstance(ph_pred, str):
+        ph_true = ph_pred = None                                   # 'spsi': from each spectrum's own magnitudes, in to_wav
+
+    def power_to_amp(P, rl):
+        amp = torch.empty_like(P)
+        _vc.check(lib.vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nf), B, F, n_bins, float(cfg_d['P_dB_norm_factor']),
+                                      float(rl), _vc.ptr(amp), _vc.current_stream()))
+        return amp
+
+    def to_wav(amp, ph):
+        if ph is None:
+            ph = audio_lib._phase_spsi_launch(amp, d_nf, vplan.n_fft, vplan.hop_length, plan=vplan)
+        w = audio_lib._griffin_lim_launch(vplan, amp, ph, d_nf, n_iter, False, momentum)
+        _vc.check(lib.vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(w), _vc.ptr(d_nf), B, F, w.shape[1],
+                                                   float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
+                                                   _vc.current_stream()))
+        return w
+
+    y_wav_true = to_wav(power_to_amp(stft_true, 1.0), ph_true) if stft_true is not None else None
+    y_wav_pred = to_wav(amp_pred if amp_pred is not None else power_to_amp(stft_pred, realse), ph_pred)
+    return y_wav_true, y_wav_pred
+
+
 def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True,
                   giffin_lim_input=False, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64,
                   vocode=True, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
@@ -274,41 +417,9 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
         raise ValueError(' - ERROR, convert_batch: cfg_d (the data-set configuration) is required')
     if isinstance(phase, str) and phase not in ('device', 'numpy', 'spsi'):
         raise ValueError(" - ERROR, convert_batch: phase must be 'device', 'numpy', 'spsi' or a [B, Fout, bins] array, got {!r}".format(phase))
-    if getattr(wav, 'ndim', 0) != 2:
-        raise ValueError(' - ERROR, convert_batch: wav must be [B, Lmax]')
-    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
-    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
-    h_lens = np.full((B,), Lmax, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
-    sr = cfg_d['sample_rate']
-    audio_lib._res_params(res_type)
-    res_in = wav_sr is not None and audio_lib._ratio(wav_sr, sr) != (1, 1)
-    res_out = vocode and out_sr is not None and audio_lib._ratio(sr, out_sr) != (1, 1)
-    if res_in:
-        # lens count samples at wav_sr; everything below (checks, tables) works on the resampled lengths
-        if h_lens.shape != (B,) or h_lens.min() <= 0 or h_lens.max() > Lmax:
-            raise ValueError(' - ERROR, convert_batch: lens must be [B] with 0 < len <= Lmax')
-        h_lens_in, Lmax_in = h_lens, Lmax
-        h_lens, Lmax = audio_lib.resample_len(h_lens_in, wav_sr, sr), audio_lib.resample_len(Lmax_in, wav_sr, sr)
-        if h_lens.min() <= n_fft // 2:
-            raise ValueError(' - ERROR, convert_batch: every utterance needs more than n_fft//2 = {} samples at {} Hz '
-                             '(shortest: {} after resampling from {} Hz)'.format(n_fft // 2, sr, int(h_lens.min()), wav_sr))
-    if h_lens.shape != (B,) or h_lens.min() <= n_fft // 2 or h_lens.max() > Lmax:
-        raise ValueError(' - ERROR, convert_batch: lens must be [B] with n_fft//2 < len <= Lmax')
-    if utt_ids is None:
-        utt_ids = np.arange(B)
-    utt_ids = np.asarray(utt_ids, dtype=np.int64).reshape(-1)
-    if utt_ids.shape != (B,) or utt_ids.min() < -2 ** 31 or utt_ids.max() >= 2 ** 31:
-        raise ValueError(' - ERROR, convert_batch: utt_ids must be {} int32 values, one per utterance'.format(B))
-    window_batch = int(window_batch)
-    if window_batch <= 0:
-        raise ValueError(' - ERROR, convert_batch: window_batch must be positive')
-    if (decoder.encoder is None) == (encoder is None):
-        raise ValueError(' - ERROR, convert_batch: pass encoder= exactly when the decoder was built without one')
-    plan = convert_plan(h_lens, cfg_d, t_s, t_e, two_pass)
-    hop, T, Fout = int(cfg_d['hop_length']), plan.T, plan.Fout
-    n_bins = 1 + n_fft // 2
-    if vocode and hop * (int(plan.n_out.min()) - 1) <= n_fft // 2:
-        raise ValueError(' - ERROR, convert_batch: every utterance needs hop_length*(frames-1) > n_fft//2 samples')
+    h = _convert_host('convert_batch', decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder,
+                      wav_sr, out_sr, res_type)
+    plan, B, Fout, n_bins, sr = h.plan, h.B, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
     both = bool(giffin_lim_input)
     h_phase = None
     if not isinstance(phase, str):
@@ -318,21 +429,8 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
         raise _vc.VCError('convert_batch needs a GPU (no CPU fallback)')
 
     # ---- uploads: the waveforms if they are on the host, one table, the host-drawn phase if asked for
-    if not torch.is_tensor(wav):
-        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
-    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
-    parts = [h_lens, plan.n_clip, plan.n_out, utt_ids, plan.win_tab, plan.utt_tab, plan.true_tab]
-    h_nsamp = hop * (plan.n_out.astype(np.int64) - 1)
-    if res_in:
-        parts.append(h_lens_in)
-    if res_out:
-        parts.append(h_nsamp)
-    h_tab = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.int32).reshape(-1) for a in parts])).pin_memory()
-    d_tab = h_tab.to('cuda', non_blocking=True)
-    offs = np.cumsum([0] + [a.size for a in parts])
-    d_lens, d_clip, d_nout, d_ids, d_win, d_utt, d_true = (d_tab[offs[i]:offs[i + 1]] for i in range(7))
-    d_extra = [d_tab[offs[i]:offs[i + 1]] for i in range(7, len(parts))]
-    d_win, d_utt, d_true = d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2)
+    up = _convert_upload(h, wav, [h.h_nsamp] if h.res_out else [])
+    d_nout, d_ids, d_utt, d_extra = up.d_nout, up.d_ids, up.d_utt, up.d_extra
     if vocode and isinstance(phase, str) and phase == 'numpy':
         h_phase = torch.from_numpy(_numpy_phase(plan, n_bins, both)).pin_memory()
         d_phase = h_phase.to('cuda', non_blocking=True)
@@ -343,31 +441,7 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
         ph_true = ph_pred = phase.to(device='cuda', dtype=torch.float32).contiguous()
 
     # ---- front-end, windows, model, stitch
-    if res_in:
-        wav = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), wav, d_extra[0])
-    mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(
-        wav, d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
-        win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
-        window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
-        mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
-        M_dB_norm_factor=cfg_d['M_dB_norm_factor'], P_dB_norm_factor=cfg_d['P_dB_norm_factor'],
-        mean_abs_amp_norm=cfg_d['mean_abs_amp_norm'], clip_output=cfg_d['clip_output'])
-    x = cut_windows(mfcc, d_win, d_clip, T)
-    mel_true = cut_windows(mel, d_true, d_clip, Fout)
-    stft_true = cut_windows(pdb, d_true, d_clip, Fout)
-    if encoder is None:
-        outs = decoder.forward_chunks(x, window_batch, n_streams=2)
-    else:
-        outs = decoder.forward_chunks(x, window_batch, n_streams=2, width=x.shape[2],
-                                      fn=lambda xb: decoder.forward(encoder.forward(xb)['y_pred']))
-    main = torch.cuda.current_stream()
-    cols = []
-    for key in ('y_mel', 'y_stft', 'y_phn'):
-        ts = [o[key] for o in outs]
-        for t in ts:
-            t.record_stream(main)
-        cols.append(ts[0] if len(ts) == 1 else torch.cat(ts, 0))
-    y_mel, y_stft, y_phn = cols
+    mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
     mel_pred = compound_stitch(y_mel, d_utt, Fout)
     phn_pred = compound_stitch(y_phn, d_utt, Fout)
     fused = vocode and float(realse) == 1.0
@@ -376,39 +450,414 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     else:
         stft_pred = compound_stitch(y_stft, d_utt, Fout)
     n_frames = [int(v) for v in plan.n_out]
-    n_samples = [int(v) for v in h_nsamp]
+    n_samples = [int(v) for v in h.h_nsamp]
     if not vocode:
         return _BATCH_NT(None, None, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
 
     # ---- vocoder
-    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
-    lib = _vc.lib()
-    if isinstance(phase, str) and phase == 'device':
-        ph_true = ph_pred = audio_lib.phase_init(d_nout, Fout, n_bins, seed, d_ids)
-    elif isinstance(phase, str) and phase == 'spsi':
-        ph_true = ph_pred = None                                   # from each spectrum's own magnitudes, in to_wav
-
-    def power_to_amp(P, rl):
-        amp = torch.empty_like(P)
-        _vc.check(lib.vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nout), B, Fout, n_bins, float(cfg_d['P_dB_norm_factor']),
-                                      float(rl), _vc.ptr(amp), _vc.current_stream()))
-        return amp
-
-    def to_wav(amp, ph):
-        if ph is None:
-            ph = audio_lib._phase_spsi_launch(amp, d_nout, vplan.n_fft, vplan.hop_length, plan=vplan)
-        w = audio_lib._griffin_lim_launch(vplan, amp, ph, d_nout, n_iter, False, momentum)
-        _vc.check(lib.vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(w), _vc.ptr(d_nout), B, Fout, w.shape[1],
-                                                   float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
-                                                   _vc.current_stream()))
-        return w
-
-    y_wav_true = to_wav(power_to_amp(stft_true, 1.0), ph_true) if both else None
-    y_wav_pred = to_wav(amp_pred if fused else power_to_amp(stft_pred, realse), ph_pred)
-    if res_out:
+    if isinstance(phase, str) and phase != 'numpy':
+        ph_true = ph_pred = phase                                  # 'device' / 'spsi': made in the tail
+    y_wav_true, y_wav_pred = _vocoder_tail(cfg_d, d_nout, d_ids, n_iter, momentum, realse, seed, ph_true, ph_pred,
+                                           stft_true if both else None, stft_pred, amp_pred if fused else None)
+    if h.res_out:
         rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
         y_wav_pred = audio_lib._resample_launch(rplan, y_wav_pred, d_extra[-1])
         if both:
             y_wav_true = audio_lib._resample_launch(rplan, y_wav_true, d_extra[-1])
-        n_samples = [int(v) for v in audio_lib.resample_len(h_nsamp, sr, out_sr)]
+        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
     return _BATCH_NT(y_wav_true, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
+
+
+# --------------------------------------------------------------------------- duration (csrc/vc_warp.hip)
+WARP_MAX_FRAMES = 16384     # vc_duration_map, vc_time_warp: input frames, output frames, table entries
+WARP_MAX_RATIO = 8.0
+WARP_Q = 65536
+FLAG_INVALID, FLAG_SHORT, FLAG_TRUNCATED = 1, 2, 4
+_MAP_NT = namedtuple('duration_map', 'pos n_out out_start out_end flags max_frames')
+_STATS_NT = namedtuple('duration_stats', 'count total')
+_DUR_NT = namedtuple('convert_duration', 'y_wav_pred n_samples mel_pred stft_pred phn_pred n_frames flags seg map max_frames '
+                                         'max_samples src_frames')
+_DUR_SEG_NT = namedtuple('duration_segments', 'labels start end n_seg')
+
+
+def _i32_device(a, shape, what):
+    """int32 of the given shape on the device: a cuda tensor is checked and used as it is, a host array goes up pinned."""
+    import torch
+    if torch.is_tensor(a) and a.is_cuda:
+        if a.dtype != torch.int32 or tuple(a.shape) != tuple(shape):
+            raise ValueError(' - ERROR, {} on the device must be int32 {}, got {} {}'.format(what, list(shape), a.dtype, list(a.shape)))
+        return a.contiguous()
+    h = np.asarray(a.cpu() if torch.is_tensor(a) else a)
+    if h.shape != tuple(shape) or h.dtype.kind not in 'iu' or (h.size and (h.min() < -2 ** 31 or h.max() >= 2 ** 31)):
+        raise ValueError(' - ERROR, {} must be integers of shape {}'.format(what, list(shape)))
+    return torch.from_numpy(np.ascontiguousarray(h, dtype=np.int32)).pin_memory().to('cuda', non_blocking=True)
+
+
+def ratio_to_q(ratio):
+    """Q16 rates as the launch takes them: float32, times 65,536 (exact), rounded to the nearest integer with ties to even,
+    clamped to [0, 8 * 65,536].  A host array gives a numpy int32 array, a tensor an int32 tensor on its device."""
+    import torch
+    if torch.is_tensor(ratio):
+        return torch.round(ratio.to(torch.float32) * float(WARP_Q)).clamp(0, WARP_MAX_RATIO * WARP_Q).to(torch.int32)
+    r = np.rint(np.asarray(ratio, dtype=np.float32) * np.float32(WARP_Q))
+    return np.clip(r, 0, WARP_MAX_RATIO * WARP_Q).astype(np.int32)
+
+
+def _check_ratio_scalar(r, what):
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not 0.0 <= float(r) <= WARP_MAX_RATIO:
+        raise ValueError(' - ERROR, {} must be a number in [0, {}], got {!r}'.format(what, WARP_MAX_RATIO, r))
+    return int(ratio_to_q(float(r)))
+
+
+def duration_max_frames(n_max, n_pieces, ratio_max_q):
+    """The default output bound of duration_map_batch in rate mode (host integers): see the proof there."""
+    n_max, p = int(n_max), min(int(n_pieces), int(n_max))
+    return max(n_max, (n_max * int(ratio_max_q) + WARP_Q - 1) // WARP_Q + (p + 1) // 2)
+
+
+def duration_map_batch(start, end, n_seg, lens, out_len=None, labels=None, ratio=None, gap_ratio=1.0, max_frames=None,
+                       min_frames=1):
+    """The integer time map of B utterances from their segment tables (vc_duration_map; the definition is in
+    include/vc_hip.h, "Duration", the numpy restatement in tests/warp_ref.py).
+
+    start, end [B, K] int32 (end exclusive) and n_seg [B]: a segment table in frames as phn_segments_batch, align_batch and
+    decode_batch return it (device tensors or host arrays; an entry with start < 0 or end == start is absent).  lens: the
+    frame counts n, host integers or an int32 [B] device tensor.  One of
+      out_len [B, K] int32   the output length of every present segment (0 deletes it),
+      ratio                  floats [C] indexed by labels [B, K] (or one number for every segment, without labels): the
+                             segment gets round(Li * ratio) frames; rounded to Q16 on the device when it is a device tensor,
+      neither                segments keep their length.
+    gap_ratio: the rate of the frames outside the segments.  Rates lie in [0, 8].  min_frames: an utterance whose total
+    would fall below it keeps the identity map (flag 2).  max_frames: the host-known bound Fw_max of the output; an
+    utterance that exceeds it is cut there (flag 4).
+
+    The default max_frames (rate mode, host lens) cannot truncate.  Proof: the pieces' input lengths Li add up to n, a
+    piece of Li == 0 gets Lo == 0, and a piece of Li > 0 gets Lo = (Li * q + 32768) >> 16 <= Li * q / 65536 + 1/2 with
+    q <= q_max, the largest Q16 rate in play (ratio's maximum and gap_ratio; 8 * 65536 for a ratio that lives on the
+    device).  There are at most P = min(2 K + 1, n) pieces of Li > 0, so the total is at most n * q_max / 65536 + P / 2, and
+    being an integer at most ceil(n * q_max / 65536) + ceil(P / 2) -- the default, taken at the longest utterance (it grows
+    with n), raised to n_max itself for the identity map of flags 1 and 2, and capped at the launch's limit of 16,384 (only
+    then can flag 4 appear).  With out_len, or with lens on the device, the bound is not derivable: pass max_frames.
+
+    Returns a namedtuple of device tensors: pos [B, max_frames] int32 (Q16 input frames, -1 from n_out on), n_out [B],
+    out_start / out_end [B, K] (the table in output frames), flags [B] (1 invalid table, 2 below min_frames: identity map;
+    4 truncated) and the host integer max_frames.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    import _vc
+    what = 'duration_map_batch'
+    if getattr(start, 'ndim', 0) != 2 or start.shape[1] < 1 or start.shape[0] < 1:
+        raise ValueError(' - ERROR, {}: start must be [B, K] with B, K >= 1'.format(what))
+    B, K = int(start.shape[0]), int(start.shape[1])
+    if out_len is not None and (ratio is not None or labels is not None):
+        raise ValueError(' - ERROR, {}: out_len excludes ratio and labels'.format(what))
+    if labels is not None and ratio is None:
+        raise ValueError(' - ERROR, {}: labels index ratio; pass both'.format(what))
+    if B > 65535 or K > WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of at most {} table entries'.format(what, WARP_MAX_FRAMES))
+    gap_q = _check_ratio_scalar(gap_ratio, what + ': gap_ratio')
+    if isinstance(min_frames, bool) or not isinstance(min_frames, (int, np.integer)) or not 0 <= min_frames <= WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: min_frames must be an integer in [0, {}]'.format(what, WARP_MAX_FRAMES))
+    lens_dev = torch.is_tensor(lens) and lens.is_cuda
+    n_max = None
+    if not lens_dev:
+        h_lens = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+        if h_lens.shape != (B,) or h_lens.dtype.kind not in 'iu' or h_lens.min() < 0 or h_lens.max() > WARP_MAX_FRAMES:
+            raise ValueError(' - ERROR, {}: lens must be {} integers in [0, {}]'.format(what, B, WARP_MAX_FRAMES))
+        n_max = int(h_lens.max())
+    q_max = gap_q
+    if ratio is not None:
+        if not torch.is_tensor(ratio):
+            ratio = np.atleast_1d(np.asarray(ratio, dtype=np.float32))
+            if ratio.ndim != 1 or not np.isfinite(ratio).all() or ratio.min() < 0 or ratio.max() > WARP_MAX_RATIO:
+                raise ValueError(' - ERROR, {}: ratio must be finite floats [C] in [0, {}]'.format(what, WARP_MAX_RATIO))
+            q_max = max(q_max, int(ratio_to_q(ratio).max()))
+        else:
+            if ratio.ndim != 1 or not ratio.is_floating_point():
+                raise ValueError(' - ERROR, {}: ratio must be floats [C]'.format(what))
+            q_max = int(WARP_MAX_RATIO * WARP_Q)
+        if ratio.shape[0] < 1 or (labels is None and ratio.shape[0] != 1):
+            raise ValueError(' - ERROR, {}: without labels ratio is one number; with labels it is [C], C >= 1'.format(what))
+    if max_frames is None:
+        if out_len is not None or n_max is None:
+            raise ValueError(' - ERROR, {}: max_frames is required with out_len and with lens on the device'.format(what))
+        max_frames = min(max(duration_max_frames(n_max, 2 * K + 1, q_max), 1), WARP_MAX_FRAMES)
+    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not 1 <= max_frames <= WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: max_frames must be an integer in [1, {}]'.format(what, WARP_MAX_FRAMES))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('duration_map_batch needs a GPU (no CPU fallback)')
+    d_start, d_end = _i32_device(start, (B, K), what + ': start'), _i32_device(end, (B, K), what + ': end')
+    d_nseg, d_lens = _i32_device(n_seg, (B,), what + ': n_seg'), _i32_device(lens, (B,), what + ': lens')
+    d_len = None if out_len is None else _i32_device(out_len, (B, K), what + ': out_len')
+    d_lab = None if labels is None else _i32_device(labels, (B, K), what + ': labels')
+    d_ratio = None
+    if ratio is not None:
+        if torch.is_tensor(ratio):
+            d_ratio = ratio_to_q(ratio.to('cuda', non_blocking=True)).contiguous()
+        else:
+            d_ratio = _i32_device(ratio_to_q(ratio), ratio.shape, what + ': ratio')
+    return _map_launch(d_start, d_end, d_nseg, d_lab, d_len, d_ratio, gap_q, d_lens, WARP_MAX_FRAMES if n_max is None else max(n_max, 1),
+                       int(min_frames), int(max_frames))
+
+
+def _map_launch(d_start, d_end, d_nseg, d_lab, d_len, d_ratio, gap_q, d_lens, in_frames, min_frames, Fw):
+    """vc_duration_map on validated device tensors: no host check, copy or wait in here."""
+    import torch
+    import _vc
+    lib = _vc.lib()
+    B, K = d_start.shape
+    dev = d_start.device
+    pos = torch.empty((B, Fw), dtype=torch.int32, device=dev)
+    tab = torch.empty((2, B, K), dtype=torch.int32, device=dev)
+    small = torch.empty((2, B), dtype=torch.int32, device=dev)
+    need = lib.vc_duration_map_workspace_bytes(B, K)
+    if need == 0:
+        raise _vc.VCError('vc_duration_map_workspace_bytes refused {} utterances of {} table entries'.format(B, K))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _vc.check(lib.vc_duration_map(_vc.ptr(d_start), _vc.ptr(d_end), _vc.ptr(d_nseg), _vc.ptr(d_lab), _vc.ptr(d_len), _vc.ptr(d_ratio),
+                                  0 if d_ratio is None else d_ratio.shape[0], gap_q, _vc.ptr(d_lens), B, K, in_frames, min_frames, Fw,
+                                  _vc.ptr(pos), _vc.ptr(small[0]), _vc.ptr(tab[0]), _vc.ptr(tab[1]), _vc.ptr(small[1]), _vc.ptr(ws),
+                                  need, _vc.current_stream()))
+    return _MAP_NT(pos, small[0], tab[0], tab[1], small[1], Fw)
+
+
+def _warp_launch(x, pos, n_out, d_lens, mode, P_dB_norm_factor=None):
+    """vc_time_warp on validated device tensors; with P_dB_norm_factor also the vocoder's magnitude: (warped, amp)."""
+    import torch
+    import _vc
+    B, F, C = x.shape
+    Fw = pos.shape[1]
+    out = torch.empty((B, Fw, C), dtype=torch.float32, device=x.device)
+    amp = torch.empty_like(out) if P_dB_norm_factor is not None else None
+    _vc.check(_vc.lib().vc_time_warp(_vc.ptr(x), _vc.ptr(pos), _vc.ptr(n_out), _vc.ptr(d_lens), B, F, Fw, C, mode, _vc.ptr(out),
+                                     _vc.ptr(amp), float(P_dB_norm_factor or 0.0), _vc.current_stream()))
+    return out if P_dB_norm_factor is None else (out, amp)
+
+
+_WARP_MODES = {'linear': 0, 'nearest': 1}                           # VC_WARP_LINEAR, VC_WARP_NEAREST
+
+
+def time_warp_batch(x, pos, n_out, lens, mode='linear', P_dB_norm_factor=None):
+    """Resamples x [B, F, C] float32 (cuda tensor or numpy array) along a time map (vc_time_warp): pos [B, Fw] int32 Q16
+    input frames and n_out [B], device tensors as duration_map_batch returns them; lens: the input frame counts, host
+    integers, an int32 [B] device tensor or None (all F).  mode 'linear': row u is a + w * (b - a) of the two input rows
+    around pos[u] (three float32 roundings; the row itself where pos[u] is a whole frame), 'nearest': the nearest row.
+    Rows from n_out on are zero.  With P_dB_norm_factor also the vocoder's magnitude of the warped spectrum (what
+    vc_power_to_amp gives with realse == 1, bit for bit): returns (warped, amp).  Nothing is copied back."""
+    import torch
+    import _vc
+    what = 'time_warp_batch'
+    if mode not in _WARP_MODES:
+        raise ValueError(" - ERROR, {}: mode must be 'linear' or 'nearest', got {!r}".format(what, mode))
+    if getattr(x, 'ndim', 0) != 3 or min(x.shape) < 1:
+        raise ValueError(' - ERROR, {}: x must be [B, F, C]'.format(what))
+    B, F, C = (int(v) for v in x.shape)
+    if not (torch.is_tensor(pos) and pos.is_cuda and pos.dtype == torch.int32 and pos.ndim == 2 and pos.shape[0] == B and pos.shape[1] >= 1):
+        raise ValueError(' - ERROR, {}: pos must be an int32 [B, Fw] device tensor'.format(what))
+    Fw = int(pos.shape[1])
+    if B > 65535 or F > WARP_MAX_FRAMES or Fw > WARP_MAX_FRAMES or max(F, Fw) * C >= 2 ** 30:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of at most {} frames in and out, frames * C < 2^30'.format(what, WARP_MAX_FRAMES))
+    if P_dB_norm_factor is not None and float(P_dB_norm_factor) == 0.0:
+        raise ValueError(' - ERROR, {}: P_dB_norm_factor is 0'.format(what))
+    if lens is not None and not (torch.is_tensor(lens) and lens.is_cuda):
+        h = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+        if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > F:
+            raise ValueError(' - ERROR, {}: lens must be {} integers in [0, {}]'.format(what, B, F))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('time_warp_batch needs a GPU (no CPU fallback)')
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    x = x.to(device='cuda', dtype=torch.float32).contiguous()
+    d_lens = None if lens is None else _i32_device(lens, (B,), what + ': lens')
+    return _warp_launch(x, pos.contiguous(), _i32_device(n_out, (B,), what + ': n_out'), d_lens, _WARP_MODES[mode], P_dB_norm_factor)
+
+
+def duration_stats_batch(labels, start, end, n_seg, n_classes):
+    """Per-class segment count and total length (frames) over a batch of segment tables, as align_batch / decode_batch
+    return them: (count [C], total [C]) int64 tensors on the tables' device.  Entries from n_seg on, absent entries
+    (start < 0 or end <= start) and labels outside [0, C) are left out.  Plain torch (index_add_): no kernel of this
+    library, nothing copied back."""
+    import torch
+    labels, start, end, n_seg = (torch.as_tensor(t) for t in (labels, start, end, n_seg))
+    C = int(n_classes)
+    K = labels.shape[-1]
+    k = torch.arange(K, device=labels.device)
+    keep = (k[None, :] < n_seg.reshape(-1, 1)) & (start >= 0) & (end > start) & (labels >= 0) & (labels < C)
+    idx = labels.clamp(0, C - 1).reshape(-1).long()
+    count = torch.zeros((C,), dtype=torch.int64, device=labels.device).index_add_(0, idx, keep.reshape(-1).long())
+    total = torch.zeros((C,), dtype=torch.int64, device=labels.device).index_add_(0, idx, ((end - start) * keep).reshape(-1).long())
+    return _STATS_NT(count, total)
+
+
+def duration_ratios(stats_src, stats_tgt, lo=0.5, hi=2.0, min_count=1):
+    """The rate table that gives the source's phonemes the target's mean durations: per class
+    clamp(mean_tgt / mean_src, lo, hi) with mean = total / count of duration_stats_batch, and 1 where either side has
+    fewer than ``min_count`` segments (or no frames).  float32 [C] on the statistics' device; no synchronisation."""
+    import torch
+    if not 0.0 <= float(lo) <= float(hi) <= WARP_MAX_RATIO:
+        raise ValueError(' - ERROR, duration_ratios: need 0 <= lo <= hi <= {}'.format(WARP_MAX_RATIO))
+    cs, ts, ct, tt = (torch.as_tensor(t) for t in (stats_src[0], stats_src[1], stats_tgt[0], stats_tgt[1]))
+    mc = max(int(min_count), 1)
+    ok = (cs >= mc) & (ct >= mc) & (ts > 0) & (tt > 0)
+    one = torch.ones_like(ts, dtype=torch.float64)
+    num = torch.where(ok, tt.double() * cs.double(), one)
+    den = torch.where(ok, ts.double() * ct.double(), one)
+    return torch.where(ok, (num / den).clamp(float(lo), float(hi)), one).to(torch.float32)
+
+
+def duration_min_frames(cfg_d):
+    """The fewest frames the vocoder takes: hop * (frames - 1) > n_fft // 2."""
+    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
+    return (n_fft // 2) // int(cfg_d['hop_length']) + 2
+
+
+def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio=None, gap_ratio=1.0, segments='decode',
+                           decode=None, out_len=None, max_frames=None, mode='linear', t_s=0, t_e=60, n_iter=200, realse=1.0,
+                           two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64, encoder=None,
+                           wav_sr=None, out_sr=None, res_type='kaiser_best'):
+    """``convert_batch`` with the timing changed as well: the stitched spectra are resampled along an integer time map
+    (duration_map_batch, time_warp_batch) before the vocoder, which rebuilds the phase for the new timing.
+
+    One of
+      rate=r            every utterance as one piece: round(frames * r) output frames (0 < r <= 8); needs no segments;
+      ratio=[C floats]  a rate per phoneme class (duration_ratios builds one from two speakers' alignments), gap_ratio for
+                        the frames outside the segments;
+      out_len [B, K]    an explicit length per segment.
+    segments (ratio / out_len): 'decode' -- decode_batch on the stitched posteriors ``phn_pred`` (probabilities: kind='prob';
+    ``decode``: a dict of its other arguments, e.g. trans, penalty, min_dur, class_map) -- or a table (labels, start, end,
+    n_seg) in stitched-frame coordinates, e.g. from align_batch.  The other arguments are convert_batch's; phase='numpy'
+    draws per host-known length and is refused here.  max_frames: the bound of the output frames (default: exact for
+    rate=, duration_map_batch's proven bound for a host ratio, required otherwise).
+
+    Every utterance keeps at least duration_min_frames(cfg_d) frames, so the vocoder never sees a length it cannot take:
+    an utterance whose table is invalid, or whose total would fall below that, keeps its own timing (flags 1, 2).
+
+    Returns a namedtuple: y_wav_pred [B, max_samples], mel_pred / stft_pred / phn_pred [B, max_frames, C] (warped; zero
+    beyond an utterance's extent), the DEVICE tensors n_frames, n_samples (= hop * (n_frames - 1), at out_sr when
+    resampled) and flags [B], seg = (labels, start, end, n_seg) the segment table in output frames, map (the
+    duration_map_batch result), the host bounds max_frames and max_samples, and src_frames (convert_batch's host
+    n_frames).  Nothing is copied back and the host waits for nothing."""
+    import torch
+    import audio_lib
+    import _vc
+    what = 'convert_duration_batch'
+    momentum = _check_momentum(momentum)
+    seed = audio_lib.check_seed(seed)
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    if isinstance(phase, str) and phase not in ('device', 'spsi'):
+        raise ValueError(" - ERROR, {}: phase must be 'device', 'spsi' or a [B, max_frames, bins] array ('numpy' needs host "
+                         "lengths), got {!r}".format(what, phase))
+    if mode not in _WARP_MODES:
+        raise ValueError(" - ERROR, {}: mode must be 'linear' or 'nearest', got {!r}".format(what, mode))
+    if sum(v is not None for v in (rate, ratio, out_len)) != 1:
+        raise ValueError(' - ERROR, {}: pass exactly one of rate, ratio and out_len'.format(what))
+    if rate is not None:
+        if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not 0.0 < float(rate) <= WARP_MAX_RATIO:
+            raise ValueError(' - ERROR, {}: rate must be a number in (0, {}], got {!r}'.format(what, WARP_MAX_RATIO, rate))
+        rate_q = int(ratio_to_q(float(rate)))
+    gap_q = _check_ratio_scalar(gap_ratio, what + ': gap_ratio')
+    table = None
+    if rate is None and not (isinstance(segments, str) and segments == 'decode'):
+        if isinstance(segments, str) or len(segments) != 4:
+            raise ValueError(" - ERROR, {}: segments must be 'decode' or (labels, start, end, n_seg)".format(what))
+        table = segments
+    if decode is not None and (rate is not None or table is not None):
+        raise ValueError(" - ERROR, {}: decode is for segments='decode'".format(what))
+    kw = dict(trans=None, penalty=0.0, init=None, final=None, min_dur=3, class_map=None, floor=1e-10)
+    extra = set(decode or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: decode takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(decode or {})
+    h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
+                      res_type)
+    plan, B, hop, Fout, n_bins = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins
+    min_frames = duration_min_frames(cfg_d)
+    if Fout > WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, WARP_MAX_FRAMES, Fout))
+    K = 1 if rate is not None else (Fout if table is None else int(table[1].shape[1]))
+    if rate is not None:
+        want = (plan.n_out.astype(np.int64) * rate_q + 32768) >> 16
+        if want.min() < min_frames:
+            raise ValueError(' - ERROR, {}: rate {} leaves an utterance {} frames; the vocoder needs {}'.format(what, rate, int(want.min()), min_frames))
+        bound = int(want.max())
+    elif ratio is not None and not torch.is_tensor(ratio):
+        r = np.atleast_1d(np.asarray(ratio, dtype=np.float32))
+        if r.ndim != 1 or not np.isfinite(r).all() or r.min() < 0 or r.max() > WARP_MAX_RATIO:
+            raise ValueError(' - ERROR, {}: ratio must be finite floats [C] in [0, {}]'.format(what, WARP_MAX_RATIO))
+        ratio = r
+        bound = duration_max_frames(Fout, 2 * K + 1, max(gap_q, int(ratio_to_q(r).max())))
+    else:
+        if ratio is not None and (ratio.ndim != 1 or not ratio.is_floating_point()):
+            raise ValueError(' - ERROR, {}: ratio must be floats [C]'.format(what))
+        bound = None
+    if max_frames is None:
+        if bound is None:
+            raise ValueError(' - ERROR, {}: max_frames is required with out_len and with a ratio on the device'.format(what))
+        max_frames = min(bound, WARP_MAX_FRAMES)
+    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not min_frames <= max_frames <= WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: max_frames must be an integer in [{}, {}]'.format(what, min_frames, WARP_MAX_FRAMES))
+    Fw = int(max_frames)
+    if not isinstance(phase, str) and tuple(phase.shape) != (B, Fw, n_bins):
+        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, B, Fw, n_bins))
+    dec = cmap = None
+    if rate is None and table is None:                              # the decoder's arguments, before anything is launched
+        import evaluation
+        C = int((encoder if encoder is not None else decoder.encoder).cfg_d['n_output'])
+        evaluation._check_decode_size(B, Fout, C, what)
+        cmap = evaluation._check_class_map(kw.pop('class_map'), C, what)
+        dec = evaluation._decode_args(C=C, what=what, kind='prob', **kw)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('convert_duration_batch needs a GPU (no CPU fallback)')
+
+    up = _convert_upload(h, wav, [])
+    d_nout = up.d_nout
+    if not isinstance(phase, str):
+        if not torch.is_tensor(phase):
+            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
+        phase = phase.to(device='cuda', dtype=torch.float32).contiguous()
+    _, _, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
+    mel_s, phn_s, stft_s = (compound_stitch(y, up.d_utt, Fout) for y in (y_mel, y_phn, y_stft))
+
+    # ---- the segment table in stitched frames, the map
+    dev = mel_s.device
+    d_lab = d_len = d_ratio = None
+    if rate is not None:
+        d_start = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+        d_end, d_nseg = d_nout.view(B, 1), torch.ones((B,), dtype=torch.int32, device=dev)
+        d_ratio = torch.full((1,), rate_q, dtype=torch.int32, device=dev)
+    else:
+        if table is None:
+            r = evaluation._decode_launch(phn_s, d_nout, evaluation._cmap_device(cmap), evaluation._decode_upload(dec))
+            d_lab, d_start, d_end, d_nseg = r.seg.labels, r.seg.start, r.seg.end, r.seg.n_seg
+        else:
+            d_lab, d_start, d_end = (_i32_device(t, (B, K), what + ': segments') for t in table[:3])
+            d_nseg = _i32_device(table[3], (B,), what + ': segments n_seg')
+        if out_len is not None:
+            d_len = _i32_device(out_len, (B, K), what + ': out_len')
+        elif torch.is_tensor(ratio):
+            d_ratio = ratio_to_q(ratio.to('cuda', non_blocking=True)).contiguous()
+        else:
+            d_ratio = _i32_device(ratio_to_q(ratio), ratio.shape, what + ': ratio')
+    m = _map_launch(d_start, d_end, d_nseg, None if d_ratio is None or rate is not None else d_lab, d_len, d_ratio, gap_q, d_nout,
+                    Fout, min_frames, Fw)
+
+    # ---- the warp, the vocoder
+    wm = _WARP_MODES[mode]
+    mel_pred = _warp_launch(mel_s, m.pos, m.n_out, d_nout, wm)
+    phn_pred = _warp_launch(phn_s, m.pos, m.n_out, d_nout, wm)
+    amp_pred = None
+    if float(realse) == 1.0:
+        stft_pred, amp_pred = _warp_launch(stft_s, m.pos, m.n_out, d_nout, wm, cfg_d['P_dB_norm_factor'])
+    else:
+        stft_pred = _warp_launch(stft_s, m.pos, m.n_out, d_nout, wm)
+    _, y_wav_pred = _vocoder_tail(cfg_d, m.n_out, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, amp_pred)
+    n_samples = (hop * (m.n_out - 1)).clamp_min(0)
+    max_samples = hop * (Fw - 1)
+    if h.res_out:
+        sr = cfg_d['sample_rate']
+        rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
+        y_wav_pred = audio_lib._resample_launch(rplan, y_wav_pred, n_samples)
+        n_samples = torch.div(n_samples.long() * rplan.up + (rplan.down - 1), rplan.down, rounding_mode='floor').to(torch.int32)
+        max_samples = int(audio_lib.resample_len(max_samples, sr, out_sr))
+    return _DUR_NT(y_wav_pred, n_samples, mel_pred, stft_pred, phn_pred, m.n_out, m.flags,
+                   _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg), m, Fw, max_samples, [int(v) for v in plan.n_out])

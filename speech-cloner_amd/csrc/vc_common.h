@@ -103,6 +103,41 @@ __device__ __forceinline__ ArgMax wave_argmax_low(float v, int idx) {
     }
     return {v, idx};
 }
+
+// Exclusive scans over a workgroup of NW waves: the value of the lanes before this one combined (the identity for lane
+// 0: 0 for the sum, -1 for the maximum) and, in `total`, of all lanes.  Inside a wave by shuffles, the waves' totals
+// through wtot[NW] in LDS; two barriers a scan, every lane of the workgroup must call it.
+template <bool SUM, int NW>
+__device__ inline int block_scan_excl(int v, int* wtot, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ident = SUM ? 0 : -1;
+    int inc = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int u = __shfl_up(inc, s, 64);
+        if (lane >= s) inc = SUM ? inc + u : max(inc, u);
+    }
+    int excl = __shfl_up(inc, 1, 64);
+    if (lane == 0) excl = ident;
+    __syncthreads();                                                // the previous scan's reads of wtot
+    if (lane == 63) wtot[wave] = inc;
+    __syncthreads();
+    int off = ident, all = ident;
+    for (int w = 0; w < NW; ++w) {
+        const int x = wtot[w];
+        if (w < wave) off = SUM ? off + x : max(off, x);
+        all = SUM ? all + x : max(all, x);
+    }
+    total = all;
+    return SUM ? excl + off : max(excl, off);
+}
+
+// The vocoder's magnitude of one normalised power value in dB (audio_lib.py:289-298 with realse == 1):
+// sqrt(db_to_power(max(0, P) / norm - 80)).  vc_compound_stitch and vc_time_warp fuse it; vc_power_to_amp's kernel
+// (vc_vocoder.hip) evaluates the same expression after its optional power law.
+__device__ __forceinline__ float power_db_to_amp(float P, float inv_norm) {
+    return exp10f(0.05f * (fmaxf(0.0f, P) * inv_norm - 80.0f));
+}
 #endif
 
 }  // namespace vc

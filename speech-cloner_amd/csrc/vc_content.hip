@@ -118,33 +118,6 @@ ppg_metrics_kernel(const float* __restrict__ ppg_a, const float* __restrict__ pp
     }
 }
 
-// Exclusive scans over the workgroup's 1,024 lanes: the value of the lanes before this one combined (identity for lane
-// 0) and, in `total`, of all lanes.  Inside a wave by shuffles, the waves' totals through LDS.
-template <bool SUM>
-__device__ inline int block_scan_excl(int v, int* wtot, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ident = SUM ? 0 : -1;
-    int inc = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int u = __shfl_up(inc, s, 64);
-        if (lane >= s) inc = SUM ? inc + u : max(inc, u);
-    }
-    int excl = __shfl_up(inc, 1, 64);
-    if (lane == 0) excl = ident;
-    __syncthreads();                                                // the previous scan's reads of wtot
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int off = ident, all = ident;
-    for (int w = 0; w < NW_S; ++w) {
-        const int x = wtot[w];
-        if (w < wave) off = SUM ? off + x : max(off, x);
-        all = SUM ? all + x : max(all, x);
-    }
-    total = all;
-    return SUM ? excl + off : max(excl, off);
-}
-
 __global__ void __launch_bounds__(NT_S)
 phn_segments_kernel(const float* __restrict__ ppg, const int32_t* __restrict__ n_frames, int max_frames, int n_classes,
                     int min_run, const int32_t* __restrict__ class_map, int32_t* __restrict__ labels,
@@ -185,15 +158,15 @@ phn_segments_kernel(const float* __restrict__ ppg, const int32_t* __restrict__ n
         const bool is_start = in && (f == 0 || mine != before);
         int tot_start, tot_surv, tot_emit;
         // the run [rs, f) with label `before` completes at a start f > 0
-        const int rs = max(block_scan_excl<false>(is_start ? f : -1, wtot, tot_start), c_start);
+        const int rs = max(vc::block_scan_excl<false, NW_S>(is_start ? f : -1, wtot, tot_start), c_start);
         const bool surv = is_start && f > 0 && f - rs >= min_run;
-        const int tp = block_scan_excl<false>(surv ? t : -1, wtot, tot_surv);         // the survivor before, as a lane of this tile
+        const int tp = vc::block_scan_excl<false, NW_S>(surv ? t : -1, wtot, tot_surv);         // the survivor before, as a lane of this tile
         bool have = c_have;
         int plab = c_slab, pend = c_send;
         if (tp >= 0) { have = true; plab = tp > 0 ? lab[tp - 1] : c_lab; pend = t0 + tp; }
         const bool head = surv && (!have || plab != before);
         const bool emit = head && before != -1;
-        const int k = c_count + block_scan_excl<true>(emit ? 1 : 0, wtot, tot_emit);
+        const int k = c_count + vc::block_scan_excl<true, NW_S>(emit ? 1 : 0, wtot, tot_emit);
         if (emit) { out_l[k] = before; out_s[k] = rs; }
         if (head && have && plab != -1) out_e[k - 1] = pend;
         // the carry

@@ -113,7 +113,7 @@ compound_stitch_kernel(const void* __restrict__ src, int bf16, const int32_t* __
         if (amp) {
             float a[V];
 #pragma unroll
-            for (int k = 0; k < V; ++k) a[k] = row >= 0 ? exp10f(0.05f * (fmaxf(0.0f, v[k]) * inv_norm - 80.0f)) : 0.0f;
+            for (int k = 0; k < V; ++k) a[k] = row >= 0 ? vc::power_db_to_amp(v[k], inv_norm) : 0.0f;
             store_vec<V>(amp + (size_t)b * slab, (size_t)i0, a);
         }
     } else {
@@ -122,7 +122,7 @@ compound_stitch_kernel(const void* __restrict__ src, int bf16, const int32_t* __
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             v[k] = row >= 0 ? load_elem(src, bf16, (size_t)row * C + c) : 0.0f;
-            a[k] = (amp && row >= 0) ? exp10f(0.05f * (fmaxf(0.0f, v[k]) * inv_norm - 80.0f)) : 0.0f;
+            a[k] = (amp && row >= 0) ? vc::power_db_to_amp(v[k], inv_norm) : 0.0f;
             if (++c == C) { c = 0; ++t; row = stitch_row(t, T, N, w0, w1); }
         }
         if (amp) store_vec<V>(amp + (size_t)b * slab, (size_t)i0, a);
