@@ -165,7 +165,10 @@ size_t vc_frontend_workspace_bytes(const vc_frontend_plan* plan, int32_t batch, 
  * its own under graph capture, replayed before the main one); with vc_set_option("fe_fused", 0) two launches, a
  * statistics pass and a feature pass.  Other configurations: STFT power + mel + raw dB with per-tile max / min / sum|x|
  * partials, then finalize (amplitude normalisation as a dB offset, amin and top_db clips, min shift, DCT, delta, clip);
- * with hop_length > n_fft/2 a third launch computes the per-utterance sum|x| first. */
+ * with hop_length > n_fft/2 a third launch computes the per-utterance sum|x| first.  These launches keep their tiles in
+ * up to 160 KB of dynamic LDS (all of them opted in above 64 KB); a configuration that vc_frontend_plan_create accepts
+ * but whose tile would need more (very large n_mels x n_mfcc, hop_length in the thousands) is refused here with an error
+ * that names the launch and its byte count. */
 int vc_frontend_f32(const vc_frontend_plan* plan, const float* d_wav, const int32_t* d_lens,
                     int32_t batch, int32_t max_samples, int32_t wav_stride, int32_t out_rows,
                     float* d_mfcc, float* d_mel_db, float* d_pow_db,

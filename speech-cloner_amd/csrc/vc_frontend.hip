@@ -35,6 +35,7 @@ constexpr int A_STRIDE = 17;      // LDS stride of one (g,k1) row of 16 complex 
 constexpr float NEG_INF = -3.402823466e38f;
 constexpr float POS_INF = 3.402823466e38f;
 constexpr int FE_STAT = 8;        // floats per tile record
+constexpr int FE_LDS_MAX = 160 * 1024;   // dynamic LDS a launch may ask for (CDNA4: 160 KB per workgroup); above 64 KB needs the opt-in
 
 struct FeDev {
     const float* window;      // [n_fft]
@@ -855,22 +856,22 @@ int vc_frontend_stages_f32(const vc_frontend_plan* plan, const float* d_wav, con
                       (size_t)plan->nnz + 2 * c.n_mels + 1 + 32 <= (size_t)FE_G400 * 13 * A_STRIDE;
         const size_t lds = a.lds_alias ? (span_pad + 400 + 416 + 2 * (size_t)FE_G400 * 13 * A_STRIDE) * 4
                                        : (span_pad + 400 + 416 + 2 * (size_t)FE_G400 * 13 * A_STRIDE + FE_G400 * 201 + 1) * 4 + mel_lds;
-        VC_REQUIRE(lds <= 160 * 1024, "hop_length too large for the 400-point kernel's LDS tile (%zu B)", lds);
+        VC_REQUIRE(lds <= FE_LDS_MAX, "hop_length too large for the 400-point kernel's LDS tile (%zu B)", lds);
+        if (int rc = vc::allow_dynamic_lds<fe_power400_kernel<80>, fe_power400_kernel<0>>(FE_LDS_MAX)) return rc;
         if (a.n_mels == 80) hipLaunchKernelGGL(fe_power400_kernel<80>, dim3(ntiles, batch), dim3(FE_THREADS), lds, st, a);
         else hipLaunchKernelGGL(fe_power400_kernel<0>, dim3(ntiles, batch), dim3(FE_THREADS), lds, st, a);
     } else {
         const size_t lds = (span_pad + 3 * (size_t)c.n_fft + (size_t)FE_GGEN * plan->n_bins) * 4 + mel_lds;
-        VC_REQUIRE(lds <= 160 * 1024, "n_fft/hop_length too large for the generic kernel's LDS tile (%zu B)", lds);
-        if (lds > 64 * 1024)
-            VC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fe_power_generic_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        VC_REQUIRE(lds <= FE_LDS_MAX, "n_fft/hop_length too large for the generic kernel's LDS tile (%zu B)", lds);
+        if (int rc = vc::allow_dynamic_lds<fe_power_generic_kernel>(FE_LDS_MAX)) return rc;
         hipLaunchKernelGGL(fe_power_generic_kernel, dim3(ntiles, batch), dim3(FE_THREADS), lds, st, a);
     }
     if (stage_mask & 4) {
         const int nt3 = (max_frames + FE_G3 - 1) / FE_G3;
         const size_t nm4 = ((size_t)c.n_mels + 3) & ~(size_t)3;
         const size_t lds = ((size_t)c.n_mfcc * (nm4 + 4) + (size_t)(FE_G3 + 2) * (nm4 + c.n_mfcc) + 4 + nm4 + 8) * 4;
-        VC_REQUIRE(lds <= 160 * 1024, "n_mels/n_mfcc too large for the finalize kernel's LDS tile (%zu B)", lds);
+        VC_REQUIRE(lds <= FE_LDS_MAX, "n_mels/n_mfcc too large for the finalize kernel's LDS tile (%zu B)", lds);
+        if (int rc = vc::allow_dynamic_lds<fe_finalize_kernel<80, 40, 201>, fe_finalize_kernel<0, 0, 0>>(FE_LDS_MAX)) return rc;
         if (a.n_mels == 80 && a.n_mfcc == 40 && a.n_bins == 201)
             hipLaunchKernelGGL((fe_finalize_kernel<80, 40, 201>), dim3(nt3, batch), dim3(FE_THREADS), lds, st, a, G);
         else hipLaunchKernelGGL((fe_finalize_kernel<0, 0, 0>), dim3(nt3, batch), dim3(FE_THREADS), lds, st, a, G);
