@@ -623,6 +623,25 @@ int vc_vocoder_plan_create(int32_t win_length, int32_t hop_length, int32_t n_fft
 void vc_vocoder_plan_destroy(vc_vocoder_plan* plan);
 /* Samples librosa.istft returns for n_frames frames: hop_length * (n_frames - 1). */
 int32_t vc_vocoder_num_samples(const vc_vocoder_plan* plan, int32_t n_frames);
+/* The caller-owned workspace of vc_griffin_lim_f32 / vc_griffin_lim_momentum_f32 (host arithmetic only; 0 for a NULL plan,
+ * batch <= 0 or max_frames <= 0; too small: VC_ERR_INVALID before any launch).  With align256(x) = x rounded up to 256,
+ * N = n_fft and FB = align256(batch * max_frames * N * 4), in this order:
+ *     offset 0             frame buffer 0   [batch, max_frames, N] float32   the windowed synthesis frames w[n] * irfft(S_f)[n]
+ *     offset FB            frame buffer 1   the same
+ *     with trace != 0      two waveforms [batch, hop * (max_frames - 1)] float32 (row stride hop * (max_frames - 1)), each
+ *                          align256(batch * hop * (max_frames - 1) * 4) bytes: waveform i of a traced run goes to number i & 1
+ *     momentum only        the state R_{i-1}, align256(batch * max_frames * slots * 8) bytes, one float2 (re, im) per slot:
+ *                          [batch, max_frames, 13, 16] on the 400-point path, where slot (k1, k2) holds bin k1 + 25 k2 of the
+ *                          400-point spectrum of the frame (k1 < 13 and k2 < 16 give 208 distinct bins up to 387; a bin above
+ *                          200 is stored as computed, the conjugate of bin 400 - k to rounding);
+ *                          [batch, max_frames, 1 + N/2] otherwise
+ *     256 spare bytes
+ *     vc_vocoder_workspace_bytes          = 2 FB + (trace ? 2 align256(batch * hop * (max_frames - 1) * 4) : 0) + 256
+ *     vc_vocoder_workspace_bytes_momentum = the same + align256(batch * max_frames * slots * 8)
+ * Launch i (0-based; launch 0 reads no frames) reads frame buffer i & 1 and writes the other, so after num_iters launches the final frames (those d_wav
+ * is the overlap-add of) are in frame buffer num_iters & 1 and the frames the last launch read in the other.  With momentum
+ * > 0 and num_iters >= 2 the state holds R_{num_iters-1}, the analysis of the last launch before its projection.  Rows at or
+ * beyond n_frames[b] of the frame buffers and of the state are never written; nothing is read before it is written. */
 size_t vc_vocoder_workspace_bytes(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames, int32_t trace);
 
 /* audio_lib.py:289-298: P = max(0, P); optional P = (mean(P)/mean(P**realse)) * P**realse (means
