@@ -1504,6 +1504,61 @@ int vc_time_warp(const float* d_src, const int32_t* d_pos, const int32_t* d_n_ou
                  int32_t max_frames, int32_t out_frames, int32_t C, int32_t mode, float* d_dst, float* d_amp,
                  float P_dB_norm_factor, void* stream);
 
+/* Pitch.  Conversion leaves the melody to the decoder and the vocoder; duration conversion moves frames, not harmonics.
+ * These two launches change the fundamental of a WAVEFORM and keep its length: overlap-add of two-period grains
+ * (time-domain PSOLA) whose positions come from integrating an F0 track -- no search for glottal epochs in the samples:
+ * for a periodic signal any placement one period apart is a valid grain sequence.  The plan (marks, grain choice,
+ * widths) is integer arithmetic on two tables; the overlap-add is a gather.  Added without a version bump.
+ * tests/pitch_ref.py restates both; the device equals it bit for bit.  All plan arithmetic is integer (int64 where noted).
+ *
+ * Inputs per utterance: x[0, len) float32 samples; len from d_len int32 [batch] (clamped to [0, max_len]), so the output of
+ * a launch that keeps its lengths on the device can be fed as it is; hop; n_frames = F frames of two int32 tables,
+ * d_period_q[f] and d_ratio_q[f] [batch, F], both Q16: the period of the signal in samples and the factor its fundamental
+ * is to be multiplied by.
+ *   Clamps   applied when a value is read:  P[f] = clamp(period_q[f], 16 << 16, 1024 << 16);
+ *            R[f] = clamp(ratio_q[f], 32768, 131072), a ratio in [0.5, 2];
+ *            S[f] = clamp((P[f] * 65536 + R[f] / 2) / R[f], 16 << 16, 2048 << 16), in int64.  No content of either table
+ *            gives a step below 16 samples, which bounds every loop.
+ *   Frames   fr(m) = min((m + hop / 2) / hop, F - 1): the front-end's centred frames.
+ *   Marks    of a step table T:  pos_0 = 0 (int64, Q16), m_k = pos_k >> 16, pos_{k+1} = pos_k + T[fr(m_k)]; the list ends
+ *            before the first m_k >= len.  Analysis marks a_0 .. a_{K-1}: T = P; synthesis marks s_0 .. s_{J-1}: T = S.
+ *            K, J <= len / 16 + 1.  The step is constant inside a frame, so an implementation may recur over frames and
+ *            expand the marks in parallel: frame f ends at Q16 position ((f + 1) * hop - hop / 2) << 16 (the last frame
+ *            and every frame cut by len: at len << 16), and the count in a frame is one ceiling division.
+ *   Grain j  k(j): the analysis mark nearest to s_j, the lower k of two equally near ones; src_j = a_k(j);
+ *            h_j = (P[fr(src_j)] + 32768) >> 16, in [16, 1024].
+ *   Window   one table W[i] = float32(0.5 + 0.5 cos(pi i / 2048)), i = 0 .. 2048, made on the host in float64, W[2048] = 0
+ *            (d_window, 2,049 floats on the device).  w_j(d) = W[(|d| * 2048 + h_j / 2) / h_j] for |d| < h_j; else grain
+ *            j does not cover the sample.
+ *   Output   for n < len:  N = sum_j x~[src_j + n - s_j] * w_j(n - s_j),  D = sum_j w_j(n - s_j)  over the covering
+ *            grains in ascending j, float32, every product and every sum rounded separately (no contraction), both sums
+ *            from +0; x~ is zero outside [0, len).  y[n] = N / max(D, w_floor) (IEEE division); y[n] = 0 for n >= len.
+ *            len samples in, len out.  A sample no grain covers is 0 / w_floor = 0.
+ *
+ * vc_psola_plan writes, per utterance and with M = vc_psola_max_marks(max_len) = max_len / 16 + 1: d_n_a = K, d_n_s = J
+ * [batch]; d_a, d_s, d_src, d_h [batch, M] int32, -1 from K (d_a) or J (the others) on; every element exactly once.  One
+ * workgroup per utterance: the tables pass through LDS in tiles of 1,024 frames, one lane per mark list walks the tile
+ * (one division per frame that holds a mark), all lanes expand the marks; the nearest-mark search is a binary search of at
+ * most 22 steps.  Every loop bound comes from F, max_len and tile sizes; nothing read from a table forms an address.
+ *
+ * vc_psola_ola_f32: grid (tiles of 1,024 outputs, utterance).  A tile stages the grains that can reach it -- s_j within
+ * [tile start - 1023, last sample + 1023], found by binary search, at most 192 -- into LDS once; each lane gathers its
+ * samples over that list.  No atomics; every element of d_y [batch, max_len] is written exactly once, the zeros from len on
+ * included; d_x [batch, max_len] is not read at or beyond len.  The plan is read defensively: n_s is clamped to [0, M], h to
+ * [16, 1024], and a staged grain whose s lies outside the searched range or whose src lies outside [0, len) covers nothing.
+ * d_y must not be d_x.  w_floor > 0.
+ *
+ * Both are functions of their own utterance alone, bit-identical alone, in any batch, from run to run and under graph
+ * replay; they take everything from device memory, allocate nothing and wait for nothing.  Limits (VC_ERR_UNSUPPORTED
+ * beyond them, nothing launched): batch <= 65,535; max_len <= 2^24; n_frames <= 2^20; hop in [1, 65,536]. */
+int32_t vc_psola_max_marks(int32_t max_len);
+int vc_psola_plan(const int32_t* d_period_q, const int32_t* d_ratio_q, const int32_t* d_len, int32_t batch, int32_t max_len,
+                  int32_t n_frames, int32_t hop, int32_t* d_n_a, int32_t* d_n_s, int32_t* d_a, int32_t* d_s, int32_t* d_src,
+                  int32_t* d_h, void* stream);
+int vc_psola_ola_f32(const float* d_x, const int32_t* d_len, const int32_t* d_n_s, const int32_t* d_s, const int32_t* d_src,
+                     const int32_t* d_h, const float* d_window, int32_t batch, int32_t max_len, float w_floor, float* d_y,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,11 @@ audio_lib's device resampler in front of and behind that chain for audio at anot
 and the vocoder, ``duration_map_batch`` (vc_duration_map: an integer time map from a segment table and per-class rates or
 explicit lengths) and ``time_warp_batch`` (vc_time_warp) resample the stitched spectra; the output lengths stay on the
 device.  ``duration_stats_batch`` / ``duration_ratios`` turn two speakers' segment tables into the rate table.
+
+``convert_pitch_batch`` is ``convert_batch`` with the melody set as well: behind the vocoder the
+converted waveform's F0 is tracked and ``pitch_shift_batch``'s launches (vc_psola_plan, vc_psola_ola_f32: overlap-add of
+grains placed by integrating the track) move it by a ratio, to a given contour or to the source's own.  ``pitch_tables``
+builds the launch's two Q16 tables from a track; ``f0_stats_batch`` / ``f0_transform`` map a contour between speakers.
 """
 from collections import namedtuple
 
@@ -861,3 +866,360 @@ def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio
         max_samples = int(audio_lib.resample_len(max_samples, sr, out_sr))
     return _DUR_NT(y_wav_pred, n_samples, mel_pred, stft_pred, phn_pred, m.n_out, m.flags,
                    _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg), m, Fw, max_samples, [int(v) for v in plan.n_out])
+
+
+# --------------------------------------------------------------------------- pitch (csrc/vc_pitch.hip)
+PSOLA_MAX_LEN = 1 << 24     # vc_psola_plan, vc_psola_ola_f32: samples per utterance
+PSOLA_MAX_FRAMES = 1 << 20
+PSOLA_MAX_HOP = 65536
+PSOLA_RATIO_MIN, PSOLA_RATIO_MAX = 0.5, 2.0
+PSOLA_WIN_N = 2048
+_PLAN_PITCH_NT = namedtuple('psola_plan', 'n_a n_s a s src h max_len')
+_SHIFT_NT = namedtuple('pitch_shift', 'y plan period_q ratio_q')
+_F0_STATS_NT = namedtuple('f0_stats', 'count mean std')
+_PITCH_NT = namedtuple('convert_pitch', _BATCH_NT._fields + ('f0_pred', 'f0_target', 'plan'))
+_psola_windows = {}
+
+
+def psola_window(device=None):
+    """The one window table of the overlap-add (include/vc_hip.h, "Pitch"): W[i] = float32(0.5 + 0.5 cos(pi i / 2048)),
+    i = 0 .. 2048, made in float64, W[2048] = 0.  A numpy array without ``device``; with one, the device's cached copy."""
+    w = (0.5 + 0.5 * np.cos(np.pi * np.arange(PSOLA_WIN_N + 1, dtype=np.float64) / PSOLA_WIN_N)).astype(np.float32)
+    w[PSOLA_WIN_N] = 0.0
+    if device is None:
+        return w
+    import torch
+    key = str(torch.device(device))
+    if key not in _psola_windows:
+        _psola_windows[key] = torch.from_numpy(w).pin_memory().to(device, non_blocking=True)
+    return _psola_windows[key]
+
+
+def _check_pitch_ratio(r, what):
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not PSOLA_RATIO_MIN <= float(r) <= PSOLA_RATIO_MAX:
+        raise ValueError(' - ERROR, {} must be a number in [{}, {}], got {!r}'.format(what, PSOLA_RATIO_MIN, PSOLA_RATIO_MAX, r))
+    return float(r)
+
+
+def pitch_tables(f0_cur, sr, ratio=None, target_f0=None, unvoiced_period=None, hop_length=80):
+    """The two Q16 tables of vc_psola_plan from an F0 track: (period_q, ratio_q), int32 in the shape of f0_cur, on its
+    device (a numpy array: on the host), computed in float64 torch and rounded once (ties to even).
+
+    f0_cur [B, F] in Hz, 0 = unvoiced (as f0_track_batch returns it).  period_q = round(sr * 65536 / f0) where f0 > 0, else
+    unvoiced_period << 16 (default: hop_length samples -- unvoiced stretches are copied grain by grain at the frame rate).
+    Exactly one of ratio -- a number in [0.5, 2] or a per-frame array / tensor in the shape of f0_cur -- and target_f0 (the
+    contour to reach: ratio_q = round(65536 * target_f0 / f0_cur) where both are voiced, else 65536).  The launch clamps
+    what it reads (periods to [16, 1024] samples, ratios to [0.5, 2]); a per-frame ratio on the host is checked here."""
+    import torch
+    what = 'pitch_tables'
+    if (ratio is None) == (target_f0 is None):
+        raise ValueError(' - ERROR, {}: pass exactly one of ratio and target_f0'.format(what))
+    if isinstance(sr, bool) or not isinstance(sr, (int, float, np.integer, np.floating)) or not 0 < float(sr) <= 2 ** 24:
+        raise ValueError(' - ERROR, {}: sr must be a positive number, got {!r}'.format(what, sr))
+    if unvoiced_period is None:
+        unvoiced_period = hop_length
+    if isinstance(unvoiced_period, bool) or not isinstance(unvoiced_period, (int, np.integer)) or not 1 <= unvoiced_period <= 32767:
+        raise ValueError(' - ERROR, {}: unvoiced_period must be an integer in [1, 32767], got {!r}'.format(what, unvoiced_period))
+    if getattr(f0_cur, 'ndim', 0) != 2 or min(f0_cur.shape) < 1:
+        raise ValueError(' - ERROR, {}: f0_cur must be [B, F]'.format(what))
+    f0 = torch.as_tensor(f0_cur).to(torch.float64)
+    voiced = f0 > 0
+    one = torch.ones_like(f0)
+    per = torch.where(voiced, torch.round(float(sr) * 65536.0 / torch.where(voiced, f0, one)), one * float(int(unvoiced_period) << 16))
+    if target_f0 is not None:
+        if tuple(getattr(target_f0, 'shape', ())) != tuple(f0.shape):
+            raise ValueError(' - ERROR, {}: target_f0 must have the shape of f0_cur, {}'.format(what, list(f0.shape)))
+        tgt = torch.as_tensor(target_f0).to(device=f0.device, dtype=torch.float64)
+        both = voiced & (tgt > 0)
+        rq = torch.where(both, torch.round(65536.0 * torch.where(both, tgt, one) / torch.where(both, f0, one)), one * 65536.0)
+    elif getattr(ratio, 'ndim', 0) == 0:
+        rq = one * float(np.rint(65536.0 * _check_pitch_ratio(ratio if not hasattr(ratio, 'item') else ratio.item(), what + ': ratio')))
+    else:
+        if tuple(ratio.shape) != tuple(f0.shape):
+            raise ValueError(' - ERROR, {}: a per-frame ratio must have the shape of f0_cur, {}'.format(what, list(f0.shape)))
+        if not torch.is_tensor(ratio):
+            r = np.asarray(ratio, dtype=np.float64)
+            if not np.isfinite(r).all() or r.min() < PSOLA_RATIO_MIN or r.max() > PSOLA_RATIO_MAX:
+                raise ValueError(' - ERROR, {}: ratio must be finite and lie in [{}, {}]'.format(what, PSOLA_RATIO_MIN, PSOLA_RATIO_MAX))
+        rq = torch.round(65536.0 * torch.as_tensor(ratio).to(device=f0.device, dtype=torch.float64))
+    to_i32 = lambda t: torch.nan_to_num(t, nan=0.0).clamp(0.0, 2.0 ** 31 - 1).to(torch.int32).contiguous()
+    return to_i32(per), to_i32(rq)
+
+
+def _psola_plan_launch(d_per, d_rat, d_lens, Lmax, hop):
+    """vc_psola_plan on validated device tensors: no host check, copy or wait in here."""
+    import torch
+    import _vc
+    lib = _vc.lib()
+    B, F = d_per.shape
+    M = lib.vc_psola_max_marks(Lmax)
+    if M == 0:
+        raise _vc.VCError('vc_psola_max_marks refused {} samples'.format(Lmax))
+    n = torch.empty((2, B), dtype=torch.int32, device=d_per.device)
+    tab = torch.empty((4, B, M), dtype=torch.int32, device=d_per.device)
+    _vc.check(lib.vc_psola_plan(_vc.ptr(d_per), _vc.ptr(d_rat), _vc.ptr(d_lens), B, Lmax, F, hop, _vc.ptr(n[0]), _vc.ptr(n[1]),
+                                _vc.ptr(tab[0]), _vc.ptr(tab[1]), _vc.ptr(tab[2]), _vc.ptr(tab[3]), _vc.current_stream()))
+    return _PLAN_PITCH_NT(n[0], n[1], tab[0], tab[1], tab[2], tab[3], Lmax)
+
+
+def _psola_ola_launch(wav, d_lens, plan, w_floor):
+    """vc_psola_ola_f32 on validated device tensors (wav [B, plan.max_len] contiguous float32)."""
+    import torch
+    import _vc
+    B, Lmax = wav.shape
+    y = torch.empty_like(wav)
+    _vc.check(_vc.lib().vc_psola_ola_f32(_vc.ptr(wav), _vc.ptr(d_lens), _vc.ptr(plan.n_s), _vc.ptr(plan.s), _vc.ptr(plan.src),
+                                         _vc.ptr(plan.h), _vc.ptr(psola_window(wav.device)), B, Lmax, w_floor, _vc.ptr(y),
+                                         _vc.current_stream()))
+    return y
+
+
+def _check_pitch_sizes(B, Lmax, F, hop, what):
+    if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not 1 <= hop <= PSOLA_MAX_HOP:
+        raise ValueError(' - ERROR, {}: hop_length must be an integer in [1, {}], got {!r}'.format(what, PSOLA_MAX_HOP, hop))
+    if isinstance(Lmax, bool) or not isinstance(Lmax, (int, np.integer)) or not 1 <= Lmax <= PSOLA_MAX_LEN:
+        raise ValueError(' - ERROR, {}: at most {} samples per utterance, at least 1 (got {!r})'.format(what, PSOLA_MAX_LEN, Lmax))
+    if not 1 <= B <= 65535 or not 1 <= F <= PSOLA_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: 1 to 65535 utterances of 1 to {} frames (got {} of {})'.format(what, PSOLA_MAX_FRAMES, B, F))
+
+
+def _check_pitch_lens(lens, B, Lmax, what):
+    import torch
+    if torch.is_tensor(lens) and lens.is_cuda:
+        return
+    h = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+    if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > Lmax:
+        raise ValueError(' - ERROR, {}: lens must be {} integers in [0, {}]'.format(what, B, Lmax))
+
+
+def _check_w_floor(w_floor, what):
+    if isinstance(w_floor, bool) or not isinstance(w_floor, (int, float, np.integer, np.floating)) or not 0.0 < float(w_floor) <= 2.0:
+        raise ValueError(' - ERROR, {}: w_floor must be a number in (0, 2], got {!r}'.format(what, w_floor))
+    return float(w_floor)
+
+
+def _check_pitch_table(t, B, what):
+    import torch
+    if getattr(t, 'ndim', 0) != 2 or t.shape[0] != B or t.shape[1] < 1:
+        raise ValueError(' - ERROR, {} must be [B, F]'.format(what))
+    return _i32_device(t, tuple(t.shape), what)
+
+
+def psola_plan_batch(period_q, ratio_q, lens, hop_length, max_len=None):
+    """The grain plan of B utterances (vc_psola_plan; the definition is in include/vc_hip.h, "Pitch", the numpy restatement
+    in tests/pitch_ref.py).  period_q, ratio_q [B, F] int32 as pitch_tables returns them; lens: the sample counts, host
+    integers or an int32 [B] device tensor; max_len: the bound Lmax of the lengths (default: the largest of host lens,
+    required with lens on the device).  Returns a namedtuple of device tensors: n_a, n_s [B] (the numbers K, J of analysis
+    and synthesis marks), a, s, src, h [B, max_len // 16 + 1] int32 (-1 beyond), and the host integer max_len.  Nothing is
+    copied back and the host waits for nothing."""
+    import torch
+    import _vc
+    what = 'psola_plan_batch'
+    if getattr(period_q, 'ndim', 0) != 2 or tuple(getattr(ratio_q, 'shape', ())) != tuple(period_q.shape):
+        raise ValueError(' - ERROR, {}: period_q and ratio_q must be [B, F], the same shape'.format(what))
+    B, F = int(period_q.shape[0]), int(period_q.shape[1])
+    if max_len is None:
+        if torch.is_tensor(lens) and lens.is_cuda:
+            raise ValueError(' - ERROR, {}: max_len is required with lens on the device'.format(what))
+        max_len = max(int(np.max(np.asarray(lens))), 1) if np.size(lens) else 1
+    _check_pitch_sizes(B, max_len, F, hop_length, what)
+    _check_pitch_lens(lens, B, max_len, what)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('psola_plan_batch needs a GPU (no CPU fallback)')
+    return _psola_plan_launch(_check_pitch_table(period_q, B, what + ': period_q'), _check_pitch_table(ratio_q, B, what + ': ratio_q'),
+                              _i32_device(lens, (B,), what + ': lens'), int(max_len), int(hop_length))
+
+
+def pitch_shift_batch(wav, lens, f0, sr, hop_length, ratio=None, target_f0=None, w_floor=0.5, unvoiced_period=None):
+    """Changes the fundamental of B waveforms and keeps their lengths: pitch_tables, vc_psola_plan, vc_psola_ola_f32.
+
+    wav [B, Lmax] float32 (cuda tensor or numpy array); lens: sample counts, host integers, an int32 [B] device tensor (as
+    convert_duration_batch returns n_samples) or None (all Lmax); f0 [B, F] in Hz, 0 = unvoiced, the track of ``wav`` at
+    ``hop_length`` (f0_track_batch's f0; F need not be 1 + Lmax // hop_length: the last frame extends to the end).  One of
+    ratio (a number in [0.5, 2] or per frame) and target_f0 [B, F].  w_floor: the least window sum an output sample is
+    divided by (a sample that fewer grains reach is damped, not amplified).
+    Returns a namedtuple: y [B, Lmax] float32 on the device (zero from an utterance's length on), the plan
+    (psola_plan_batch's result) and the two tables.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    import _vc
+    what = 'pitch_shift_batch'
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    if torch.is_tensor(wav) and wav.dtype != torch.float32:
+        raise ValueError(' - ERROR, {}: wav must be float32, got {}'.format(what, wav.dtype))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    if getattr(f0, 'ndim', 0) != 2 or f0.shape[0] != B or f0.shape[1] < 1:
+        raise ValueError(' - ERROR, {}: f0 must be [B, F] with B = {}'.format(what, B))
+    _check_pitch_sizes(B, Lmax, int(f0.shape[1]), hop_length, what)
+    w_floor = _check_w_floor(w_floor, what)
+    if lens is None:
+        lens = np.full((B,), Lmax, dtype=np.int64)
+    _check_pitch_lens(lens, B, Lmax, what)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('pitch_shift_batch needs a GPU (no CPU fallback)')
+    if not torch.is_tensor(f0):
+        f0 = torch.from_numpy(np.ascontiguousarray(f0))
+    if torch.is_tensor(ratio) or torch.is_tensor(target_f0):
+        ratio, target_f0 = (t.to('cuda', non_blocking=True) if torch.is_tensor(t) else t for t in (ratio, target_f0))
+    per, rat = pitch_tables(f0.to('cuda', non_blocking=True), sr, ratio=ratio, target_f0=target_f0, unvoiced_period=unvoiced_period,
+                            hop_length=int(hop_length))
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
+    d_lens = _i32_device(lens, (B,), what + ': lens')
+    plan = _psola_plan_launch(per, rat, d_lens, Lmax, int(hop_length))
+    return _SHIFT_NT(_psola_ola_launch(wav, d_lens, plan, w_floor), plan, per, rat)
+
+
+def f0_stats_batch(f0, n_frames=None):
+    """Count, mean and standard deviation (population) of log F0 over the voiced frames of a batch of tracks, pooled:
+    f0 [B, F] in Hz, 0 = unvoiced; n_frames [B] (host integers or a tensor; None = all F): frames from it on are left out.
+    A namedtuple (count int64, mean, std float64) of 0-d tensors on f0's device; without a voiced frame mean = std = 0.
+    Plain torch: no kernel of this library, nothing copied back."""
+    import torch
+    if getattr(f0, 'ndim', 0) != 2:
+        raise ValueError(' - ERROR, f0_stats_batch: f0 must be [B, F]')
+    f0 = torch.as_tensor(f0)
+    B, F = f0.shape
+    keep = f0 > 0
+    if n_frames is not None:
+        n = torch.as_tensor(n_frames).to(f0.device).reshape(-1)
+        if n.shape[0] != B:
+            raise ValueError(' - ERROR, f0_stats_batch: n_frames must hold {} counts'.format(B))
+        keep = keep & (torch.arange(F, device=f0.device)[None, :] < n[:, None])
+    lf = torch.where(keep, torch.log(torch.where(keep, f0, torch.ones_like(f0)).to(torch.float64)), torch.zeros((), dtype=torch.float64, device=f0.device))
+    count = keep.sum()
+    den = count.clamp_min(1).to(torch.float64)
+    mean = lf.sum() / den
+    var = (torch.where(keep, lf - mean, torch.zeros_like(lf)) ** 2).sum() / den
+    return _F0_STATS_NT(count, mean, torch.sqrt(var))
+
+
+def f0_transform(f0, stats_src, stats_tgt):
+    """The log-Gaussian mapping of an F0 contour from one speaker's statistics to another's:
+    exp((log f0 - mean_src) * std_tgt / std_src + mean_tgt) where f0 > 0; unvoiced frames stay 0.  Where std_src is 0 the
+    contour is moved by the means alone.  stats_*: (count, mean, std) as f0_stats_batch returns them (tensors or numbers).
+    float32 on f0's device; no synchronisation."""
+    import torch
+    if len(stats_src) != 3 or len(stats_tgt) != 3:
+        raise ValueError(' - ERROR, f0_transform: stats must be (count, mean, std) as f0_stats_batch returns them')
+    f0 = torch.as_tensor(f0)
+    as64 = lambda v: torch.as_tensor(v).to(device=f0.device, dtype=torch.float64)
+    ms, ss, mt, st = as64(stats_src[1]), as64(stats_src[2]), as64(stats_tgt[1]), as64(stats_tgt[2])
+    voiced = f0 > 0
+    lf = torch.log(torch.where(voiced, f0, torch.ones_like(f0)).to(torch.float64))
+    slope = torch.where(ss > 0, st / torch.where(ss > 0, ss, torch.ones_like(ss)), torch.ones_like(ss))
+    out = torch.exp((lf - ms) * slope + mt)
+    return torch.where(voiced, out, torch.zeros_like(out)).to(torch.float32)
+
+
+def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None,
+                        t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None,
+                        window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+    """``convert_batch`` with the melody set as well: after the vocoder the converted waveform's F0
+    is tracked (f0_track_batch's launches, at the model's rate and hop), and pitch_shift_batch's launches move it to the
+    target before the output is resampled.
+
+    pitch:
+      a number r         every voiced frame's fundamental times r (0.5 <= r <= 2);
+      [B, Fout] floats   the contour to reach, in Hz per output frame, 0 = leave the frame as it is;
+      'source'           the INPUT's own contour: tracked on ``wav`` at the model's rate, mapped by
+                         f0_transform(., stats_src, stats_tgt) when both are given (f0_stats_batch of the two speakers),
+                         and aligned to the output frames by the plan's n_s (output frame u is input frame n_s + u).
+    f0_args: a dict of f0_track_batch's tracker arguments (frame_length, fmin, fmax, threshold, jump_cost, switch_cost,
+    n_cand, ceiling).  The other arguments are convert_batch's; phase='numpy' and giffin_lim_input are not offered here.
+    Returns convert_batch's fields (y_wav_true None) plus f0_pred [B, Fout] (the track of the unshifted conversion),
+    f0_target [B, Fout] (None for a number) and the grain plan.  Every check and table is made on the host before the first
+    launch; after the uploads nothing is copied to the host and the host waits for nothing."""
+    import torch
+    import audio_lib
+    import evaluation
+    import _vc
+    what = 'convert_pitch_batch'
+    momentum = _check_momentum(momentum)
+    seed = audio_lib.check_seed(seed)
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    if isinstance(phase, str) and phase not in ('device', 'spsi'):
+        raise ValueError(" - ERROR, {}: phase must be 'device', 'spsi' or a [B, Fout, bins] array, got {!r}".format(what, phase))
+    if pitch is None:
+        raise ValueError(" - ERROR, {}: pitch is required: a ratio, a [B, Fout] contour or 'source'".format(what))
+    source = isinstance(pitch, str)
+    if source and pitch != 'source':
+        raise ValueError(" - ERROR, {}: pitch must be a ratio, a [B, Fout] contour or 'source', got {!r}".format(what, pitch))
+    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and not source):
+        raise ValueError(" - ERROR, {}: stats_src and stats_tgt go together and with pitch='source'".format(what))
+    scalar = not source and getattr(pitch, 'ndim', 0) == 0
+    if scalar:
+        pitch = _check_pitch_ratio(pitch, what + ': pitch')
+    w_floor = _check_w_floor(w_floor, what)
+    kw = dict(frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5, switch_cost=0.1, n_cand=8, ceiling=1.0)
+    extra = set(f0_args or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: f0_args takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(f0_args or {})
+    h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
+                      res_type)
+    plan, B, hop, Fout, n_bins, sr = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    f0a = evaluation._f0_args(sr, hop, kw['frame_length'], kw['fmin'], kw['fmax'], kw['threshold'], what)
+    n_cand, ceiling = evaluation._track_args(kw['n_cand'], kw['ceiling'], what)
+    costs = evaluation._viterbi_costs(f0a[5], kw['jump_cost'], kw['switch_cost'], what)
+    Lout = hop * (Fout - 1)
+    _check_pitch_sizes(B, Lout, Fout, hop, what)
+    if max(Lout, int(h.h_lens.max())) > evaluation.F0_MAX_SAMPLES:
+        raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
+    if not isinstance(phase, str) and tuple(phase.shape) != (B, Fout, n_bins):
+        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, B, Fout, n_bins))
+    if not source and not scalar and tuple(pitch.shape) != (B, Fout):
+        raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per output frame)'.format(what, B, Fout))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('convert_pitch_batch needs a GPU (no CPU fallback)')
+
+    up = _convert_upload(h, wav, [h.h_nsamp, plan.n_out, plan.n_src])
+    d_nsamp, d_fout, d_fsrc = up.d_extra[-3:]
+    if not isinstance(phase, str):
+        if not torch.is_tensor(phase):
+            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
+        phase = phase.to(device='cuda', dtype=torch.float32).contiguous()
+    if not source and not scalar:
+        if not torch.is_tensor(pitch):
+            pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
+        pitch = pitch.to(device='cuda', non_blocking=True)
+    psola_window('cuda')
+    if h.res_in:                                                    # once, here: the source's track needs the model's rate too
+        w16 = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), up.wav, up.d_extra[0])
+        h, up = h._replace(res_in=False), up._replace(wav=w16)
+
+    # ---- convert_batch's model pass, stitch and vocoder
+    mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
+    mel_pred = compound_stitch(y_mel, up.d_utt, Fout)
+    phn_pred = compound_stitch(y_phn, up.d_utt, Fout)
+    amp_pred = None
+    if float(realse) == 1.0:
+        stft_pred, amp_pred = compound_stitch(y_stft, up.d_utt, Fout, P_dB_norm_factor=cfg_d['P_dB_norm_factor'])
+    else:
+        stft_pred = compound_stitch(y_stft, up.d_utt, Fout)
+    _, y0 =_vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, amp_pred)
+
+    # ---- the conversion's own track, the target, the shift
+    f0_pred = evaluation._f0_track_launch(y0, d_nsamp, d_fout, f0a, n_cand, ceiling, costs)[0]
+    f0_target = None
+    if source:
+        f0_in = evaluation._f0_track_launch(up.wav, up.d_lens, d_fsrc, f0a, n_cand, ceiling, costs)[0]
+        u = torch.arange(Fout, device=f0_in.device)[None, :]
+        idx = up.d_true[:, 1:2].long() + u
+        ok = (u < d_fout[:, None]) & (idx < d_fsrc[:, None])
+        f0_target = torch.where(ok, torch.gather(f0_in, 1, idx.clamp(0, f0_in.shape[1] - 1)), torch.zeros((), device=f0_in.device))
+        if stats_src is not None:
+            f0_target = f0_transform(f0_target, stats_src, stats_tgt)
+    elif not scalar:
+        f0_target = pitch.to(torch.float32)
+    per, rat = pitch_tables(f0_pred, sr, ratio=pitch if scalar else None, target_f0=f0_target, hop_length=hop)
+    pp = _psola_plan_launch(per, rat, d_nsamp, Lout, hop)
+    y_wav_pred = _psola_ola_launch(y0, d_nsamp, pp, w_floor)
+    n_samples = [int(v) for v in h.h_nsamp]
+    if h.res_out:
+        y_wav_pred = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y_wav_pred, d_nsamp)
+        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
+    return _PITCH_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
+                     f0_pred, f0_target, pp)
