@@ -1559,6 +1559,62 @@ int vc_psola_ola_f32(const float* d_x, const int32_t* d_len, const int32_t* d_n_
                      const int32_t* d_h, const float* d_window, int32_t batch, int32_t max_len, float w_floor, float* d_y,
                      void* stream);
 
+/* Differential-spectrum conversion (Kobayashi & Toda; sprocket's DIFFVC).  The other conversion entry points SYNTHESISE the
+ * converted spectrum with Griffin-Lim.  These two launches FILTER the source recording by the difference between the
+ * converted and the source spectral envelope instead: excitation and phase stay the source's own, and the cost is one
+ * STFT / ISTFT pass.  Added without a version bump.  tests/diff_ref.py restates both in float64 and the gain in float32.
+ *
+ * Gain.  d_pred, d_true [batch, max_frames, n_bins] float32: the front-end's normalised power dB (stft_pred, stft_true of
+ * conversion.convert_batch).  For every frame f < n_frames[b] (clamped to [0, max_frames]; NULL: all) and bin k:
+ *     d[k]  = (max(pred, 0) - max(tru, 0)) / P_dB_norm_factor                 IEEE float32 division
+ *     s0[k] = sum_{j = -h .. h} c[j] * d[refl(k + j)]                         h = (n_taps - 1) / 2
+ *             c = d_taps, float32 [n_taps] from the caller (symmetric by convention), n_taps odd, <= 65; refl mirrors about
+ *             bin 0 and about bin n_bins - 1 without repeating the edge (as often as it takes: n_bins may be smaller than
+ *             h); the sum starts from +0 and ascends in j; every product and every sum is rounded once (no fused
+ *             multiply-add)
+ *     s[k]  = min(max(alpha * s0[k], -max_cut_db), max_boost_db)              a power ratio in dB
+ *     G[k]  = exp2f(s[k] * float32(log2(10) / 20))                            an amplitude ratio
+ * Rows at or beyond n_frames[b] are written as 0; every element of d_gain [batch, max_frames, n_bins] is written exactly
+ * once.  One launch: a workgroup takes a tile of 16 frames, puts each frame's n_bins differences into LDS once with the
+ * mirrored edges folded into the index, and every lane then takes bins.  The rows (201 floats) do not start on 16-byte
+ * boundaries: they are read element by element, and the flat output slab is stored 16 bytes per lane where its length and
+ * address allow.  VC_ERR_INVALID before the launch for a NULL pointer, batch outside [1, 65535], max_frames < 1,
+ * n_bins outside [2, 2049], n_taps even or outside [1, 65], a non-finite float, P_dB_norm_factor == 0, alpha outside [0, 1]
+ * or a negative clamp.
+ *
+ * Filter.  With the plan's padded window w, N = n_fft, hop, and per utterance len = d_len[b] clamped to [0, wav_stride] and
+ * F_b = min(n_frames[b], max_frames, 1 + len / hop) (d_n_frames NULL: without the first), a negative count counting as 0:
+ *     y_b = istft(G_b[f] * stft(x_b)[f], f < F_b)        in librosa's sense (center=True, reflect padding)
+ *   input    x_b[0, len) of d_wav [batch, wav_stride], reflect-padded by N / 2 about sample 0 and about sample len - 1: the
+ *            signal's own end, not hop * (F_b - 1).  Nothing at or beyond min(len, wav_stride) is read.
+ *   synthesis  synthesis window, overlap-add divided by the window sum-square, trimmed by N / 2: what the Griffin-Lim
+ *            iteration kernel and its overlap-add kernel do
+ *   output   hop * (F_b - 1) samples, then zeros up to out_stride; every element of d_out [batch, out_stride] is written once
+ *   short    len <= N / 2 or hop * (F_b - 1) <= N / 2 gives a row of zeros; no length forms an address outside the buffers,
+ *            and the lengths are read on the device
+ * d_gain [batch, max_frames, n_bins] with n_bins = 1 + N / 2, real: the filter is zero-phase.  n_fft is NOT zero-padded, so
+ * the product G * Z is a CIRCULAR convolution within a frame: a gain whose impulse response is longer than the window's
+ * taper wraps around the frame's ends, damped only by the synthesis window.  This is not removed; a smooth gain (the taps
+ * above) keeps its response short.
+ * Workspace (vc_stft_filter_workspace_bytes; 0 for a NULL plan, batch <= 0 or max_frames <= 0; 4-byte aligned): one frame
+ * buffer [batch, max_frames, N] float32 rounded up to 256 bytes, whose rows at or beyond F_b are not written, then
+ * align256(4 * batch) bytes -- 256 up to 64 utterances -- in which the filter kernel leaves F_b [batch] int32 (0 for a
+ * zero row): the overlap-add kernel takes its frame counts from there, since F_b depends on lengths only the device knows.
+ * Two launches: the filter kernel (16 frames per workgroup at n_fft == 400, 4 otherwise; gather of the padded waveform,
+ * forward transform, G * Z in registers, inverse transform, window), then the vocoder's overlap-add kernel.  VC_ERR_INVALID
+ * before any launch for a NULL pointer (d_n_frames excepted), batch outside [1, 65535], max_frames < 1, wav_stride < 1 or
+ * out_stride < hop * (max_frames - 1); VC_ERR_WORKSPACE for a workspace that is too small.
+ *
+ * Neither call allocates, sets memory, uses atomics or synchronises; both are capturable from the first call, functions of
+ * their own utterance alone and bit-identical alone, in any batch and under graph replay. */
+int vc_spectral_diff_gain_f32(const float* d_pred, const float* d_true, const int32_t* d_n_frames, int32_t batch,
+                              int32_t max_frames, int32_t n_bins, float P_dB_norm_factor, float alpha, float max_boost_db,
+                              float max_cut_db, const float* d_taps, int32_t n_taps, float* d_gain, void* stream);
+size_t vc_stft_filter_workspace_bytes(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames);
+int vc_stft_filter_f32(const vc_vocoder_plan* plan, const float* d_wav, int32_t wav_stride, const int32_t* d_len,
+                       const float* d_gain, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_out,
+                       int32_t out_stride, void* d_workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ cases of them):
   phase_spsi(amp, n_frames)  -> torch.cuda tensor [B, Fmax, bins], a deterministic initial phase computed from the
                              magnitudes (single-pass spectrogram inversion; include/vc_hip.h vc_phase_spsi);
                              the batched vocoder calls take it as ``phase0='spsi'``
+  stft_filter_batch(wav, lens, gain, n_frames) -> torch.cuda tensor [B, hop*(F-1)]: istft(gain * stft(wav)), one
+                             transform pass that keeps the input's phase (include/vc_hip.h vc_stft_filter_f32)
 
 The Griffin-Lim entry points take ``momentum`` (default 0.0, the reference's algorithm): fast
 Griffin-Lim as in librosa.griffinlim / torchaudio GriffinLim, see include/vc_hip.h
@@ -458,6 +460,59 @@ def griffin_lim_batch(amp, n_frames=None, win_length=400, hop_length=80, num_ite
     if phase0.shape != amp.shape:
         raise ValueError(' - ERROR, griffin_lim_batch: phase0 must have the shape of amp')
     return _griffin_lim_launch(plan, amp, phase0, d_nf, num_iters, trace, momentum)
+
+
+def _stft_filter_launch(plan, wav, d_len, gain, d_nf):
+    """vc_stft_filter_f32 on validated device tensors (wav [B, Lmax], gain [B, Fmax, bins] float32 contiguous, d_len int32
+    [B], d_nf int32 [B] or None): no host check, copy or wait in here."""
+    import torch
+    B, Fmax, _ = gain.shape
+    L = plan.hop_length * (Fmax - 1)
+    out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
+    ws = torch.empty(_vc.lib().vc_stft_filter_workspace_bytes(plan.handle, B, Fmax), dtype=torch.uint8, device=wav.device)
+    _vc.check(_vc.lib().vc_stft_filter_f32(plan.handle, _vc.ptr(wav), wav.shape[1], _vc.ptr(d_len), _vc.ptr(gain), _vc.ptr(d_nf), B,
+                                           Fmax, _vc.ptr(out), L, _vc.ptr(ws), ws.numel(), _vc.current_stream()))
+    return out
+
+
+def stft_filter_batch(wav, lens, gain, n_frames=None, win_length=400, hop_length=80, n_fft=None):
+    """y = istft(gain * stft(wav)) for a ragged batch, in librosa's sense (vc_stft_filter_f32, include/vc_hip.h,
+    "Differential-spectrum conversion"): one transform pass, the source's own phase.
+
+    wav [B, Lmax] float32 (numpy or tensor); lens: the sample counts, host integers or an int32 [B] device tensor (None =
+    all Lmax); gain [B, F, 1 + n_fft//2] float32, real (zero-phase; the filtering is circular within a frame); n_frames:
+    the frames to use per utterance, host integers or an int32 [B] device tensor (None = 1 + len // hop_length); in every
+    case at most F and at most 1 + len // hop_length are used.
+    Returns y [B, hop_length * (F - 1)] float32 on the device: hop_length * (frames - 1) samples per utterance, zeros
+    beyond; an utterance shorter than the reflect padding (len <= n_fft//2, or hop_length * (frames - 1) <= n_fft//2) gives a
+    row of zeros.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    what = 'stft_filter_batch'
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    plan_key = (int(win_length), int(hop_length), int(n_fft or win_length))
+    nb = 1 + plan_key[2] // 2
+    if getattr(gain, 'ndim', 0) != 3 or gain.shape[0] != B or gain.shape[1] < 2 or gain.shape[2] != nb:
+        raise ValueError(' - ERROR, {}: gain must be [{}, F, {}] with F >= 2'.format(what, B, nb))
+    if B > 65535:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances'.format(what))
+    for v, hi, name in ((lens, Lmax, 'lens'), (n_frames, int(gain.shape[1]), 'n_frames')):
+        if v is None or (torch.is_tensor(v) and v.is_cuda):
+            if v is not None and (v.dtype != torch.int32 or tuple(v.shape) != (B,)):
+                raise ValueError(' - ERROR, {}: {} on the device must be int32 [{}]'.format(what, name, B))
+            continue
+        h = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+        if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > hi:
+            raise ValueError(' - ERROR, {}: {} must be {} integers in [0, {}]'.format(what, name, B, hi))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('stft_filter_batch needs a GPU (no CPU fallback)')
+    plan = _get_voc_plan(*plan_key)
+    as_dev = lambda t: (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))).to(
+        device='cuda', dtype=torch.float32).contiguous()
+    d_len = _int32_device(np.full((B,), Lmax, np.int64) if lens is None else lens, B, 'lens')
+    d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
+    return _stft_filter_launch(plan, as_dev(wav), d_len, as_dev(gain), d_nf)
 
 
 def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None, verbose=True, phase0=None,

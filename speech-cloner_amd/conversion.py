@@ -25,6 +25,11 @@ device.  ``duration_stats_batch`` / ``duration_ratios`` turn two speakers' segme
 converted waveform's F0 is tracked and ``pitch_shift_batch``'s launches (vc_psola_plan, vc_psola_ola_f32: overlap-add of
 grains placed by integrating the track) move it by a ratio, to a given contour or to the source's own.  ``pitch_tables``
 builds the launch's two Q16 tables from a track; ``f0_stats_batch`` / ``f0_transform`` map a contour between speakers.
+
+``convert_diff_batch`` makes the waveform without a vocoder: ``diff_gain_batch``
+(vc_spectral_diff_gain_f32) turns the converted and the source spectrum into a smoothed, clamped gain per frame and bin, and
+``audio_lib.stft_filter_batch`` (vc_stft_filter_f32) filters the source recording by it in one STFT / ISTFT pass, optionally
+after ``pitch_shift_batch``'s launches moved the source's fundamental.
 """
 from collections import namedtuple
 
@@ -1223,3 +1228,210 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
         n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
     return _PITCH_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
                      f0_pred, f0_target, pp)
+
+
+# --------------------------------------------------------------------------- differential spectrum (csrc/vc_vocoder.hip)
+DIFF_MAX_HALF_WIDTH = 32    # vc_spectral_diff_gain_f32: at most 65 taps
+_DIFF_NT = namedtuple('convert_diff', 'y_wav_pred n_samples mel_true mel_pred stft_true stft_pred phn_pred gain n_frames f0_src')
+
+
+def diff_smoothing_taps(half_width=8):
+    """The smoothing taps of the differential gain along frequency: a Hann shape over 2 * half_width + 1 bins,
+    0.5 + 0.5 cos(pi j / (half_width + 1)) for j = -half_width .. half_width (no zero end taps), computed in float64,
+    normalised to sum 1 and rounded to float32; half_width = 0 gives the single tap 1.  Host only."""
+    if isinstance(half_width, bool) or not isinstance(half_width, (int, np.integer)) or not 0 <= half_width <= DIFF_MAX_HALF_WIDTH:
+        raise ValueError(' - ERROR, diff_smoothing_taps: half_width must be an integer in [0, {}], got {!r}'.format(DIFF_MAX_HALF_WIDTH, half_width))
+    h = int(half_width)
+    c = 0.5 + 0.5 * np.cos(np.pi * np.arange(-h, h + 1, dtype=np.float64) / (h + 1))
+    c = 0.5 * (c + c[::-1])                                          # symmetric to the last bit
+    return (c / c.sum()).astype(np.float32)
+
+
+def _check_diff_args(alpha, max_boost_db, max_cut_db, what):
+    out = []
+    for v, name, hi in ((alpha, 'alpha', 1.0), (max_boost_db, 'max_boost_db', None), (max_cut_db, 'max_cut_db', None)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= float(np.finfo(np.float32).max) \
+                or (hi is not None and float(v) > hi):                  # NaN fails the comparison; finite as a float32
+            raise ValueError(' - ERROR, {}: {} must be a finite number {}, got {!r}'.format(
+                what, name, 'in [0, 1]' if hi is not None else 'that is not negative', v))
+        out.append(float(v))
+    return tuple(out)
+
+
+def _check_diff_taps(half_width, taps, what):
+    """float32 [n_taps] on the host: ``taps`` when given (odd, at most 65, finite), else diff_smoothing_taps(half_width)."""
+    if taps is None:
+        return diff_smoothing_taps(half_width)
+    import torch
+    t = np.asarray(taps.cpu() if torch.is_tensor(taps) else taps, dtype=np.float32)
+    if t.ndim != 1 or t.size % 2 != 1 or t.size > 2 * DIFF_MAX_HALF_WIDTH + 1 or not np.isfinite(t).all():
+        raise ValueError(' - ERROR, {}: taps must be an odd number of finite floats, at most {}'.format(what, 2 * DIFF_MAX_HALF_WIDTH + 1))
+    return np.ascontiguousarray(t)
+
+
+def _diff_gain_launch(stft_pred, stft_true, d_nf, norm, alpha, boost, cut, d_taps):
+    """vc_spectral_diff_gain_f32 on validated device tensors: no host check, copy or wait in here."""
+    import torch
+    import _vc
+    B, F, nb = stft_pred.shape
+    gain = torch.empty_like(stft_pred)
+    _vc.check(_vc.lib().vc_spectral_diff_gain_f32(_vc.ptr(stft_pred), _vc.ptr(stft_true), _vc.ptr(d_nf), B, F, nb, norm, alpha, boost,
+                                                  cut, _vc.ptr(d_taps), d_taps.shape[0], _vc.ptr(gain), _vc.current_stream()))
+    return gain
+
+
+def diff_gain_batch(stft_pred, stft_true, n_frames, P_dB_norm_factor, alpha=1.0, max_boost_db=20.0, max_cut_db=30.0, half_width=8,
+                    taps=None):
+    """The gain of the differential filter (vc_spectral_diff_gain_f32; the definition is in include/vc_hip.h,
+    "Differential-spectrum conversion", the restatement in tests/diff_ref.py): per frame and bin the difference of the two
+    spectra in dB, smoothed along frequency by ``taps`` (default diff_smoothing_taps(half_width)), scaled by alpha, clamped
+    to [-max_cut_db, max_boost_db] and turned into an amplitude ratio.
+
+    stft_pred, stft_true [B, F, bins] float32: the front-end's normalised power dB, as convert_batch(vocode=False) returns
+    them.  n_frames: host integers, an int32 [B] device tensor or None (all F).  Returns the gain [B, F, bins] float32 on
+    the device, 0 in the rows at or beyond n_frames.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    import _vc
+    what = 'diff_gain_batch'
+    alpha, boost, cut = _check_diff_args(alpha, max_boost_db, max_cut_db, what)
+    h_taps = _check_diff_taps(half_width, taps, what)
+    norm = float(P_dB_norm_factor)
+    if not np.isfinite(norm) or norm == 0.0:
+        raise ValueError(' - ERROR, {}: P_dB_norm_factor must be finite and not 0'.format(what))
+    if getattr(stft_pred, 'ndim', 0) != 3 or tuple(getattr(stft_true, 'shape', ())) != tuple(stft_pred.shape) or min(stft_pred.shape) < 1:
+        raise ValueError(' - ERROR, {}: stft_pred and stft_true must be [B, F, bins], the same shape'.format(what))
+    B, F, nb = (int(v) for v in stft_pred.shape)
+    if B > 65535 or not 2 <= nb <= 2049:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of 2 to 2049 bins'.format(what))
+    if n_frames is not None and not (torch.is_tensor(n_frames) and n_frames.is_cuda):
+        h = np.asarray(n_frames.cpu() if torch.is_tensor(n_frames) else n_frames)
+        if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > F:
+            raise ValueError(' - ERROR, {}: n_frames must be {} integers in [0, {}]'.format(what, B, F))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('diff_gain_batch needs a GPU (no CPU fallback)')
+    as_dev = lambda t: (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))).to(
+        device='cuda', dtype=torch.float32).contiguous()
+    d_nf = None if n_frames is None else _i32_device(n_frames, (B,), what + ': n_frames')
+    d_taps = torch.from_numpy(h_taps).pin_memory().to('cuda', non_blocking=True)
+    return _diff_gain_launch(as_dev(stft_pred), as_dev(stft_true), d_nf, norm, alpha, boost, cut, d_taps)
+
+
+def diff_frames(plan, hop):
+    """(n_use [B], n_samples [B]) int64 on the host from a convert_plan: n_use = min(n_out, n_clip), the frames of an
+    utterance that the model converted AND the source covers; n_samples = hop * (n_use - 1)."""
+    n_use = np.minimum(plan.n_out, plan.n_clip).astype(np.int64)
+    return n_use, int(hop) * (n_use - 1)
+
+
+def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None,
+                       stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None,
+                       window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+    """``convert_batch`` without a vocoder: the source recording is FILTERED by the difference between
+    the converted and the source spectral envelope (diff_gain_batch, audio_lib.stft_filter_batch), so its excitation and
+    phase stay natural and the waveform costs one transform pass instead of a Griffin-Lim run.  t_s is fixed at 0: output
+    frame u is input frame u, and the output covers n_use = min(n_out, n_clip) frames of convert_plan per utterance -- the
+    whole windows the model converted, cut where the source ends.
+
+    alpha, max_boost_db, max_cut_db, half_width: diff_gain_batch's (none of the defaults is tuned by ear).
+    pitch: None, or what moves the SOURCE's fundamental before the filter (pitch_shift_batch's launches on a track of the
+    source at the model's rate; the overlap-add keeps the envelope, which the filter then converts):
+      a number r         every voiced frame's fundamental times r (0.5 <= r <= 2);
+      [B, Fout] floats   the contour to reach, in Hz per frame, 0 = leave the frame as it is;
+      'source'           the source's own contour mapped by f0_transform(., stats_src, stats_tgt): both are required.
+    w_floor, f0_args: as convert_pitch_batch.  The other arguments are convert_batch's.
+    Returns a namedtuple: y_wav_pred [B, hop * (Fout - 1)] (the filtered source at the level convert_batch sets,
+    15 * mean_abs_amp_norm; zero beyond an utterance's n_samples), n_samples (hop * (n_use - 1) on the host, at out_sr when
+    given), mel_true / mel_pred / stft_true / stft_pred / phn_pred as convert_batch(vocode=False) returns them, gain
+    [B, Fout, bins], n_frames (n_use on the host) and f0_src (the source's track [B, 1 + Lmax // hop], None without pitch).
+    Every check and table is made on the host before the first launch; after the uploads nothing is copied to the host and
+    the host waits for nothing."""
+    import torch
+    import audio_lib
+    import evaluation
+    import _vc
+    what = 'convert_diff_batch'
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    alpha, boost, cut = _check_diff_args(alpha, max_boost_db, max_cut_db, what)
+    h_taps = _check_diff_taps(half_width, None, what)
+    source = isinstance(pitch, str)
+    if source and pitch != 'source':
+        raise ValueError(" - ERROR, {}: pitch must be None, a ratio, a [B, Fout] contour or 'source', got {!r}".format(what, pitch))
+    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and not source):
+        raise ValueError(" - ERROR, {}: stats_src and stats_tgt go together and with pitch='source'".format(what))
+    if source and stats_src is None:
+        raise ValueError(" - ERROR, {}: pitch='source' needs stats_src and stats_tgt (the source's own contour unmapped changes nothing)".format(what))
+    if source and (len(stats_src) != 3 or len(stats_tgt) != 3):
+        raise ValueError(' - ERROR, {}: stats must be (count, mean, std) as f0_stats_batch returns them'.format(what))
+    scalar = pitch is not None and not source and getattr(pitch, 'ndim', 0) == 0
+    if scalar:
+        pitch = _check_pitch_ratio(pitch.item() if hasattr(pitch, 'item') else pitch, what + ': pitch')
+    w_floor = _check_w_floor(w_floor, what)
+    kw = dict(frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5, switch_cost=0.1, n_cand=8, ceiling=1.0)
+    extra = set(f0_args or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: f0_args takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(f0_args or {})
+    h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type)
+    plan, B, hop, Fout, n_bins, sr = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    n_use, h_nsamp = diff_frames(plan, hop)
+    if int(h_nsamp.min()) <= h.n_fft // 2:
+        raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples'.format(what))
+    Lmax = int(audio_lib.resample_len(int(wav.shape[1]), wav_sr, sr)) if h.res_in else int(wav.shape[1])
+    if pitch is not None:
+        f0a = evaluation._f0_args(sr, hop, kw['frame_length'], kw['fmin'], kw['fmax'], kw['threshold'], what)
+        n_cand, ceiling = evaluation._track_args(kw['n_cand'], kw['ceiling'], what)
+        costs = evaluation._viterbi_costs(f0a[5], kw['jump_cost'], kw['switch_cost'], what)
+        _check_pitch_sizes(B, Lmax, 1 + Lmax // hop, hop, what)
+        if Lmax > evaluation.F0_MAX_SAMPLES:
+            raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
+        if not source and not scalar and tuple(getattr(pitch, 'shape', ())) != (B, Fout):
+            raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per frame)'.format(what, B, Fout))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('convert_diff_batch needs a GPU (no CPU fallback)')
+
+    # ---- uploads: the waveforms if they are on the host, one table, the taps, a contour
+    up = _convert_upload(h, wav, [n_use, h_nsamp, plan.n_src])
+    d_nuse, d_nsamp, d_fsrc = up.d_extra[-3:]
+    d_taps = torch.from_numpy(h_taps).pin_memory().to('cuda', non_blocking=True)
+    if pitch is not None and not source and not scalar:
+        if not torch.is_tensor(pitch):
+            pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
+        pitch = pitch.to(device='cuda', non_blocking=True)
+    if pitch is not None:
+        psola_window('cuda')
+    if h.res_in:                                                    # once, here: the filter and the tracker need the model's rate too
+        w16 = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), up.wav, up.d_extra[0])
+        h, up = h._replace(res_in=False), up._replace(wav=w16)
+
+    # ---- convert_batch(vocode=False): front-end, windows, model, the three stitches
+    mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
+    mel_pred = compound_stitch(y_mel, up.d_utt, Fout)
+    phn_pred = compound_stitch(y_phn, up.d_utt, Fout)
+    stft_pred = compound_stitch(y_stft, up.d_utt, Fout)
+
+    # ---- the source's fundamental, moved before the filter
+    x, f0_src = up.wav, None
+    if pitch is not None:
+        f0_src = evaluation._f0_track_launch(x, up.d_lens, d_fsrc, f0a, n_cand, ceiling, costs)[0]
+        target = None
+        if source:
+            target = f0_transform(f0_src, stats_src, stats_tgt)
+        elif not scalar:
+            n = min(Fout, f0_src.shape[1])                          # t_s == 0: frame u of the contour is frame u of the source
+            target = torch.zeros_like(f0_src)
+            target[:, :n] = pitch[:, :n].to(torch.float32)
+        per, rat = pitch_tables(f0_src, sr, ratio=pitch if scalar else None, target_f0=target, hop_length=hop)
+        x = _psola_ola_launch(x, up.d_lens, _psola_plan_launch(per, rat, up.d_lens, x.shape[1], hop), w_floor)
+
+    # ---- gain, filter, level
+    gain = _diff_gain_launch(stft_pred, stft_true, d_nuse, float(cfg_d['P_dB_norm_factor']), alpha, boost, cut, d_taps)
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
+    y = audio_lib._stft_filter_launch(vplan, x, up.d_lens, gain, d_nuse)
+    _vc.check(_vc.lib().vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(y), _vc.ptr(d_nuse), B, Fout, y.shape[1], 0.0,
+                                                     float(15 * cfg_d['mean_abs_amp_norm']), _vc.current_stream()))
+    n_samples = [int(v) for v in h_nsamp]
+    if h.res_out:
+        y = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y, d_nsamp)
+        n_samples = [int(v) for v in audio_lib.resample_len(h_nsamp, sr, out_sr)]
+    return _DIFF_NT(y, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, gain, [int(v) for v in n_use], f0_src)

@@ -313,6 +313,257 @@ gl_iter_generic_kernel(GlArgs a) {
     }
 }
 
+// ---- STFT-domain filter (include/vc_hip.h, "Differential-spectrum conversion"): frames of istft(G * stft(x)).
+// The iteration kernels with two changes: the gather reads the reflect-padded WAVEFORM (not the overlap-add of stored
+// frames), and the projection amp * Z / |Z| is the product G * Z.  Same tiles, same LDS, same transforms.
+struct SfArgs {
+    const float* wav;        // [B][wav_stride]
+    const int32_t* len;      // [B]
+    const float* gain;       // [B][maxF][nb]
+    const int32_t* n_frames; // [B] or null
+    float* frames;           // [B][maxF][N]
+    int32_t* f_out;          // [B]: F_b for the overlap-add launch behind this one
+    const float* window;     // [N] | tw400[416] | twg[2N]
+    int wav_stride, maxF, nb, N, hop, span;
+};
+
+// F_b, 0 for an utterance the reflect padding does not fit; len: the clamped sample count
+__device__ __forceinline__ int sf_frames(const SfArgs& a, int b, int& len) {
+    len = min(max(a.len[b], 0), a.wav_stride);
+    int F = min(a.maxF, 1 + len / a.hop);
+    if (a.n_frames) F = min(F, max(a.n_frames[b], 0));
+    return (len <= a.N / 2 || a.hop * (F - 1) <= a.N / 2) ? 0 : F;
+}
+
+// Samples of the reflect-padded signal x[0, len) this tile needs -> xs[0..span); len > N / 2, F >= 2
+__device__ __forceinline__ void sf_gather_tile(const SfArgs& a, const float* x, int len, int F, int f0, float* xs) {
+    const int half = a.N / 2;
+    const int end = a.hop * (F - 1) + a.N;                // <= len + N: the padded signal
+    for (int i = threadIdx.x; i < a.span; i += VT) {
+        const int p = f0 * a.hop + i;
+        float v = 0.0f;
+        if (p < end) {
+            int n = p - half;
+            n = n < 0 ? -n : (n >= len ? 2 * (len - 1) - n : n);
+            v = x[min(max(n, 0), len - 1)];
+        }
+        xs[i] = v;
+    }
+}
+
+__global__ void __launch_bounds__(VT)
+stft_filter400_kernel(SfArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NROW = VG * 13;
+    float* win = reinterpret_cast<float*>(smem);       // [400]
+    float* tw = win + 400;                             // [2][208]
+    float* Are = tw + 416;                             // [NROW*17]
+    float* Aim = Are + NROW * VA_STRIDE;
+    float* xs = Aim + NROW * VA_STRIDE;                // [span]
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int len;
+    const int F = sf_frames(a, b, len);
+    const int f0 = blockIdx.x * VG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    if (f0 >= F) return;
+    const int nvalid = min(VG, F - f0);
+
+    copy_lds(win, a.window, 816);
+    float gr[16];                                      // the gains of this thread's 16 slots, as amr[] of the iteration kernel
+    {
+        const int g = min(tid / 13, VG - 1), k1 = tid - (tid / 13) * 13;
+        const bool live = tid < NROW && g < nvalid;
+        const float* src = a.gain + ((size_t)b * a.maxF + f0 + (live ? g : 0)) * 201;
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            bool cj;
+            const int bin = vcfe::src_bin(live ? k1 : 0, k2, cj);      // a conjugate slot: the gain of its mirror bin
+            const float v = src[bin];
+            gr[k2] = live ? v : 0.0f;
+        }
+    }
+    __syncthreads();
+    sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
+    __syncthreads();
+    {   // forward step 1+2: thread (g, n2)
+        const int g = tid >> 4, n2 = tid & 15;
+        const float* xp = xs + g * a.hop + n2;
+        float v[25], ar[13], ai[13];
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
+        vcfe::rdft25_13(v, ar, ai);
+        const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+        for (int k1 = 0; k1 < 13; ++k1) {
+            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
+            Are[i0 + VA_STRIDE * k1] = ar[k1];
+            Aim[i0 + VA_STRIDE * k1] = ai[k1];
+        }
+    }
+    __syncthreads();
+    // thread (g, k1): forward 16-point stage, G * Z, inverse 16-point stage, conjugate twiddle -> B[k1][n2]
+    if (tid < NROW) {
+        const int k1 = tid - (tid / 13) * 13;
+        float zr[16], zi[16], yr[16], yi[16];
+#pragma unroll
+        for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = Are[VA_STRIDE * tid + n2]; zi[n2] = Aim[VA_STRIDE * tid + n2]; }
+        vcfe::cdft16(zr, zi, yr, yi);
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            zr[k2] = gr[k2] * yr[k2];
+            zi[k2] = gr[k2] * yi[k2];
+        }
+        vcfe::cidft16(zr, zi, yr, yi);
+#pragma unroll
+        for (int n2 = 0; n2 < 16; ++n2) {
+            vcfe::cmul(yr[n2], yi[n2], tw[k1 * 16 + n2], -tw[208 + k1 * 16 + n2]);
+            Are[VA_STRIDE * tid + n2] = yr[n2];
+            Aim[VA_STRIDE * tid + n2] = yi[n2];
+        }
+    }
+    __syncthreads();
+    // thread (g, n2): hermitian 25-point inverse, synthesis window, store the frame
+    {
+        const int g = tid >> 4, n2 = tid & 15;
+        if (g < nvalid) {
+            float br[13], bi[13], x[25];
+            const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+            for (int k1 = 0; k1 < 13; ++k1) { br[k1] = Are[i0 + VA_STRIDE * k1]; bi[k1] = Aim[i0 + VA_STRIDE * k1]; }
+            vcfe::hdft25_real(br, bi, x);
+            float* out = a.frames + ((size_t)b * a.maxF + f0 + g) * 400 + n2;
+#pragma unroll
+            for (int n1 = 0; n1 < 25; ++n1) out[16 * n1] = x[n1] * win[16 * n1 + n2] * (1.0f / 400.0f);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(VT)
+stft_filter_generic_kernel(SfArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int N = a.N, nb = a.nb;
+    float* win = reinterpret_cast<float*>(smem);       // [N]
+    float* twr = win + N;                              // [N]
+    float* twi = twr + N;                              // [N]
+    float* Sr = twi + N;                               // [VGG][nb]
+    float* Si = Sr + VGG * nb;
+    float* xs = Si + VGG * nb;                         // [span]
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int len;
+    const int F = sf_frames(a, b, len);
+    const int f0 = blockIdx.x * VGG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    if (f0 >= F) return;
+    const int nvalid = min(VGG, F - f0);
+    copy_lds(win, a.window, N);
+    copy_lds(twr, a.window + N + 416, 2 * N);
+    __syncthreads();
+    sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
+    __syncthreads();
+    for (int idx = tid; idx < nvalid * nb; idx += VT) {
+        const int g = idx / nb, k = idx - g * nb;
+        const float gn = a.gain[((size_t)b * a.maxF + f0 + g) * nb + k];
+        const float* xp = xs + g * a.hop;
+        float re = 0.0f, im = 0.0f;
+        int m = 0;
+        for (int n = 0; n < N; ++n) {
+            const float xv = xp[n] * win[n];
+            re = fmaf(xv, twr[m], re);
+            im = fmaf(xv, twi[m], im);
+            m += k; if (m >= N) m -= N;
+        }
+        Sr[idx] = gn * re;
+        Si[idx] = gn * im;
+    }
+    __syncthreads();
+    const float invN = 1.0f / (float)N;
+    for (int idx = tid; idx < nvalid * N; idx += VT) {
+        const int g = idx / N, n = idx - g * N;
+        const float* sr = Sr + g * nb;
+        const float* si = Si + g * nb;
+        float acc = 0.0f;
+        int m = n;
+        for (int k = 1; k < nb - 1; ++k) {
+            acc = fmaf(sr[k], twr[m], acc);
+            acc = fmaf(si[k], twi[m], acc);
+            m += n; if (m >= N) m -= N;
+        }
+        const float edge = sr[0] + ((n & 1) ? -sr[nb - 1] : sr[nb - 1]);
+        a.frames[((size_t)b * a.maxF + f0 + g) * N + n] = (edge + 2.0f * acc) * invN * win[n];
+    }
+}
+
+// ---- the gain of the differential filter (include/vc_hip.h).  grid (tiles of gt frames, B).  A tile's differences go to
+// LDS once, nb a frame; the smoothing reads them with the mirrored edges folded into the index (a bin whose taps all fall
+// inside the row takes the plain loop).  Each lane then takes four consecutive elements of the tile's flat output.
+constexpr int DG_MAX_TAPS = 65;
+
+__device__ __forceinline__ int refl_bin(int i, int nb) {
+    const int P = 2 * (nb - 1);
+    int m = i % P;
+    if (m < 0) m += P;
+    return m < nb ? m : P - m;
+}
+
+// sum_j c[j] * d[.] ascending in j from +0, every product and every sum rounded on its own
+__device__ __forceinline__ float smooth_rn(const float* c, const float* d, int k, int h, int nb) {
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+    if (k - h >= 0 && k + h < nb) {
+        const float* p = d + (k - h);
+        for (int j = 0; j <= 2 * h; ++j) { const float m = c[j] * p[j]; acc = acc + m; }
+    } else {
+        for (int j = 0; j <= 2 * h; ++j) { const float m = c[j] * d[refl_bin(k - h + j, nb)]; acc = acc + m; }
+    }
+    return acc;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(VT)
+diff_gain_kernel(const float* __restrict__ pred, const float* __restrict__ tru, const int32_t* __restrict__ n_frames, int maxF,
+                 int nb, int gt, float norm, float alpha, float boost, float cut, const float* __restrict__ taps, int n_taps,
+                 float* __restrict__ gain) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* c = reinterpret_cast<float*>(smem);         // [DG_MAX_TAPS + 3]
+    float* d = c + DG_MAX_TAPS + 3;                    // [gt][nb]
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int F = n_frames ? min(max(n_frames[b], 0), maxF) : maxF;
+    const int f0 = blockIdx.x * gt;
+    const int rows = min(gt, maxF - f0);               // rows of this tile inside the slab: all are written
+    const int live = min(max(F - f0, 0), rows);        // ... of which these hold a gain
+    const size_t base = ((size_t)b * maxF + f0) * nb;
+    if (tid < n_taps) c[tid] = taps[tid];
+    for (int i = tid; i < live * nb; i += VT)          // rows of 201 floats: element by element, as vc_compound_stitch reads
+        d[i] = (fmaxf(pred[base + i], 0.0f) - fmaxf(tru[base + i], 0.0f)) / norm;
+    __syncthreads();
+    const int h = (n_taps - 1) / 2;
+    const int total = rows * nb;
+    for (int e0 = tid * 4; e0 < total; e0 += VT * 4) {
+        float v[4];
+        int g = e0 / nb, k = e0 - g * nb;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float G = 0.0f;
+            if (g < live) {
+                const float s0 = smooth_rn(c, d + g * nb, k, h, nb);
+                const float s = fminf(fmaxf(alpha * s0, -cut), boost);
+                G = exp2f(s * 0.16609640474436813f);   // float32(log2(10) / 20): power dB -> amplitude ratio
+            }
+            v[q] = G;
+            if (++k == nb) { k = 0; ++g; }
+        }
+        if (VEC) {
+            *reinterpret_cast<float4*>(gain + base + e0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (e0 + q < total) gain[base + e0 + q] = v[q];
+        }
+    }
+}
+
 // wav[b][n] = trimmed, normalised overlap-add of the frames; optionally accumulates
 // sum (wav - prev_wav)^2 into *delta (what the reference's verbose mode prints).
 __global__ void __launch_bounds__(VT)
@@ -623,6 +874,82 @@ int vc_inv_preemphasis_normalize(const vc_vocoder_plan* p, float* d_wav, const i
     VC_REQUIRE(p && d_wav && batch > 0 && max_frames >= 1 && wav_stride >= 0, "vc_inv_preemphasis_normalize: bad arguments");
     hipLaunchKernelGGL(inv_preemph_norm_kernel, dim3(batch), dim3(PT), 0, (hipStream_t)stream, d_wav, d_n_frames, max_frames,
                        p->hop, wav_stride, coeff, mean_abs_amp_norm);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+int vc_spectral_diff_gain_f32(const float* d_pred, const float* d_true, const int32_t* d_n_frames, int32_t batch,
+                              int32_t max_frames, int32_t n_bins, float P_dB_norm_factor, float alpha, float max_boost_db,
+                              float max_cut_db, const float* d_taps, int32_t n_taps, float* d_gain, void* stream) {
+    const char* fn = "vc_spectral_diff_gain_f32";
+    VC_REQUIRE(d_pred && d_true && d_taps && d_gain, "%s: NULL argument", fn);
+    VC_REQUIRE(batch >= 1 && batch <= 65535 && max_frames >= 1 && n_bins >= 2 && n_bins <= 2049,
+               "%s: bad shape (batch %d in [1, 65535], max_frames %d >= 1, n_bins %d in [2, 2049])", fn, batch, max_frames, n_bins);
+    VC_REQUIRE(n_taps >= 1 && n_taps <= DG_MAX_TAPS && (n_taps & 1), "%s: n_taps must be odd and in [1, %d] (got %d)", fn,
+               DG_MAX_TAPS, n_taps);
+    VC_REQUIRE(std::isfinite(P_dB_norm_factor) && P_dB_norm_factor != 0.0f && std::isfinite(alpha) &&
+               std::isfinite(max_boost_db) && std::isfinite(max_cut_db), "%s: a float argument is not finite, or P_dB_norm_factor is 0", fn);
+    VC_REQUIRE(alpha >= 0.0f && alpha <= 1.0f, "%s: alpha must be in [0, 1] (got %g)", fn, (double)alpha);
+    VC_REQUIRE(max_boost_db >= 0.0f && max_cut_db >= 0.0f, "%s: the clamps must not be negative (got %g, %g)", fn,
+               (double)max_boost_db, (double)max_cut_db);
+    VC_REQUIRE((long long)max_frames * n_bins < (1ll << 31), "%s: an utterance holds more than 2^31 values", fn);
+    // 16 frames a tile while their differences fit 64 KB of LDS with the taps, else 4 (n_bins <= 2049: 33 KB)
+    const int gt = (size_t)16 * n_bins * sizeof(float) <= 60 * 1024 ? 16 : 4;
+    const size_t smem = sizeof(float) * ((size_t)DG_MAX_TAPS + 3 + (size_t)gt * n_bins);
+    const dim3 grid(((unsigned)max_frames + gt - 1) / gt, (unsigned)batch);
+    const bool vec = ((long long)max_frames * n_bins) % 4 == 0 && ((uintptr_t)d_gain & 15) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (vec)
+        hipLaunchKernelGGL((diff_gain_kernel<true>), grid, dim3(VT), smem, st, d_pred, d_true, d_n_frames, max_frames, n_bins, gt,
+                           P_dB_norm_factor, alpha, max_boost_db, max_cut_db, d_taps, n_taps, d_gain);
+    else
+        hipLaunchKernelGGL((diff_gain_kernel<false>), grid, dim3(VT), smem, st, d_pred, d_true, d_n_frames, max_frames, n_bins, gt,
+                           P_dB_norm_factor, alpha, max_boost_db, max_cut_db, d_taps, n_taps, d_gain);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+// frame buffer, then the table F_b [batch] int32 the filter kernel leaves for the overlap-add (the spare bytes up to 64
+// utterances, rounded up to 256 beyond)
+static size_t sf_frames_bytes(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames) {
+    return ((size_t)batch * max_frames * plan->N * sizeof(float) + 255) & ~(size_t)255;
+}
+
+size_t vc_stft_filter_workspace_bytes(const vc_vocoder_plan* plan, int32_t batch, int32_t max_frames) {
+    if (!plan || batch <= 0 || max_frames <= 0) return 0;
+    return sf_frames_bytes(plan, batch, max_frames) + (((size_t)batch * sizeof(int32_t) + 255) & ~(size_t)255);
+}
+
+int vc_stft_filter_f32(const vc_vocoder_plan* p, const float* d_wav, int32_t wav_stride, const int32_t* d_len,
+                       const float* d_gain, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_out,
+                       int32_t out_stride, void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "vc_stft_filter_f32";
+    VC_REQUIRE(p && d_wav && d_len && d_gain && d_out && d_workspace, "%s: NULL argument", fn);
+    VC_REQUIRE(batch >= 1 && batch <= 65535 && max_frames >= 1 && wav_stride >= 1,
+               "%s: bad shape (batch %d in [1, 65535], max_frames %d >= 1, wav_stride %d >= 1)", fn, batch, max_frames, wav_stride);
+    VC_REQUIRE((long long)p->hop * (max_frames - 1) + p->N < (1ll << 31), "%s: %d frames exceed 2^31 samples", fn, max_frames);
+    VC_REQUIRE(out_stride >= p->hop * (max_frames - 1) && out_stride >= 1, "%s: out_stride %d < %d samples", fn, out_stride,
+               p->hop * (max_frames - 1));
+    VC_REQUIRE(((uintptr_t)d_workspace & 3) == 0, "%s: workspace must be 4-byte aligned", fn);
+    if (workspace_bytes < vc_stft_filter_workspace_bytes(p, batch, max_frames))
+        return vc::set_error(VC_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes,
+                             vc_stft_filter_workspace_bytes(p, batch, max_frames));
+    const bool fast = (p->N == 400);
+    if (int rc = vc::allow_dynamic_lds<stft_filter400_kernel, stft_filter_generic_kernel>(160 * 1024)) return rc;
+    SfArgs a;
+    a.wav = d_wav; a.len = d_len; a.gain = d_gain; a.n_frames = d_n_frames;
+    a.frames = reinterpret_cast<float*>(d_workspace);
+    a.f_out = reinterpret_cast<int32_t*>((char*)d_workspace + sf_frames_bytes(p, batch, max_frames));
+    a.window = p->d_tables;
+    a.wav_stride = wav_stride; a.maxF = max_frames; a.nb = p->nb; a.N = p->N; a.hop = p->hop;
+    a.span = fast ? p->span : p->span_g;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
+    if (fast) hipLaunchKernelGGL(stft_filter400_kernel, grid, dim3(VT), p->smem400, st, a);
+    else hipLaunchKernelGGL(stft_filter_generic_kernel, grid, dim3(VT), p->smem_gen, st, a);
+    const dim3 ogrid(((unsigned)out_stride + VT - 1) / VT, (unsigned)batch);
+    hipLaunchKernelGGL(gl_ola_kernel, ogrid, dim3(VT), (size_t)p->N * sizeof(float), st, a.frames, a.f_out, p->d_tables,
+                       max_frames, p->N, p->hop, p->nov, d_out, out_stride, (const float*)nullptr, 0, (float*)nullptr);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }
