@@ -532,50 +532,53 @@ split16_kernel(const float* __restrict__ X, int M, int C, int ldx, int T, const 
     const int m = blockIdx.x * rpb + r;
     const int mm = min(m, M - 1);
     const bool pooled = pool && (mm % T) != T - 1;
-    const int ng = C / (4 * tpr);                      // float4 groups per thread (<= 4)
-    float4 v[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (g < ng) {
-            const int c = (g * tpr + t) * 4;
-            float4 x = *reinterpret_cast<const float4*>(X + (size_t)mm * ldx + c);
-            float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (scale) sc = *reinterpret_cast<const float4*>(scale + c);
-            if (shift) sh = *reinterpret_cast<const float4*>(shift + c);
-            if (scale || shift || relu) {
-                x.x = pro_val(x.x, sc.x, sh.x, relu); x.y = pro_val(x.y, sc.y, sh.y, relu);
-                x.z = pro_val(x.z, sc.z, sh.z, relu); x.w = pro_val(x.w, sc.w, sh.w, relu);
-            }
-            if (pooled) {
-                float4 y = *reinterpret_cast<const float4*>(X + (size_t)(mm + 1) * ldx + c);
-                if (scale || shift || relu) {
-                    y.x = pro_val(y.x, sc.x, sh.x, relu); y.y = pro_val(y.y, sc.y, sh.y, relu);
-                    y.z = pro_val(y.z, sc.z, sh.z, relu); y.w = pro_val(y.w, sc.w, sh.w, relu);
-                }
-                x.x = fmaxf(x.x, y.x); x.y = fmaxf(x.y, y.y); x.z = fmaxf(x.z, y.z); x.w = fmaxf(x.w, y.w);
-            }
-            v[g] = x;
-        }
-    }
+    const int ng = C / (4 * tpr);                      // float4 groups per thread: <= 4, or an odd count (C = 64 * odd)
     // s = 2^(14 - floor(log2 amax)); all-zero windows and windows holding Inf / NaN keep s = 1 (Inf / NaN propagate)
     float s, rs;
     w16_scale(wmaxg[mm / T], s, rs);
-    if (m < M) {
-        if (t == 0) row_scale[m] = rs;
-        _Float16* o = out + (size_t)m * 2 * C;
+    if (m < M && t == 0) row_scale[m] = rs;
+#pragma unroll 1
+    for (int gb = 0; gb < ng; gb += 4) {               // four groups at a time (one pass unless C = 64 * odd > 256)
+        float4 v[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            if (g < ng) {
-                const int c = (g * tpr + t) * 4;
-                const float xs[4] = {v[g].x * s, v[g].y * s, v[g].z * s, v[g].w * s};
-                f16x4 hi, lo;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    hi[i] = (_Float16)xs[i];
-                    lo[i] = (_Float16)(xs[i] - (float)hi[i]);
+            if (gb + g < ng) {
+                const int c = ((gb + g) * tpr + t) * 4;
+                float4 x = *reinterpret_cast<const float4*>(X + (size_t)mm * ldx + c);
+                float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (scale) sc = *reinterpret_cast<const float4*>(scale + c);
+                if (shift) sh = *reinterpret_cast<const float4*>(shift + c);
+                if (scale || shift || relu) {
+                    x.x = pro_val(x.x, sc.x, sh.x, relu); x.y = pro_val(x.y, sc.y, sh.y, relu);
+                    x.z = pro_val(x.z, sc.z, sh.z, relu); x.w = pro_val(x.w, sc.w, sh.w, relu);
                 }
-                *reinterpret_cast<f16x4*>(o + c) = hi;
-                *reinterpret_cast<f16x4*>(o + C + c) = lo;
+                if (pooled) {
+                    float4 y = *reinterpret_cast<const float4*>(X + (size_t)(mm + 1) * ldx + c);
+                    if (scale || shift || relu) {
+                        y.x = pro_val(y.x, sc.x, sh.x, relu); y.y = pro_val(y.y, sc.y, sh.y, relu);
+                        y.z = pro_val(y.z, sc.z, sh.z, relu); y.w = pro_val(y.w, sc.w, sh.w, relu);
+                    }
+                    x.x = fmaxf(x.x, y.x); x.y = fmaxf(x.y, y.y); x.z = fmaxf(x.z, y.z); x.w = fmaxf(x.w, y.w);
+                }
+                v[g] = x;
+            }
+        }
+        if (m < M) {
+            _Float16* o = out + (size_t)m * 2 * C;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (gb + g < ng) {
+                    const int c = ((gb + g) * tpr + t) * 4;
+                    const float xs[4] = {v[g].x * s, v[g].y * s, v[g].z * s, v[g].w * s};
+                    f16x4 hi, lo;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        hi[i] = (_Float16)xs[i];
+                        lo[i] = (_Float16)(xs[i] - (float)hi[i]);
+                    }
+                    *reinterpret_cast<f16x4*>(o + c) = hi;
+                    *reinterpret_cast<f16x4*>(o + C + c) = lo;
+                }
             }
         }
     }
@@ -772,7 +775,6 @@ int vc_split16(const float* d_X, int32_t M, int32_t C, int32_t ldx, int32_t T, c
     int tl = 4;                                        // threads per row: C / 4 up to 256, a power of two
     while ((1 << tl) < C / 4 && tl < 8) ++tl;
     while (C % (4 << tl)) --tl;                        // C = 64 * odd: fewer threads, more groups
-    VC_REQUIRE(C / (4 << tl) <= 4, "vc_split16: unsupported channel count %d", C);
     const int rpb = 256 >> tl;
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned* wmax = reinterpret_cast<unsigned*>(d_row_scale + M);       // scratch behind the M scales: one word per window
@@ -843,14 +845,15 @@ int vc_gemm16(const vc_gemm16_desc* d, void* stream) {
     for (int i = 0; i < d->n_pairs; ++i) {
         const vc_gemm16_pair& s = d->pairs[i];
         G16Pair& p = a.p[i];
-        VC_REQUIRE(s.d_Bt0 && s.d_Bt1 && (reinterpret_cast<uintptr_t>(s.d_Bt0) & 15) == 0 && (reinterpret_cast<uintptr_t>(s.d_Bt1) & 15) == 0,
-                   "vc_gemm16: pair %d: NULL / unaligned weights", i);
+        // a single 128-column filter (nrows1 = -1) never reads d_Bt1: NULL is accepted there
+        VC_REQUIRE(s.d_Bt0 && (s.d_Bt1 || s.nrows1 == -1) && (reinterpret_cast<uintptr_t>(s.d_Bt0) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(s.d_Bt1) & 15) == 0, "vc_gemm16: pair %d: NULL / unaligned weights", i);
         // (atomic accumulation: c_off* are element offsets of each filter's [rows, ldc] block from d_C, any alignment)
         VC_REQUIRE(s.c_off0 >= 0 && s.c_off1 >= 0 && (atomic || ((s.c_off0 & 3) == 0 && (s.c_off1 & 3) == 0 && s.c_off0 + 128 <= d->ldc &&
                    s.c_off1 + 128 <= d->ldc)), "vc_gemm16: pair %d: bad output columns", i);
         VC_REQUIRE(s.row0 >= 0 && s.nrows0 >= 0 && s.nrows1 >= -1 && s.row0 + (s.nrows0 > s.nrows1 ? s.nrows0 : s.nrows1) <= d->M,
                    "vc_gemm16: pair %d: bad row range", i);
-        p.Bt0 = s.d_Bt0; p.Bt1 = s.d_Bt1; p.c_off0 = s.c_off0; p.c_off1 = s.c_off1;
+        p.Bt0 = s.d_Bt0; p.Bt1 = s.d_Bt1 ? s.d_Bt1 : s.d_Bt0; p.c_off0 = s.c_off0; p.c_off1 = s.c_off1;
         p.row0 = s.row0;
         p.s_off0 = atomic ? s.s_off0 : s.c_off0;
         p.s_off1 = atomic ? s.s_off1 : s.c_off1;
