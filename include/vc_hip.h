@@ -1559,6 +1559,63 @@ int vc_psola_ola_f32(const float* d_x, const int32_t* d_len, const int32_t* d_n_
                      const int32_t* d_h, const float* d_window, int32_t batch, int32_t max_len, float w_floor, float* d_y,
                      void* stream);
 
+/* Time scale.  Duration conversion warps SPECTRA along vc_duration_map's time map and leaves the phase to the vocoder.
+ * These two launches move a WAVEFORM along the same map: waveform-similarity overlap-add (WSOLA, Verhelst & Roelands).
+ * Grains of 2 S samples are copied from the input, one every S output samples; each is chosen within +-tol samples of
+ * where the map points so that it continues its predecessor's waveform.  No F0 track is needed, and the local phase of a
+ * natural recording survives -- what the differential route (below) needs to change its timing.  Added without a version
+ * bump.  tests/wsola_ref.py restates both; every decision is integer arithmetic and the device equals it bit for bit.
+ *
+ * Inputs per utterance: x[0, len) float32 in a row of d_x [batch, x_stride]; len from d_len int32 [batch], clamped to
+ * [0, max_len]; pos[0, n_out) int32 Q16 input frames in a row of d_pos [batch, out_frames] exactly as vc_duration_map
+ * writes them, n_out from d_n_out [batch], clamped to [0, out_frames]; every pos is clamped to >= 0 when read and the -1
+ * padding from n_out on is never read.  Scalars: hop (samples per frame), group g >= 1, S = g * hop (the synthesis hop),
+ * tol >= 0 (the search half width in samples), qscale (float32 > 0).
+ *   Sizes      out_len = hop * (n_out - 1) when n_out >= 2 and len >= 1, else 0;
+ *              K = ceil(out_len / S) + 1 when out_len > 0, else 0.
+ *   Quantised  q[n] = clamp(rint(float32(x[n] * qscale)), -32767, 32767) as an integer: the product rounded once to
+ *              float32, then to the nearest integer with ties to even; NaN gives 0, +-inf +-32767.  q~ and x~ are q and x
+ *              extended by zeros outside [0, len).
+ *   Targets    u_k = min(k * g, n_out - 1);  tau_k = clamp((int64(pos[u_k]) * hop + 32768) >> 16, 0, len - 1): frame u is
+ *              centred on sample u * hop, the front-end's convention.
+ *   Recurrence a_0 = tau_0, cost_0 = 0.  For k >= 1 with n_k = a_{k-1} + S (the natural continuation) and every d in
+ *              [-tol, tol]:  cost(d) = sum_{i = -S}^{S - 1} | q~[tau_k + d + i] - q~[n_k + i] |, exact in int32
+ *              (65534 * 2048 < 2^31).  The d of the smallest (cost, |d|, d) in lexicographic order is taken:
+ *              a_k = tau_k + d, cost_k = cost(d).  |a_k - tau_k| <= tol always: the chain cannot drift from the map.
+ *   Output     for m in [0, out_len): k = m / S, r = m - k * S, A = x~[a_k + r], B = x~[a_{k+1} + r - S],
+ *              y[m] = A + T[r] * (B - A) as three separately rounded float32 operations (no contraction);
+ *              T[r] = float32(0.5 - 0.5 cos(pi r / S)), r in [0, S), made on the host in float64 (d_window, S floats on the
+ *              device).  y is zero from out_len to the row's end, hop * (out_frames - 1).
+ * Consequences: where a grain is the natural continuation of its predecessor, A == B and y copies x bit for bit; with the
+ * identity map d = 0 costs 0 and wins every tie, so y == x[:out_len]; a signal of integer period P <= 2 tol + 1 always has
+ * a candidate of cost 0 while grains and candidates stay inside [0, len), so y[m] == x[(m + a_0) mod P] at any rate.
+ *
+ * vc_wsola_plan writes, per utterance and with M = vc_wsola_max_grains(out_frames, hop, group) =
+ * ceil(hop * (out_frames - 1) / S) + 1 (a host-only query; 0 beyond the limits): d_a [batch, M] int32, INT32_MIN from K on;
+ * d_cost [batch, M] int32, -1 from K on; d_n_grains = K and d_out_len [batch]; every element exactly once.  One workgroup of
+ * 512 lanes per utterance (the chain over k is sequential): per step the 2 S reference samples and the 2 S + 2 tol samples of
+ * the candidate span go into LDS as biased 16-bit integers, two to a dword; candidates go in pairs (2 p, 2 p + 1) that share their dwords, up to 8 lanes share a pair's window, and
+ * the 64-bit key (cost, |d|, d) is reduced over the wave by shuffles and over the waves through LDS.
+ *
+ * vc_wsola_ola_f32: grid (tiles of 1,024 outputs, utterance).  d_y [batch, hop * (out_frames - 1)], every element written
+ * exactly once, the zeros from out_len on included (a row of no samples -- out_frames == 1 -- launches nothing); d_x is not
+ * read at or beyond len.  The plan is read defensively: d_n_grains is clamped to [0, M], d_out_len to the row, a grain at or
+ * beyond the count or with a outside [-2^24, 2^24] covers nothing (its samples count as 0), and no plan value forms an
+ * address unchecked.  d_y must not be d_x.
+ *
+ * Both are functions of their own utterance alone, bit-identical alone, in any batch, from run to run and under graph
+ * replay; they take everything from device memory, allocate nothing and wait for nothing.  VC_ERR_INVALID before any HIP
+ * call for a NULL pointer, a size below 1, tol < 0, x_stride < max_len or a qscale that is not positive and finite.  Limits
+ * (VC_ERR_UNSUPPORTED beyond them, nothing launched): batch <= 65,535; max_len <= 2^24; out_frames <= 16,384; hop in
+ * [1, 1024]; S in [1, 1024]; tol in [0, 1024]. */
+int32_t vc_wsola_max_grains(int32_t out_frames, int32_t hop, int32_t group);
+int vc_wsola_plan(const float* d_x, int32_t x_stride, const int32_t* d_len, const int32_t* d_pos, const int32_t* d_n_out,
+                  int32_t batch, int32_t max_len, int32_t out_frames, int32_t hop, int32_t group, int32_t tol, float qscale,
+                  int32_t* d_a, int32_t* d_cost, int32_t* d_n_grains, int32_t* d_out_len, void* stream);
+int vc_wsola_ola_f32(const float* d_x, int32_t x_stride, const int32_t* d_len, const int32_t* d_a, const int32_t* d_n_grains,
+                     const int32_t* d_out_len, const float* d_window, int32_t batch, int32_t max_len, int32_t out_frames,
+                     int32_t hop, int32_t group, float* d_y, void* stream);
+
 /* Differential-spectrum conversion (Kobayashi & Toda; sprocket's DIFFVC).  The other conversion entry points SYNTHESISE the
  * converted spectrum with Griffin-Lim.  These two launches FILTER the source recording by the difference between the
  * converted and the source spectral envelope instead: excitation and phase stay the source's own, and the cost is one

@@ -301,6 +301,10 @@ _SIGS = {
     'vc_psola_max_marks': (C.c_int32, [C.c_int32]),
     'vc_psola_plan': (C.c_int, [_P, _P, _P] + [C.c_int32] * 4 + [_P] * 7),
     'vc_psola_ola_f32': (C.c_int, [_P] * 7 + [C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    # waveform time scaling (csrc/vc_wsola.hip)
+    'vc_wsola_max_grains': (C.c_int32, [C.c_int32] * 3),
+    'vc_wsola_plan': (C.c_int, [_P, C.c_int32, _P, _P, _P] + [C.c_int32] * 6 + [C.c_float] + [_P] * 5),
+    'vc_wsola_ola_f32': (C.c_int, [_P, C.c_int32] + [_P] * 5 + [C.c_int32] * 5 + [_P, _P]),
     # differential-spectrum conversion (csrc/vc_vocoder.hip)
     'vc_spectral_diff_gain_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                                             _P, C.c_int32, _P, _P]),
@@ -341,7 +345,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then the
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the
                 # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '

@@ -30,6 +30,11 @@ builds the launch's two Q16 tables from a track; ``f0_stats_batch`` / ``f0_trans
 (vc_spectral_diff_gain_f32) turns the converted and the source spectrum into a smoothed, clamped gain per frame and bin, and
 ``audio_lib.stft_filter_batch`` (vc_stft_filter_f32) filters the source recording by it in one STFT / ISTFT pass, optionally
 after ``pitch_shift_batch``'s launches moved the source's fundamental.
+
+``convert_diff_duration_batch`` is ``convert_diff_batch`` with the timing changed as well: the FILTERED
+waveform is moved along ``duration_map_batch``'s time map by ``time_scale_batch`` (vc_wsola_plan, vc_wsola_ola_f32:
+waveform-similarity overlap-add -- copied grains, each chosen near the map so that it continues its predecessor), which
+keeps the recording's local phase; ``wsola_plan_batch`` returns the grain positions alone.
 """
 from collections import namedtuple
 
@@ -1435,3 +1440,285 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
         y = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y, d_nsamp)
         n_samples = [int(v) for v in audio_lib.resample_len(h_nsamp, sr, out_sr)]
     return _DIFF_NT(y, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, gain, [int(v) for v in n_use], f0_src)
+
+
+# --------------------------------------------------------------------------- time scale (csrc/vc_wsola.hip)
+WSOLA_MAX_LEN = 1 << 24     # vc_wsola_plan, vc_wsola_ola_f32: samples per utterance
+WSOLA_MAX_FRAMES = 16384    # output frames
+WSOLA_MAX_HOP = 1024
+WSOLA_MAX_S = 1024          # group * hop_length, the synthesis hop
+WSOLA_MAX_TOL = 1024
+_PLAN_WSOLA_NT = namedtuple('wsola_plan', 'a cost n_grains out_len hop group tol max_len out_frames')
+_SCALE_NT = namedtuple('time_scale', 'y n_samples plan')
+_DIFF_DUR_NT = namedtuple('convert_diff_duration', _DIFF_NT._fields + ('flags', 'seg', 'map', 'plan', 'max_frames', 'max_samples',
+                                                                       'src_frames'))
+_wsola_windows = {}
+
+
+def wsola_window(S, device=None):
+    """The cross-fade table of the time-scale overlap-add (include/vc_hip.h, "Time scale"): T[r] = float32(0.5 - 0.5
+    cos(pi r / S)), r = 0 .. S - 1, made in float64.  A numpy array without ``device``; with one, the device's cached copy."""
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= S <= WSOLA_MAX_S:
+        raise ValueError(' - ERROR, wsola_window: S must be an integer in [1, {}], got {!r}'.format(WSOLA_MAX_S, S))
+    S = int(S)
+    w = (0.5 - 0.5 * np.cos(np.pi * np.arange(S, dtype=np.float64) / S)).astype(np.float32)
+    if device is None:
+        return w
+    import torch
+    key = (str(torch.device(device)), S)
+    if key not in _wsola_windows:
+        _wsola_windows[key] = torch.from_numpy(w).pin_memory().to(device, non_blocking=True)
+    return _wsola_windows[key]
+
+
+def _check_wsola_args(B, Lmax, Fw, hop, group, tol, qscale, what):
+    """(hop, group, tol, qscale) as the launches take them; ValueError beyond their limits."""
+    for v, name, hi in ((hop, 'hop_length', WSOLA_MAX_HOP), (group, 'group', WSOLA_MAX_S)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError(' - ERROR, {}: {} must be an integer in [1, {}], got {!r}'.format(what, name, hi, v))
+    S = int(group) * int(hop)
+    if S > WSOLA_MAX_S:
+        raise ValueError(' - ERROR, {}: group * hop_length must be at most {}, got {}'.format(what, WSOLA_MAX_S, S))
+    if tol is None:
+        tol = S
+    if isinstance(tol, bool) or not isinstance(tol, (int, np.integer)) or not 0 <= tol <= WSOLA_MAX_TOL:
+        raise ValueError(' - ERROR, {}: tol must be an integer in [0, {}], got {!r}'.format(what, WSOLA_MAX_TOL, tol))
+    if isinstance(qscale, bool) or not isinstance(qscale, (int, float, np.integer, np.floating)) \
+            or not 0.0 < float(qscale) <= float(np.finfo(np.float32).max) or float(np.float32(qscale)) == 0.0:
+        raise ValueError(' - ERROR, {}: qscale must be a positive finite float32, got {!r}'.format(what, qscale))
+    if not 1 <= B <= 65535 or not 1 <= Lmax <= WSOLA_MAX_LEN or not 1 <= Fw <= WSOLA_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: 1 to 65535 utterances of 1 to {} samples and 1 to {} output frames (got {} of {} and {})'.format(
+            what, WSOLA_MAX_LEN, WSOLA_MAX_FRAMES, B, Lmax, Fw))
+    return int(hop), int(group), int(tol), float(qscale)
+
+
+def _check_count(v, B, hi, what):
+    """lens / n_out on the host: B integers in [0, hi]; a device tensor is clamped by the launch."""
+    import torch
+    if torch.is_tensor(v) and v.is_cuda:
+        return
+    h = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+    if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > hi:
+        raise ValueError(' - ERROR, {} must be {} integers in [0, {}]'.format(what, B, hi))
+
+
+def _wsola_plan_launch(wav, d_lens, pos, d_nout, hop, group, tol, qscale):
+    """vc_wsola_plan on validated device tensors: no host check, copy or wait in here."""
+    import torch
+    import _vc
+    lib = _vc.lib()
+    B, Lmax = wav.shape
+    Fw = pos.shape[1]
+    M = lib.vc_wsola_max_grains(Fw, hop, group)
+    if M == 0:
+        raise _vc.VCError('vc_wsola_max_grains refused {} frames at hop {} and group {}'.format(Fw, hop, group))
+    tab = torch.empty((2, B, M), dtype=torch.int32, device=wav.device)
+    n = torch.empty((2, B), dtype=torch.int32, device=wav.device)
+    _vc.check(lib.vc_wsola_plan(_vc.ptr(wav), Lmax, _vc.ptr(d_lens), _vc.ptr(pos), _vc.ptr(d_nout), B, Lmax, Fw, hop, group, tol, qscale,
+                                _vc.ptr(tab[0]), _vc.ptr(tab[1]), _vc.ptr(n[0]), _vc.ptr(n[1]), _vc.current_stream()))
+    return _PLAN_WSOLA_NT(tab[0], tab[1], n[0], n[1], hop, group, tol, Lmax, Fw)
+
+
+def _wsola_ola_launch(wav, d_lens, plan):
+    """vc_wsola_ola_f32 on validated device tensors (wav [B, plan.max_len] contiguous float32)."""
+    import torch
+    import _vc
+    B, Lmax = wav.shape
+    y = torch.empty((B, plan.hop * (plan.out_frames - 1)), dtype=torch.float32, device=wav.device)
+    _vc.check(_vc.lib().vc_wsola_ola_f32(_vc.ptr(wav), Lmax, _vc.ptr(d_lens), _vc.ptr(plan.a), _vc.ptr(plan.n_grains), _vc.ptr(plan.out_len),
+                                         _vc.ptr(wsola_window(plan.group * plan.hop, wav.device)), B, Lmax, plan.out_frames, plan.hop,
+                                         plan.group, _vc.ptr(y) if y.numel() else None, _vc.current_stream()))
+    return y
+
+
+def _wsola_inputs(what, wav, lens, pos, n_out, hop_length, group, tol, qscale):
+    """The checks and uploads that wsola_plan_batch and time_scale_batch share: (wav, d_lens, pos, d_nout, hop, group, tol,
+    qscale) on the device; every ValueError before anything is uploaded."""
+    import torch
+    import _vc
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    if torch.is_tensor(wav) and wav.dtype != torch.float32:
+        raise ValueError(' - ERROR, {}: wav must be float32, got {}'.format(what, wav.dtype))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    if getattr(pos, 'ndim', 0) != 2 or pos.shape[0] != B or pos.shape[1] < 1:
+        raise ValueError(' - ERROR, {}: pos must be [B, out_frames] with B = {}'.format(what, B))
+    Fw = int(pos.shape[1])
+    if (pos.dtype != torch.int32) if torch.is_tensor(pos) else (np.asarray(pos).dtype.kind not in 'iu'):
+        raise ValueError(' - ERROR, {}: pos must be int32 (Q16 frames), got {}'.format(what, pos.dtype))
+    hop, group, tol, qscale = _check_wsola_args(B, Lmax, Fw, hop_length, group, tol, qscale, what)
+    if lens is None:
+        lens = np.full((B,), Lmax, dtype=np.int64)
+    _check_count(lens, B, Lmax, what + ': lens')
+    _check_count(n_out, B, Fw, what + ': n_out')
+    if not torch.cuda.is_available():
+        raise _vc.VCError('{} needs a GPU (no CPU fallback)'.format(what))
+    d_pos = _i32_device(pos, (B, Fw), what + ': pos')
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
+    wsola_window(group * hop, wav.device)
+    return wav, _i32_device(lens, (B,), what + ': lens'), d_pos, _i32_device(n_out, (B,), what + ': n_out'), hop, group, tol, qscale
+
+
+def wsola_plan_batch(wav, lens, pos, n_out, hop_length, group=2, tol=None, qscale=32768.0):
+    """The grain plan of time_scale_batch alone (vc_wsola_plan; the definition is in include/vc_hip.h, "Time scale", the numpy
+    restatement in tests/wsola_ref.py): for every grain k of an utterance the input sample a_k it is centred on -- within
+    ``tol`` samples of where the map points, chosen so that it continues grain k - 1 -- and the cost it was chosen at.
+
+    The arguments are time_scale_batch's.  Returns a namedtuple: the device tensors a, cost [B, M] int32 (INT32_MIN and -1
+    from an utterance's grain count on; M = ceil(hop * (out_frames - 1) / S) + 1), n_grains and out_len [B], and the host
+    integers hop, group, tol, max_len, out_frames.  Nothing is copied back and the host waits for nothing."""
+    wav, d_lens, d_pos, d_nout, hop, group, tol, qscale = _wsola_inputs('wsola_plan_batch', wav, lens, pos, n_out, hop_length, group, tol,
+                                                                        qscale)
+    return _wsola_plan_launch(wav, d_lens, d_pos, d_nout, hop, group, tol, qscale)
+
+
+def time_scale_batch(wav, lens, pos, n_out, hop_length, group=2, tol=None, qscale=32768.0):
+    """Moves B waveforms along a time map and keeps their pitch and local phase: waveform-similarity overlap-add
+    (vc_wsola_plan, vc_wsola_ola_f32).
+
+    wav [B, Lmax] float32 (cuda tensor or numpy array); lens: sample counts, host integers, an int32 [B] device tensor or
+    None (all Lmax).  pos [B, out_frames] int32 Q16 input FRAMES and n_out [B] as duration_map_batch returns them (frame u
+    is centred on sample u * hop_length); n_out may be host integers too.  group: frames per synthesis hop (S = group *
+    hop_length samples; a grain is 2 S long, S <= 1024); tol: the search half width in samples (default S: at 16 kHz and
+    hop 80, 10 ms, periods down to 50 Hz); qscale: the factor that takes the samples to 16-bit integers for the similarity
+    search (32768 for a waveform within [-1, 1]; larger values clip, smaller ones lose resolution -- the output samples are
+    always copied from ``wav`` itself).
+    Returns a namedtuple: y [B, hop_length * (out_frames - 1)] float32 on the device (zero from an utterance's length on),
+    n_samples [B] (DEVICE int32: hop_length * (n_out - 1)) and plan (wsola_plan_batch's result).  Nothing is copied back and
+    the host waits for nothing."""
+    wav, d_lens, d_pos, d_nout, hop, group, tol, qscale = _wsola_inputs('time_scale_batch', wav, lens, pos, n_out, hop_length, group, tol,
+                                                                        qscale)
+    plan = _wsola_plan_launch(wav, d_lens, d_pos, d_nout, hop, group, tol, qscale)
+    return _SCALE_NT(_wsola_ola_launch(wav, d_lens, plan), plan.out_len, plan)
+
+
+def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio=None, gap_ratio=1.0, segments='decode',
+                                decode=None, out_len=None, max_frames=None, group=2, tol=None, qscale=32768.0, alpha=1.0,
+                                max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None, stats_src=None, stats_tgt=None,
+                                w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None, window_batch=64, encoder=None,
+                                wav_sr=None, out_sr=None, res_type='kaiser_best'):
+    """``convert_diff_batch`` with the timing changed as well: the source is filtered exactly as there
+    (gain, filter, level, and ``pitch=`` before the filter), then the FILTERED WAVEFORM is moved along an integer time map by
+    time_scale_batch -- grains of the natural recording, so its excitation and local phase survive -- and only then
+    resampled to out_sr.
+
+    rate / ratio / gap_ratio / segments / decode / out_len / max_frames: convert_duration_batch's, with the map built over
+    the n_use = min(n_out, n_clip) frames the filter covers (segments='decode' decodes ``phn_pred`` over those frames) and
+    min_frames = 2: an utterance whose table is invalid or whose total would fall below 2 frames keeps its timing (flags
+    1, 2).  group, tol, qscale: time_scale_batch's.  The other arguments are convert_diff_batch's.
+    Returns convert_diff_batch's fields -- y_wav_pred [B, max_samples] at the NEW timing; mel_true / mel_pred / stft_true /
+    stft_pred / phn_pred / gain / f0_src stay at the SOURCE's timing -- with n_samples and n_frames as DEVICE tensors (the
+    output's; n_samples at out_sr when resampled), plus flags [B], seg = (labels, start, end, n_seg) in output frames, map
+    (the duration_map_batch result), plan (the wsola_plan_batch result) and the host bounds max_frames, max_samples and
+    src_frames (n_use).  After the uploads nothing is copied to the host and the host waits for nothing."""
+    import torch
+    import audio_lib
+    import _vc
+    what = 'convert_diff_duration_batch'
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    if sum(v is not None for v in (rate, ratio, out_len)) != 1:
+        raise ValueError(' - ERROR, {}: pass exactly one of rate, ratio and out_len'.format(what))
+    if rate is not None:
+        if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not 0.0 < float(rate) <= WARP_MAX_RATIO:
+            raise ValueError(' - ERROR, {}: rate must be a number in (0, {}], got {!r}'.format(what, WARP_MAX_RATIO, rate))
+        rate_q = int(ratio_to_q(float(rate)))
+    gap_q = _check_ratio_scalar(gap_ratio, what + ': gap_ratio')
+    table = None
+    if rate is None and not (isinstance(segments, str) and segments == 'decode'):
+        if isinstance(segments, str) or len(segments) != 4:
+            raise ValueError(" - ERROR, {}: segments must be 'decode' or (labels, start, end, n_seg)".format(what))
+        table = segments
+    if decode is not None and (rate is not None or table is not None):
+        raise ValueError(" - ERROR, {}: decode is for segments='decode'".format(what))
+    kw = dict(trans=None, penalty=0.0, init=None, final=None, min_dur=3, class_map=None, floor=1e-10)
+    extra = set(decode or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: decode takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(decode or {})
+    h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type)
+    plan, B, hop, Fout = h.plan, h.B, h.hop, h.plan.Fout
+    min_frames = 2
+    n_use, h_nsamp = diff_frames(plan, hop)
+    if Fout > WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, WARP_MAX_FRAMES, Fout))
+    K = 1 if rate is not None else (Fout if table is None else int(table[1].shape[1]))
+    if rate is not None:
+        want = (n_use * rate_q + 32768) >> 16
+        if want.min() < min_frames:
+            raise ValueError(' - ERROR, {}: rate {} leaves an utterance {} frames; at least {} are needed'.format(what, rate, int(want.min()), min_frames))
+        bound = int(want.max())
+    elif ratio is not None and not torch.is_tensor(ratio):
+        r = np.atleast_1d(np.asarray(ratio, dtype=np.float32))
+        if r.ndim != 1 or not np.isfinite(r).all() or r.min() < 0 or r.max() > WARP_MAX_RATIO:
+            raise ValueError(' - ERROR, {}: ratio must be finite floats [C] in [0, {}]'.format(what, WARP_MAX_RATIO))
+        ratio = r
+        bound = duration_max_frames(Fout, 2 * K + 1, max(gap_q, int(ratio_to_q(r).max())))
+    else:
+        if ratio is not None and (ratio.ndim != 1 or not ratio.is_floating_point()):
+            raise ValueError(' - ERROR, {}: ratio must be floats [C]'.format(what))
+        bound = None
+    if max_frames is None:
+        if bound is None:
+            raise ValueError(' - ERROR, {}: max_frames is required with out_len and with a ratio on the device'.format(what))
+        max_frames = min(bound, WARP_MAX_FRAMES)
+    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not min_frames <= max_frames <= WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: max_frames must be an integer in [{}, {}]'.format(what, min_frames, WARP_MAX_FRAMES))
+    Fw = int(max_frames)
+    hop, group, tol, qscale = _check_wsola_args(B, hop * (Fout - 1), Fw, hop, group, tol, qscale, what)
+    dec = cmap = None
+    if rate is None and table is None:                              # the decoder's arguments, before anything is launched
+        import evaluation
+        C = int((encoder if encoder is not None else decoder.encoder).cfg_d['n_output'])
+        evaluation._check_decode_size(B, Fout, C, what)
+        cmap = evaluation._check_class_map(kw.pop('class_map'), C, what)
+        dec = evaluation._decode_args(C=C, what=what, kind='prob', **kw)
+
+    # ---- convert_diff_batch's launches at the model's rate (its own checks run before its first launch), then two tables
+    d = convert_diff_batch(decoder, wav, lens=lens, cfg_d=cfg_d, alpha=alpha, max_boost_db=max_boost_db, max_cut_db=max_cut_db,
+                           half_width=half_width, pitch=pitch, stats_src=stats_src, stats_tgt=stats_tgt, w_floor=w_floor,
+                           f0_args=f0_args, t_e=t_e, two_pass=two_pass, utt_ids=utt_ids, window_batch=window_batch, encoder=encoder,
+                           wav_sr=wav_sr, out_sr=None, res_type=res_type)
+    dev = d.y_wav_pred.device
+    d_nuse = _i32_device(n_use, (B,), what + ': n_use')
+    d_nsamp = _i32_device(h_nsamp, (B,), what + ': n_samples')
+    wsola_window(group * hop, dev)
+
+    # ---- the segment table in source frames, the map (as convert_duration_batch builds it)
+    d_lab = d_len = d_ratio = None
+    if rate is not None:
+        d_start = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+        d_end, d_nseg = d_nuse.view(B, 1), torch.ones((B,), dtype=torch.int32, device=dev)
+        d_ratio = torch.full((1,), rate_q, dtype=torch.int32, device=dev)
+    else:
+        if table is None:
+            r = evaluation._decode_launch(d.phn_pred, d_nuse, evaluation._cmap_device(cmap), evaluation._decode_upload(dec))
+            d_lab, d_start, d_end, d_nseg = r.seg.labels, r.seg.start, r.seg.end, r.seg.n_seg
+        else:
+            d_lab, d_start, d_end = (_i32_device(t, (B, K), what + ': segments') for t in table[:3])
+            d_nseg = _i32_device(table[3], (B,), what + ': segments n_seg')
+        if out_len is not None:
+            d_len = _i32_device(out_len, (B, K), what + ': out_len')
+        elif torch.is_tensor(ratio):
+            d_ratio = ratio_to_q(ratio.to('cuda', non_blocking=True)).contiguous()
+        else:
+            d_ratio = _i32_device(ratio_to_q(ratio), ratio.shape, what + ': ratio')
+    m = _map_launch(d_start, d_end, d_nseg, None if d_ratio is None or rate is not None else d_lab, d_len, d_ratio, gap_q, d_nuse,
+                    Fout, min_frames, Fw)
+
+    # ---- the filtered waveform along the map, the output resampler
+    x = d.y_wav_pred.contiguous()
+    wplan = _wsola_plan_launch(x, d_nsamp, m.pos, m.n_out, hop, group, tol, qscale)
+    y = _wsola_ola_launch(x, d_nsamp, wplan)
+    n_samples = wplan.out_len
+    max_samples = hop * (Fw - 1)
+    if h.res_out:
+        sr = cfg_d['sample_rate']
+        rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
+        y = audio_lib._resample_launch(rplan, y, n_samples)
+        n_samples = torch.div(n_samples.long() * rplan.up + (rplan.down - 1), rplan.down, rounding_mode='floor').to(torch.int32)
+        max_samples = int(audio_lib.resample_len(max_samples, sr, out_sr))
+    return _DIFF_DUR_NT(y, n_samples, d.mel_true, d.mel_pred, d.stft_true, d.stft_pred, d.phn_pred, d.gain, m.n_out, d.f0_src, m.flags,
+                        _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg), m, wplan, Fw, max_samples, [int(v) for v in n_use])
