@@ -1672,6 +1672,64 @@ int vc_stft_filter_f32(const vc_vocoder_plan* plan, const float* d_wav, int32_t 
                        const float* d_gain, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_out,
                        int32_t out_stride, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Postfilters.  A decoder trained on a squared error predicts trajectories -- one spectral bin followed along time -- with
+ * too little variance, most of all at the fast modulation frequencies: the muffled sound that realse patches with a power
+ * law.  These four launches restore the statistics of natural trajectories: Toda's global-variance (GV) filter and
+ * Takamichi's modulation-spectrum (MS) filter, which generalises it.  Added without a version bump.
+ * tests/postfilter_ref.py restates all four in float64 and in float32.
+ *
+ * Data.  d_x [batch, max_frames, channels] float32, channels contiguous: stft_pred, mel_pred or any dB-linear feature.
+ * n = d_n_frames[b] (int32 [batch] on the device; NULL: max_frames), clamped to [0, max_frames] when read.  Output rows at or
+ * beyond n are written as 0.  Constants: segment length 64 frames, hop 32, 33 modulation bins; window
+ * w[t] = float32(0.5 - 0.5 cos(2 pi t / 64)), the periodic Hann window, whose half-overlapped copies sum to 1;
+ * tiny = 2^-40; floor = 1e-20 (float32).  Unless said otherwise every operation below is one float32 operation rounded once.
+ *
+ * vc_traj_stats_f32 -> d_stats [batch, channels, 2] = (mean, population variance) over f < n, both 0 when n == 0:
+ *     r = x[0];  mean = r + (sum_f (x[f] - r)) / n;  var = (sum_f (x[f] - mean)^2) / n
+ *   so a constant channel has mean == its value and var == 0 exactly.  Order of both sums: the frames f = w, w + 8, w + 16, ...
+ *   are added in ascending f for each w in 0 .. 7, starting from 0; then the eight partial sums are added in ascending w.
+ *   Grid (channel tiles of 64, utterance), two passes over the utterance; a function of the utterance alone.
+ *
+ * vc_gv_filter_f32.  With var, mean from d_stats and the target d_gv_t [channels]:
+ *     g = 1 + alpha * (sqrt(gv_t[c] / var) - 1), clamped to [1 / g_max, g_max]
+ *     g = 1 where var <= tiny, where gv_t[c] <= 0 (or NaN) or where the quotient overflows
+ *     d = (g - 1) * (x - mean);  y = x + d, and y = x where d == 0 (so that -0 stays -0)
+ *   The product and the sum are not contracted.  alpha = 0 returns x bit for bit.
+ *
+ * vc_ms_stats_f32 -> d_ms [batch, channels, 33, 3] = (count, sum s, sum s^2) per modulation bin m = 0 .. 32:
+ *     segment j = 0 .. ceil(n / 32) covers frames [32 j - 32, 32 j + 32); a frame outside [0, n) takes the value of the
+ *     nearest frame inside (edge hold);  v[t] = w[t] * (x[.] - mean),  X_j = DFT64(v), bins 0 .. 32
+ *     p = Re^2 + Im^2;  where floor < p <= FLT_MAX:  s = logf(p), count += 1, sum += s, sum2 += s * s
+ *   Order: the segments j = w, w + 4, ... in ascending j for each w in 0 .. 3, then the four partial sums in ascending w.
+ *   n == 0 gives zeros.  mean is READ from d_stats (the variance there is not used).  The transform's own order of operations
+ *   (csrc/pf_dft64.h) is not part of the definition; the tests bound it.
+ *
+ * vc_ms_filter_f32.  d_coef [channels, 33, 2] = (a, b) and the clamps lo <= 0 <= hi, natural-log amplitude exponents:
+ *     g_0 = 1;  for m >= 1: g_m = expf(min(max(a * s + b, lo), hi)) with s as above, and g_m = 1 where p is not above the floor
+ *     c_j = iDFT64((g - 1) X_j)                                      (with the 1 / 64)
+ *     d = c_early[f] + c_late[f]: the two segments that cover frame f, j = f / 32 and j + 1, the earlier one first
+ *     y = x + d, and y = x where d == 0
+ *   The correction is additive, so a table of zeros (exp(0) - 1 == 0) returns x bit for bit whatever the transforms round to.
+ *   Grid (tiles of 32 frames, channel tiles of 64, utterance): a workgroup computes both segments that cover its 32 frames,
+ *   so every segment is transformed twice and nothing is exchanged between workgroups.  One logf and one expf per bin and
+ *   segment.  The gain is real and the transform is NOT zero-padded, so the modification is CIRCULAR within a segment: what a
+ *   gain's impulse response pushes past one end of the 64 frames comes back at the other.  The analysis window tapers the
+ *   input to 0 there, which damps the effect but does not remove it; gains that vary smoothly over m keep the response short.
+ *
+ * All four: every output element is written exactly once; no atomics, no allocation, no memset, no host wait; capturable in a
+ * graph from the first call; functions of their own utterance alone, bit-identical alone, in any batch, under any max_frames
+ * and under replay.  VC_ERR_INVALID before any HIP call, outputs untouched, for a NULL pointer (d_n_frames excepted), a size
+ * below 1, alpha outside [0, 1], g_max below 1, a non-finite scalar, lo > 0, hi < 0, or d_y == d_x.  Limits
+ * (VC_ERR_UNSUPPORTED beyond them, nothing launched): batch <= 65,535, max_frames <= 16,384, channels <= 2,049. */
+int vc_traj_stats_f32(const float* d_x, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t channels,
+                      float* d_stats, void* stream);
+int vc_gv_filter_f32(const float* d_x, const int32_t* d_n_frames, const float* d_stats, const float* d_gv_t, int32_t batch,
+                     int32_t max_frames, int32_t channels, float alpha, float g_max, float* d_y, void* stream);
+int vc_ms_stats_f32(const float* d_x, const int32_t* d_n_frames, const float* d_stats, int32_t batch, int32_t max_frames,
+                    int32_t channels, float* d_ms, void* stream);
+int vc_ms_filter_f32(const float* d_x, const int32_t* d_n_frames, const float* d_stats, const float* d_coef, int32_t batch,
+                     int32_t max_frames, int32_t channels, float lo, float hi, float* d_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

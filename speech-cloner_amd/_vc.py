@@ -310,6 +310,11 @@ _SIGS = {
                                             _P, C.c_int32, _P, _P]),
     'vc_stft_filter_workspace_bytes': (C.c_size_t, [_P, C.c_int32, C.c_int32]),
     'vc_stft_filter_f32': (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P]),
+    # postfilters (csrc/vc_postfilter.hip)
+    'vc_traj_stats_f32': (C.c_int, [_P, _P] + [C.c_int32] * 3 + [_P, _P]),
+    'vc_gv_filter_f32': (C.c_int, [_P] * 4 + [C.c_int32] * 3 + [C.c_float] * 2 + [_P, _P]),
+    'vc_ms_stats_f32': (C.c_int, [_P] * 3 + [C.c_int32] * 3 + [_P, _P]),
+    'vc_ms_filter_f32': (C.c_int, [_P] * 4 + [C.c_int32] * 3 + [C.c_float] * 2 + [_P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -345,7 +350,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the
                 # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '

@@ -1722,3 +1722,67 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
         max_samples = int(audio_lib.resample_len(max_samples, sr, out_sr))
     return _DIFF_DUR_NT(y, n_samples, d.mel_true, d.mel_pred, d.stft_true, d.stft_pred, d.phn_pred, d.gain, m.n_out, d.f0_src, m.flags,
                         _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg), m, wplan, Fw, max_samples, [int(v) for v in n_use])
+
+
+# --------------------------------------------------------------------------- postfilter (csrc/vc_postfilter.hip)
+_POST_NT = namedtuple('convert_postfilter', _BATCH_NT._fields + ('stft_raw',))
+
+
+def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mode='ms', k=0.85, alpha=1.0, max_db=20.0, g_max=4.0,
+                             t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0,
+                             utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+    """``convert_batch`` with the predicted spectrum postfiltered before the vocoder: the stitched ``stft_pred`` goes through
+    postfilter.apply_batch (mode 'ms', 'gv' or 'ms+gv'; k, alpha, max_db, g_max are its arguments) with the frame counts the
+    device already holds, then through vc_power_to_amp (``realse`` still applies) and the vocoder.
+
+    model: a postfilter.Model (postfilter.fit on the target speaker's natural spectra and on stft_pred of training
+    utterances) or postfilter.upload's device tables -- upload once per model when the call has to stay free of
+    host-to-device copies.  The other arguments are convert_batch's; the true spectrum is not vocoded, and phase='numpy'
+    is convert_batch's alone.  mel_pred is left as predicted.
+
+    Returns convert_batch's fields (y_wav_true None) plus stft_raw, the spectrum as stitched; stft_pred is the filtered
+    one.  With k = 0 and alpha = 0 the filters return their input bit for bit and so does the call: y_wav_pred equals
+    convert_batch's.  Nothing is copied to the host and the host waits for nothing.  Nobody has listened to the result
+    (DESIGN.md section 28)."""
+    import torch
+    import audio_lib
+    import postfilter
+    import _vc
+    what = 'convert_postfilter_batch'
+    momentum = _check_momentum(momentum)
+    seed = audio_lib.check_seed(seed)
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    if model is None:
+        raise ValueError(' - ERROR, {}: model (postfilter.fit or postfilter.upload) is required'.format(what))
+    if isinstance(phase, str) and phase not in ('device', 'spsi'):
+        raise ValueError(" - ERROR, {}: phase must be 'device', 'spsi' or a [B, Fout, bins] array, got {!r}".format(what, phase))
+    postfilter.check_apply_args(mode, k, alpha, max_db, g_max, what)
+    h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
+                      res_type)
+    plan, B, Fout, n_bins, sr = h.plan, h.B, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    if Fout > postfilter.MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, postfilter.MAX_FRAMES, Fout))
+    if not isinstance(phase, str) and tuple(phase.shape) != (B, Fout, n_bins):
+        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, B, Fout, n_bins))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('convert_postfilter_batch needs a GPU (no CPU fallback)')
+    tables = model if isinstance(model, postfilter.Tables) else postfilter.upload(model, k)
+    if tables.gv_t.shape[0] != n_bins:
+        raise ValueError(' - ERROR, {}: the model has {} channels, the spectrum {}'.format(what, tables.gv_t.shape[0], n_bins))
+
+    up = _convert_upload(h, wav, [h.h_nsamp] if h.res_out else [])
+    if not isinstance(phase, str):
+        if not torch.is_tensor(phase):
+            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
+        phase = phase.to(device='cuda', dtype=torch.float32).contiguous()
+    mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
+    mel_pred, phn_pred, stft_raw = (compound_stitch(y, up.d_utt, Fout) for y in (y_mel, y_phn, y_stft))
+    stft_pred = postfilter.apply_batch(stft_raw, up.d_nout, tables, mode=mode, k=k, alpha=alpha, max_db=max_db, g_max=g_max)
+    _, y_wav_pred = _vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, None)
+    n_samples = [int(v) for v in h.h_nsamp]
+    if h.res_out:
+        y_wav_pred = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y_wav_pred, up.d_extra[-1])
+        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
+    return _POST_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
+                    stft_raw)
