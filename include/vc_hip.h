@@ -1730,6 +1730,94 @@ int vc_ms_stats_f32(const float* d_x, const int32_t* d_n_frames, const float* d_
 int vc_ms_filter_f32(const float* d_x, const int32_t* d_n_frames, const float* d_stats, const float* d_coef, int32_t batch,
                      int32_t max_frames, int32_t channels, float lo, float hi, float* d_y, void* stream);
 
+/* Harmonic-plus-noise vocoder (the STRAIGHT / WORLD / HNM family).  The Griffin-Lim route invents a phase for a magnitude; the
+ * differential route keeps the source's excitation.  These five launches WRITE the waveform from a spectral envelope and an
+ * F0 contour in one pass: harmonics of the asked-for pitch with minimum-phase phases where a frame is voiced, envelope-shaped
+ * noise where it is not and above a voiced cutoff.  Added without a version bump.  tests/hnm_ref.py restates all five: the
+ * integers exactly, the rest in float64 with a float32 error model.  n = d_n_frames[b] (NULL: max_frames) is clamped to
+ * [0, max_frames] when read; F = max_frames, N = n_fft, nb = 1 + N / 2.
+ *
+ * vc_env_cepstral_f32.  d_amp [batch, F, nb] float32 linear magnitudes (vc_power_to_amp's, vc_compound_stitch's);
+ * d_table float32 [N, 2] = (cos, sin)(2 pi m / N), made by the caller in float64 and indexed by (n k) mod N in integers;
+ * order L, 1 <= L < N / 2; iters >= 0; floor > 0.  Per frame f < n:
+ *     a_k = logf(max(amp_k, floor))                  (a NaN magnitude counts as floor);      A = a
+ *     iters + 1 times:
+ *       c_n = (A_0 + (-1)^n A_{N/2} + 2 sum_{k = 1}^{N/2 - 1} A_k cos(2 pi n k / N)) / N      n = 0 .. L
+ *       E_k = c_0 + 2 sum_{n = 1}^{L} c_n cos(2 pi n k / N)
+ *       on all but the last pass A_k = max(a_k, E_k)                                   (Roebel & Rodet's true envelope)
+ *     env_log = E and theta_k = -2 sum_{n = 1}^{L} c_n sin(2 pi n k / N) from the last pass: the minimum phase of exp(E).
+ *   Both sums run in ascending index from +0, one fused multiply-add per term, so the only difference from a float64
+ *   restatement on the same table is float32 summation (tests/hnm_ref.py bounds it).  Rows f >= n of both outputs are 0.
+ *   Grid (tiles of up to 8 frames, utterance): the table, the tile's a and A and its cepstra live in LDS (at most 64 KB; fewer
+ *   frames per tile where a long transform needs it, which does not change a value); per pass one lane per (frame, n), a
+ *   barrier, one lane per (frame, k), a barrier.  Limits: n_fft <= 2,048, iters <= 1,024.
+ *
+ * vc_hnm_plan.  d_f0 [batch, F] float32 Hz, 0 = unvoiced (vc_f0_yin_f32's, vc_f0_viterbi_f32's).  All outputs are integers
+ * and equal the restatement bit for bit; rows f >= n are 0.
+ *     voiced[f] uint8   1 where f0_lo <= f0 <= f0_hi (false for NaN and the infinities)
+ *     inc[f]    uint32  the phase advance per sample in units of 2^-32 turn: rint(f0 * float32(2^32 / sr)), the product
+ *                       rounded once to float32, ties to even; an unvoiced frame takes the value of the nearest voiced frame
+ *                       before it, a leading unvoiced run that of the first voiced frame; 0 everywhere without a voiced frame
+ *     slope[f]  int32   floor((inc[f + 1] - inc[f]) / hop) in int64, 0 for f = n - 1
+ *     phase[f]  uint32  the phase at sample f hop: the exclusive sum, modulo 2^32, over frames of
+ *                       hop inc[f] + slope[f] hop (hop - 1) / 2
+ *     flags[b]  int32   bit 0: some f0 != 0 (NaN included) below n was outside the limits and counted as unvoiced
+ *   Inside interval f (samples f hop + j, 0 <= j < hop) the phase is phase[f] + j inc[f] + slope[f] j (j - 1) / 2 mod 2^32.
+ *   One workgroup of 256 lanes per utterance walks the frames in tiles of 256; the last voiced frame is carried by a maximum
+ *   scan and the phase by a wrapping sum scan (addition modulo 2^32 is associative: the parallel scan IS the sequential sum).
+ *   0 < f0_lo <= f0_hi <= sr / 2; hop <= 4,096.
+ *
+ * vc_noise_init_f32.  d_noise [batch, max_len]: noise[i] = float32(sqrt(12)) * (U - 0.5), U = (x >> 8) * 2^-24 (the
+ * difference is exact, the product rounded once): unit variance.  x is word i % 4 of the Philox4x32-10 block with counter
+ * (i / 4, utt_id, 0, 0) and key (seed low, seed high) -- vc_phase_init's addressing with the sample index for the element, so
+ * an utterance's noise depends on (seed, utt_id) alone.  d_utt_id NULL: the row index.  0 from d_lens[b] (clamped to
+ * [0, max_len]; NULL: max_len) on.
+ *
+ * vc_hnm_noise_gain_f32.  d_gain [batch, F, n_bins]: gscale * exp2f(env_log * float32(log2 e)) in unvoiced frames (all bins)
+ * and, in voiced frames, for bins >= cutoff_bin; 0 below cutoff_bin in voiced frames and for f >= n.  With
+ * gscale = noise_level / sqrt(sum w^2) of the vocoder plan's window, vc_stft_filter_f32 applied to the unit-variance noise
+ * with this gain gives noise of the envelope's magnitude in expectation (E |STFT|^2 = sum w^2 for white noise).
+ *
+ * vc_hnm_synth_f32.  d_y [batch, hop (F - 1)].  Interval f < n - 1 has the ends e in {f, f + 1}.  With
+ * K_e = min(256, (cutoff_inc - 1) / inc[e]) where voiced[e] and inc[e] > 0, else 0 -- harmonic k is ALIVE at end e when
+ * k inc[e] < cutoff_inc, and at most vc_hnm_max_harmonics() = 256 are -- the interval evaluates k = 1 .. max(K_f, K_{f+1}):
+ *     position  q = k inc[e] N as a 64-bit integer: bin i = q >> 32, fraction r = float32(q mod 2^32) * 2^-32;
+ *               lerp(x) = fma(r, x[min(i + 1, nb - 1)] - x[i], x[i])
+ *     a_e = scale * exp2f(lerp(env_log[e]) * float32(log2 e)) at a live end, 0 at a dead one;   scale = 2 / sum w
+ *     t_e = lerp(theta[e]) at a live end, the other end's at a dead one
+ *     u = float32(j) / float32(hop) (IEEE);  a = fma(u, a_{f+1} - a_f, a_f);  t = fma(u, t_{f+1} - t_f, t_f): equal ends give
+ *               the end value exactly
+ *     x = fma(t, float32(1 / (2 pi)), float32(int32(k phi_j mod 2^32)) * 2^-32)  turns;   phi_j the plan's phase at j
+ *     acc = fma(a, cos2pi(x), acc), from +0, k ascending;  cos2pi: x - rint(x) (exact), z = 1/4 - |x|, z P(z^2) with the
+ *               five float32 coefficients of csrc/vc_hnm.hip (3.1e-8 from sin(2 pi z) before rounding)
+ *     y = acc, or with d_add: acc + add where a harmonic was evaluated and add itself where none was.
+ *   Onsets, offsets and harmonics that cross the cutoff so fade over one hop.  Samples from hop (n - 1) on are 0.
+ *   Grid (tiles of vc_hnm_tile_intervals() = 16 intervals, utterance): a tile writes (a_e[k], t_e[k]) for its 17 frames into
+ *   LDS -- the exponentials are per frame -- then every lane takes samples 256 apart and loops over k.  cutoff_inc in
+ *   [1, 2^31]; hop <= 4,096; n_fft <= 2,048; d_add must not be d_y.
+ *
+ * All five: every output element is written exactly once; no atomics, no allocation, no memset, no host wait; capturable in a
+ * graph from the first call; functions of their own utterance alone, bit-identical alone, in any batch and under replay.
+ * VC_ERR_INVALID before any HIP call for a NULL pointer (d_n_frames, d_lens, d_utt_id, d_add excepted), a size below 1 or a
+ * scalar outside what is said above.  Limits (VC_ERR_UNSUPPORTED beyond them, nothing launched): batch <= 65,535,
+ * max_frames <= 16,384, and those named with each call. */
+int32_t vc_hnm_max_harmonics(void);
+int32_t vc_hnm_tile_intervals(void);
+int vc_env_cepstral_f32(const float* d_amp, const int32_t* d_n_frames, const float* d_table, int32_t batch, int32_t max_frames,
+                        int32_t n_fft, int32_t order, int32_t iters, float floor, float* d_env_log, float* d_theta,
+                        void* stream);
+int vc_hnm_plan(const float* d_f0, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t sr, int32_t hop,
+                float f0_lo, float f0_hi, uint8_t* d_voiced, uint32_t* d_inc, int32_t* d_slope, uint32_t* d_phase,
+                int32_t* d_flags, void* stream);
+int vc_noise_init_f32(const int32_t* d_lens, const int32_t* d_utt_id, int32_t batch, int32_t max_len, int64_t seed,
+                      float* d_noise, void* stream);
+int vc_hnm_noise_gain_f32(const float* d_env_log, const uint8_t* d_voiced, const int32_t* d_n_frames, int32_t batch,
+                          int32_t max_frames, int32_t n_bins, int32_t cutoff_bin, float gscale, float* d_gain, void* stream);
+int vc_hnm_synth_f32(const float* d_env_log, const float* d_theta, const uint8_t* d_voiced, const uint32_t* d_inc,
+                     const int32_t* d_slope, const uint32_t* d_phase, const int32_t* d_n_frames, const float* d_add,
+                     int32_t batch, int32_t max_frames, int32_t n_fft, int32_t hop, int64_t cutoff_inc, float scale, float* d_y,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,6 +315,14 @@ _SIGS = {
     'vc_gv_filter_f32': (C.c_int, [_P] * 4 + [C.c_int32] * 3 + [C.c_float] * 2 + [_P, _P]),
     'vc_ms_stats_f32': (C.c_int, [_P] * 3 + [C.c_int32] * 3 + [_P, _P]),
     'vc_ms_filter_f32': (C.c_int, [_P] * 4 + [C.c_int32] * 3 + [C.c_float] * 2 + [_P, _P]),
+    # harmonic-plus-noise vocoder (csrc/vc_hnm.hip)
+    'vc_hnm_max_harmonics': (C.c_int32, []),
+    'vc_hnm_tile_intervals': (C.c_int32, []),
+    'vc_env_cepstral_f32': (C.c_int, [_P, _P, _P] + [C.c_int32] * 5 + [C.c_float, _P, _P, _P]),
+    'vc_hnm_plan': (C.c_int, [_P, _P] + [C.c_int32] * 4 + [C.c_float] * 2 + [_P] * 6),
+    'vc_noise_init_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
+    'vc_hnm_noise_gain_f32': (C.c_int, [_P, _P, _P] + [C.c_int32] * 4 + [C.c_float, _P, _P]),
+    'vc_hnm_synth_f32': (C.c_int, [_P] * 8 + [C.c_int32] * 4 + [C.c_int64, C.c_float, _P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -350,7 +358,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then the
                 # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '

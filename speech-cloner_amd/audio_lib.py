@@ -25,6 +25,10 @@ cases of them):
   stft_filter_batch(wav, lens, gain, n_frames) -> torch.cuda tensor [B, hop*(F-1)]: istft(gain * stft(wav)), one
                              transform pass that keeps the input's phase (include/vc_hip.h vc_stft_filter_f32)
 
+  envelope_batch / hnm_plan_batch / noise_batch / hnm_synth_batch: the harmonic-plus-noise vocoder -- a spectral envelope
+                             and an F0 contour in, a waveform out, no phase iteration (include/vc_hip.h,
+                             "Harmonic-plus-noise vocoder")
+
 The Griffin-Lim entry points take ``momentum`` (default 0.0, the reference's algorithm): fast
 Griffin-Lim as in librosa.griffinlim / torchaudio GriffinLim, see include/vc_hip.h
 vc_griffin_lim_momentum_f32.
@@ -33,6 +37,7 @@ All arithmetic runs in hand-written HIP kernels (csrc/vc_frontend.hip) through t
 ``vc_frontend_f32`` (include/vc_hip.h); torch only owns the device buffers.  There is no
 CPU path: without the native library or a GPU the calls raise.
 """
+import collections
 import ctypes as C
 import math
 
@@ -261,6 +266,13 @@ class _VocPlan:
     def spsi_workspace(self, batch, max_frames, device):
         """Scratch for ONE vc_phase_spsi call at this plan's bins, like workspace()."""
         return _spsi_workspace(batch, max_frames, self.n_bins, device)
+
+    def window_sums(self):
+        """(sum w, sum w^2) of the plan's window as the device holds it (float32 values of the periodic Hann window, summed
+        in float64): what calibrates the harmonic-plus-noise vocoder."""
+        i = np.arange(self.win_length)
+        w = (0.5 - 0.5 * np.cos(2.0 * np.pi * i / self.win_length)).astype(np.float32).astype(np.float64)
+        return float(w.sum()), float((w * w).sum())
 
 
 def check_momentum(momentum):
@@ -513,6 +525,244 @@ def stft_filter_batch(wav, lens, gain, n_frames=None, win_length=400, hop_length
     d_len = _int32_device(np.full((B,), Lmax, np.int64) if lens is None else lens, B, 'lens')
     d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
     return _stft_filter_launch(plan, as_dev(wav), d_len, as_dev(gain), d_nf)
+
+
+# --------------------------------------------------------------------------- harmonic-plus-noise vocoder
+HnmPlan = collections.namedtuple('HnmPlan', 'voiced inc slope phase flags')
+HnmSynth = collections.namedtuple('HnmSynth', 'y env_log theta plan gain')
+_ENV_TABLES = {}
+
+
+def _env_table(n_fft):
+    """float32 [n_fft, 2] on the device: (cos, sin)(2 pi m / n_fft), made in float64 (vc_env_cepstral_f32's table)."""
+    import torch
+    t = _ENV_TABLES.get(n_fft)
+    if t is None:
+        m = np.arange(n_fft)
+        h = np.stack([np.cos(2.0 * np.pi * m / n_fft), np.sin(2.0 * np.pi * m / n_fft)], axis=1).astype(np.float32)
+        t = _ENV_TABLES[n_fft] = torch.from_numpy(h).to('cuda')
+    return t
+
+
+def _hnm_count(v, B, hi, what, name):
+    """Host check of a per-utterance count (host integers, an int32 [B] device tensor or None)."""
+    import torch
+    if v is None:
+        return
+    if torch.is_tensor(v) and v.is_cuda:
+        if v.dtype != torch.int32 or tuple(v.shape) != (B,):
+            raise ValueError(' - ERROR, {}: {} on the device must be int32 [{}]'.format(what, name, B))
+        return
+    h = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+    if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > hi:
+        raise ValueError(' - ERROR, {}: {} must be {} integers in [0, {}]'.format(what, name, B, hi))
+
+
+def _hnm_float(v, what, name, lo=None, positive=False):
+    f = float(v)
+    if not math.isfinite(f) or (positive and f <= 0.0) or (lo is not None and f < lo):
+        raise ValueError(' - ERROR, {}: {} must be finite{}, got {!r}'.format(
+            what, name, ' and positive' if positive else '' if lo is None else ' and at least {}'.format(lo), v))
+    return f
+
+
+def _check_envelope_args(what, shape, n_fft, order, iters, floor):
+    n_fft, order, iters = int(n_fft), int(order), int(iters)
+    if n_fft < 4 or n_fft % 2 or n_fft > 2048:
+        raise ValueError(' - ERROR, {}: n_fft must be even and in [4, 2048], got {}'.format(what, n_fft))
+    if len(shape) != 3 or min(shape) < 1 or shape[2] != 1 + n_fft // 2:
+        raise ValueError(' - ERROR, {}: amp must be [B, F, {}]'.format(what, 1 + n_fft // 2))
+    if shape[0] > 65535 or shape[1] > 16384:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of 16384 frames'.format(what))
+    if not 1 <= order < n_fft // 2:
+        raise ValueError(' - ERROR, {}: order must be in [1, {}), got {}'.format(what, n_fft // 2, order))
+    if not 0 <= iters <= 1024:
+        raise ValueError(' - ERROR, {}: iters must be in [0, 1024], got {}'.format(what, iters))
+    return n_fft, order, iters, _hnm_float(floor, what, 'floor', positive=True)
+
+
+def _as_cuda_f32(t):
+    import torch
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
+    return t.to(device='cuda', dtype=torch.float32).contiguous()
+
+
+def _envelope_launch(amp, d_nf, n_fft, order, iters, floor):
+    import torch
+    B, F, _ = amp.shape
+    env_log, theta = torch.empty_like(amp), torch.empty_like(amp)
+    _vc.check(_vc.lib().vc_env_cepstral_f32(_vc.ptr(amp), _vc.ptr(d_nf), _vc.ptr(_env_table(n_fft)), B, F, n_fft, order, iters,
+                                            floor, _vc.ptr(env_log), _vc.ptr(theta), _vc.current_stream()))
+    return env_log, theta
+
+
+def envelope_batch(amp, n_frames=None, n_fft=400, order=24, iters=16, floor=1e-5):
+    """Spectral envelope and its minimum phase from magnitudes (vc_env_cepstral_f32, include/vc_hip.h): the true-envelope
+    iteration on a cepstrum of ``order`` coefficients.  amp [B, F, 1 + n_fft//2] float32 linear magnitudes; n_frames host
+    integers or an int32 [B] device tensor (None = all F).  Returns (env_log, theta), float32 [B, F, bins] on the device:
+    the natural log of the envelope and its minimum phase in radians; rows beyond n_frames are 0."""
+    import torch
+    what = 'envelope_batch'
+    n_fft, order, iters, floor = _check_envelope_args(what, tuple(getattr(amp, 'shape', ())), n_fft, order, iters, floor)
+    B, F = int(amp.shape[0]), int(amp.shape[1])
+    _hnm_count(n_frames, B, F, what, 'n_frames')
+    if not torch.cuda.is_available():
+        raise _vc.VCError('envelope_batch needs a GPU (no CPU fallback)')
+    d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
+    return _envelope_launch(_as_cuda_f32(amp), d_nf, n_fft, order, iters, floor)
+
+
+def _check_plan_args(what, shape, sr, hop_length, f0_lo, f0_hi):
+    sr, hop_length = int(sr), int(hop_length)
+    if len(shape) != 2 or min(shape) < 1 or shape[0] > 65535 or shape[1] > 16384:
+        raise ValueError(' - ERROR, {}: f0 must be [B, F] with B <= 65535 and F <= 16384'.format(what))
+    if sr < 1 or not 1 <= hop_length <= 4096:
+        raise ValueError(' - ERROR, {}: need sr >= 1 and hop_length in [1, 4096], got {}, {}'.format(what, sr, hop_length))
+    f0_lo = _hnm_float(f0_lo, what, 'f0_lo', positive=True)
+    f0_hi = _hnm_float(sr / 4.0 if f0_hi is None else f0_hi, what, 'f0_hi', positive=True)
+    if not f0_lo <= f0_hi <= sr / 2.0:
+        raise ValueError(' - ERROR, {}: need f0_lo <= f0_hi <= sr / 2, got {}, {}'.format(what, f0_lo, f0_hi))
+    return sr, hop_length, f0_lo, f0_hi
+
+
+def _hnm_plan_launch(f0, d_nf, sr, hop_length, f0_lo, f0_hi):
+    import torch
+    B, F = f0.shape
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=f0.device)
+    pl = HnmPlan(torch.empty((B, F), dtype=torch.uint8, device=f0.device), i32(B, F), i32(B, F), i32(B, F), i32(B))
+    _vc.check(_vc.lib().vc_hnm_plan(_vc.ptr(f0), _vc.ptr(d_nf), B, F, sr, hop_length, f0_lo, f0_hi, _vc.ptr(pl.voiced),
+                                    _vc.ptr(pl.inc), _vc.ptr(pl.slope), _vc.ptr(pl.phase), _vc.ptr(pl.flags),
+                                    _vc.current_stream()))
+    return pl
+
+
+def hnm_plan_batch(f0, n_frames, sr, hop_length, f0_lo=40.0, f0_hi=None):
+    """The integer phase track of an F0 contour (vc_hnm_plan, include/vc_hip.h).  f0 [B, F] float32 Hz, 0 = unvoiced;
+    n_frames host integers, an int32 [B] device tensor or None; f0_hi defaults to sr / 4.  Returns HnmPlan(voiced uint8
+    [B, F], inc, slope, phase int32 [B, F] -- inc and phase hold uint32 bit patterns -- and flags int32 [B], bit 0: some
+    non-zero f0 lay outside the limits and counted as unvoiced), all on the device."""
+    import torch
+    what = 'hnm_plan_batch'
+    sr, hop_length, f0_lo, f0_hi = _check_plan_args(what, tuple(getattr(f0, 'shape', ())), sr, hop_length, f0_lo, f0_hi)
+    B, F = int(f0.shape[0]), int(f0.shape[1])
+    _hnm_count(n_frames, B, F, what, 'n_frames')
+    if not torch.cuda.is_available():
+        raise _vc.VCError('hnm_plan_batch needs a GPU (no CPU fallback)')
+    d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
+    return _hnm_plan_launch(_as_cuda_f32(f0), d_nf, sr, hop_length, f0_lo, f0_hi)
+
+
+def _noise_launch(d_lens, B, Lmax, seed, d_id):
+    import torch
+    out = torch.empty((B, Lmax), dtype=torch.float32, device='cuda')
+    _vc.check(_vc.lib().vc_noise_init_f32(_vc.ptr(d_lens), _vc.ptr(d_id), B, Lmax, seed - 2 ** 64 if seed >= 2 ** 63 else seed,
+                                          _vc.ptr(out), _vc.current_stream()))
+    return out
+
+
+def noise_batch(lens, Lmax, seed=0, utt_ids=None):
+    """Unit-variance uniform noise on the device (vc_noise_init_f32, include/vc_hip.h): float32 [B, Lmax],
+    sqrt(12) * (U - 1/2) with U from Philox4x32-10 addressed by (seed, utt_ids[b], sample) as phase_init addresses its
+    elements -- an utterance's noise does not depend on the batch or on Lmax.  Zero from lens[b] on.  lens: host integers or
+    an int32 [B] device tensor; utt_ids likewise (default 0 .. B-1)."""
+    import torch
+    what = 'noise_batch'
+    seed, Lmax = check_seed(seed), int(Lmax)
+    B = int(lens.shape[0]) if torch.is_tensor(lens) else len(lens)
+    if B < 1 or B > 65535 or Lmax < 1:
+        raise ValueError(' - ERROR, {}: need 1 <= B <= 65535 and Lmax >= 1'.format(what))
+    _hnm_count(lens, B, Lmax, what, 'lens')
+    if utt_ids is not None and (int(utt_ids.shape[0]) if torch.is_tensor(utt_ids) else len(utt_ids)) != B:
+        raise ValueError(' - ERROR, {}: utt_ids must have one entry per utterance ({})'.format(what, B))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('noise_batch needs a GPU (no CPU fallback)')
+    d_id = None if utt_ids is None else _int32_device(utt_ids, B, 'utt_ids')
+    return _noise_launch(_int32_device(lens, B, 'lens'), B, Lmax, seed, d_id)
+
+
+def hnm_cutoff(voiced_cutoff_hz, sr, n_fft, f0_lo):
+    """(cutoff_inc, cutoff_bin) of a voiced cutoff in Hz: the phase advance per sample in units of 2^-32 turn (at most 2^31,
+    Nyquist) and the first bin at or above the cutoff.  ValueError when cutoff / f0_lo exceeds the harmonic cap (256)."""
+    what = 'hnm_synth_batch'
+    c = _hnm_float(voiced_cutoff_hz, what, 'voiced_cutoff_hz', positive=True)
+    c = min(c, sr / 2.0)
+    if c / f0_lo > 256:
+        raise ValueError(' - ERROR, {}: voiced_cutoff_hz / f0_lo = {:.1f} exceeds the 256 harmonics a frame can hold'.format(
+            what, c / f0_lo))
+    return max(1, min(int(round(c * 2.0 ** 32 / sr)), 2 ** 31)), int(math.ceil(c * n_fft / sr))
+
+
+def _hnm_synth_launch(plan, env_log, theta, pl, d_nf, cutoff_inc, add):
+    import torch
+    B, F, _ = env_log.shape
+    y = torch.empty((B, plan.hop_length * (F - 1)), dtype=torch.float32, device=env_log.device)
+    _vc.check(_vc.lib().vc_hnm_synth_f32(_vc.ptr(env_log), _vc.ptr(theta), _vc.ptr(pl.voiced), _vc.ptr(pl.inc), _vc.ptr(pl.slope),
+                                         _vc.ptr(pl.phase), _vc.ptr(d_nf), _vc.ptr(add), B, F, plan.n_fft, plan.hop_length,
+                                         cutoff_inc, 2.0 / plan.window_sums()[0], _vc.ptr(y), _vc.current_stream()))
+    return y
+
+
+def _hnm_noise_launch(plan, env_log, pl, d_nf, d_lens, cutoff_bin, noise_level, seed, d_id):
+    """The noise branch on device tensors: the gain, the noise, and the existing vc_stft_filter_f32 launch.  (filtered, gain)."""
+    import torch
+    B, F, nb = env_log.shape
+    gain = torch.empty_like(env_log)
+    _vc.check(_vc.lib().vc_hnm_noise_gain_f32(_vc.ptr(env_log), _vc.ptr(pl.voiced), _vc.ptr(d_nf), B, F, nb, cutoff_bin,
+                                              noise_level / math.sqrt(plan.window_sums()[1]), _vc.ptr(gain),
+                                              _vc.current_stream()))
+    noise = _noise_launch(d_lens, B, plan.hop_length * (F - 1), seed, d_id)
+    return _stft_filter_launch(plan, noise, d_lens, gain, d_nf), gain
+
+
+def _hnm_chain(plan, amp, f0, d_nf, d_lens, sr, order, iters, floor, f0_lo, f0_hi, cutoff, noise_level, seed, d_id, noise):
+    """Every launch of hnm_synth_batch on validated device tensors: no host check, copy or wait in here."""
+    env_log, theta = _envelope_launch(amp, d_nf, plan.n_fft, order, iters, floor)
+    pl = _hnm_plan_launch(f0, d_nf, sr, plan.hop_length, f0_lo, f0_hi)
+    add = gain = None
+    if noise:
+        add, gain = _hnm_noise_launch(plan, env_log, pl, d_nf, d_lens, cutoff[1], noise_level, seed, d_id)
+    return HnmSynth(_hnm_synth_launch(plan, env_log, theta, pl, d_nf, cutoff[0], add), env_log, theta, pl, gain)
+
+
+def hnm_synth_batch(amp, f0, n_frames=None, sr=16000, win_length=400, hop_length=80, n_fft=None, order=24, iters=16,
+                    floor=1e-5, voiced_cutoff_hz=4000.0, noise_level=1.0, seed=0, utt_ids=None, noise=True, f0_lo=40.0,
+                    f0_hi=None):
+    """The harmonic-plus-noise vocoder (include/vc_hip.h): magnitudes and an F0 contour in, a waveform out, one pass.
+
+    amp [B, F, 1 + n_fft//2] float32 linear magnitudes (the envelope is estimated from them: envelope_batch); f0 [B, F]
+    float32 Hz, 0 = unvoiced; n_frames host integers or an int32 [B] device tensor (None = all F).  Voiced frames get
+    harmonics of f0 below voiced_cutoff_hz, with the envelope's minimum phase, at 2 / sum(w) times the envelope -- the
+    magnitude an STFT with the plan's window reads back; unvoiced frames, and voiced ones above the cutoff, get noise
+    (noise_batch(seed, utt_ids)) shaped by stft_filter_batch's launch to noise_level times the envelope; noise=False
+    leaves it out.  Returns HnmSynth(y [B, hop_length * (F - 1)], env_log, theta, plan, gain), all on the device; y is zero
+    beyond hop_length * (n_frames - 1) samples.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    what = 'hnm_synth_batch'
+    win_length = int(win_length)
+    n_fft_ = int(n_fft or win_length)
+    shape = tuple(getattr(amp, 'shape', ()))
+    n_fft_, order, iters, floor = _check_envelope_args(what, shape, n_fft_, order, iters, floor)
+    B, F = int(shape[0]), int(shape[1])
+    if tuple(getattr(f0, 'shape', ())) != (B, F) or F < 2:
+        raise ValueError(' - ERROR, {}: f0 must be [{}, {}] with at least 2 frames'.format(what, B, F))
+    sr, hop_length, f0_lo, f0_hi = _check_plan_args(what, (B, F), sr, hop_length, f0_lo, f0_hi)
+    if not 1 <= win_length <= n_fft_ or hop_length > n_fft_:
+        raise ValueError(' - ERROR, {}: need win_length <= n_fft and hop_length <= n_fft'.format(what))
+    cutoff = hnm_cutoff(voiced_cutoff_hz, sr, n_fft_, f0_lo)
+    noise_level = _hnm_float(noise_level, what, 'noise_level', lo=0.0)
+    seed = check_seed(seed)
+    _hnm_count(n_frames, B, F, what, 'n_frames')
+    if utt_ids is not None and (int(utt_ids.shape[0]) if torch.is_tensor(utt_ids) else len(utt_ids)) != B:
+        raise ValueError(' - ERROR, {}: utt_ids must have one entry per utterance ({})'.format(what, B))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('hnm_synth_batch needs a GPU (no CPU fallback)')
+    plan = _get_voc_plan(win_length, hop_length, n_fft_)
+    d_nf = _int32_device(np.full((B,), F, np.int64) if n_frames is None else n_frames, B, 'n_frames')
+    d_lens = (d_nf - 1).clamp_(min=0).mul_(hop_length) if noise else None
+    d_id = None if utt_ids is None else _int32_device(utt_ids, B, 'utt_ids')
+    return _hnm_chain(plan, _as_cuda_f32(amp), _as_cuda_f32(f0), d_nf, d_lens, sr, order, iters, floor, f0_lo, f0_hi, cutoff,
+                      noise_level, seed, d_id, bool(noise))
 
 
 def griffin_lim_alg(stft_amp, win_length, hop_length, num_iters=300, n_fft=None, verbose=True, phase0=None,

@@ -1123,6 +1123,36 @@ def f0_transform(f0, stats_src, stats_tgt):
     return torch.where(voiced, out, torch.zeros_like(out)).to(torch.float32)
 
 
+def _tracker_args(f0_args, sr, hop, what):
+    """f0_args (a dict of f0_track_batch's tracker arguments, or None) checked on the host: (f0a, n_cand, ceiling, costs) as
+    evaluation._f0_track_launch takes them."""
+    import evaluation
+    kw = dict(frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5, switch_cost=0.1, n_cand=8, ceiling=1.0)
+    extra = set(f0_args or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: f0_args takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(f0_args or {})
+    f0a = evaluation._f0_args(sr, hop, kw['frame_length'], kw['fmin'], kw['fmax'], kw['threshold'], what)
+    n_cand, ceiling = evaluation._track_args(kw['n_cand'], kw['ceiling'], what)
+    return f0a, n_cand, ceiling, evaluation._viterbi_costs(f0a[5], kw['jump_cost'], kw['switch_cost'], what)
+
+
+def _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt):
+    """pitch='source' on the device: the input's contour (up.wav at the model's rate, tracked by f0_track_batch's launches),
+    aligned to the output frames by the plan's n_s (output frame u is input frame n_s + u; up.d_true[:, 1]) and mapped by
+    f0_transform when the speakers' statistics are given.  [B, Fout] float32, 0 beyond an utterance's frames."""
+    import torch
+    import evaluation
+    f0_in = evaluation._f0_track_launch(up.wav, up.d_lens, d_fsrc, *tracker)[0]
+    u = torch.arange(Fout, device=f0_in.device)[None, :]
+    idx = up.d_true[:, 1:2].long() + u
+    ok = (u < d_fout[:, None]) & (idx < d_fsrc[:, None])
+    f0_target = torch.where(ok, torch.gather(f0_in, 1, idx.clamp(0, f0_in.shape[1] - 1)), torch.zeros((), device=f0_in.device))
+    if stats_src is not None:
+        f0_target = f0_transform(f0_target, stats_src, stats_tgt)
+    return f0_target
+
+
 def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None,
                         t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None,
                         window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
@@ -1163,17 +1193,10 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
     if scalar:
         pitch = _check_pitch_ratio(pitch, what + ': pitch')
     w_floor = _check_w_floor(w_floor, what)
-    kw = dict(frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5, switch_cost=0.1, n_cand=8, ceiling=1.0)
-    extra = set(f0_args or {}) - set(kw)
-    if extra:
-        raise ValueError(' - ERROR, {}: f0_args takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
-    kw.update(f0_args or {})
+    tracker = _tracker_args(f0_args, cfg_d['sample_rate'], int(cfg_d['hop_length']), what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
                       res_type)
     plan, B, hop, Fout, n_bins, sr = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
-    f0a = evaluation._f0_args(sr, hop, kw['frame_length'], kw['fmin'], kw['fmax'], kw['threshold'], what)
-    n_cand, ceiling = evaluation._track_args(kw['n_cand'], kw['ceiling'], what)
-    costs = evaluation._viterbi_costs(f0a[5], kw['jump_cost'], kw['switch_cost'], what)
     Lout = hop * (Fout - 1)
     _check_pitch_sizes(B, Lout, Fout, hop, what)
     if max(Lout, int(h.h_lens.max())) > evaluation.F0_MAX_SAMPLES:
@@ -1212,16 +1235,10 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
     _, y0 =_vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, amp_pred)
 
     # ---- the conversion's own track, the target, the shift
-    f0_pred = evaluation._f0_track_launch(y0, d_nsamp, d_fout, f0a, n_cand, ceiling, costs)[0]
+    f0_pred = evaluation._f0_track_launch(y0, d_nsamp, d_fout, *tracker)[0]
     f0_target = None
     if source:
-        f0_in = evaluation._f0_track_launch(up.wav, up.d_lens, d_fsrc, f0a, n_cand, ceiling, costs)[0]
-        u = torch.arange(Fout, device=f0_in.device)[None, :]
-        idx = up.d_true[:, 1:2].long() + u
-        ok = (u < d_fout[:, None]) & (idx < d_fsrc[:, None])
-        f0_target = torch.where(ok, torch.gather(f0_in, 1, idx.clamp(0, f0_in.shape[1] - 1)), torch.zeros((), device=f0_in.device))
-        if stats_src is not None:
-            f0_target = f0_transform(f0_target, stats_src, stats_tgt)
+        f0_target = _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt)
     elif not scalar:
         f0_target = pitch.to(torch.float32)
     per, rat = pitch_tables(f0_pred, sr, ratio=pitch if scalar else None, target_f0=f0_target, hop_length=hop)
@@ -1233,6 +1250,107 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
         n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
     return _PITCH_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
                      f0_pred, f0_target, pp)
+
+
+_HNM_NT = namedtuple('convert_hnm', _BATCH_NT._fields + ('f0_target', 'env_log', 'plan'))
+
+
+def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats_src=None, stats_tgt=None, f0_args=None, order=24,
+                      iters=16, voiced_cutoff_hz=4000.0, noise_level=1.0, realse=1.0, floor=1e-5, f0_lo=40.0, f0_hi=None, t_s=0,
+                      t_e=60, two_pass=True, seed=0, utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None,
+                      res_type='kaiser_best'):
+    """``convert_batch`` with the harmonic-plus-noise vocoder in Griffin-Lim's place: the decoder's
+    spectrum gives the envelope, an F0 contour the excitation, and audio_lib.hnm_synth_batch's launches write the waveform
+    in one pass -- no phase iteration, and the pitch is the one asked for.
+
+    pitch:
+      'source'           the INPUT's own contour, tracked on ``wav`` at the model's rate, aligned to the output frames by the
+                         plan's n_s and mapped by f0_transform(., stats_src, stats_tgt) when both are given;
+      a number r         that contour times r (0.5 <= r <= 2);
+      [B, Fout] floats   the contour itself, Hz per output frame, 0 = unvoiced.
+    f0_args: the tracker's arguments as in convert_pitch_batch; order, iters, floor: envelope_batch's; voiced_cutoff_hz,
+    noise_level, seed, utt_ids, f0_lo, f0_hi: hnm_synth_batch's.  The magnitude is made as convert_batch makes it (fused in
+    the stitch at realse == 1, else vc_power_to_amp); after the synthesiser come convert_batch's de-emphasis and level
+    (the spectra are those of the pre-emphasised signal) and the resampling to out_sr.
+    Returns convert_batch's fields (y_wav_true None) plus f0_target [B, Fout], env_log [B, Fout, bins] and the phase plan.
+    Every check and table is made on the host before the first launch; after the uploads nothing is copied to the host and
+    the host waits for nothing."""
+    import torch
+    import audio_lib
+    import _vc
+    what = 'convert_hnm_batch'
+    seed = audio_lib.check_seed(seed)
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    source = isinstance(pitch, str)
+    if pitch is None or (source and pitch != 'source'):
+        raise ValueError(" - ERROR, {}: pitch must be 'source', a ratio or a [B, Fout] contour, got {!r}".format(what, pitch))
+    scalar = not source and getattr(pitch, 'ndim', 0) == 0
+    contour = not source and not scalar
+    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and contour):
+        raise ValueError(" - ERROR, {}: stats_src and stats_tgt go together and with the source's contour".format(what))
+    if scalar:
+        pitch = _check_pitch_ratio(pitch, what + ': pitch')
+    sr, hop = int(cfg_d['sample_rate']), int(cfg_d['hop_length'])
+    tracker = None if contour else _tracker_args(f0_args, sr, hop, what)
+    h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
+                      res_type)
+    plan, B, Fout, n_bins = h.plan, h.B, h.plan.Fout, h.n_bins
+    n_fft, order, iters, floor = audio_lib._check_envelope_args(what, (B, Fout, n_bins), h.n_fft, order, iters, floor)
+    _, _, f0_lo, f0_hi = audio_lib._check_plan_args(what, (B, Fout), sr, hop, f0_lo, f0_hi)
+    cutoff = audio_lib.hnm_cutoff(voiced_cutoff_hz, sr, n_fft, f0_lo)
+    noise_level = audio_lib._hnm_float(noise_level, what, 'noise_level', lo=0.0)
+    if contour and tuple(pitch.shape) != (B, Fout):
+        raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per output frame)'.format(what, B, Fout))
+    if not contour:
+        import evaluation
+        if int(h.h_lens.max()) > evaluation.F0_MAX_SAMPLES:
+            raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('convert_hnm_batch needs a GPU (no CPU fallback)')
+
+    up = _convert_upload(h, wav, [h.h_nsamp, plan.n_out, plan.n_src])
+    d_nsamp, d_fout, d_fsrc = up.d_extra[-3:]
+    if contour:
+        if not torch.is_tensor(pitch):
+            pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
+        pitch = pitch.to(device='cuda', non_blocking=True)
+    elif h.res_in:                                                  # once, here: the source's track needs the model's rate too
+        w16 = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), up.wav, up.d_extra[0])
+        h, up = h._replace(res_in=False), up._replace(wav=w16)
+
+    # ---- convert_batch's model pass and stitch, the magnitude as convert_batch makes it
+    mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
+    mel_pred = compound_stitch(y_mel, up.d_utt, Fout)
+    phn_pred = compound_stitch(y_phn, up.d_utt, Fout)
+    if float(realse) == 1.0:
+        stft_pred, amp_pred = compound_stitch(y_stft, up.d_utt, Fout, P_dB_norm_factor=cfg_d['P_dB_norm_factor'])
+    else:
+        stft_pred = compound_stitch(y_stft, up.d_utt, Fout)
+        amp_pred = torch.empty_like(stft_pred)
+        _vc.check(_vc.lib().vc_power_to_amp(_vc.ptr(stft_pred), _vc.ptr(up.d_nout), B, Fout, n_bins, float(cfg_d['P_dB_norm_factor']),
+                                            float(realse), _vc.ptr(amp_pred), _vc.current_stream()))
+
+    # ---- the contour, the synthesiser, de-emphasis and level
+    if contour:
+        f0_target = pitch.to(torch.float32).contiguous()
+    else:
+        f0_target = _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt)
+        if scalar:
+            f0_target = f0_target * float(pitch)
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, n_fft)
+    syn = audio_lib._hnm_chain(vplan, amp_pred, f0_target, up.d_nout, d_nsamp, sr, order, iters, floor, f0_lo, f0_hi, cutoff,
+                               noise_level, seed, up.d_ids, noise_level > 0.0)
+    y_wav_pred = syn.y
+    _vc.check(_vc.lib().vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(y_wav_pred), _vc.ptr(up.d_nout), B, Fout, y_wav_pred.shape[1],
+                                                     float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
+                                                     _vc.current_stream()))
+    n_samples = [int(v) for v in h.h_nsamp]
+    if h.res_out:
+        y_wav_pred = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y_wav_pred, d_nsamp)
+        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
+    return _HNM_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
+                   f0_target, syn.env_log, syn.plan)
 
 
 # --------------------------------------------------------------------------- differential spectrum (csrc/vc_vocoder.hip)

@@ -138,6 +138,19 @@ __device__ inline int block_scan_excl(int v, int* wtot, int& total) {
 __device__ __forceinline__ float power_db_to_amp(float P, float inv_norm) {
     return exp10f(0.05f * (fmaxf(0.0f, P) * inv_norm - 80.0f));
 }
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): vc_phase_init and vc_noise_init_f32 address it alike.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
 #endif
 
 }  // namespace vc

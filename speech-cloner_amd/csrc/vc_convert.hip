@@ -130,20 +130,6 @@ compound_stitch_kernel(const void* __restrict__ src, int bf16, const int32_t* __
     store_vec<V>(dst + (size_t)b * slab, (size_t)i0, v);
 }
 
-// ---- Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // ---- initial phase.  grid (tiles of CT Philox blocks, B); one block of four words = elements 4j .. 4j+3 of the
 // utterance's flat [Fmax * bins] slab.  VEC: the slab length is a multiple of 4, so the four go out as one 16-byte store.
 template <bool VEC>
@@ -159,7 +145,7 @@ phase_init_kernel(const int32_t* __restrict__ n_frames, const int32_t* __restric
     float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (e0 < lim) {
         uint32_t x[4];
-        philox4x32_10((uint32_t)(e0 >> 2), (uint32_t)(utt_id ? utt_id[b] : b), 0u, 0u, seed_lo, seed_hi, x);
+        vc::philox4x32_10((uint32_t)(e0 >> 2), (uint32_t)(utt_id ? utt_id[b] : b), 0u, 0u, seed_lo, seed_hi, x);
 #pragma unroll
         for (int k = 0; k < 4; ++k)                                // one rounding: (x >> 8) * 2^-24 is exact
             v[k] = (e0 + k < lim) ? __fmul_rn(3.14159265358979323846f, (float)(x[k] >> 8) * 5.9604644775390625e-8f) : 0.0f;
