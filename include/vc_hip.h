@@ -919,7 +919,8 @@ int vc_resample_f32(const vc_resample_plan* plan, const float* d_in, const int32
  * total = D(Fa-1, Fb-1), path_len = L(Fa-1, Fb-1), mcd = total / path_len (float32 division).  band >= 0 allows cell
  * (i, j) iff |j * (Fa-1) - i * (Fb-1)| <= band * max(Fa-1, Fb-1), tested in 64-bit integers; every other cell has
  * D = +inf and L = 0; the end cell is always allowed.  band = -1: no band.  A band that disconnects the end from the
- * start gives total = +inf.
+ * start (band = 0 with Fa != Fb, for one) gives total = +inf; path_len and mcd then hold what the recurrence leaves in
+ * the end cell and mean nothing, and vc_dtw_backtrack writes no path.
  *
  * vc_dtw_f32: d_ca [batch, max_a, n_coef], d_cb [batch, max_b, n_coef] float32, contiguous; d_len_a / d_len_b int32
  * [batch] ON THE DEVICE, clamped to [1, max]; 1 <= max_a, max_b <= 16,384, n_coef <= 32 (else VC_ERR_UNSUPPORTED);
@@ -927,7 +928,9 @@ int vc_resample_f32(const vc_resample_plan* plan, const float* d_in, const int32
  * (want_path = 0) uses 16 bytes of workspace per column of B and pair.  want_path = 1 also stores two bits per cell
  * (0 diagonal, 1 up, 2 left; row-major, sixteen columns to a word) and gives bit-identical total / path_len;
  * VC_ERR_UNSUPPORTED when the codes of the batch exceed 2^31 bytes (one pair of 16,384 x 16,384 takes 2^26).
- * vc_dtw_workspace_size: bytes for either mode (host arithmetic only; 0 for a shape the launch would refuse).
+ * vc_dtw_workspace_size: bytes for either mode (host arithmetic only; 0 for a shape the launch would refuse).  The
+ * workspace is 16-byte aligned (VC_ERR_INVALID otherwise) and may be exactly that long (VC_ERR_WORKSPACE when shorter);
+ * its contents before the launch do not matter.
  * vc_dtw_backtrack: from the workspace a want_path launch filled (same batch, max_a, max_b) and its d_total /
  * d_path_len, d_path [batch, max_a + max_b - 1, 2] int32: the cells (i, j) from (0, 0) to (Fa-1, Fb-1), rows from
  * path_len on filled with -1 (all rows when total is not finite).
@@ -983,8 +986,8 @@ int vc_frame_mcd_f32(const float* d_ca, const float* d_cb, const int32_t* d_len_
  *
  * vc_f0_metrics_f32: the figures of `batch` pairs of tracks d_f0_a [batch, max_a], d_f0_b [batch, max_b] (0 = unvoiced)
  * with d_len_a / d_len_b int32 [batch] on the device, clamped to [1, max].  The cells are d_path [batch, max_path, 2]
- * int32 with d_path_len [batch] -- exactly what vc_dtw_backtrack and vc_dtw_f32 write -- or, with d_path = d_path_len =
- * NULL and max_path = 0, the cells (i, i), i < min(len_a, len_b).  A cell outside [0, len_a) x [0, len_b) is skipped and
+ * int32 with d_path_len [batch] (clamped to [0, max_path]) -- exactly what vc_dtw_backtrack and vc_dtw_f32 write -- or,
+ * with d_path = d_path_len = NULL and max_path = 0, the cells (i, i), i < min(len_a, len_b).  A cell outside [0, len_a) x [0, len_b) is skipped and
  * not counted.  Per pair: d_counts [batch, 3] int32 = n_cells, n_both_voiced, n_vuv_mismatch (one side voiced, the other
  * not); d_values [batch, 4] float32 = vuv_error (n_vuv_mismatch / n_cells), f0_rmse_cents
  * (sqrt(mean (1200 log2(fa / fb))^2) over the both-voiced cells), f0_rmse_hz, logf0_corr (Pearson correlation of log2 f0
@@ -1088,16 +1091,19 @@ int vc_f0_viterbi_f32(const float* d_pitch, const float* d_cost, const int32_t* 
  * frame.  The only launch that reads the waveform.  Limits: batch <= 65,535, max_len <= 2^30, frame_length <= 8,192,
  * hop <= 65,536.  vc_frame_energy_tile is host arithmetic (0 for values the launch would refuse).
  * vc_activity_mask: d_energy (modes 1, 3) and d_f0 (modes 2, 3) [batch, max_frames] float32, d_n_frames int32 [batch] on
- * the device, clamped to [1, max_frames]; d_mask [batch, max_frames] uint8, 0 from the row's frame count on.  One
- * workgroup per utterance; max_frames <= 16,384.
+ * the device, clamped to [1, max_frames]; d_mask [batch, max_frames] uint8, 0 from the row's frame count on.  The
+ * pointer of a mode that does not use it may be NULL.  In the energy modes ratio must lie in (0, 1): 0, 1 or a NaN are
+ * refused with VC_ERR_INVALID (a ratio of 0 would be "e > 0" alone).  One workgroup per utterance; max_frames <= 16,384.
  * vc_mask_compact: d_mask_a [batch, max_a] with d_frames_a; d_mask_b [batch, max_b] with d_frames_b, or NULL, NULL, 0.
  * d_index [batch, max_a], d_n_active, d_n_kept, d_n_intervals [batch], d_intervals [batch, (max_a + 1) / 2, 2], int32.
  * One workgroup per utterance, positions by a sum scan in a fixed order; max_a, max_b <= 16,384.
- * vc_compact_rows_f32: d_dst[b, k, :] = d_src[b, d_index[b, k], :] for k < min(d_n_kept[b], index_frames), zeros beyond;
+ * vc_compact_rows_f32: d_dst[b, k, :] = d_src[b, d_index[b, k], :] for k < min(d_n_kept[b], index_frames), zeros beyond
+ * (a negative d_n_kept counts as 0), and zeros for an index outside [0, src_frames);
  * d_src [batch, src_frames, n_cols], d_index [batch, index_frames], d_dst [batch, dst_frames, n_cols].  The indices live
  * on the device (vc_gather_rows takes a host-built list of the whole batch).  n_cols <= 4,096.
  * vc_path_map: d_path_out[b, p] = (d_index_a[b, i], d_index_b[b, j]) for the cell (i, j) = d_path_in[b, p], p <
- * d_path_len[b]; (-1, -1) beyond, and for a cell outside [0, max_a) x [0, max_b).  d_path_in NULL: the cells (p, p).
+ * d_path_len[b] (clamped to [0, max_path]); (-1, -1) beyond, and for a cell outside [0, max_a) x [0, max_b).  d_path_in
+ * NULL: the cells (p, p).
  * d_path_out may be d_path_in.  After it the path indexes the original frames, and vc_f0_metrics_f32 runs unchanged on
  * the original tracks and lengths.
  *

@@ -37,7 +37,8 @@ def frames(x, hop, W):
     F = n_frames(len(x), hop)
     idx = (np.arange(F) * hop - W // 2)[:, None] + np.arange(W)[None, :]
     ok = (idx >= 0) & (idx < len(x))
-    return np.where(ok, x[np.clip(idx, 0, len(x) - 1)], 0).astype(x.dtype)
+    src = x if len(x) else np.zeros(1, x.dtype)                       # an empty utterance: one frame of zeros
+    return np.where(ok, src[np.clip(idx, 0, len(src) - 1)], 0).astype(x.dtype)
 
 
 def frame_energy(x, hop=80, W=400, dtype=np.float64):

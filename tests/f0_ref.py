@@ -44,7 +44,8 @@ def frames(x, hop, W, tau_max, f0=0, f1=None):
     span = W + tau_max + 1
     idx = (np.arange(f0, f1) * hop - (W + tau_max) // 2)[:, None] + np.arange(span)[None, :]
     ok = (idx >= 0) & (idx < len(x))
-    return np.where(ok, x[np.clip(idx, 0, len(x) - 1)], 0).astype(x.dtype)
+    src = x if len(x) else np.zeros(1, x.dtype)                       # an empty utterance: one frame of zeros
+    return np.where(ok, src[np.clip(idx, 0, len(src) - 1)], 0).astype(x.dtype)
 
 
 def difference(fr, W, tau_max, dtype=np.float64):
@@ -109,12 +110,14 @@ def refine(dp, tau, sr, dtype=np.float64):
     return dtype(sr) / (dtype(tau) + off)
 
 
-def yin(x, sr=16000, hop=80, W=512, fmin=60.0, fmax=400.0, threshold=0.15, dtype=np.float64, details=False, block=256):
+def yin(x, sr=16000, hop=80, W=512, fmin=60.0, fmax=400.0, threshold=0.15, dtype=np.float64, details=False, block=256,
+        tau_min=None, tau_max=None):
     """(f0 [F], aperiodicity [F]) in ``dtype``; with details also a dict: tau [F] (0 unvoiced), marginal [F] (bool: the
     voicing decision or the choice of the dip changes when the threshold moves by MARGIN either way), floor_cents [F],
     floor_ap [F] (what a relative error of (W + tau_max) 2^-24 in every d' can move the result by; see
-    tests/test_f0_gpu.py)."""
-    tau_min, tau_max = lag_range(sr, fmin, fmax)
+    tests/test_f0_gpu.py).  ``tau_min`` / ``tau_max``: the lag range itself, in place of the one fmin and fmax give."""
+    if tau_min is None or tau_max is None:
+        tau_min, tau_max = lag_range(sr, fmin, fmax)
     x = np.asarray(x, dtype=np.float32)                                # the samples are float32 on either side
     F = n_frames(len(x), hop)
     f0, ap = np.zeros(F, dtype), np.ones(F, dtype)
@@ -144,6 +147,38 @@ def yin(x, sr=16000, hop=80, W=512, fmin=60.0, fmax=400.0, threshold=0.15, dtype
     if details:
         return f0, ap, dict(tau=taus, marginal=marginal, floor_cents=floor_c, floor_ap=floor_a)
     return f0, ap
+
+
+def dprime(x, hop, W, tau_max, dtype=np.float64, block=256):
+    """(d' [F, tau_max + 2] in ``dtype``, computed [F, tau_max + 2] bool: False where d' is set, not calculated -- lag 0
+    and every lag whose running sum is zero) for any hop, W and tau_max."""
+    x = np.asarray(x, dtype=np.float32)
+    F = n_frames(len(x), hop)
+    dp, comp = np.empty((F, tau_max + 2), dtype), np.empty((F, tau_max + 2), bool)
+    for b0 in range(0, F, block):
+        d = difference(frames(x, hop, W, tau_max, b0, b0 + block), W, tau_max, dtype)
+        dp[b0:b0 + block] = normalise(d, dtype)
+        comp[b0:b0 + block] = running_sum(d, dtype) > 0
+    comp[:, 0] = False
+    return dp, comp
+
+
+def candidates(x, sr, hop, W, tau_min, tau_max, n_cand, ceiling, dtype=np.float64):
+    """The candidates of include/vc_hip.h, "Pitch tracking", for any configuration: f0_track_ref's selection and its
+    marginal frames on this module's d'.  dict(lag [F, n_cand] (0 beyond n), f0, pitch, cost (0, 0, 1 beyond n), n [F],
+    aperiodicity [F], marginal [F], dp)."""
+    import f0_track_ref as tr                                          # (it imports this module)
+    dp, comp = dprime(x, hop, W, tau_max, dtype)
+    lags, n = tr.select(dp, tau_min, tau_max, n_cand, dtype(ceiling))
+    F = dp.shape[0]
+    f0, cost = np.zeros((F, n_cand), dtype), np.ones((F, n_cand), dtype)
+    for f in range(F):
+        for k in range(n[f]):
+            f0[f, k] = refine(dp[f], int(lags[f, k]), sr, dtype)
+            cost[f, k] = dp[f, lags[f, k]]
+    pitch = np.where(f0 > 0, np.log2(np.where(f0 > 0, f0, 1)), 0).astype(dtype)
+    return dict(lag=lags, f0=f0, pitch=pitch, cost=cost, n=n.astype(np.int64), aperiodicity=dp[:, tau_min:tau_max + 1].min(1),
+                marginal=tr.marginal_frames(dp, comp, tau_min, tau_max, n_cand, ceiling, W), dp=dp)
 
 
 def cents(fa, fb):

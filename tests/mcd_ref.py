@@ -89,7 +89,10 @@ def dtw_loop(ca, cb, scale=1.0, band=None, dtype=np.float64):
 
 
 def dtw(ca, cb, scale=1.0, band=None, dtype=np.float64, want_path=True):
-    """The same recurrence, one anti-diagonal k = i + j at a time.  Arrays are indexed by i + 1 (index 0: row -1)."""
+    """The same recurrence, one anti-diagonal k = i + j at a time.  Arrays are indexed by i + 1 (index 0: row -1).
+    A band that cuts the end cell off from the start (band = 0 with Fa != Fb, for one) leaves total = +inf: there is no
+    path (None; the device's is all -1) and the length returned is not defined (it is whatever the recurrence leaves in
+    the end cell, which is always allowed)."""
     ca, cb = np.asarray(ca, dtype=dtype), np.asarray(cb, dtype=dtype)
     Fa, Fb = len(ca), len(cb)
     inf = dtype(np.inf)
