@@ -1214,7 +1214,9 @@ int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const i
  * Limits (VC_ERR_UNSUPPORTED beyond them): components 1 <= M <= 256; feature width 1 <= D <= 64; batch <= 65,535;
  * max_frames * D <= 2^30; groups <= 4,096; models of one table <= 4,097 (4,096 speakers and the UBM).  Lengths d_len int32 [batch] ON THE DEVICE, clamped to
  * [0, max_frames]; masks uint8 [batch, max_frames] on the device or NULL (every frame); a frame is KEPT when its mask is
- * set and it lies below the length.  float32 arithmetic unless said otherwise.
+ * set and it lies below the length.  float32 arithmetic unless said otherwise.  A d_len outside [0, max_frames], of any
+ * magnitude, is clamped and never refused, in all four launches that take it (features, loglik, score, accumulate); features,
+ * cepstra, ll and mask bytes from len on are not read.
  *
  * vc_spk_features_f32: d_cep [batch, max_frames, n_coef] (what vc_mel_cepstra writes), n_coef <= 32; d_feat
  * [batch, max_frames, D], D = n_coef * (1 + deltas).  Columns 0 .. n_coef-1 are the cepstra; with deltas = 1 columns
@@ -1231,6 +1233,8 @@ int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const i
  * read, vc_gmm_table_floats(n_models, M, D) = (n_models + 1) M D + M floats: the means transposed to [model][d][m],
  * 1 / var [d][m] (the float64 quotient of the widened variance, rounded once) and
  *     c_m = log w_m - 0.5 * sum_d log(2 pi var_md)         (float64, d ascending, rounded once).
+ * A weight of exactly 0 gives c_m = -inf: that component adds nothing to any ll and has responsibility 0 for every frame (no
+ * NaN follows from it as long as one weight is positive).
  *
  * vc_gmm_loglik_f32: per frame x of utterance b, with the means of model d_model[b] (clamped to [0, n_models)):
  *     l_m = c_m - 0.5 * sum_d (x_d - mu_md)^2 * (1 / var_md)    the DIRECT form: the expanded x^2 a - 2 x b product
@@ -1249,10 +1253,13 @@ int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const i
  * tree (lane t adds lane t + 128, then t + 64, ... t + 1), each figure is rounded once.  No kept frame: n_frames = 0 and
  * NaN figures.  d_ll_b NULL: ll_b and llr are NaN.
  *
- * vc_gmm_accumulate_f32: the fused E-step.  d_group [batch] int32 in [0, n_groups), or any other value to leave the
- * utterance out.  d_ll is vc_gmm_loglik_f32's output for model `model` of the table.  In FLOAT64:
+ * vc_gmm_accumulate_f32: the fused E-step.  d_group [batch] int32 in [0, n_groups), or any other value (negative, n_groups,
+ * 0x7fffffff: of any magnitude) to leave the utterance out.  d_ll is vc_gmm_loglik_f32's output for model `model` of the
+ * table.  In FLOAT64:
  *     N [n_groups, M], S1, S2 [n_groups, M, D] = the sums of gamma, gamma x, gamma x^2 over the kept frames of the group's
  *     utterances, gamma = exp(l_m - ll) (float32, l_m as above);  L [n_groups] = the sum of ll over the same frames.
+ * KEPT FRAMES ONLY: a frame the mask drops contributes nothing to N, S1, S2 or L whatever its features and its ll hold (inf
+ * and NaN included); frames from len on are not read at all.
  * gamma is formed and folded into the sums; no [frames, M] array exists.  Grid = (chunks of 64 components) x
  * (P = vc_gmm_partitions(n_groups) = max(1, 128 / n_groups) frame partitions) x n_groups: constants and arguments, never
  * a property of the device.  Tile k of utterance b goes to partition (b + k) mod P; a partition walks its utterances
@@ -1262,7 +1269,8 @@ int vc_edit_distance_i32(const int32_t* d_seq_a, const int32_t* d_seq_b, const i
  *     n_groups * P * ceil(M / 64) * (64 (1 + 2 D) + 1) * 8 bytes rounded up to 256, and 0 when P = 1 (n_groups > 64: the
  *     workgroups write the outputs themselves);
  * independent of the number of frames, 33,820,672 bytes at most (n_groups = 1, M = 256, D = 64).  Too small:
- * VC_ERR_WORKSPACE.
+ * VC_ERR_WORKSPACE.  The workspace may be exactly that long, must be 8-byte aligned (VC_ERR_INVALID otherwise) and need not be
+ * cleared: every word read was written by the same call.  Where the query returns 0 it may be NULL with 0 bytes.
  *
  * vc_gmm_update_f32: one launch, elementwise, float64 arithmetic on the float64 statistics, each output rounded once.
  *   mode 0 (EM, n_groups = 1): w_m = max(N_m / sum_k N_k, 2^-40) -- NOT renormalised after the floor (the sum over k

@@ -22,8 +22,8 @@
 // (G groups), P = vc_gmm_partitions(G) = max(1, 128 / G): a function of the arguments, never of the device.  Workgroup
 // (c, p, g) walks the utterances b = 0, 1, ... of group g and of each the tiles k with (b + k) % P == p, ascending.  Per
 // tile: features, ll and the keep flags to LDS; lane (m = t & 63, r = t >> 6) forms gamma of component 64 c + m for frames
-// 8 r .. 8 r + 7 into LDS [frame][m]; then lane (m, q = t >> 6) adds, frame by frame, gamma * x and gamma * x^2 of the
-// dimensions d = q, q + 4, ... into float64 REGISTERS (at most 16 dimensions, 32 accumulators and N: the accumulators
+// 8 r .. 8 r + 7 into LDS [frame][m]; then lane (m, q = t >> 6) adds, frame by frame (a frame the mask drops is skipped:
+// its features may hold anything), gamma * x and gamma * x^2 of the dimensions d = q, q + 4, ... into float64 REGISTERS (at most 16 dimensions, 32 accumulators and N: the accumulators
 // never touch LDS, whose banks then carry only the float32 tile: gamma read lane-consecutive, x as a broadcast).  One
 // partial block per workgroup at the end; gmm_reduce_kernel adds the partitions of an element in the order 0 .. P - 1.
 // With P = 1 (G > 64) the workgroup writes the outputs itself and there is no workspace.
@@ -286,6 +286,7 @@ gmm_accumulate_kernel(const float* __restrict__ x, const float* __restrict__ ll,
             }
             __syncthreads();
             for (int f = 0; f < nf; ++f) {
+                if (!keep[f]) continue;                             // uniform over the workgroup; a dropped frame's x is not used
                 const double gm = (double)gam[f * CHUNK + ml];
                 if (r == 0) nsum += gm;
 #pragma unroll

@@ -33,6 +33,42 @@ def features(cep, length, mask=None, deltas=True, cmn=True, dtype=np.float64):
     return out
 
 
+def _delta_f32(c, length):
+    """The delta columns as the device forms them: two rounded differences, one fused multiply-add (formed in float64, where
+    2 d2 + d1 of two float32 is exact unless their exponents lie more than 29 apart, and rounded once), one correctly rounded
+    division."""
+    idx = lambda k: np.clip(np.arange(length) + k, 0, max(length - 1, 0))
+    d1 = (c[idx(1)] - c[idx(-1)]).astype(np.float32)
+    d2 = (c[idx(2)] - c[idx(-2)]).astype(np.float32)
+    return ((2.0 * d2.astype(np.float64) + d1.astype(np.float64)).astype(np.float32) / np.float32(10)).astype(np.float32)
+
+
+def features_f32(cep, length, mask=None, deltas=True, cmn=True):
+    """features() in float32 with the device's operation order: the column sums of the kept frames in float64, lane r of
+    four adding the kept frames r, r + 4, ... ascending, the partial sums added as ((0 + 1) + 2) + 3, the quotient rounded
+    to float32 once, one rounded subtraction.  ``length`` is clamped to [0, F] as the launch clamps it."""
+    cep = np.asarray(cep, np.float32)
+    F, n_coef = cep.shape
+    length = min(max(int(length), 0), F)
+    D = n_coef * (2 if deltas else 1)
+    out = np.zeros((F, D), np.float32)
+    if not length:
+        return out
+    c = cep[:length]
+    f = np.concatenate([c, _delta_f32(c, length)], 1) if deltas else c.copy()
+    if cmn:
+        keep = np.ones(length, bool) if mask is None else np.asarray(mask[:length]).astype(bool)
+        part = np.zeros((4, D))
+        for r in range(4):
+            for t in np.nonzero(keep[r::4])[0]:
+                part[r] += f[r + 4 * t].astype(np.float64)
+        if keep.any():
+            mean = ((((part[0] + part[1]) + part[2]) + part[3]) / float(keep.sum())).astype(np.float32)
+            f = (f - mean).astype(np.float32)
+    out[:length] = f
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------- model
 def log_norm(w, var):
     """c_m = log w_m - 0.5 sum_d log(2 pi var_md), float64."""
