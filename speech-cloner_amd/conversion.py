@@ -266,6 +266,40 @@ _HOST_NT = namedtuple('convert_host', 'plan B hop n_fft n_bins h_lens h_lens_in 
 _UP_NT = namedtuple('convert_upload', 'wav d_lens d_clip d_nout d_ids d_win d_utt d_true d_extra')
 
 
+def _need_cfg(cfg_d, what):
+    if cfg_d is None:
+        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+
+
+def _need_gpu(what):
+    """The last check of every entry point: nothing before it touches the device."""
+    import torch
+    import _vc
+    if not torch.cuda.is_available():
+        raise _vc.VCError('{} needs a GPU (no CPU fallback)'.format(what))
+
+
+def _check_phase(phase, what, shape=None, allowed=('device', 'spsi'), frames='Fout', note=''):
+    """phase= of a conversion: one of the strings ``allowed``, or an array of ``shape`` (None before the plan is known: only
+    the string is checked then)."""
+    if isinstance(phase, str):
+        if phase not in allowed:
+            raise ValueError(' - ERROR, {}: phase must be {} or a [B, {}, bins] array{}, got {!r}'.format(
+                what, ', '.join(repr(a) for a in allowed), frames, note, phase))
+    elif shape is not None and tuple(phase.shape) != tuple(shape):
+        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, *shape))
+
+
+def _phase_upload(phase):
+    """A phase given as an array, on the device; a string passes through (the vocoder tail makes that phase)."""
+    import torch
+    if isinstance(phase, str):
+        return phase
+    if not torch.is_tensor(phase):
+        phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
+    return phase.to(device='cuda', dtype=torch.float32).contiguous()
+
+
 def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
                   res_type):
     """The host checks and tables that convert_batch and convert_duration_batch share, before anything touches the GPU."""
@@ -329,16 +363,26 @@ def _convert_upload(h, wav, extra):
     return _UP_NT(wav, d_lens, d_clip, d_nout, d_ids, d_win.view(-1, 2), d_utt.view(-1, 3), d_true.view(-1, 2), d_extra)
 
 
+def _resample_input(h, up, cfg_d, wav_sr, res_type):
+    """The input at the model's rate, resampled once: (h, up) with the waveform replaced and res_in cleared.  An entry point
+    that reads up.wav itself (a tracker, the differential filter) calls this before _convert_model, which then finds
+    nothing left to do."""
+    import audio_lib
+    if not h.res_in:
+        return h, up
+    wav = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, cfg_d['sample_rate'], res_type), up.wav, up.d_extra[0])
+    return h._replace(res_in=False), up._replace(wav=wav)
+
+
 def _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type):
     """Input resampling, front-end, windows and the model over window chunks: (mel_true, stft_true [B, Fout, C] and the
     window batches y_mel, y_stft, y_phn [W, T, C] that compound_stitch takes)."""
     import torch
     import audio_lib
-    plan, hop, wav = h.plan, h.hop, up.wav
-    if h.res_in:
-        wav = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, cfg_d['sample_rate'], res_type), wav, up.d_extra[0])
+    h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)
+    plan, hop = h.plan, h.hop
     mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(
-        wav, up.d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
+        up.wav, up.d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
         win_length=cfg_d['win_length'], n_mels=cfg_d['n_mels'], n_mfcc=cfg_d['n_mfcc'], n_fft=cfg_d['n_fft'],
         window=cfg_d['window'], mfcc_normaleze_first_mfcc=cfg_d['mfcc_normaleze_first_mfcc'],
         mfcc_norm_factor=cfg_d['mfcc_norm_factor'], calc_mfcc_derivate=cfg_d['calc_mfcc_derivate'],
@@ -365,39 +409,68 @@ def _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type):
 def _vocoder_tail(cfg_d, d_nf, d_ids, n_iter, momentum, realse, seed, ph_true, ph_pred, stft_true, stft_pred, amp_pred):
     """The vocoder behind a conversion, on frame counts that only the device needs to know (d_nf int32 [B]): the phase
     start, the magnitudes, Griffin-Lim, de-emphasis and level.  stft_pred [B, F, bins]; amp_pred: its magnitude where a
-    kernel before this already made it (realse == 1), else None (vc_power_to_amp here); stft_true: None, or the true
+    kernel before this already made it (realse == 1), else None (made here); stft_true: None, or the true
     spectrum to vocode as well.  ph_*: 'device' (one vc_phase_init from seed and d_ids, shared by both spectra), 'spsi' (from
     each spectrum's own magnitudes) or a [B, F, bins] tensor.  Returns (y_wav_true | None, y_wav_pred) at the model's rate."""
-    import torch
     import audio_lib
-    import _vc
-    B, F, n_bins = stft_pred.shape
-    hop = int(cfg_d['hop_length'])
-    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
-    lib = _vc.lib()
+    _, F, n_bins = stft_pred.shape
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], int(cfg_d['hop_length']), cfg_d['n_fft'])
     if isinstance(ph_pred, str) and ph_pred == 'device':
         ph_true = ph_pred = audio_lib.phase_init(d_nf, F, n_bins, seed, d_ids)
     elif isinstance(ph_pred, str):
         ph_true = ph_pred = None                                   # 'spsi': from each spectrum's own magnitudes, in to_wav
 
-    def power_to_amp(P, rl):
-        amp = torch.empty_like(P)
-        _vc.check(lib.vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nf), B, F, n_bins, float(cfg_d['P_dB_norm_factor']),
-                                      float(rl), _vc.ptr(amp), _vc.current_stream()))
-        return amp
-
     def to_wav(amp, ph):
         if ph is None:
             ph = audio_lib._phase_spsi_launch(amp, d_nf, vplan.n_fft, vplan.hop_length, plan=vplan)
         w = audio_lib._griffin_lim_launch(vplan, amp, ph, d_nf, n_iter, False, momentum)
-        _vc.check(lib.vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(w), _vc.ptr(d_nf), B, F, w.shape[1],
-                                                   float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
-                                                   _vc.current_stream()))
-        return w
+        return _deemphasis_level(vplan, w, d_nf, F, cfg_d, cfg_d['pre_emphasis'])
 
-    y_wav_true = to_wav(power_to_amp(stft_true, 1.0), ph_true) if stft_true is not None else None
-    y_wav_pred = to_wav(amp_pred if amp_pred is not None else power_to_amp(stft_pred, realse), ph_pred)
+    y_wav_true = to_wav(_power_to_amp(stft_true, d_nf, cfg_d, 1.0), ph_true) if stft_true is not None else None
+    y_wav_pred = to_wav(amp_pred if amp_pred is not None else _power_to_amp(stft_pred, d_nf, cfg_d, realse), ph_pred)
     return y_wav_true, y_wav_pred
+
+
+def _power_to_amp(P, d_nf, cfg_d, realse):
+    """The vocoder's magnitude of the spectrum P [B, F, bins] over d_nf frames per utterance."""
+    import torch
+    import _vc
+    B, F, n_bins = P.shape
+    amp = torch.empty_like(P)
+    _vc.check(_vc.lib().vc_power_to_amp(_vc.ptr(P), _vc.ptr(d_nf), B, F, n_bins, float(cfg_d['P_dB_norm_factor']), float(realse),
+                                        _vc.ptr(amp), _vc.current_stream()))
+    return amp
+
+
+def _deemphasis_level(vplan, w, d_nf, F, cfg_d, pre_emphasis):
+    """In place: the waveforms w [B, L] of d_nf frames (of at most F) de-emphasised and
+    brought to the level 15 * mean_abs_amp_norm.  pre_emphasis 0.0 sets the level alone.  Returns w."""
+    import _vc
+    _vc.check(_vc.lib().vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(w), _vc.ptr(d_nf), w.shape[0], F, w.shape[1],
+                                                     float(pre_emphasis), float(15 * cfg_d['mean_abs_amp_norm']),
+                                                     _vc.current_stream()))
+    return w
+
+
+def _stitch(y_mel, y_phn, y_stft, d_utt, Fout, P_dB_norm_factor=None):
+    """The three window batches of _convert_model stitched, launched in this order: (mel, phn, stft, amp).  With
+    P_dB_norm_factor the spectrum's launch writes the vocoder's magnitude as well (realse == 1); amp is None without."""
+    mel = compound_stitch(y_mel, d_utt, Fout)
+    phn = compound_stitch(y_phn, d_utt, Fout)
+    if P_dB_norm_factor is None:
+        return mel, phn, compound_stitch(y_stft, d_utt, Fout), None
+    return (mel, phn) + compound_stitch(y_stft, d_utt, Fout, P_dB_norm_factor=P_dB_norm_factor)
+
+
+def _resample_output(y, h_nsamp, d_nsamp, res_out, cfg_d, out_sr, res_type):
+    """The output tail on host-known sample counts: (y resampled to out_sr when res_out, n_samples as a host list at the rate
+    returned).  d_nsamp: h_nsamp on the device, read only when res_out."""
+    import audio_lib
+    if not res_out:
+        return y, [int(v) for v in h_nsamp]
+    sr = cfg_d['sample_rate']
+    y = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y, d_nsamp)
+    return y, [int(v) for v in audio_lib.resample_len(h_nsamp, sr, out_sr)]
 
 
 def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True,
@@ -425,62 +498,44 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     copied to the host and the host waits for nothing."""
     import torch
     import audio_lib
-    import _vc
+    what = 'convert_batch'
     momentum = _check_momentum(momentum)
     seed = audio_lib.check_seed(seed)
-    if cfg_d is None:
-        raise ValueError(' - ERROR, convert_batch: cfg_d (the data-set configuration) is required')
-    if isinstance(phase, str) and phase not in ('device', 'numpy', 'spsi'):
-        raise ValueError(" - ERROR, convert_batch: phase must be 'device', 'numpy', 'spsi' or a [B, Fout, bins] array, got {!r}".format(phase))
-    h = _convert_host('convert_batch', decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder,
-                      wav_sr, out_sr, res_type)
-    plan, B, Fout, n_bins, sr = h.plan, h.B, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    _need_cfg(cfg_d, what)
+    _check_phase(phase, what, None, ('device', 'numpy', 'spsi'))
+    h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
+                      res_type)
+    plan, Fout, n_bins = h.plan, h.plan.Fout, h.n_bins
     both = bool(giffin_lim_input)
-    h_phase = None
-    if not isinstance(phase, str):
-        if tuple(phase.shape) != (B, Fout, n_bins):
-            raise ValueError(' - ERROR, convert_batch: phase must be [{}, {}, {}]'.format(B, Fout, n_bins))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('convert_batch needs a GPU (no CPU fallback)')
+    _check_phase(phase, what, (h.B, Fout, n_bins), ('device', 'numpy', 'spsi'))
+    _need_gpu(what)
 
     # ---- uploads: the waveforms if they are on the host, one table, the host-drawn phase if asked for
     up = _convert_upload(h, wav, [h.h_nsamp] if h.res_out else [])
-    d_nout, d_ids, d_utt, d_extra = up.d_nout, up.d_ids, up.d_utt, up.d_extra
+    ph_true = ph_pred = phase                                      # 'device' / 'spsi': made in the vocoder tail
     if vocode and isinstance(phase, str) and phase == 'numpy':
-        h_phase = torch.from_numpy(_numpy_phase(plan, n_bins, both)).pin_memory()
-        d_phase = h_phase.to('cuda', non_blocking=True)
+        d_phase = torch.from_numpy(_numpy_phase(plan, n_bins, both)).pin_memory().to('cuda', non_blocking=True)
         ph_true, ph_pred = d_phase[0], d_phase[-1]
-    elif vocode and not isinstance(phase, str):
-        if not torch.is_tensor(phase):
-            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
-        ph_true = ph_pred = phase.to(device='cuda', dtype=torch.float32).contiguous()
+    elif vocode:
+        ph_true = ph_pred = _phase_upload(phase)
 
     # ---- front-end, windows, model, stitch
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
-    mel_pred = compound_stitch(y_mel, d_utt, Fout)
-    phn_pred = compound_stitch(y_phn, d_utt, Fout)
     fused = vocode and float(realse) == 1.0
-    if fused:
-        stft_pred, amp_pred = compound_stitch(y_stft, d_utt, Fout, P_dB_norm_factor=cfg_d['P_dB_norm_factor'])
-    else:
-        stft_pred = compound_stitch(y_stft, d_utt, Fout)
-    n_frames = [int(v) for v in plan.n_out]
-    n_samples = [int(v) for v in h.h_nsamp]
-    if not vocode:
-        return _BATCH_NT(None, None, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
+    mel_pred, phn_pred, stft_pred, amp_pred = _stitch(y_mel, y_phn, y_stft, up.d_utt, Fout,
+                                                      cfg_d['P_dB_norm_factor'] if fused else None)
 
-    # ---- vocoder
-    if isinstance(phase, str) and phase != 'numpy':
-        ph_true = ph_pred = phase                                  # 'device' / 'spsi': made in the tail
-    y_wav_true, y_wav_pred = _vocoder_tail(cfg_d, d_nout, d_ids, n_iter, momentum, realse, seed, ph_true, ph_pred,
-                                           stft_true if both else None, stft_pred, amp_pred if fused else None)
-    if h.res_out:
-        rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
-        y_wav_pred = audio_lib._resample_launch(rplan, y_wav_pred, d_extra[-1])
-        if both:
-            y_wav_true = audio_lib._resample_launch(rplan, y_wav_true, d_extra[-1])
-        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
-    return _BATCH_NT(y_wav_true, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, n_frames)
+    # ---- vocoder, output rate
+    y_wav_true = y_wav_pred = None
+    if vocode:
+        y_wav_true, y_wav_pred = _vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, ph_true, ph_pred,
+                                               stft_true if both else None, stft_pred, amp_pred)
+    d_nsamp = up.d_extra[-1] if h.res_out else None
+    y_wav_pred, n_samples = _resample_output(y_wav_pred, h.h_nsamp, d_nsamp, h.res_out, cfg_d, out_sr, res_type)
+    if both:
+        y_wav_true, _ = _resample_output(y_wav_true, h.h_nsamp, d_nsamp, h.res_out, cfg_d, out_sr, res_type)
+    return _BATCH_NT(y_wav_true, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred,
+                     [int(v) for v in plan.n_out])
 
 
 # --------------------------------------------------------------------------- duration (csrc/vc_warp.hip)
@@ -558,7 +613,6 @@ def duration_map_batch(start, end, n_seg, lens, out_len=None, labels=None, ratio
     out_start / out_end [B, K] (the table in output frames), flags [B] (1 invalid table, 2 below min_frames: identity map;
     4 truncated) and the host integer max_frames.  Nothing is copied back and the host waits for nothing."""
     import torch
-    import _vc
     what = 'duration_map_batch'
     if getattr(start, 'ndim', 0) != 2 or start.shape[1] < 1 or start.shape[0] < 1:
         raise ValueError(' - ERROR, {}: start must be [B, K] with B, K >= 1'.format(what))
@@ -598,8 +652,7 @@ def duration_map_batch(start, end, n_seg, lens, out_len=None, labels=None, ratio
         max_frames = min(max(duration_max_frames(n_max, 2 * K + 1, q_max), 1), WARP_MAX_FRAMES)
     if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not 1 <= max_frames <= WARP_MAX_FRAMES:
         raise ValueError(' - ERROR, {}: max_frames must be an integer in [1, {}]'.format(what, WARP_MAX_FRAMES))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('duration_map_batch needs a GPU (no CPU fallback)')
+    _need_gpu(what)
     d_start, d_end = _i32_device(start, (B, K), what + ': start'), _i32_device(end, (B, K), what + ': end')
     d_nseg, d_lens = _i32_device(n_seg, (B,), what + ': n_seg'), _i32_device(lens, (B,), what + ': lens')
     d_len = None if out_len is None else _i32_device(out_len, (B, K), what + ': out_len')
@@ -659,7 +712,6 @@ def time_warp_batch(x, pos, n_out, lens, mode='linear', P_dB_norm_factor=None):
     Rows from n_out on are zero.  With P_dB_norm_factor also the vocoder's magnitude of the warped spectrum (what
     vc_power_to_amp gives with realse == 1, bit for bit): returns (warped, amp).  Nothing is copied back."""
     import torch
-    import _vc
     what = 'time_warp_batch'
     if mode not in _WARP_MODES:
         raise ValueError(" - ERROR, {}: mode must be 'linear' or 'nearest', got {!r}".format(what, mode))
@@ -677,8 +729,7 @@ def time_warp_batch(x, pos, n_out, lens, mode='linear', P_dB_norm_factor=None):
         h = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
         if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > F:
             raise ValueError(' - ERROR, {}: lens must be {} integers in [0, {}]'.format(what, B, F))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('time_warp_batch needs a GPU (no CPU fallback)')
+    _need_gpu(what)
     if not torch.is_tensor(x):
         x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
     x = x.to(device='cuda', dtype=torch.float32).contiguous()
@@ -725,6 +776,128 @@ def duration_min_frames(cfg_d):
     return (n_fft // 2) // int(cfg_d['hop_length']) + 2
 
 
+_DUR_REQ_NT = namedtuple('duration_request', 'rate rate_q ratio out_len gap_q table decode K Fw min_frames dec cmap')
+
+
+def _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len):
+    """The duration arguments of convert_duration_batch and convert_diff_duration_batch, as far as they can be checked
+    without a plan: rate_q / gap_q (Q16), table (the caller's segment table, None for rate= and for 'decode') and decode (the
+    phone-loop decoder's keywords with their defaults).  K, Fw, min_frames come from _duration_bound, dec and cmap from
+    _duration_decoder."""
+    if sum(v is not None for v in (rate, ratio, out_len)) != 1:
+        raise ValueError(' - ERROR, {}: pass exactly one of rate, ratio and out_len'.format(what))
+    rate_q = None
+    if rate is not None:
+        if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not 0.0 < float(rate) <= WARP_MAX_RATIO:
+            raise ValueError(' - ERROR, {}: rate must be a number in (0, {}], got {!r}'.format(what, WARP_MAX_RATIO, rate))
+        rate_q = int(ratio_to_q(float(rate)))
+    gap_q = _check_ratio_scalar(gap_ratio, what + ': gap_ratio')
+    table = None
+    if rate is None and not (isinstance(segments, str) and segments == 'decode'):
+        if isinstance(segments, str) or len(segments) != 4:
+            raise ValueError(" - ERROR, {}: segments must be 'decode' or (labels, start, end, n_seg)".format(what))
+        table = segments
+    if decode is not None and (rate is not None or table is not None):
+        raise ValueError(" - ERROR, {}: decode is for segments='decode'".format(what))
+    kw = dict(trans=None, penalty=0.0, init=None, final=None, min_dur=3, class_map=None, floor=1e-10)
+    extra = set(decode or {}) - set(kw)
+    if extra:
+        raise ValueError(' - ERROR, {}: decode takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
+    kw.update(decode or {})
+    return _DUR_REQ_NT(rate, rate_q, ratio, out_len, gap_q, table, kw, None, None, None, None, None)
+
+
+def _duration_bound(what, req, n_frames, Fout, min_frames, max_frames, needs):
+    """After _convert_host: the table width K and the output bound Fw (max_frames, or its default where one can be derived)
+    for utterances of n_frames (int64 [B], at most Fout) input frames.  min_frames: the fewest frames an output may have;
+    needs: how the error of a rate= that falls below it ends."""
+    import torch
+    rate, ratio, table = req.rate, req.ratio, req.table
+    if Fout > WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, WARP_MAX_FRAMES, Fout))
+    K = 1 if rate is not None else (Fout if table is None else int(table[1].shape[1]))
+    if rate is not None:
+        want = (n_frames * req.rate_q + 32768) >> 16
+        if want.min() < min_frames:
+            raise ValueError(' - ERROR, {}: rate {} leaves an utterance {} frames; {}'.format(what, rate, int(want.min()),
+                                                                                              needs.format(min_frames)))
+        bound = int(want.max())
+    elif ratio is not None and not torch.is_tensor(ratio):
+        r = np.atleast_1d(np.asarray(ratio, dtype=np.float32))
+        if r.ndim != 1 or not np.isfinite(r).all() or r.min() < 0 or r.max() > WARP_MAX_RATIO:
+            raise ValueError(' - ERROR, {}: ratio must be finite floats [C] in [0, {}]'.format(what, WARP_MAX_RATIO))
+        ratio = r
+        bound = duration_max_frames(Fout, 2 * K + 1, max(req.gap_q, int(ratio_to_q(r).max())))
+    else:
+        if ratio is not None and (ratio.ndim != 1 or not ratio.is_floating_point()):
+            raise ValueError(' - ERROR, {}: ratio must be floats [C]'.format(what))
+        bound = None
+    if max_frames is None:
+        if bound is None:
+            raise ValueError(' - ERROR, {}: max_frames is required with out_len and with a ratio on the device'.format(what))
+        max_frames = min(bound, WARP_MAX_FRAMES)
+    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not min_frames <= max_frames <= WARP_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: max_frames must be an integer in [{}, {}]'.format(what, min_frames, WARP_MAX_FRAMES))
+    return req._replace(ratio=ratio, K=K, Fw=int(max_frames), min_frames=min_frames)
+
+
+def _duration_decoder(what, req, decoder, encoder, B, Fout):
+    """The last host check of a duration request: with segments='decode', the phone-loop decoder's arguments (dec, cmap),
+    before anything is launched."""
+    if req.rate is not None or req.table is not None:
+        return req
+    import evaluation
+    kw = dict(req.decode)
+    C = int((encoder if encoder is not None else decoder.encoder).cfg_d['n_output'])
+    evaluation._check_decode_size(B, Fout, C, what)
+    cmap = evaluation._check_class_map(kw.pop('class_map'), C, what)
+    return req._replace(dec=evaluation._decode_args(C=C, what=what, kind='prob', **kw), cmap=cmap)
+
+
+def _duration_map(what, req, d_nf, phn, Fout):
+    """The device side of a duration request: the segment table in input frames -- one piece per utterance for rate=, decoded
+    from the posteriors phn [B, Fout, C] over d_nf [B] frames, or the caller's table -- and vc_duration_map over it.  Returns
+    (map, seg): duration_map_batch's result and (labels, start, end, n_seg) in OUTPUT frames."""
+    import torch
+    B, K, dev = d_nf.shape[0], req.K, d_nf.device
+    d_lab = d_len = d_ratio = None
+    if req.rate is not None:
+        d_start = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+        d_end, d_nseg = d_nf.view(B, 1), torch.ones((B,), dtype=torch.int32, device=dev)
+        d_ratio = torch.full((1,), req.rate_q, dtype=torch.int32, device=dev)
+    else:
+        if req.table is None:
+            import evaluation
+            r = evaluation._decode_launch(phn, d_nf, evaluation._cmap_device(req.cmap), evaluation._decode_upload(req.dec))
+            d_lab, d_start, d_end, d_nseg = r.seg.labels, r.seg.start, r.seg.end, r.seg.n_seg
+        else:
+            d_lab, d_start, d_end = (_i32_device(t, (B, K), what + ': segments') for t in req.table[:3])
+            d_nseg = _i32_device(req.table[3], (B,), what + ': segments n_seg')
+        if req.out_len is not None:
+            d_len = _i32_device(req.out_len, (B, K), what + ': out_len')
+        elif torch.is_tensor(req.ratio):
+            d_ratio = ratio_to_q(req.ratio.to('cuda', non_blocking=True)).contiguous()
+        else:
+            d_ratio = _i32_device(ratio_to_q(req.ratio), req.ratio.shape, what + ': ratio')
+    m = _map_launch(d_start, d_end, d_nseg, None if d_ratio is None or req.rate is not None else d_lab, d_len, d_ratio, req.gap_q,
+                    d_nf, Fout, req.min_frames, req.Fw)
+    return m, _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg)
+
+
+def _resample_output_device(y, n_samples, max_samples, res_out, cfg_d, out_sr, res_type):
+    """The output tail on sample counts that only the device knows (n_samples int32 [B], at most the host's max_samples):
+    (y, n_samples, max_samples), at out_sr when res_out."""
+    import torch
+    import audio_lib
+    if not res_out:
+        return y, n_samples, max_samples
+    sr = cfg_d['sample_rate']
+    rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
+    y = audio_lib._resample_launch(rplan, y, n_samples)
+    n_samples = torch.div(n_samples.long() * rplan.up + (rplan.down - 1), rplan.down, rounding_mode='floor').to(torch.int32)
+    return y, n_samples, int(audio_lib.resample_len(max_samples, sr, out_sr))
+
+
 def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio=None, gap_ratio=1.0, segments='decode',
                            decode=None, out_len=None, max_frames=None, mode='linear', t_s=0, t_e=60, n_iter=200, realse=1.0,
                            two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64, encoder=None,
@@ -751,110 +924,32 @@ def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio
     resampled) and flags [B], seg = (labels, start, end, n_seg) the segment table in output frames, map (the
     duration_map_batch result), the host bounds max_frames and max_samples, and src_frames (convert_batch's host
     n_frames).  Nothing is copied back and the host waits for nothing."""
-    import torch
     import audio_lib
-    import _vc
     what = 'convert_duration_batch'
+    note = " ('numpy' needs host lengths)"
     momentum = _check_momentum(momentum)
     seed = audio_lib.check_seed(seed)
-    if cfg_d is None:
-        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
-    if isinstance(phase, str) and phase not in ('device', 'spsi'):
-        raise ValueError(" - ERROR, {}: phase must be 'device', 'spsi' or a [B, max_frames, bins] array ('numpy' needs host "
-                         "lengths), got {!r}".format(what, phase))
+    _need_cfg(cfg_d, what)
+    _check_phase(phase, what, None, ('device', 'spsi'), 'max_frames', note)
     if mode not in _WARP_MODES:
         raise ValueError(" - ERROR, {}: mode must be 'linear' or 'nearest', got {!r}".format(what, mode))
-    if sum(v is not None for v in (rate, ratio, out_len)) != 1:
-        raise ValueError(' - ERROR, {}: pass exactly one of rate, ratio and out_len'.format(what))
-    if rate is not None:
-        if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not 0.0 < float(rate) <= WARP_MAX_RATIO:
-            raise ValueError(' - ERROR, {}: rate must be a number in (0, {}], got {!r}'.format(what, WARP_MAX_RATIO, rate))
-        rate_q = int(ratio_to_q(float(rate)))
-    gap_q = _check_ratio_scalar(gap_ratio, what + ': gap_ratio')
-    table = None
-    if rate is None and not (isinstance(segments, str) and segments == 'decode'):
-        if isinstance(segments, str) or len(segments) != 4:
-            raise ValueError(" - ERROR, {}: segments must be 'decode' or (labels, start, end, n_seg)".format(what))
-        table = segments
-    if decode is not None and (rate is not None or table is not None):
-        raise ValueError(" - ERROR, {}: decode is for segments='decode'".format(what))
-    kw = dict(trans=None, penalty=0.0, init=None, final=None, min_dur=3, class_map=None, floor=1e-10)
-    extra = set(decode or {}) - set(kw)
-    if extra:
-        raise ValueError(' - ERROR, {}: decode takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
-    kw.update(decode or {})
+    req = _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
                       res_type)
-    plan, B, hop, Fout, n_bins = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins
-    min_frames = duration_min_frames(cfg_d)
-    if Fout > WARP_MAX_FRAMES:
-        raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, WARP_MAX_FRAMES, Fout))
-    K = 1 if rate is not None else (Fout if table is None else int(table[1].shape[1]))
-    if rate is not None:
-        want = (plan.n_out.astype(np.int64) * rate_q + 32768) >> 16
-        if want.min() < min_frames:
-            raise ValueError(' - ERROR, {}: rate {} leaves an utterance {} frames; the vocoder needs {}'.format(what, rate, int(want.min()), min_frames))
-        bound = int(want.max())
-    elif ratio is not None and not torch.is_tensor(ratio):
-        r = np.atleast_1d(np.asarray(ratio, dtype=np.float32))
-        if r.ndim != 1 or not np.isfinite(r).all() or r.min() < 0 or r.max() > WARP_MAX_RATIO:
-            raise ValueError(' - ERROR, {}: ratio must be finite floats [C] in [0, {}]'.format(what, WARP_MAX_RATIO))
-        ratio = r
-        bound = duration_max_frames(Fout, 2 * K + 1, max(gap_q, int(ratio_to_q(r).max())))
-    else:
-        if ratio is not None and (ratio.ndim != 1 or not ratio.is_floating_point()):
-            raise ValueError(' - ERROR, {}: ratio must be floats [C]'.format(what))
-        bound = None
-    if max_frames is None:
-        if bound is None:
-            raise ValueError(' - ERROR, {}: max_frames is required with out_len and with a ratio on the device'.format(what))
-        max_frames = min(bound, WARP_MAX_FRAMES)
-    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not min_frames <= max_frames <= WARP_MAX_FRAMES:
-        raise ValueError(' - ERROR, {}: max_frames must be an integer in [{}, {}]'.format(what, min_frames, WARP_MAX_FRAMES))
-    Fw = int(max_frames)
-    if not isinstance(phase, str) and tuple(phase.shape) != (B, Fw, n_bins):
-        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, B, Fw, n_bins))
-    dec = cmap = None
-    if rate is None and table is None:                              # the decoder's arguments, before anything is launched
-        import evaluation
-        C = int((encoder if encoder is not None else decoder.encoder).cfg_d['n_output'])
-        evaluation._check_decode_size(B, Fout, C, what)
-        cmap = evaluation._check_class_map(kw.pop('class_map'), C, what)
-        dec = evaluation._decode_args(C=C, what=what, kind='prob', **kw)
-    if not torch.cuda.is_available():
-        raise _vc.VCError('convert_duration_batch needs a GPU (no CPU fallback)')
+    plan, B, hop, Fout = h.plan, h.B, h.hop, h.plan.Fout
+    req = _duration_bound(what, req, plan.n_out.astype(np.int64), Fout, duration_min_frames(cfg_d), max_frames,
+                          'the vocoder needs {}')
+    Fw = req.Fw
+    _check_phase(phase, what, (B, Fw, h.n_bins), ('device', 'spsi'), 'max_frames', note)
+    req = _duration_decoder(what, req, decoder, encoder, B, Fout)
+    _need_gpu(what)
 
     up = _convert_upload(h, wav, [])
     d_nout = up.d_nout
-    if not isinstance(phase, str):
-        if not torch.is_tensor(phase):
-            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
-        phase = phase.to(device='cuda', dtype=torch.float32).contiguous()
+    phase = _phase_upload(phase)
     _, _, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
-    mel_s, phn_s, stft_s = (compound_stitch(y, up.d_utt, Fout) for y in (y_mel, y_phn, y_stft))
-
-    # ---- the segment table in stitched frames, the map
-    dev = mel_s.device
-    d_lab = d_len = d_ratio = None
-    if rate is not None:
-        d_start = torch.zeros((B, 1), dtype=torch.int32, device=dev)
-        d_end, d_nseg = d_nout.view(B, 1), torch.ones((B,), dtype=torch.int32, device=dev)
-        d_ratio = torch.full((1,), rate_q, dtype=torch.int32, device=dev)
-    else:
-        if table is None:
-            r = evaluation._decode_launch(phn_s, d_nout, evaluation._cmap_device(cmap), evaluation._decode_upload(dec))
-            d_lab, d_start, d_end, d_nseg = r.seg.labels, r.seg.start, r.seg.end, r.seg.n_seg
-        else:
-            d_lab, d_start, d_end = (_i32_device(t, (B, K), what + ': segments') for t in table[:3])
-            d_nseg = _i32_device(table[3], (B,), what + ': segments n_seg')
-        if out_len is not None:
-            d_len = _i32_device(out_len, (B, K), what + ': out_len')
-        elif torch.is_tensor(ratio):
-            d_ratio = ratio_to_q(ratio.to('cuda', non_blocking=True)).contiguous()
-        else:
-            d_ratio = _i32_device(ratio_to_q(ratio), ratio.shape, what + ': ratio')
-    m = _map_launch(d_start, d_end, d_nseg, None if d_ratio is None or rate is not None else d_lab, d_len, d_ratio, gap_q, d_nout,
-                    Fout, min_frames, Fw)
+    mel_s, phn_s, stft_s, _ = _stitch(y_mel, y_phn, y_stft, up.d_utt, Fout)
+    m, seg = _duration_map(what, req, d_nout, phn_s, Fout)        # the segment table in stitched frames, the map
 
     # ---- the warp, the vocoder
     wm = _WARP_MODES[mode]
@@ -866,16 +961,10 @@ def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio
     else:
         stft_pred = _warp_launch(stft_s, m.pos, m.n_out, d_nout, wm)
     _, y_wav_pred = _vocoder_tail(cfg_d, m.n_out, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, amp_pred)
-    n_samples = (hop * (m.n_out - 1)).clamp_min(0)
-    max_samples = hop * (Fw - 1)
-    if h.res_out:
-        sr = cfg_d['sample_rate']
-        rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
-        y_wav_pred = audio_lib._resample_launch(rplan, y_wav_pred, n_samples)
-        n_samples = torch.div(n_samples.long() * rplan.up + (rplan.down - 1), rplan.down, rounding_mode='floor').to(torch.int32)
-        max_samples = int(audio_lib.resample_len(max_samples, sr, out_sr))
-    return _DUR_NT(y_wav_pred, n_samples, mel_pred, stft_pred, phn_pred, m.n_out, m.flags,
-                   _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg), m, Fw, max_samples, [int(v) for v in plan.n_out])
+    y_wav_pred, n_samples, max_samples = _resample_output_device(y_wav_pred, (hop * (m.n_out - 1)).clamp_min(0), hop * (Fw - 1),
+                                                                 h.res_out, cfg_d, out_sr, res_type)
+    return _DUR_NT(y_wav_pred, n_samples, mel_pred, stft_pred, phn_pred, m.n_out, m.flags, seg, m, Fw, max_samples,
+                   [int(v) for v in plan.n_out])
 
 
 # --------------------------------------------------------------------------- pitch (csrc/vc_pitch.hip)
@@ -1023,7 +1112,6 @@ def psola_plan_batch(period_q, ratio_q, lens, hop_length, max_len=None):
     and synthesis marks), a, s, src, h [B, max_len // 16 + 1] int32 (-1 beyond), and the host integer max_len.  Nothing is
     copied back and the host waits for nothing."""
     import torch
-    import _vc
     what = 'psola_plan_batch'
     if getattr(period_q, 'ndim', 0) != 2 or tuple(getattr(ratio_q, 'shape', ())) != tuple(period_q.shape):
         raise ValueError(' - ERROR, {}: period_q and ratio_q must be [B, F], the same shape'.format(what))
@@ -1034,8 +1122,7 @@ def psola_plan_batch(period_q, ratio_q, lens, hop_length, max_len=None):
         max_len = max(int(np.max(np.asarray(lens))), 1) if np.size(lens) else 1
     _check_pitch_sizes(B, max_len, F, hop_length, what)
     _check_pitch_lens(lens, B, max_len, what)
-    if not torch.cuda.is_available():
-        raise _vc.VCError('psola_plan_batch needs a GPU (no CPU fallback)')
+    _need_gpu(what)
     return _psola_plan_launch(_check_pitch_table(period_q, B, what + ': period_q'), _check_pitch_table(ratio_q, B, what + ': ratio_q'),
                               _i32_device(lens, (B,), what + ': lens'), int(max_len), int(hop_length))
 
@@ -1051,7 +1138,6 @@ def pitch_shift_batch(wav, lens, f0, sr, hop_length, ratio=None, target_f0=None,
     Returns a namedtuple: y [B, Lmax] float32 on the device (zero from an utterance's length on), the plan
     (psola_plan_batch's result) and the two tables.  Nothing is copied back and the host waits for nothing."""
     import torch
-    import _vc
     what = 'pitch_shift_batch'
     if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
         raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
@@ -1065,8 +1151,7 @@ def pitch_shift_batch(wav, lens, f0, sr, hop_length, ratio=None, target_f0=None,
     if lens is None:
         lens = np.full((B,), Lmax, dtype=np.int64)
     _check_pitch_lens(lens, B, Lmax, what)
-    if not torch.cuda.is_available():
-        raise _vc.VCError('pitch_shift_batch needs a GPU (no CPU fallback)')
+    _need_gpu(what)
     if not torch.is_tensor(f0):
         f0 = torch.from_numpy(np.ascontiguousarray(f0))
     if torch.is_tensor(ratio) or torch.is_tensor(target_f0):
@@ -1123,18 +1208,54 @@ def f0_transform(f0, stats_src, stats_tgt):
     return torch.where(voiced, out, torch.zeros_like(out)).to(torch.float32)
 
 
-def _tracker_args(f0_args, sr, hop, what):
-    """f0_args (a dict of f0_track_batch's tracker arguments, or None) checked on the host: (f0a, n_cand, ceiling, costs) as
-    evaluation._f0_track_launch takes them."""
-    import evaluation
+def _tracker_keys(f0_args, what):
+    """f0_args (a dict of f0_track_batch's tracker arguments, or None): the keys checked, the defaults filled in."""
     kw = dict(frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5, switch_cost=0.1, n_cand=8, ceiling=1.0)
     extra = set(f0_args or {}) - set(kw)
     if extra:
         raise ValueError(' - ERROR, {}: f0_args takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
     kw.update(f0_args or {})
+    return kw
+
+
+def _tracker_args(kw, sr, hop, what):
+    """The values of _tracker_keys' dict checked on the host: (f0a, n_cand, ceiling, costs) as evaluation._f0_track_launch
+    takes them."""
+    import evaluation
     f0a = evaluation._f0_args(sr, hop, kw['frame_length'], kw['fmin'], kw['fmax'], kw['threshold'], what)
     n_cand, ceiling = evaluation._track_args(kw['n_cand'], kw['ceiling'], what)
     return f0a, n_cand, ceiling, evaluation._viterbi_costs(f0a[5], kw['jump_cost'], kw['switch_cost'], what)
+
+
+def _parse_pitch(pitch, stats_src, stats_tgt, what, none_ok, stats_kinds, forms, stats_with):
+    """pitch= of convert_pitch_batch, convert_hnm_batch and convert_diff_batch: (kind, value) with kind None, 'source', 'ratio'
+    (value: the checked float) or 'contour' (its shape is checked once the plan is known: _check_contour).  none_ok: whether
+    pitch=None is a request; stats_kinds: the kinds that stats_src / stats_tgt may come with.  forms, stats_with: the
+    caller's wording of the choices and of that rule, for its messages."""
+    source = isinstance(pitch, str)
+    if (pitch is None and not none_ok) or (source and pitch != 'source'):
+        raise ValueError(' - ERROR, {}: pitch must be {}, got {!r}'.format(what, forms, pitch))
+    kind = None if pitch is None else 'source' if source else 'ratio' if getattr(pitch, 'ndim', 0) == 0 else 'contour'
+    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and kind not in stats_kinds):
+        raise ValueError(' - ERROR, {}: stats_src and stats_tgt go together and with {}'.format(what, stats_with))
+    if kind == 'ratio':
+        pitch = _check_pitch_ratio(pitch, what + ': pitch')
+    return kind, pitch
+
+
+def _check_contour(kind, pitch, B, Fout, what, per='output frame'):
+    if kind == 'contour' and tuple(getattr(pitch, 'shape', ())) != (B, Fout):
+        raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per {})'.format(what, B, Fout, per))
+
+
+def _contour_upload(kind, pitch):
+    """A contour given on the host goes up pinned; every other kind of pitch= passes through."""
+    import torch
+    if kind != 'contour':
+        return pitch
+    if not torch.is_tensor(pitch):
+        pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
+    return pitch.to(device='cuda', non_blocking=True)
 
 
 def _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt):
@@ -1174,80 +1295,52 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
     import torch
     import audio_lib
     import evaluation
-    import _vc
     what = 'convert_pitch_batch'
     momentum = _check_momentum(momentum)
     seed = audio_lib.check_seed(seed)
-    if cfg_d is None:
-        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
-    if isinstance(phase, str) and phase not in ('device', 'spsi'):
-        raise ValueError(" - ERROR, {}: phase must be 'device', 'spsi' or a [B, Fout, bins] array, got {!r}".format(what, phase))
+    _need_cfg(cfg_d, what)
+    _check_phase(phase, what)
     if pitch is None:
         raise ValueError(" - ERROR, {}: pitch is required: a ratio, a [B, Fout] contour or 'source'".format(what))
-    source = isinstance(pitch, str)
-    if source and pitch != 'source':
-        raise ValueError(" - ERROR, {}: pitch must be a ratio, a [B, Fout] contour or 'source', got {!r}".format(what, pitch))
-    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and not source):
-        raise ValueError(" - ERROR, {}: stats_src and stats_tgt go together and with pitch='source'".format(what))
-    scalar = not source and getattr(pitch, 'ndim', 0) == 0
-    if scalar:
-        pitch = _check_pitch_ratio(pitch, what + ': pitch')
+    kind, pitch = _parse_pitch(pitch, stats_src, stats_tgt, what, False, ('source',), "a ratio, a [B, Fout] contour or 'source'",
+                               "pitch='source'")
     w_floor = _check_w_floor(w_floor, what)
-    tracker = _tracker_args(f0_args, cfg_d['sample_rate'], int(cfg_d['hop_length']), what)
+    tracker = _tracker_args(_tracker_keys(f0_args, what), cfg_d['sample_rate'], int(cfg_d['hop_length']), what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
                       res_type)
-    plan, B, hop, Fout, n_bins, sr = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
     Lout = hop * (Fout - 1)
     _check_pitch_sizes(B, Lout, Fout, hop, what)
     if max(Lout, int(h.h_lens.max())) > evaluation.F0_MAX_SAMPLES:
         raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
-    if not isinstance(phase, str) and tuple(phase.shape) != (B, Fout, n_bins):
-        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, B, Fout, n_bins))
-    if not source and not scalar and tuple(pitch.shape) != (B, Fout):
-        raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per output frame)'.format(what, B, Fout))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('convert_pitch_batch needs a GPU (no CPU fallback)')
+    _check_phase(phase, what, (B, Fout, h.n_bins))
+    _check_contour(kind, pitch, B, Fout, what)
+    _need_gpu(what)
 
     up = _convert_upload(h, wav, [h.h_nsamp, plan.n_out, plan.n_src])
     d_nsamp, d_fout, d_fsrc = up.d_extra[-3:]
-    if not isinstance(phase, str):
-        if not torch.is_tensor(phase):
-            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
-        phase = phase.to(device='cuda', dtype=torch.float32).contiguous()
-    if not source and not scalar:
-        if not torch.is_tensor(pitch):
-            pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
-        pitch = pitch.to(device='cuda', non_blocking=True)
+    phase = _phase_upload(phase)
+    pitch = _contour_upload(kind, pitch)
     psola_window('cuda')
-    if h.res_in:                                                    # once, here: the source's track needs the model's rate too
-        w16 = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), up.wav, up.d_extra[0])
-        h, up = h._replace(res_in=False), up._replace(wav=w16)
+    h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)       # here: the source's track needs the model's rate too
 
     # ---- convert_batch's model pass, stitch and vocoder
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
-    mel_pred = compound_stitch(y_mel, up.d_utt, Fout)
-    phn_pred = compound_stitch(y_phn, up.d_utt, Fout)
-    amp_pred = None
-    if float(realse) == 1.0:
-        stft_pred, amp_pred = compound_stitch(y_stft, up.d_utt, Fout, P_dB_norm_factor=cfg_d['P_dB_norm_factor'])
-    else:
-        stft_pred = compound_stitch(y_stft, up.d_utt, Fout)
-    _, y0 =_vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, amp_pred)
+    mel_pred, phn_pred, stft_pred, amp_pred = _stitch(y_mel, y_phn, y_stft, up.d_utt, Fout,
+                                                      cfg_d['P_dB_norm_factor'] if float(realse) == 1.0 else None)
+    _, y0 = _vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, amp_pred)
 
     # ---- the conversion's own track, the target, the shift
     f0_pred = evaluation._f0_track_launch(y0, d_nsamp, d_fout, *tracker)[0]
     f0_target = None
-    if source:
+    if kind == 'source':
         f0_target = _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt)
-    elif not scalar:
+    elif kind == 'contour':
         f0_target = pitch.to(torch.float32)
-    per, rat = pitch_tables(f0_pred, sr, ratio=pitch if scalar else None, target_f0=f0_target, hop_length=hop)
+    per, rat = pitch_tables(f0_pred, sr, ratio=pitch if kind == 'ratio' else None, target_f0=f0_target, hop_length=hop)
     pp = _psola_plan_launch(per, rat, d_nsamp, Lout, hop)
-    y_wav_pred = _psola_ola_launch(y0, d_nsamp, pp, w_floor)
-    n_samples = [int(v) for v in h.h_nsamp]
-    if h.res_out:
-        y_wav_pred = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y_wav_pred, d_nsamp)
-        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
+    y_wav_pred, n_samples = _resample_output(_psola_ola_launch(y0, d_nsamp, pp, w_floor), h.h_nsamp, d_nsamp, h.res_out, cfg_d,
+                                             out_sr, res_type)
     return _PITCH_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
                      f0_pred, f0_target, pp)
 
@@ -1277,22 +1370,13 @@ def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats
     the host waits for nothing."""
     import torch
     import audio_lib
-    import _vc
     what = 'convert_hnm_batch'
     seed = audio_lib.check_seed(seed)
-    if cfg_d is None:
-        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
-    source = isinstance(pitch, str)
-    if pitch is None or (source and pitch != 'source'):
-        raise ValueError(" - ERROR, {}: pitch must be 'source', a ratio or a [B, Fout] contour, got {!r}".format(what, pitch))
-    scalar = not source and getattr(pitch, 'ndim', 0) == 0
-    contour = not source and not scalar
-    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and contour):
-        raise ValueError(" - ERROR, {}: stats_src and stats_tgt go together and with the source's contour".format(what))
-    if scalar:
-        pitch = _check_pitch_ratio(pitch, what + ': pitch')
+    _need_cfg(cfg_d, what)
+    kind, pitch = _parse_pitch(pitch, stats_src, stats_tgt, what, False, ('source', 'ratio'),
+                               "'source', a ratio or a [B, Fout] contour", "the source's contour")
     sr, hop = int(cfg_d['sample_rate']), int(cfg_d['hop_length'])
-    tracker = None if contour else _tracker_args(f0_args, sr, hop, what)
+    tracker = None if kind == 'contour' else _tracker_args(_tracker_keys(f0_args, what), sr, hop, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
                       res_type)
     plan, B, Fout, n_bins = h.plan, h.B, h.plan.Fout, h.n_bins
@@ -1300,55 +1384,37 @@ def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats
     _, _, f0_lo, f0_hi = audio_lib._check_plan_args(what, (B, Fout), sr, hop, f0_lo, f0_hi)
     cutoff = audio_lib.hnm_cutoff(voiced_cutoff_hz, sr, n_fft, f0_lo)
     noise_level = audio_lib._hnm_float(noise_level, what, 'noise_level', lo=0.0)
-    if contour and tuple(pitch.shape) != (B, Fout):
-        raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per output frame)'.format(what, B, Fout))
-    if not contour:
+    _check_contour(kind, pitch, B, Fout, what)
+    if kind != 'contour':
         import evaluation
         if int(h.h_lens.max()) > evaluation.F0_MAX_SAMPLES:
             raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('convert_hnm_batch needs a GPU (no CPU fallback)')
+    _need_gpu(what)
 
     up = _convert_upload(h, wav, [h.h_nsamp, plan.n_out, plan.n_src])
     d_nsamp, d_fout, d_fsrc = up.d_extra[-3:]
-    if contour:
-        if not torch.is_tensor(pitch):
-            pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
-        pitch = pitch.to(device='cuda', non_blocking=True)
-    elif h.res_in:                                                  # once, here: the source's track needs the model's rate too
-        w16 = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), up.wav, up.d_extra[0])
-        h, up = h._replace(res_in=False), up._replace(wav=w16)
+    pitch = _contour_upload(kind, pitch)
+    h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)       # here: the source's track needs the model's rate too
 
     # ---- convert_batch's model pass and stitch, the magnitude as convert_batch makes it
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
-    mel_pred = compound_stitch(y_mel, up.d_utt, Fout)
-    phn_pred = compound_stitch(y_phn, up.d_utt, Fout)
-    if float(realse) == 1.0:
-        stft_pred, amp_pred = compound_stitch(y_stft, up.d_utt, Fout, P_dB_norm_factor=cfg_d['P_dB_norm_factor'])
-    else:
-        stft_pred = compound_stitch(y_stft, up.d_utt, Fout)
-        amp_pred = torch.empty_like(stft_pred)
-        _vc.check(_vc.lib().vc_power_to_amp(_vc.ptr(stft_pred), _vc.ptr(up.d_nout), B, Fout, n_bins, float(cfg_d['P_dB_norm_factor']),
-                                            float(realse), _vc.ptr(amp_pred), _vc.current_stream()))
+    mel_pred, phn_pred, stft_pred, amp_pred = _stitch(y_mel, y_phn, y_stft, up.d_utt, Fout,
+                                                      cfg_d['P_dB_norm_factor'] if float(realse) == 1.0 else None)
+    if amp_pred is None:
+        amp_pred = _power_to_amp(stft_pred, up.d_nout, cfg_d, realse)
 
     # ---- the contour, the synthesiser, de-emphasis and level
-    if contour:
+    if kind == 'contour':
         f0_target = pitch.to(torch.float32).contiguous()
     else:
         f0_target = _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt)
-        if scalar:
+        if kind == 'ratio':
             f0_target = f0_target * float(pitch)
     vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, n_fft)
     syn = audio_lib._hnm_chain(vplan, amp_pred, f0_target, up.d_nout, d_nsamp, sr, order, iters, floor, f0_lo, f0_hi, cutoff,
                                noise_level, seed, up.d_ids, noise_level > 0.0)
-    y_wav_pred = syn.y
-    _vc.check(_vc.lib().vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(y_wav_pred), _vc.ptr(up.d_nout), B, Fout, y_wav_pred.shape[1],
-                                                     float(cfg_d['pre_emphasis']), float(15 * cfg_d['mean_abs_amp_norm']),
-                                                     _vc.current_stream()))
-    n_samples = [int(v) for v in h.h_nsamp]
-    if h.res_out:
-        y_wav_pred = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y_wav_pred, d_nsamp)
-        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
+    y_wav_pred = _deemphasis_level(vplan, syn.y, up.d_nout, Fout, cfg_d, cfg_d['pre_emphasis'])
+    y_wav_pred, n_samples = _resample_output(y_wav_pred, h.h_nsamp, d_nsamp, h.res_out, cfg_d, out_sr, res_type)
     return _HNM_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
                    f0_target, syn.env_log, syn.plan)
 
@@ -1414,7 +1480,6 @@ def diff_gain_batch(stft_pred, stft_true, n_frames, P_dB_norm_factor, alpha=1.0,
     them.  n_frames: host integers, an int32 [B] device tensor or None (all F).  Returns the gain [B, F, bins] float32 on
     the device, 0 in the rows at or beyond n_frames.  Nothing is copied back and the host waits for nothing."""
     import torch
-    import _vc
     what = 'diff_gain_batch'
     alpha, boost, cut = _check_diff_args(alpha, max_boost_db, max_cut_db, what)
     h_taps = _check_diff_taps(half_width, taps, what)
@@ -1430,8 +1495,7 @@ def diff_gain_batch(stft_pred, stft_true, n_frames, P_dB_norm_factor, alpha=1.0,
         h = np.asarray(n_frames.cpu() if torch.is_tensor(n_frames) else n_frames)
         if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > F:
             raise ValueError(' - ERROR, {}: n_frames must be {} integers in [0, {}]'.format(what, B, F))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('diff_gain_batch needs a GPU (no CPU fallback)')
+    _need_gpu(what)
     as_dev = lambda t: (t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))).to(
         device='cuda', dtype=torch.float32).contiguous()
     d_nf = None if n_frames is None else _i32_device(n_frames, (B,), what + ': n_frames')
@@ -1471,92 +1535,66 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
     import torch
     import audio_lib
     import evaluation
-    import _vc
     what = 'convert_diff_batch'
-    if cfg_d is None:
-        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    _need_cfg(cfg_d, what)
     alpha, boost, cut = _check_diff_args(alpha, max_boost_db, max_cut_db, what)
     h_taps = _check_diff_taps(half_width, None, what)
-    source = isinstance(pitch, str)
-    if source and pitch != 'source':
-        raise ValueError(" - ERROR, {}: pitch must be None, a ratio, a [B, Fout] contour or 'source', got {!r}".format(what, pitch))
-    if (stats_src is None) != (stats_tgt is None) or (stats_src is not None and not source):
-        raise ValueError(" - ERROR, {}: stats_src and stats_tgt go together and with pitch='source'".format(what))
-    if source and stats_src is None:
+    if hasattr(pitch, 'item') and getattr(pitch, 'ndim', None) == 0:
+        pitch = pitch.item()                                        # a 0-d array or tensor counts as a number here
+    kind, pitch = _parse_pitch(pitch, stats_src, stats_tgt, what, True, ('source',),
+                               "None, a ratio, a [B, Fout] contour or 'source'", "pitch='source'")
+    if kind == 'source' and stats_src is None:
         raise ValueError(" - ERROR, {}: pitch='source' needs stats_src and stats_tgt (the source's own contour unmapped changes nothing)".format(what))
-    if source and (len(stats_src) != 3 or len(stats_tgt) != 3):
+    if kind == 'source' and (len(stats_src) != 3 or len(stats_tgt) != 3):
         raise ValueError(' - ERROR, {}: stats must be (count, mean, std) as f0_stats_batch returns them'.format(what))
-    scalar = pitch is not None and not source and getattr(pitch, 'ndim', 0) == 0
-    if scalar:
-        pitch = _check_pitch_ratio(pitch.item() if hasattr(pitch, 'item') else pitch, what + ': pitch')
     w_floor = _check_w_floor(w_floor, what)
-    kw = dict(frame_length=512, fmin=60.0, fmax=400.0, threshold=0.15, jump_cost=0.5, switch_cost=0.1, n_cand=8, ceiling=1.0)
-    extra = set(f0_args or {}) - set(kw)
-    if extra:
-        raise ValueError(' - ERROR, {}: f0_args takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
-    kw.update(f0_args or {})
+    f0_kw = _tracker_keys(f0_args, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type)
-    plan, B, hop, Fout, n_bins, sr = h.plan, h.B, h.hop, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
     n_use, h_nsamp = diff_frames(plan, hop)
     if int(h_nsamp.min()) <= h.n_fft // 2:
         raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples'.format(what))
     Lmax = int(audio_lib.resample_len(int(wav.shape[1]), wav_sr, sr)) if h.res_in else int(wav.shape[1])
-    if pitch is not None:
-        f0a = evaluation._f0_args(sr, hop, kw['frame_length'], kw['fmin'], kw['fmax'], kw['threshold'], what)
-        n_cand, ceiling = evaluation._track_args(kw['n_cand'], kw['ceiling'], what)
-        costs = evaluation._viterbi_costs(f0a[5], kw['jump_cost'], kw['switch_cost'], what)
+    if kind is not None:
+        tracker = _tracker_args(f0_kw, sr, hop, what)
         _check_pitch_sizes(B, Lmax, 1 + Lmax // hop, hop, what)
         if Lmax > evaluation.F0_MAX_SAMPLES:
             raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
-        if not source and not scalar and tuple(getattr(pitch, 'shape', ())) != (B, Fout):
-            raise ValueError(' - ERROR, {}: a pitch contour must be [{}, {}] (Hz per frame)'.format(what, B, Fout))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('convert_diff_batch needs a GPU (no CPU fallback)')
+        _check_contour(kind, pitch, B, Fout, what, 'frame')
+    _need_gpu(what)
 
     # ---- uploads: the waveforms if they are on the host, one table, the taps, a contour
     up = _convert_upload(h, wav, [n_use, h_nsamp, plan.n_src])
     d_nuse, d_nsamp, d_fsrc = up.d_extra[-3:]
     d_taps = torch.from_numpy(h_taps).pin_memory().to('cuda', non_blocking=True)
-    if pitch is not None and not source and not scalar:
-        if not torch.is_tensor(pitch):
-            pitch = torch.from_numpy(np.ascontiguousarray(pitch, dtype=np.float32)).pin_memory()
-        pitch = pitch.to(device='cuda', non_blocking=True)
-    if pitch is not None:
+    pitch = _contour_upload(kind, pitch)
+    if kind is not None:
         psola_window('cuda')
-    if h.res_in:                                                    # once, here: the filter and the tracker need the model's rate too
-        w16 = audio_lib._resample_launch(audio_lib._get_res_plan(wav_sr, sr, res_type), up.wav, up.d_extra[0])
-        h, up = h._replace(res_in=False), up._replace(wav=w16)
+    h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)       # here: the filter and the tracker need the model's rate too
 
     # ---- convert_batch(vocode=False): front-end, windows, model, the three stitches
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
-    mel_pred = compound_stitch(y_mel, up.d_utt, Fout)
-    phn_pred = compound_stitch(y_phn, up.d_utt, Fout)
-    stft_pred = compound_stitch(y_stft, up.d_utt, Fout)
+    mel_pred, phn_pred, stft_pred, _ = _stitch(y_mel, y_phn, y_stft, up.d_utt, Fout)
 
     # ---- the source's fundamental, moved before the filter
     x, f0_src = up.wav, None
-    if pitch is not None:
-        f0_src = evaluation._f0_track_launch(x, up.d_lens, d_fsrc, f0a, n_cand, ceiling, costs)[0]
+    if kind is not None:
+        f0_src = evaluation._f0_track_launch(x, up.d_lens, d_fsrc, *tracker)[0]
         target = None
-        if source:
+        if kind == 'source':
             target = f0_transform(f0_src, stats_src, stats_tgt)
-        elif not scalar:
+        elif kind == 'contour':
             n = min(Fout, f0_src.shape[1])                          # t_s == 0: frame u of the contour is frame u of the source
             target = torch.zeros_like(f0_src)
             target[:, :n] = pitch[:, :n].to(torch.float32)
-        per, rat = pitch_tables(f0_src, sr, ratio=pitch if scalar else None, target_f0=target, hop_length=hop)
+        per, rat = pitch_tables(f0_src, sr, ratio=pitch if kind == 'ratio' else None, target_f0=target, hop_length=hop)
         x = _psola_ola_launch(x, up.d_lens, _psola_plan_launch(per, rat, up.d_lens, x.shape[1], hop), w_floor)
 
     # ---- gain, filter, level
     gain = _diff_gain_launch(stft_pred, stft_true, d_nuse, float(cfg_d['P_dB_norm_factor']), alpha, boost, cut, d_taps)
     vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
-    y = audio_lib._stft_filter_launch(vplan, x, up.d_lens, gain, d_nuse)
-    _vc.check(_vc.lib().vc_inv_preemphasis_normalize(vplan.handle, _vc.ptr(y), _vc.ptr(d_nuse), B, Fout, y.shape[1], 0.0,
-                                                     float(15 * cfg_d['mean_abs_amp_norm']), _vc.current_stream()))
-    n_samples = [int(v) for v in h_nsamp]
-    if h.res_out:
-        y = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y, d_nsamp)
-        n_samples = [int(v) for v in audio_lib.resample_len(h_nsamp, sr, out_sr)]
+    y = _deemphasis_level(vplan, audio_lib._stft_filter_launch(vplan, x, up.d_lens, gain, d_nuse), d_nuse, Fout, cfg_d, 0.0)
+    y, n_samples = _resample_output(y, h_nsamp, d_nsamp, h.res_out, cfg_d, out_sr, res_type)
     return _DIFF_NT(y, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, gain, [int(v) for v in n_use], f0_src)
 
 
@@ -1653,7 +1691,6 @@ def _wsola_inputs(what, wav, lens, pos, n_out, hop_length, group, tol, qscale):
     """The checks and uploads that wsola_plan_batch and time_scale_batch share: (wav, d_lens, pos, d_nout, hop, group, tol,
     qscale) on the device; every ValueError before anything is uploaded."""
     import torch
-    import _vc
     if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
         raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
     if torch.is_tensor(wav) and wav.dtype != torch.float32:
@@ -1669,8 +1706,7 @@ def _wsola_inputs(what, wav, lens, pos, n_out, hop_length, group, tol, qscale):
         lens = np.full((B,), Lmax, dtype=np.int64)
     _check_count(lens, B, Lmax, what + ': lens')
     _check_count(n_out, B, Fw, what + ': n_out')
-    if not torch.cuda.is_available():
-        raise _vc.VCError('{} needs a GPU (no CPU fallback)'.format(what))
+    _need_gpu(what)
     d_pos = _i32_device(pos, (B, Fw), what + ': pos')
     if not torch.is_tensor(wav):
         wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
@@ -1731,115 +1767,34 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
     output's; n_samples at out_sr when resampled), plus flags [B], seg = (labels, start, end, n_seg) in output frames, map
     (the duration_map_batch result), plan (the wsola_plan_batch result) and the host bounds max_frames, max_samples and
     src_frames (n_use).  After the uploads nothing is copied to the host and the host waits for nothing."""
-    import torch
-    import audio_lib
-    import _vc
     what = 'convert_diff_duration_batch'
-    if cfg_d is None:
-        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
-    if sum(v is not None for v in (rate, ratio, out_len)) != 1:
-        raise ValueError(' - ERROR, {}: pass exactly one of rate, ratio and out_len'.format(what))
-    if rate is not None:
-        if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)) or not 0.0 < float(rate) <= WARP_MAX_RATIO:
-            raise ValueError(' - ERROR, {}: rate must be a number in (0, {}], got {!r}'.format(what, WARP_MAX_RATIO, rate))
-        rate_q = int(ratio_to_q(float(rate)))
-    gap_q = _check_ratio_scalar(gap_ratio, what + ': gap_ratio')
-    table = None
-    if rate is None and not (isinstance(segments, str) and segments == 'decode'):
-        if isinstance(segments, str) or len(segments) != 4:
-            raise ValueError(" - ERROR, {}: segments must be 'decode' or (labels, start, end, n_seg)".format(what))
-        table = segments
-    if decode is not None and (rate is not None or table is not None):
-        raise ValueError(" - ERROR, {}: decode is for segments='decode'".format(what))
-    kw = dict(trans=None, penalty=0.0, init=None, final=None, min_dur=3, class_map=None, floor=1e-10)
-    extra = set(decode or {}) - set(kw)
-    if extra:
-        raise ValueError(' - ERROR, {}: decode takes {}, got {}'.format(what, sorted(kw), sorted(extra)))
-    kw.update(decode or {})
+    _need_cfg(cfg_d, what)
+    req = _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len)
     h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type)
-    plan, B, hop, Fout = h.plan, h.B, h.hop, h.plan.Fout
-    min_frames = 2
-    n_use, h_nsamp = diff_frames(plan, hop)
-    if Fout > WARP_MAX_FRAMES:
-        raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, WARP_MAX_FRAMES, Fout))
-    K = 1 if rate is not None else (Fout if table is None else int(table[1].shape[1]))
-    if rate is not None:
-        want = (n_use * rate_q + 32768) >> 16
-        if want.min() < min_frames:
-            raise ValueError(' - ERROR, {}: rate {} leaves an utterance {} frames; at least {} are needed'.format(what, rate, int(want.min()), min_frames))
-        bound = int(want.max())
-    elif ratio is not None and not torch.is_tensor(ratio):
-        r = np.atleast_1d(np.asarray(ratio, dtype=np.float32))
-        if r.ndim != 1 or not np.isfinite(r).all() or r.min() < 0 or r.max() > WARP_MAX_RATIO:
-            raise ValueError(' - ERROR, {}: ratio must be finite floats [C] in [0, {}]'.format(what, WARP_MAX_RATIO))
-        ratio = r
-        bound = duration_max_frames(Fout, 2 * K + 1, max(gap_q, int(ratio_to_q(r).max())))
-    else:
-        if ratio is not None and (ratio.ndim != 1 or not ratio.is_floating_point()):
-            raise ValueError(' - ERROR, {}: ratio must be floats [C]'.format(what))
-        bound = None
-    if max_frames is None:
-        if bound is None:
-            raise ValueError(' - ERROR, {}: max_frames is required with out_len and with a ratio on the device'.format(what))
-        max_frames = min(bound, WARP_MAX_FRAMES)
-    if isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or not min_frames <= max_frames <= WARP_MAX_FRAMES:
-        raise ValueError(' - ERROR, {}: max_frames must be an integer in [{}, {}]'.format(what, min_frames, WARP_MAX_FRAMES))
-    Fw = int(max_frames)
+    B, hop, Fout = h.B, h.hop, h.plan.Fout
+    n_use, h_nsamp = diff_frames(h.plan, hop)
+    req = _duration_bound(what, req, n_use, Fout, 2, max_frames, 'at least {} are needed')
+    Fw = req.Fw
     hop, group, tol, qscale = _check_wsola_args(B, hop * (Fout - 1), Fw, hop, group, tol, qscale, what)
-    dec = cmap = None
-    if rate is None and table is None:                              # the decoder's arguments, before anything is launched
-        import evaluation
-        C = int((encoder if encoder is not None else decoder.encoder).cfg_d['n_output'])
-        evaluation._check_decode_size(B, Fout, C, what)
-        cmap = evaluation._check_class_map(kw.pop('class_map'), C, what)
-        dec = evaluation._decode_args(C=C, what=what, kind='prob', **kw)
+    req = _duration_decoder(what, req, decoder, encoder, B, Fout)
 
     # ---- convert_diff_batch's launches at the model's rate (its own checks run before its first launch), then two tables
     d = convert_diff_batch(decoder, wav, lens=lens, cfg_d=cfg_d, alpha=alpha, max_boost_db=max_boost_db, max_cut_db=max_cut_db,
                            half_width=half_width, pitch=pitch, stats_src=stats_src, stats_tgt=stats_tgt, w_floor=w_floor,
                            f0_args=f0_args, t_e=t_e, two_pass=two_pass, utt_ids=utt_ids, window_batch=window_batch, encoder=encoder,
                            wav_sr=wav_sr, out_sr=None, res_type=res_type)
-    dev = d.y_wav_pred.device
     d_nuse = _i32_device(n_use, (B,), what + ': n_use')
     d_nsamp = _i32_device(h_nsamp, (B,), what + ': n_samples')
-    wsola_window(group * hop, dev)
-
-    # ---- the segment table in source frames, the map (as convert_duration_batch builds it)
-    d_lab = d_len = d_ratio = None
-    if rate is not None:
-        d_start = torch.zeros((B, 1), dtype=torch.int32, device=dev)
-        d_end, d_nseg = d_nuse.view(B, 1), torch.ones((B,), dtype=torch.int32, device=dev)
-        d_ratio = torch.full((1,), rate_q, dtype=torch.int32, device=dev)
-    else:
-        if table is None:
-            r = evaluation._decode_launch(d.phn_pred, d_nuse, evaluation._cmap_device(cmap), evaluation._decode_upload(dec))
-            d_lab, d_start, d_end, d_nseg = r.seg.labels, r.seg.start, r.seg.end, r.seg.n_seg
-        else:
-            d_lab, d_start, d_end = (_i32_device(t, (B, K), what + ': segments') for t in table[:3])
-            d_nseg = _i32_device(table[3], (B,), what + ': segments n_seg')
-        if out_len is not None:
-            d_len = _i32_device(out_len, (B, K), what + ': out_len')
-        elif torch.is_tensor(ratio):
-            d_ratio = ratio_to_q(ratio.to('cuda', non_blocking=True)).contiguous()
-        else:
-            d_ratio = _i32_device(ratio_to_q(ratio), ratio.shape, what + ': ratio')
-    m = _map_launch(d_start, d_end, d_nseg, None if d_ratio is None or rate is not None else d_lab, d_len, d_ratio, gap_q, d_nuse,
-                    Fout, min_frames, Fw)
+    wsola_window(group * hop, d.y_wav_pred.device)
+    m, seg = _duration_map(what, req, d_nuse, d.phn_pred, Fout)   # the segment table in source frames, the map
 
     # ---- the filtered waveform along the map, the output resampler
     x = d.y_wav_pred.contiguous()
     wplan = _wsola_plan_launch(x, d_nsamp, m.pos, m.n_out, hop, group, tol, qscale)
-    y = _wsola_ola_launch(x, d_nsamp, wplan)
-    n_samples = wplan.out_len
-    max_samples = hop * (Fw - 1)
-    if h.res_out:
-        sr = cfg_d['sample_rate']
-        rplan = audio_lib._get_res_plan(sr, out_sr, res_type)
-        y = audio_lib._resample_launch(rplan, y, n_samples)
-        n_samples = torch.div(n_samples.long() * rplan.up + (rplan.down - 1), rplan.down, rounding_mode='floor').to(torch.int32)
-        max_samples = int(audio_lib.resample_len(max_samples, sr, out_sr))
+    y, n_samples, max_samples = _resample_output_device(_wsola_ola_launch(x, d_nsamp, wplan), wplan.out_len, hop * (Fw - 1), h.res_out,
+                                                        cfg_d, out_sr, res_type)
     return _DIFF_DUR_NT(y, n_samples, d.mel_true, d.mel_pred, d.stft_true, d.stft_pred, d.phn_pred, d.gain, m.n_out, d.f0_src, m.flags,
-                        _DUR_SEG_NT(d_lab, m.out_start, m.out_end, d_nseg), m, wplan, Fw, max_samples, [int(v) for v in n_use])
+                        seg, m, wplan, Fw, max_samples, [int(v) for v in n_use])
 
 
 # --------------------------------------------------------------------------- postfilter (csrc/vc_postfilter.hip)
@@ -1862,45 +1817,34 @@ def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mo
     one.  With k = 0 and alpha = 0 the filters return their input bit for bit and so does the call: y_wav_pred equals
     convert_batch's.  Nothing is copied to the host and the host waits for nothing.  Nobody has listened to the result
     (DESIGN.md section 28)."""
-    import torch
     import audio_lib
     import postfilter
-    import _vc
     what = 'convert_postfilter_batch'
     momentum = _check_momentum(momentum)
     seed = audio_lib.check_seed(seed)
-    if cfg_d is None:
-        raise ValueError(' - ERROR, {}: cfg_d (the data-set configuration) is required'.format(what))
+    _need_cfg(cfg_d, what)
     if model is None:
         raise ValueError(' - ERROR, {}: model (postfilter.fit or postfilter.upload) is required'.format(what))
-    if isinstance(phase, str) and phase not in ('device', 'spsi'):
-        raise ValueError(" - ERROR, {}: phase must be 'device', 'spsi' or a [B, Fout, bins] array, got {!r}".format(what, phase))
+    _check_phase(phase, what)
     postfilter.check_apply_args(mode, k, alpha, max_db, g_max, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
                       res_type)
-    plan, B, Fout, n_bins, sr = h.plan, h.B, h.plan.Fout, h.n_bins, cfg_d['sample_rate']
+    plan, Fout, n_bins = h.plan, h.plan.Fout, h.n_bins
     if Fout > postfilter.MAX_FRAMES:
         raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, postfilter.MAX_FRAMES, Fout))
-    if not isinstance(phase, str) and tuple(phase.shape) != (B, Fout, n_bins):
-        raise ValueError(' - ERROR, {}: phase must be [{}, {}, {}]'.format(what, B, Fout, n_bins))
-    if not torch.cuda.is_available():
-        raise _vc.VCError('convert_postfilter_batch needs a GPU (no CPU fallback)')
+    _check_phase(phase, what, (h.B, Fout, n_bins))
+    _need_gpu(what)
     tables = model if isinstance(model, postfilter.Tables) else postfilter.upload(model, k)
     if tables.gv_t.shape[0] != n_bins:
         raise ValueError(' - ERROR, {}: the model has {} channels, the spectrum {}'.format(what, tables.gv_t.shape[0], n_bins))
 
     up = _convert_upload(h, wav, [h.h_nsamp] if h.res_out else [])
-    if not isinstance(phase, str):
-        if not torch.is_tensor(phase):
-            phase = torch.from_numpy(np.ascontiguousarray(phase, dtype=np.float32))
-        phase = phase.to(device='cuda', dtype=torch.float32).contiguous()
+    phase = _phase_upload(phase)
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
-    mel_pred, phn_pred, stft_raw = (compound_stitch(y, up.d_utt, Fout) for y in (y_mel, y_phn, y_stft))
+    mel_pred, phn_pred, stft_raw, _ = _stitch(y_mel, y_phn, y_stft, up.d_utt, Fout)
     stft_pred = postfilter.apply_batch(stft_raw, up.d_nout, tables, mode=mode, k=k, alpha=alpha, max_db=max_db, g_max=g_max)
     _, y_wav_pred = _vocoder_tail(cfg_d, up.d_nout, up.d_ids, n_iter, momentum, realse, seed, phase, phase, None, stft_pred, None)
-    n_samples = [int(v) for v in h.h_nsamp]
-    if h.res_out:
-        y_wav_pred = audio_lib._resample_launch(audio_lib._get_res_plan(sr, out_sr, res_type), y_wav_pred, up.d_extra[-1])
-        n_samples = [int(v) for v in audio_lib.resample_len(h.h_nsamp, sr, out_sr)]
+    y_wav_pred, n_samples = _resample_output(y_wav_pred, h.h_nsamp, up.d_extra[-1] if h.res_out else None, h.res_out, cfg_d, out_sr,
+                                             res_type)
     return _POST_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
                     stft_raw)
