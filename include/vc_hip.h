@@ -1832,6 +1832,79 @@ int vc_hnm_synth_f32(const float* d_env_log, const float* d_theta, const uint8_t
                      int32_t batch, int32_t max_frames, int32_t n_fft, int32_t hop, int64_t cutoff_inc, float scale, float* d_y,
                      void* stream);
 
+/* Noise suppression.  Every conversion route assumes a clean recording; these two launches, with vc_stft_filter_f32 behind
+ * them, take stationary noise out of a waveform first: linear short-time power, then a noise tracker and a suppression
+ * gain in one scan over time, then the filter.  Added without a version bump.  tests/denoise_ref.py restates both in float64
+ * and, in the operation order below, in float32.
+ *
+ * Power.  P[b, f, k] = |stft(x_b)[f, k]|^2 with exactly the framing of vc_stft_filter_f32 above: the plan's padded window,
+ * reflect padding by N / 2 about sample 0 and about sample len - 1 (len = d_len[b] clamped to [0, wav_stride]),
+ * F_b = min(n_frames[b], max_frames, 1 + len / hop) (d_n_frames NULL: without the first; a negative count counts as 0), and
+ * the "short" rule: len <= N / 2 or hop * (F_b - 1) <= N / 2 gives F_b = 0.  d_power [batch, max_frames, 1 + N / 2] float32:
+ * every element is written once, rows at or beyond F_b as 0.  d_frames_out [batch] int32 receives F_b, so the launches
+ * behind this one read it on the device and the host never learns it.  One launch, no workspace: 16 frames per workgroup
+ * and the 25 x 16 transform at n_fft == 400, 4 frames and the direct transform otherwise (the forward halves of the filter
+ * kernels).  VC_ERR_INVALID before the launch for a NULL pointer (d_n_frames excepted), batch outside [1, 65535],
+ * max_frames < 1 or wav_stride < 1.
+ *
+ * Gain.  d_power [batch, max_frames, n_bins]; F = d_n_frames[b] clamped to [0, max_frames] (NULL: max_frames); d_noise0
+ * [batch, n_bins] or NULL: the noise power to start from.  The tracker is Gerkmann & Hendriks (2012): the speech-presence
+ * probability under a FIXED prior SNR xi_h1 weighs the periodogram against the running estimate; it is continuous in its
+ * input apart from the 0.99 guard.  The rule is Wiener (rule 0) or Ephraim & Malah's log-MMSE (rule 1) on the
+ * decision-directed a-priori SNR with Cappe's lower limit xi_min.  float32 throughout, no fused multiply-add, IEEE
+ * division; every product and every sum is rounded once.  Per (b, k), y = P[b, f, k]:
+ *     k1 = 1 + xi_h1;  c1 = xi_h1 / k1;  q_spp = 1 - a_spp;  q_n = 1 - a_noise;  q_dd = 1 - a_dd
+ *     n0 = min(n_init, F)
+ *     s  = noise0[b, k] if given, else (sum_{f < n0} P[f, k], ascending from +0) / float(n0);   s = max(s, FLT_MIN)
+ *     pb = 0.5
+ *     for f in 0 .. F - 1:
+ *         t  = min((y / s) * c1, 80)
+ *         p  = 1 / (1 + k1 * exp(-t))
+ *         pb = a_spp * pb + q_spp * p
+ *         if pb > 0.99f: p = min(p, 0.99f)
+ *         e  = (1 - p) * y + p * s
+ *         s  = max(a_noise * s + q_n * e, FLT_MIN)
+ *         g  = min(y / s, gamma_max)
+ *         r  = 1 if f == 0 else min(A / s, gamma_max)
+ *         xi = max(a_dd * r + q_dd * max(g - 1, 0), xi_min)
+ *         w  = xi / (1 + xi)
+ *         G  = w                                             rule 0
+ *         G  = w * exp(0.5 * E1(max(w * g, 1e-6f)))          rule 1
+ *         G  = min(max(G, gain_min), 1);   A = (G * G) * y
+ *         gain[f, k] = G;  noise[f, k] = s
+ * E1 in Horner form, Abramowitz & Stegun: on x <= 1 (5.1.53)  (((((a5 x + a4) x + a3) x + a2) x + a1) x + a0) - ln x  with
+ * a0 .. a5 = -0.57721566, 0.99999193, -0.24991055, 0.05519968, -0.00976004, 0.00107857; on x > 1 (5.1.56)
+ * (exp(-x) / x) * (n / d), n = (((x + 8.5733287401) x + 18.0590169730) x + 8.6347608925) x + 0.2677737343,
+ * d = (((x + 9.5733223454) x + 25.6329561486) x + 21.0996530827) x + 3.9584969228.
+ * Hence: a_noise == 1 freezes s bit for bit; scaling P and noise0 by 2^m scales noise by exactly 2^m and leaves gain
+ * bit-identical (away from FLT_MIN and overflow); rule 0 with a_dd == 0, a_noise == 1 and noise0 given involves no
+ * transcendental and is reproducible bit for bit.
+ * d_gain and (optional) d_noise [batch, max_frames, n_bins]: every element written exactly once, rows at or beyond F as 0.
+ * One launch, grid (64-bin groups, batch), one lane per (utterance, bin) walking time with the next frames of P prefetched
+ * into registers: latency-bound by design.  VC_ERR_INVALID before the launch for NULL d_power, d_gain or cfg, batch outside
+ * [1, 65535], max_frames < 1, n_bins outside [2, 2049], rule not 0 or 1, n_init < 1, a_spp or a_dd outside [0, 1], a_noise
+ * outside (0, 1], a non-finite or non-positive xi_h1, xi_min or gamma_max, gain_min outside (0, 1].
+ *
+ * Neither call allocates, sets memory, uses atomics or synchronises; both are capturable from the first call, functions of
+ * their own utterance alone and bit-identical alone, in any batch and under graph replay. */
+typedef struct vc_denoise_cfg {
+    int32_t rule;       /* 0: Wiener, 1: log-MMSE */
+    int32_t n_init;     /* frames averaged for the first noise estimate when d_noise0 is NULL */
+    float a_spp;        /* smoothing of the speech-presence probability */
+    float a_noise;      /* smoothing of the noise power */
+    float a_dd;         /* decision-directed weight */
+    float xi_h1;        /* the tracker's fixed prior SNR (linear) */
+    float xi_min;       /* lower limit of the a-priori SNR (linear) */
+    float gain_min;     /* gain floor (amplitude) */
+    float gamma_max;    /* upper limit of the a-posteriori SNR */
+} vc_denoise_cfg;
+int vc_stft_power_f32(const vc_vocoder_plan* plan, const float* d_wav, int32_t wav_stride, const int32_t* d_len,
+                      const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_power, int32_t* d_frames_out,
+                      void* stream);
+int vc_noise_gain_f32(const float* d_power, const int32_t* d_n_frames, const float* d_noise0, int32_t batch,
+                      int32_t max_frames, int32_t n_bins, const vc_denoise_cfg* cfg, float* d_gain, float* d_noise,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,12 @@ class FrontendCfg(C.Structure):
                 ('clip_output', C.c_int32)]
 
 
+class DenoiseCfg(C.Structure):
+    """struct vc_denoise_cfg (include/vc_hip.h, "Noise suppression")."""
+    _fields_ = [('rule', C.c_int32), ('n_init', C.c_int32), ('a_spp', C.c_float), ('a_noise', C.c_float), ('a_dd', C.c_float),
+                ('xi_h1', C.c_float), ('xi_min', C.c_float), ('gain_min', C.c_float), ('gamma_max', C.c_float)]
+
+
 VC_F32, VC_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 GEMM_PLAIN, GEMM_HIGHWAY = 0, 1
@@ -323,6 +329,9 @@ _SIGS = {
     'vc_noise_init_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, _P, _P]),
     'vc_hnm_noise_gain_f32': (C.c_int, [_P, _P, _P] + [C.c_int32] * 4 + [C.c_float, _P, _P]),
     'vc_hnm_synth_f32': (C.c_int, [_P] * 8 + [C.c_int32] * 4 + [C.c_int64, C.c_float, _P, _P]),
+    # noise suppression (csrc/vc_vocoder.hip, csrc/vc_denoise.hip)
+    'vc_stft_power_f32': (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    'vc_noise_gain_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -358,7 +367,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then the
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then vc_stft_power_f32 / vc_noise_gain_f32, then the
                 # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '

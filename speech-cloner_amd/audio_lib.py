@@ -527,6 +527,79 @@ def stft_filter_batch(wav, lens, gain, n_frames=None, win_length=400, hop_length
     return _stft_filter_launch(plan, as_dev(wav), d_len, as_dev(gain), d_nf)
 
 
+def _stft_power_launch(plan, wav, d_len, d_nf, Fmax):
+    """vc_stft_power_f32 on validated device tensors (wav [B, Lmax] float32 contiguous, d_len int32 [B], d_nf int32 [B] or
+    None): (power [B, Fmax, bins], the frame counts the device used, int32 [B]); no host check, copy or wait in here."""
+    import torch
+    B = wav.shape[0]
+    power = torch.empty((B, Fmax, plan.n_bins), dtype=torch.float32, device=wav.device)
+    d_fout = torch.empty((B,), dtype=torch.int32, device=wav.device)
+    _vc.check(_vc.lib().vc_stft_power_f32(plan.handle, _vc.ptr(wav), wav.shape[1], _vc.ptr(d_len), _vc.ptr(d_nf), B, Fmax,
+                                          _vc.ptr(power), _vc.ptr(d_fout), _vc.current_stream()))
+    return power, d_fout
+
+
+def _check_stft_wave_args(what, wav, lens, n_frames, win_length, hop_length, n_fft):
+    """The host checks stft_power_batch and enhance.denoise_batch share, in stft_filter_batch's style: (B, Lmax, Fmax, plan key).
+    Fmax = 1 + Lmax // hop_length; ValueError before the GPU is touched."""
+    import torch
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    for v, name in ((win_length, 'win_length'), (hop_length, 'hop_length')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(' - ERROR, {}: {} must be a positive integer, got {!r}'.format(what, name, v))
+    if n_fft is not None and (isinstance(n_fft, bool) or not isinstance(n_fft, (int, np.integer)) or n_fft < win_length):
+        raise ValueError(' - ERROR, {}: n_fft must be None or an integer >= win_length, got {!r}'.format(what, n_fft))
+    plan_key = (int(win_length), int(hop_length), int(n_fft or win_length))
+    if plan_key[2] % 2 or plan_key[2] > 4096 or plan_key[1] > plan_key[2]:
+        raise ValueError(' - ERROR, {}: need n_fft even, n_fft <= 4096 and hop_length <= n_fft (got {}, {})'.format(
+            what, plan_key[2], plan_key[1]))
+    if B > 65535:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances'.format(what))
+    Fmax = 1 + Lmax // plan_key[1]
+    for v, hi, name in ((lens, Lmax, 'lens'), (n_frames, Fmax, 'n_frames')):
+        if v is None or (torch.is_tensor(v) and v.is_cuda):
+            if v is not None and (v.dtype != torch.int32 or tuple(v.shape) != (B,)):
+                raise ValueError(' - ERROR, {}: {} on the device must be int32 [{}]'.format(what, name, B))
+            continue
+        h = np.asarray(v.cpu() if torch.is_tensor(v) else v)
+        if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > hi:
+            raise ValueError(' - ERROR, {}: {} must be {} integers in [0, {}]'.format(what, name, B, hi))
+    return B, Lmax, Fmax, plan_key
+
+
+def _stft_wave_upload(wav, lens, n_frames, B, Lmax):
+    """(wav float32 contiguous, d_len int32 [B], d_nf int32 [B] or None) on the device, after _check_stft_wave_args."""
+    import torch
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
+    d_len = _int32_device(np.full((B,), Lmax, np.int64) if lens is None else lens, B, 'lens')
+    d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
+    return wav, d_len, d_nf
+
+
+def stft_power_batch(wav, lens, n_frames=None, win_length=400, hop_length=80, n_fft=None):
+    """P = |stft(wav)|^2, linear and unnormalised, for a ragged batch (vc_stft_power_f32, include/vc_hip.h, "Noise
+    suppression"): exactly the frames stft_filter_batch transforms -- the same window, reflect padding and frame counts.
+
+    wav [B, Lmax] float32 (numpy or tensor); lens: the sample counts, host integers or an int32 [B] device tensor (None =
+    all Lmax); n_frames: the frames to use per utterance, host integers or an int32 [B] device tensor (None = 1 + len //
+    hop_length); in every case at most 1 + len // hop_length are used.
+    Returns (power [B, 1 + Lmax // hop_length, 1 + n_fft//2] float32, n_frames_device int32 [B]), both on the device: rows
+    at or beyond an utterance's frame count are 0, and an utterance shorter than the reflect padding (len <= n_fft//2, or
+    hop_length * (frames - 1) <= n_fft//2) has the count 0.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    what = 'stft_power_batch'
+    B, Lmax, Fmax, plan_key = _check_stft_wave_args(what, wav, lens, n_frames, win_length, hop_length, n_fft)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('stft_power_batch needs a GPU (no CPU fallback)')
+    plan = _get_voc_plan(*plan_key)
+    wav, d_len, d_nf = _stft_wave_upload(wav, lens, n_frames, B, Lmax)
+    return _stft_power_launch(plan, wav, d_len, d_nf, Fmax)
+
+
 # --------------------------------------------------------------------------- harmonic-plus-noise vocoder
 HnmPlan = collections.namedtuple('HnmPlan', 'voiced inc slope phase flags')
 HnmSynth = collections.namedtuple('HnmSynth', 'y env_log theta plan gain')

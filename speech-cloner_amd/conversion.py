@@ -262,7 +262,7 @@ def _numpy_phase(plan, n_bins, both):
     return ph
 
 
-_HOST_NT = namedtuple('convert_host', 'plan B hop n_fft n_bins h_lens h_lens_in h_nsamp utt_ids res_in res_out window_batch')
+_HOST_NT = namedtuple('convert_host', 'plan B hop n_fft n_bins h_lens h_lens_in h_nsamp utt_ids res_in res_out window_batch denoise')
 _UP_NT = namedtuple('convert_upload', 'wav d_lens d_clip d_nout d_ids d_win d_utt d_true d_extra')
 
 
@@ -300,9 +300,31 @@ def _phase_upload(phase):
     return phase.to(device='cuda', dtype=torch.float32).contiguous()
 
 
+def _check_denoise(what, denoise, cfg_d, B):
+    """denoise= of a conversion, on the host: None for None / False, else (vc_denoise_cfg, noise0 or None).  True means
+    enhance.denoise_batch's defaults; a dict holds its noise-suppression keywords (enhance.GAIN_KEYS without return_noise:
+    the conversion returns no noise track)."""
+    if denoise is None or denoise is False:
+        return None
+    import enhance
+    if denoise is True:
+        denoise = {}
+    if not isinstance(denoise, dict):
+        raise ValueError(' - ERROR, {}: denoise must be None, True or a dict of enhance.denoise_batch keywords, got {!r}'.format(
+            what, denoise))
+    if 'return_noise' in denoise:
+        raise ValueError(' - ERROR, {}: denoise: return_noise is not offered here (call enhance.denoise_batch)'.format(what))
+    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
+    cfg, noise0, _ = enhance.check_gain_keywords(what + ': denoise', denoise, int(cfg_d['hop_length']), cfg_d['sample_rate'])
+    enhance._check_noise0(what + ': denoise', noise0, B, 1 + n_fft // 2)
+    return cfg, noise0
+
+
 def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
-                  res_type):
-    """The host checks and tables that convert_batch and convert_duration_batch share, before anything touches the GPU."""
+                  res_type, denoise=None):
+    """The host checks and tables that convert_batch and convert_duration_batch share, before anything touches the GPU.
+    denoise: the entry point's own argument (_check_denoise); when it is on, every length is cut to whole hops first --
+    len' = hop * (len // hop), what the noise filter returns -- so under one hop is dropped and no frame count changes."""
     import audio_lib
     if getattr(wav, 'ndim', 0) != 2:
         raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
@@ -325,6 +347,12 @@ def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, 
                              '(shortest: {} after resampling from {} Hz)'.format(what, n_fft // 2, sr, int(h_lens.min()), wav_sr))
     if h_lens.shape != (B,) or h_lens.min() <= n_fft // 2 or h_lens.max() > Lmax:
         raise ValueError(' - ERROR, {}: lens must be [B] with n_fft//2 < len <= Lmax'.format(what))
+    denoise = _check_denoise(what, denoise, cfg_d, B)
+    if denoise is not None:
+        h_lens = int(cfg_d['hop_length']) * (h_lens // int(cfg_d['hop_length']))
+        if h_lens.min() <= n_fft // 2:
+            raise ValueError(' - ERROR, {}: denoise: every utterance needs more than n_fft//2 = {} samples after the cut to '
+                             'whole hops (shortest: {})'.format(what, n_fft // 2, int(h_lens.min())))
     if utt_ids is None:
         utt_ids = np.arange(B)
     utt_ids = np.asarray(utt_ids, dtype=np.int64).reshape(-1)
@@ -340,7 +368,7 @@ def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, 
     if vocode and hop * (int(plan.n_out.min()) - 1) <= n_fft // 2:
         raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples'.format(what))
     return _HOST_NT(plan, B, hop, n_fft, 1 + n_fft // 2, h_lens, h_lens_in, hop * (plan.n_out.astype(np.int64) - 1), utt_ids,
-                    res_in, res_out, window_batch)
+                    res_in, res_out, window_batch, denoise)
 
 
 def _convert_upload(h, wav, extra):
@@ -374,12 +402,30 @@ def _resample_input(h, up, cfg_d, wav_sr, res_type):
     return h._replace(res_in=False), up._replace(wav=wav)
 
 
+def _denoise_input(h, up, cfg_d, denoise):
+    """The input with its stationary noise suppressed, once: (h, up) with the waveform replaced by enhance.denoise_batch's
+    output and h.denoise cleared.  denoise: h.denoise, the checked request of _convert_host (None: nothing is launched).
+    Runs right after _resample_input, at the model's rate; an entry point that reads up.wav itself (a tracker, the
+    differential filter) calls this before _convert_model, which then finds nothing left to do.  The lengths were cut to
+    whole hops on the host, so the filter's hop * (F - 1) samples are every utterance's whole length."""
+    import audio_lib
+    import enhance
+    if denoise is None:
+        return h, up
+    cfg, noise0 = denoise
+    plan = audio_lib._get_voc_plan(cfg_d['win_length'], h.hop, cfg_d['n_fft'])
+    r = enhance._denoise_launch(plan, up.wav, up.d_lens, None, 1 + up.wav.shape[1] // h.hop, cfg,
+                                None if noise0 is None else enhance._as_cuda_f32(noise0), False)
+    return h._replace(denoise=None), up._replace(wav=r.y)
+
+
 def _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type):
-    """Input resampling, front-end, windows and the model over window chunks: (mel_true, stft_true [B, Fout, C] and the
-    window batches y_mel, y_stft, y_phn [W, T, C] that compound_stitch takes)."""
+    """Input resampling, noise suppression (h.denoise), front-end, windows and the model over window chunks: (mel_true,
+    stft_true [B, Fout, C] and the window batches y_mel, y_stft, y_phn [W, T, C] that compound_stitch takes)."""
     import torch
     import audio_lib
     h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)
+    h, up = _denoise_input(h, up, cfg_d, h.denoise)
     plan, hop = h.plan, h.hop
     mfcc, mel, pdb = audio_lib.calc_MFCC_input_batch(
         up.wav, up.d_lens, sr=cfg_d['sample_rate'], pre_emphasis=cfg_d['pre_emphasis'], hop_length=hop,
@@ -475,7 +521,7 @@ def _resample_output(y, h_nsamp, d_nsamp, res_out, cfg_d, out_sr, res_type):
 
 def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True,
                   giffin_lim_input=False, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64,
-                  vocode=True, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+                  vocode=True, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
     """``conversion2`` (two_pass) / ``conversion`` for a ragged batch, waveforms in, waveforms out, on the device.
 
     wav [B, Lmax] float32 (numpy or cuda tensor), lens: host ints (None = all Lmax).  cfg_d: the data-set
@@ -491,6 +537,10 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     wav_sr: the sample rate of ``wav`` (None = cfg_d['sample_rate']); another rate is resampled on the device first
     (audio_lib.resample_batch, ``res_type``), and ``lens`` then count samples at wav_sr.  out_sr: the rate of the returned
     waveforms (None = cfg_d['sample_rate']); n_samples is then reported at out_sr.
+    denoise: None / False (today's launches and nothing else), True (enhance.denoise_batch at its defaults) or a dict of its
+    noise-suppression keywords: stationary noise is taken out of the input at the model's rate, right after the input
+    resampler, before anything reads the waveform.  Every utterance is first cut to whole hops (under one hop is dropped, no
+    frame count changes); mel_true / stft_true are then those of the DENOISED input.
     Returns a namedtuple of cuda tensors -- y_wav_pred, y_wav_true (None unless giffin_lim_input) [B, hop*(Fout-1)],
     mel_pred / stft_pred / phn_pred and mel_true / stft_true [B, Fout, C], zero beyond an utterance's own extent --
     and the host counts n_frames [B] (= N_b * n_timesteps) and n_samples [B] (= hop * (n_frames - 1)).
@@ -504,7 +554,7 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     _need_cfg(cfg_d, what)
     _check_phase(phase, what, None, ('device', 'numpy', 'spsi'))
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
-                      res_type)
+                      res_type, denoise)
     plan, Fout, n_bins = h.plan, h.plan.Fout, h.n_bins
     both = bool(giffin_lim_input)
     _check_phase(phase, what, (h.B, Fout, n_bins), ('device', 'numpy', 'spsi'))
@@ -901,7 +951,7 @@ def _resample_output_device(y, n_samples, max_samples, res_out, cfg_d, out_sr, r
 def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio=None, gap_ratio=1.0, segments='decode',
                            decode=None, out_len=None, max_frames=None, mode='linear', t_s=0, t_e=60, n_iter=200, realse=1.0,
                            two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64, encoder=None,
-                           wav_sr=None, out_sr=None, res_type='kaiser_best'):
+                           wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
     """``convert_batch`` with the timing changed as well: the stitched spectra are resampled along an integer time map
     (duration_map_batch, time_warp_batch) before the vocoder, which rebuilds the phase for the new timing.
 
@@ -913,7 +963,8 @@ def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio
     segments (ratio / out_len): 'decode' -- decode_batch on the stitched posteriors ``phn_pred`` (probabilities: kind='prob';
     ``decode``: a dict of its other arguments, e.g. trans, penalty, min_dur, class_map) -- or a table (labels, start, end,
     n_seg) in stitched-frame coordinates, e.g. from align_batch.  The other arguments are convert_batch's; phase='numpy'
-    draws per host-known length and is refused here.  max_frames: the bound of the output frames (default: exact for
+    draws per host-known length and is refused here; denoise: the input denoised first, mel / stft of the denoised input.
+    max_frames: the bound of the output frames (default: exact for
     rate=, duration_map_batch's proven bound for a host ratio, required otherwise).
 
     Every utterance keeps at least duration_min_frames(cfg_d) frames, so the vocoder never sees a length it cannot take:
@@ -935,7 +986,7 @@ def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio
         raise ValueError(" - ERROR, {}: mode must be 'linear' or 'nearest', got {!r}".format(what, mode))
     req = _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type)
+                      res_type, denoise)
     plan, B, hop, Fout = h.plan, h.B, h.hop, h.plan.Fout
     req = _duration_bound(what, req, plan.n_out.astype(np.int64), Fout, duration_min_frames(cfg_d), max_frames,
                           'the vocoder needs {}')
@@ -1276,7 +1327,7 @@ def _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt):
 
 def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None,
                         t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None,
-                        window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+                        window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
     """``convert_batch`` with the melody set as well: after the vocoder the converted waveform's F0
     is tracked (f0_track_batch's launches, at the model's rate and hop), and pitch_shift_batch's launches move it to the
     target before the output is resampled.
@@ -1289,6 +1340,8 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
                          and aligned to the output frames by the plan's n_s (output frame u is input frame n_s + u).
     f0_args: a dict of f0_track_batch's tracker arguments (frame_length, fmin, fmax, threshold, jump_cost, switch_cost,
     n_cand, ceiling).  The other arguments are convert_batch's; phase='numpy' and giffin_lim_input are not offered here.
+    denoise: as convert_batch's -- the input is denoised once, at the model's rate, before the model, a tracker or a
+    filter reads it, and mel_true / stft_true are those of the denoised input.
     Returns convert_batch's fields (y_wav_true None) plus f0_pred [B, Fout] (the track of the unshifted conversion),
     f0_target [B, Fout] (None for a number) and the grain plan.  Every check and table is made on the host before the first
     launch; after the uploads nothing is copied to the host and the host waits for nothing."""
@@ -1307,7 +1360,7 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
     w_floor = _check_w_floor(w_floor, what)
     tracker = _tracker_args(_tracker_keys(f0_args, what), cfg_d['sample_rate'], int(cfg_d['hop_length']), what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type)
+                      res_type, denoise)
     plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
     Lout = hop * (Fout - 1)
     _check_pitch_sizes(B, Lout, Fout, hop, what)
@@ -1323,6 +1376,7 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
     pitch = _contour_upload(kind, pitch)
     psola_window('cuda')
     h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)       # here: the source's track needs the model's rate too
+    h, up = _denoise_input(h, up, cfg_d, h.denoise)
 
     # ---- convert_batch's model pass, stitch and vocoder
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
@@ -1351,7 +1405,7 @@ _HNM_NT = namedtuple('convert_hnm', _BATCH_NT._fields + ('f0_target', 'env_log',
 def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats_src=None, stats_tgt=None, f0_args=None, order=24,
                       iters=16, voiced_cutoff_hz=4000.0, noise_level=1.0, realse=1.0, floor=1e-5, f0_lo=40.0, f0_hi=None, t_s=0,
                       t_e=60, two_pass=True, seed=0, utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None,
-                      res_type='kaiser_best'):
+                      res_type='kaiser_best', denoise=None):
     """``convert_batch`` with the harmonic-plus-noise vocoder in Griffin-Lim's place: the decoder's
     spectrum gives the envelope, an F0 contour the excitation, and audio_lib.hnm_synth_batch's launches write the waveform
     in one pass -- no phase iteration, and the pitch is the one asked for.
@@ -1365,6 +1419,8 @@ def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats
     noise_level, seed, utt_ids, f0_lo, f0_hi: hnm_synth_batch's.  The magnitude is made as convert_batch makes it (fused in
     the stitch at realse == 1, else vc_power_to_amp); after the synthesiser come convert_batch's de-emphasis and level
     (the spectra are those of the pre-emphasised signal) and the resampling to out_sr.
+    denoise: as convert_batch's -- the input is denoised once, at the model's rate, before the model, a tracker or a
+    filter reads it, and mel_true / stft_true are those of the denoised input.
     Returns convert_batch's fields (y_wav_true None) plus f0_target [B, Fout], env_log [B, Fout, bins] and the phase plan.
     Every check and table is made on the host before the first launch; after the uploads nothing is copied to the host and
     the host waits for nothing."""
@@ -1378,7 +1434,7 @@ def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats
     sr, hop = int(cfg_d['sample_rate']), int(cfg_d['hop_length'])
     tracker = None if kind == 'contour' else _tracker_args(_tracker_keys(f0_args, what), sr, hop, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type)
+                      res_type, denoise)
     plan, B, Fout, n_bins = h.plan, h.B, h.plan.Fout, h.n_bins
     n_fft, order, iters, floor = audio_lib._check_envelope_args(what, (B, Fout, n_bins), h.n_fft, order, iters, floor)
     _, _, f0_lo, f0_hi = audio_lib._check_plan_args(what, (B, Fout), sr, hop, f0_lo, f0_hi)
@@ -1395,6 +1451,7 @@ def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats
     d_nsamp, d_fout, d_fsrc = up.d_extra[-3:]
     pitch = _contour_upload(kind, pitch)
     h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)       # here: the source's track needs the model's rate too
+    h, up = _denoise_input(h, up, cfg_d, h.denoise)
 
     # ---- convert_batch's model pass and stitch, the magnitude as convert_batch makes it
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
@@ -1512,7 +1569,7 @@ def diff_frames(plan, hop):
 
 def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None,
                        stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None,
-                       window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+                       window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
     """``convert_batch`` without a vocoder: the source recording is FILTERED by the difference between
     the converted and the source spectral envelope (diff_gain_batch, audio_lib.stft_filter_batch), so its excitation and
     phase stay natural and the waveform costs one transform pass instead of a Griffin-Lim run.  t_s is fixed at 0: output
@@ -1526,6 +1583,8 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
       [B, Fout] floats   the contour to reach, in Hz per frame, 0 = leave the frame as it is;
       'source'           the source's own contour mapped by f0_transform(., stats_src, stats_tgt): both are required.
     w_floor, f0_args: as convert_pitch_batch.  The other arguments are convert_batch's.
+    denoise: as convert_batch's -- here it matters most: the filter passes the SOURCE recording, so with denoise the tracker
+    and the filter read the denoised waveform, and mel_true / stft_true (hence the gain) are those of the denoised input.
     Returns a namedtuple: y_wav_pred [B, hop * (Fout - 1)] (the filtered source at the level convert_batch sets,
     15 * mean_abs_amp_norm; zero beyond an utterance's n_samples), n_samples (hop * (n_use - 1) on the host, at out_sr when
     given), mel_true / mel_pred / stft_true / stft_pred / phn_pred as convert_batch(vocode=False) returns them, gain
@@ -1549,7 +1608,8 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
         raise ValueError(' - ERROR, {}: stats must be (count, mean, std) as f0_stats_batch returns them'.format(what))
     w_floor = _check_w_floor(w_floor, what)
     f0_kw = _tracker_keys(f0_args, what)
-    h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type)
+    h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type,
+                      denoise)
     plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
     n_use, h_nsamp = diff_frames(plan, hop)
     if int(h_nsamp.min()) <= h.n_fft // 2:
@@ -1571,6 +1631,7 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
     if kind is not None:
         psola_window('cuda')
     h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)       # here: the filter and the tracker need the model's rate too
+    h, up = _denoise_input(h, up, cfg_d, h.denoise)
 
     # ---- convert_batch(vocode=False): front-end, windows, model, the three stitches
     mel_true, stft_true, y_mel, y_stft, y_phn = _convert_model(decoder, encoder, h, up, cfg_d, wav_sr, res_type)
@@ -1752,7 +1813,7 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
                                 decode=None, out_len=None, max_frames=None, group=2, tol=None, qscale=32768.0, alpha=1.0,
                                 max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None, stats_src=None, stats_tgt=None,
                                 w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None, window_batch=64, encoder=None,
-                                wav_sr=None, out_sr=None, res_type='kaiser_best'):
+                                wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
     """``convert_diff_batch`` with the timing changed as well: the source is filtered exactly as there
     (gain, filter, level, and ``pitch=`` before the filter), then the FILTERED WAVEFORM is moved along an integer time map by
     time_scale_batch -- grains of the natural recording, so its excitation and local phase survive -- and only then
@@ -1761,7 +1822,7 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
     rate / ratio / gap_ratio / segments / decode / out_len / max_frames: convert_duration_batch's, with the map built over
     the n_use = min(n_out, n_clip) frames the filter covers (segments='decode' decodes ``phn_pred`` over those frames) and
     min_frames = 2: an utterance whose table is invalid or whose total would fall below 2 frames keeps its timing (flags
-    1, 2).  group, tol, qscale: time_scale_batch's.  The other arguments are convert_diff_batch's.
+    1, 2).  group, tol, qscale: time_scale_batch's.  The other arguments are convert_diff_batch's, denoise included.
     Returns convert_diff_batch's fields -- y_wav_pred [B, max_samples] at the NEW timing; mel_true / mel_pred / stft_true /
     stft_pred / phn_pred / gain / f0_src stay at the SOURCE's timing -- with n_samples and n_frames as DEVICE tensors (the
     output's; n_samples at out_sr when resampled), plus flags [B], seg = (labels, start, end, n_seg) in output frames, map
@@ -1770,7 +1831,8 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
     what = 'convert_diff_duration_batch'
     _need_cfg(cfg_d, what)
     req = _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len)
-    h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type)
+    h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type,
+                      denoise)
     B, hop, Fout = h.B, h.hop, h.plan.Fout
     n_use, h_nsamp = diff_frames(h.plan, hop)
     req = _duration_bound(what, req, n_use, Fout, 2, max_frames, 'at least {} are needed')
@@ -1782,7 +1844,7 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
     d = convert_diff_batch(decoder, wav, lens=lens, cfg_d=cfg_d, alpha=alpha, max_boost_db=max_boost_db, max_cut_db=max_cut_db,
                            half_width=half_width, pitch=pitch, stats_src=stats_src, stats_tgt=stats_tgt, w_floor=w_floor,
                            f0_args=f0_args, t_e=t_e, two_pass=two_pass, utt_ids=utt_ids, window_batch=window_batch, encoder=encoder,
-                           wav_sr=wav_sr, out_sr=None, res_type=res_type)
+                           wav_sr=wav_sr, out_sr=None, res_type=res_type, denoise=denoise)
     d_nuse = _i32_device(n_use, (B,), what + ': n_use')
     d_nsamp = _i32_device(h_nsamp, (B,), what + ': n_samples')
     wsola_window(group * hop, d.y_wav_pred.device)
@@ -1803,7 +1865,8 @@ _POST_NT = namedtuple('convert_postfilter', _BATCH_NT._fields + ('stft_raw',))
 
 def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mode='ms', k=0.85, alpha=1.0, max_db=20.0, g_max=4.0,
                              t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0,
-                             utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best'):
+                             utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best',
+                             denoise=None):
     """``convert_batch`` with the predicted spectrum postfiltered before the vocoder: the stitched ``stft_pred`` goes through
     postfilter.apply_batch (mode 'ms', 'gv' or 'ms+gv'; k, alpha, max_db, g_max are its arguments) with the frame counts the
     device already holds, then through vc_power_to_amp (``realse`` still applies) and the vocoder.
@@ -1811,7 +1874,8 @@ def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mo
     model: a postfilter.Model (postfilter.fit on the target speaker's natural spectra and on stft_pred of training
     utterances) or postfilter.upload's device tables -- upload once per model when the call has to stay free of
     host-to-device copies.  The other arguments are convert_batch's; the true spectrum is not vocoded, and phase='numpy'
-    is convert_batch's alone.  mel_pred is left as predicted.
+    is convert_batch's alone.  mel_pred is left as predicted.  denoise: as convert_batch's (mel_true / stft_true are those
+    of the denoised input).
 
     Returns convert_batch's fields (y_wav_true None) plus stft_raw, the spectrum as stitched; stft_pred is the filtered
     one.  With k = 0 and alpha = 0 the filters return their input bit for bit and so does the call: y_wav_pred equals
@@ -1828,7 +1892,7 @@ def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mo
     _check_phase(phase, what)
     postfilter.check_apply_args(mode, k, alpha, max_db, g_max, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type)
+                      res_type, denoise)
     plan, Fout, n_bins = h.plan, h.plan.Fout, h.n_bins
     if Fout > postfilter.MAX_FRAMES:
         raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, postfilter.MAX_FRAMES, Fout))

@@ -495,6 +495,117 @@ stft_filter_generic_kernel(SfArgs a) {
     }
 }
 
+// ---- linear short-time power (include/vc_hip.h, "Noise suppression"): P = |stft(x)|^2 with the filter's framing.  The
+// forward half of the filter kernels, then re^2 + im^2 instead of the gain and the inverse half.  A workgroup owns the rows
+// of its tile: rows at or beyond F_b are written as 0 here, so the launch needs no memset and writes every element once.
+__device__ __forceinline__ void sp_zero_rows(float* dst, int n) {
+    for (int i = threadIdx.x; i < n; i += VT) dst[i] = 0.0f;
+}
+
+__global__ void __launch_bounds__(VT)
+stft_power400_kernel(SfArgs a, float* __restrict__ power) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NROW = VG * 13;
+    float* win = reinterpret_cast<float*>(smem);       // [400]
+    float* tw = win + 400;                             // [2][208]
+    float* Are = tw + 416;                             // [NROW*17]; later the tile's power [VG][201]
+    float* Aim = Are + NROW * VA_STRIDE;
+    float* xs = Aim + NROW * VA_STRIDE;                // [span]
+    static_assert(VG * 201 <= NROW * VA_STRIDE, "the power tile must fit the transform's rows");
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int len;
+    const int F = sf_frames(a, b, len);
+    const int f0 = blockIdx.x * VG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    const int nrows = min(VG, a.maxF - f0);            // rows of d_power this tile owns
+    float* dst = power + ((size_t)b * a.maxF + f0) * 201;
+    if (f0 >= F) { sp_zero_rows(dst, nrows * 201); return; }
+    const int nvalid = min(VG, F - f0);
+
+    copy_lds(win, a.window, 816);
+    __syncthreads();
+    sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
+    __syncthreads();
+    {   // forward step 1+2: thread (g, n2)
+        const int g = tid >> 4, n2 = tid & 15;
+        const float* xp = xs + g * a.hop + n2;
+        float v[25], ar[13], ai[13];
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
+        vcfe::rdft25_13(v, ar, ai);
+        const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+        for (int k1 = 0; k1 < 13; ++k1) {
+            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
+            Are[i0 + VA_STRIDE * k1] = ar[k1];
+            Aim[i0 + VA_STRIDE * k1] = ai[k1];
+        }
+    }
+    __syncthreads();
+    // thread (g, k1): forward 16-point stage; its 16 slots are the bins k1 + 25 k2 and the mirrors of those above 200
+    float yr[16], yi[16];
+    if (tid < NROW) {
+        float zr[16], zi[16];
+#pragma unroll
+        for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = Are[VA_STRIDE * tid + n2]; zi[n2] = Aim[VA_STRIDE * tid + n2]; }
+        vcfe::cdft16(zr, zi, yr, yi);
+    }
+    __syncthreads();                                   // every row of Are has been read
+    if (tid < NROW) {
+        const int g = tid / 13, k1 = tid - g * 13;
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            bool cj;
+            const int bin = vcfe::src_bin(k1, k2, cj);
+            // the mirrors of k1 == 0 are the bins 25, 50, .. 175 again: each bin is stored by one slot
+            if (!cj || k1 != 0) Are[g * 201 + bin] = yr[k2] * yr[k2] + yi[k2] * yi[k2];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < nrows * 201; i += VT) dst[i] = i < nvalid * 201 ? Are[i] : 0.0f;
+}
+
+__global__ void __launch_bounds__(VT)
+stft_power_generic_kernel(SfArgs a, float* __restrict__ power) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int N = a.N, nb = a.nb;
+    float* win = reinterpret_cast<float*>(smem);       // [N]
+    float* twr = win + N;                              // [N]
+    float* twi = twr + N;                              // [N]
+    float* xs = twi + N;                               // [span]
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int len;
+    const int F = sf_frames(a, b, len);
+    const int f0 = blockIdx.x * VGG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    const int nrows = min(VGG, a.maxF - f0);
+    float* dst = power + ((size_t)b * a.maxF + f0) * nb;
+    if (f0 >= F) { sp_zero_rows(dst, nrows * nb); return; }
+    const int nvalid = min(VGG, F - f0);
+    copy_lds(win, a.window, N);
+    copy_lds(twr, a.window + N + 416, 2 * N);
+    __syncthreads();
+    sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
+    __syncthreads();
+    for (int idx = tid; idx < nrows * nb; idx += VT) {
+        float re = 0.0f, im = 0.0f;
+        if (idx < nvalid * nb) {
+            const int g = idx / nb, k = idx - g * nb;
+            const float* xp = xs + g * a.hop;
+            int m = 0;
+            for (int n = 0; n < N; ++n) {
+                const float xv = xp[n] * win[n];
+                re = fmaf(xv, twr[m], re);
+                im = fmaf(xv, twi[m], im);
+                m += k; if (m >= N) m -= N;
+            }
+        }
+        dst[idx] = re * re + im * im;
+    }
+}
+
 // ---- the gain of the differential filter (include/vc_hip.h).  grid (tiles of gt frames, B).  A tile's differences go to
 // LDS once, nb a frame; the smoothing reads them with the mirrored edges folded into the index (a bin whose taps all fall
 // inside the row takes the plain loop).  Each lane then takes four consecutive elements of the tile's flat output.
@@ -950,6 +1061,29 @@ int vc_stft_filter_f32(const vc_vocoder_plan* p, const float* d_wav, int32_t wav
     const dim3 ogrid(((unsigned)out_stride + VT - 1) / VT, (unsigned)batch);
     hipLaunchKernelGGL(gl_ola_kernel, ogrid, dim3(VT), (size_t)p->N * sizeof(float), st, a.frames, a.f_out, p->d_tables,
                        max_frames, p->N, p->hop, p->nov, d_out, out_stride, (const float*)nullptr, 0, (float*)nullptr);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+int vc_stft_power_f32(const vc_vocoder_plan* p, const float* d_wav, int32_t wav_stride, const int32_t* d_len,
+                      const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_power, int32_t* d_frames_out,
+                      void* stream) {
+    const char* fn = "vc_stft_power_f32";
+    VC_REQUIRE(p && d_wav && d_len && d_power && d_frames_out, "%s: NULL argument", fn);
+    VC_REQUIRE(batch >= 1 && batch <= 65535 && max_frames >= 1 && wav_stride >= 1,
+               "%s: bad shape (batch %d in [1, 65535], max_frames %d >= 1, wav_stride %d >= 1)", fn, batch, max_frames, wav_stride);
+    VC_REQUIRE((long long)p->hop * (max_frames - 1) + p->N < (1ll << 31), "%s: %d frames exceed 2^31 samples", fn, max_frames);
+    const bool fast = (p->N == 400);
+    if (int rc = vc::allow_dynamic_lds<stft_power400_kernel, stft_power_generic_kernel>(160 * 1024)) return rc;
+    SfArgs a;
+    a.wav = d_wav; a.len = d_len; a.gain = nullptr; a.n_frames = d_n_frames; a.frames = nullptr; a.f_out = d_frames_out;
+    a.window = p->d_tables;
+    a.wav_stride = wav_stride; a.maxF = max_frames; a.nb = p->nb; a.N = p->N; a.hop = p->hop;
+    a.span = fast ? p->span : p->span_g;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
+    if (fast) hipLaunchKernelGGL(stft_power400_kernel, grid, dim3(VT), p->smem400, st, a, d_power);
+    else hipLaunchKernelGGL(stft_power_generic_kernel, grid, dim3(VT), p->smem_gen, st, a, d_power);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }
