@@ -1905,6 +1905,81 @@ int vc_noise_gain_f32(const float* d_power, const int32_t* d_n_frames, const flo
                       int32_t max_frames, int32_t n_bins, const vc_denoise_cfg* cfg, float* d_gain, float* d_noise,
                       void* stream);
 
+/* Intelligibility.  The scores of a TIME-ALIGNED pair, clean reference x against processed signal y (a denoiser's, a
+ * resampler's, a filter's output): STOI (Taal, Hendriks, Heusdens & Jensen 2011), ESTOI (Jensen & Taal 2016) and SI-SDR
+ * (Le Roux, Wisdom, Erdogan & Hershey 2019).  Added without a version bump.  csrc/vc_stoi.hip; tests/stoi_ref.py restates
+ * every stage in float64 and the band and score stages, in the operation order below, in float32.
+ *
+ * Constants.  The waveforms are at 10 kHz (resample first).  W = 256, H = 128, a 512-point transform, N = 30 frames per
+ * segment, clip c = 1 + 10^(15 / 20), eps = 2^-52 (the same float32 constant on both sides).  w = hanning(W + 2)[1 : -1],
+ * w[n] = 0.5 - 0.5 cos(2 pi (n + 1) / (W + 1)), computed in float64 on the device and rounded once.
+ *
+ * Framing (MATLAB's).  A signal of L samples has the frames that start at i H for every i H < L - W: F = ceil((L - W) / H),
+ * 0 for L <= W.  L = d_lens[b] clamped to [0, max_len] (NULL: max_len); no sample at or beyond L is read.
+ *
+ * vc_stoi_energy_f32.  d_energy [batch, max_frames] float32: e[f] = sum_n (x[f H + n] w[n])^2 of the REFERENCE, rows at or
+ * beyond F as 0; d_n_frames [batch] int32 receives F.  Lane l of a wave adds n = l, l + 64, l + 128, l + 192 in that order,
+ * the 64 partial sums are added in a butterfly.  max_frames must hold ceil((max_len - W) / H) frames and be at most 16,384.
+ *
+ * vc_stoi_keep_f32.  The frames with e[f] > float32(ratio * max_f e[f]), ratio = 10^(-dyn / 10) in (0, 1), ascending:
+ * d_index [batch, max_frames] int32, -1 from K on; d_n_kept [batch] receives K.  An utterance with no frame, or of digital
+ * silence (max e = 0), has K = 0: nothing is kept "instead", unlike vc_mask_compact, so silence cannot reach a score.
+ * (vc_activity_mask and vc_mask_compact are not used: the first reads one frame of an utterance that has none, the second
+ * keeps all frames when none is active.)  One workgroup of 1,024 lanes per utterance: max_frames <= 16,384, 209 s.
+ *
+ * vc_stoi_bands_f32.  d_T [2, batch, max_m, n_bands] float32, signal 0 the reference and 1 the processed one, both through the
+ * REFERENCE's list.  M = max(K - 1, 0) clamped to max_m frames; rows at or beyond M as 0.  Frame m is the frame m of the
+ * overlap-add (hop H) of the kept, windowed frames, which is never built:
+ *     n <  H:  z[n] = (w[n + H] x[idx[m - 1] H + H + n]  +  w[n] x[idx[m] H + n]) w[n]      (m = 0: the second product alone)
+ *     n >= H:  z[n] = (w[n] x[idx[m] H + n]  +  w[n - H] x[idx[m + 1] H + n - H]) w[n]
+ *     X = the 512-point transform of z followed by 256 zeros;  T[m, j] = sqrt(sum_{k = lo_j}^{hi_j - 1} |X[k]|^2), k ascending
+ * d_bands [n_bands, 2] int32 holds (lo_j, hi_j), clamped on the device to 0 <= lo <= hi <= 257; n_bands in [1, 32].  An
+ * entry of d_index outside [0, (max_len - W) / H] counts as a frame of zeros.  The transform is a radix-2 Stockham
+ * autosort, decimation in frequency: stage t = 0 .. 8 has stride s = 2^t and, for j < 256, p = j / s, q = j % s,
+ *     out[q + 2 s p] = in[j] + in[j + 256];   out[q + 2 s p + s] = (in[j] - in[j + 256]) tw[p s]
+ * with tw[i] = exp(-2 pi i sqrt(-1) / 512) from float64, the complex product as (ar wr - ai wi, ar wi + ai wr), no
+ * product at stage 8 (tw[0]), and stage 0 reduced to out[2 j] = z[j], out[2 j + 1] = z[j] tw[j].  float32, no fused
+ * multiply-add.  One wave per (signal, utterance, frame), four frames per workgroup, 35 KB of LDS; grid (ceil(max_m / 4),
+ * batch, 2).
+ *
+ * vc_stoi_score_f32.  Two launches.  S = max(M - N + 1, 0) clamped to max_seg segments; segment s is T[s : s + N].
+ * mode 0 (STOI), per band j, x and y the N values of the band, all sums ascending from +0:
+ *     a = sqrt(sum x^2) / (sqrt(sum y^2) + eps);   y' = min(a y, c x)
+ *     mx = (sum x) / N;  my = (sum y') / N;  dx = sqrt(sum (x - mx)^2) + eps;  dy = sqrt(sum (y' - my)^2) + eps
+ *     d_j = sum ((x - mx) / dx) ((y' - my) / dy);      seg[s] = (sum_j d_j) / n_bands
+ * mode 1 (ESTOI): per band j, mx_j, dx_j, my_j, dy_j as above on x and y themselves; per frame n, xr_j = (x[n, j] - mx_j) /
+ * dx_j and yr_j likewise, ax = (sum_j xr_j) / n_bands, ex = sqrt(sum_j (xr_j - ax)^2) + eps, ay and ey likewise,
+ *     p_n = sum_j ((xr_j - ax) / ex) ((yr_j - ay) / ey);      seg[s] = (sum_n p_n) / N
+ * float32, no fused multiply-add, IEEE division.  d_seg [batch, max_seg]: every element written once, those at or beyond S
+ * as 0.  d_score [batch] = float32((sum_{s < S} seg[s] in float64: lane t of 256 adds s = t, t + 256, ..., then a fixed
+ * tree) / S); d_n_segments [batch] int32 = S.  S = 0 (too short, or nothing kept) gives score 0: read the count; no NaN is
+ * produced.  A band that is zero in y, or in both, contributes d_j = 0.  max_seg <= 16,384.
+ *
+ * vc_si_sdr_f32.  Over the first L samples, with zero_mean each signal less its own mean:
+ *     alpha = <y, x> / <x, x>;   si_sdr = 10 log10(|alpha x|^2 / |alpha x - y|^2),  the residual summed element by element
+ * One workgroup of 1,024 lanes per utterance; every sum in float64, lane t adding i = t, t + 1024, ..., then the tree of
+ * vc_speech_gain_f32; one rounding to float32 at the end.  L = 0 or <x, x> = 0: si_sdr 0 and valid 0.  A zero residual
+ * gives +inf (y == x: the right answer; a multiple of x only where alpha x - y vanishes exactly); alpha = 0 (y orthogonal
+ * to x, or zero) gives -inf.
+ *
+ * None of the five calls allocates, sets memory, uses atomics or synchronises; every output element is written exactly
+ * once; all are capturable from the first call, functions of their own utterance alone and bit-identical alone, in any
+ * batch and under graph replay.  VC_ERR_INVALID before the launch for a NULL pointer (d_lens excepted), batch outside
+ * [1, 65535], max_len outside [1, 2^30], ld < max_len, max_frames, max_m or max_seg outside [1, 16384],
+ * max_frames below the frames of max_len (energy), n_bands outside [1, 32], ratio outside (0, 1), mode or zero_mean not
+ * 0 or 1. */
+int vc_stoi_energy_f32(const float* d_ref, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld, float* d_energy,
+                       int32_t* d_n_frames, int32_t max_frames, void* stream);
+int vc_stoi_keep_f32(const float* d_energy, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float ratio,
+                     int32_t* d_index, int32_t* d_n_kept, void* stream);
+int vc_stoi_bands_f32(const float* d_ref, const float* d_deg, int32_t batch, int32_t max_len, int32_t ld, const int32_t* d_index,
+                      const int32_t* d_n_kept, int32_t max_frames, const int32_t* d_bands, int32_t n_bands, float* d_T, int32_t max_m,
+                      void* stream);
+int vc_stoi_score_f32(const float* d_T, const int32_t* d_n_kept, int32_t batch, int32_t max_frames, int32_t max_m, int32_t n_bands,
+                      int32_t mode, float* d_seg, int32_t max_seg, float* d_score, int32_t* d_n_segments, void* stream);
+int vc_si_sdr_f32(const float* d_ref, const float* d_deg, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld,
+                  int32_t zero_mean, float* d_si_sdr, uint8_t* d_valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,9 @@ two.  The same number, frame by frame (``align='frame'``), compares two conversi
   content_batch(ppg_a, ppg_b, len_a, len_b, ...)                the three above in one (mask_a, mask_b as in mcd_batch)
   content_wav_batch(encoder, wav_a, lens_a, wav_b, lens_b, cfg_d, ...)   resampler, front-end, convert_batch's windows and the encoder on both sides first
   class_map(names, fold=TIMIT_FOLD_39, drop=...)                the int32 table [C] of the usual 61-to-39 folding (host only)
+  stoi_batch(ref, deg, lens, wav_sr, extended, ...)             STOI / ESTOI of a TIME-ALIGNED pair -> (score, n_segments, n_kept, seg)
+  si_sdr_batch(ref, deg, lens, zero_mean)                       scale-invariant SDR of such a pair in dB -> (si_sdr, valid)
+  stoi_bands(fs, n_fft, n_bands, f_min)                         the one-third-octave band table int32 [n_bands, 2] (host only)
 
 mcd_batch (mask_a, mask_b), mcd_wav_batch and score_wav_batch (mask='energy' | 'voiced' | 'energy+voiced') leave silent
 frames out of the DTW, the MCD and the F0 figures; without a mask they are what they were.
@@ -36,7 +39,7 @@ Definitions (include/vc_hip.h, "Evaluation"):
 Lengths are host integers.  Every check is made on the host before the first launch; after that nothing is copied to
 the host and the host waits for nothing.  All arithmetic runs in csrc/vc_dtw.hip, csrc/vc_f0.hip (the pitch tracker
 and its figures), csrc/vc_f0_track.hip (the Viterbi decoding of F0 candidates, section 19), csrc/vc_activity.hip (the masks) and csrc/vc_content.hip (the content scores,
-DESIGN.md section 17); there is no CPU path.  Speaker similarity (GMM-UBM, log-likelihood ratios) lives in speaker.py.
+DESIGN.md section 17) and csrc/vc_stoi.hip (the intelligibility scores, section 31); there is no CPU path.  Speaker similarity (GMM-UBM, log-likelihood ratios) lives in speaker.py.
 """
 from collections import namedtuple
 
@@ -1884,3 +1887,177 @@ def phn_v_from_alignment(start, end, seq, names, hop_length, n_samples):
         b = n_samples if n == len(vis) - 1 else int(end[s]) * hop - h2
         out.append((a, b, names[int(seq[s])]))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- intelligibility
+STOI_SR = 10000             # vc_stoi_*: the rate the scores are defined at
+STOI_W = 256
+STOI_HOP = 128
+STOI_NFFT = 512
+STOI_SEG = 30               # frames per segment
+STOI_MAX_BANDS = 32
+_STOI = namedtuple('stoi', 'score n_segments n_kept seg')
+_SI_SDR = namedtuple('si_sdr', 'si_sdr valid')
+_STOI_BANDS = {}
+
+
+def stoi_frames(n):
+    """The frames of n samples under STOI's framing (MATLAB's): starts i * 128 for every i * 128 < n - 256."""
+    n = int(n)
+    return 0 if n <= STOI_W else (n - STOI_W + STOI_HOP - 1) // STOI_HOP
+
+
+def stoi_bands(fs=10000, n_fft=512, n_bands=15, f_min=150.0):
+    """The one-third-octave band table of STOI, int32 [n_bands, 2]: band j takes the bins [lo_j, hi_j) of an n_fft-point
+    transform at rate fs, lo_j = argmin |f - f_min 2^((2j - 1) / 6)|, hi_j = argmin |f - f_min 2^((2j + 1) / 6)| over
+    f = linspace(0, fs, n_fft + 1)[: n_fft // 2 + 1].  Host only.  The defaults give the lower edges 7 9 11 14 17 22 27 34
+    43 55 69 87 109 138 174 and the last upper edge 219."""
+    for v, name in ((fs, 'fs'), (n_fft, 'n_fft'), (n_bands, 'n_bands')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(' - ERROR, stoi_bands: {} must be a positive integer, got {!r}'.format(name, v))
+    if isinstance(f_min, bool) or not isinstance(f_min, (int, float, np.integer, np.floating)) or not 0.0 < f_min < float('inf'):
+        raise ValueError(' - ERROR, stoi_bands: f_min must be a positive number, got {!r}'.format(f_min))
+    if n_fft % 2:
+        raise ValueError(' - ERROR, stoi_bands: n_fft must be even, got {!r}'.format(n_fft))
+    f = np.linspace(0.0, float(fs), int(n_fft) + 1)[:int(n_fft) // 2 + 1]
+    j = np.arange(int(n_bands), dtype=np.float64)
+    lo = np.argmin(np.abs(f[None, :] - (float(f_min) * 2.0 ** ((2.0 * j - 1.0) / 6.0))[:, None]), axis=1)
+    hi = np.argmin(np.abs(f[None, :] - (float(f_min) * 2.0 ** ((2.0 * j + 1.0) / 6.0))[:, None]), axis=1)
+    return np.stack([lo, hi], axis=1).astype(np.int32)
+
+
+def _stoi_bands_device():
+    import torch
+    t = _STOI_BANDS.get('default')
+    if t is None:
+        t = _STOI_BANDS['default'] = torch.from_numpy(stoi_bands()).pin_memory().to('cuda', non_blocking=True)
+    return t
+
+
+def _check_pair(what, ref, deg, lens, allow_device_lens=True):
+    """Host checks of a time-aligned pair: (B, Lmax).  ValueError before the GPU is touched."""
+    import torch
+    for v, name in ((ref, 'ref'), (deg, 'deg')):
+        if getattr(v, 'ndim', 0) != 2 or min(v.shape) < 1:
+            raise ValueError(' - ERROR, {}: {} must be [B, Lmax]'.format(what, name))
+    if tuple(ref.shape) != tuple(deg.shape):
+        raise ValueError(' - ERROR, {}: ref and deg are time-aligned and must have one shape, got {} and {}'.format(
+            what, tuple(ref.shape), tuple(deg.shape)))
+    B, Lmax = int(ref.shape[0]), int(ref.shape[1])
+    if B > 65535 or Lmax > 2 ** 30:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of at most 2^30 samples'.format(what))
+    if lens is not None and torch.is_tensor(lens) and lens.is_cuda:
+        if not allow_device_lens:
+            raise ValueError(' - ERROR, {}: lens must be host integers when the pair is resampled'.format(what))
+        if lens.dtype != torch.int32 or tuple(lens.shape) != (B,):
+            raise ValueError(' - ERROR, {}: lens on the device must be int32 [{}]'.format(what, B))
+    elif lens is not None:
+        h = np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)
+        if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > Lmax:
+            raise ValueError(' - ERROR, {}: lens must be {} integers in [0, {}]'.format(what, B, Lmax))
+    return B, Lmax
+
+
+def _pair_device(x):
+    import torch
+    x = _to_device(x, torch.float32)
+    if x.shape[0] == 1:                                             # (the stride of a one-row tensor is arbitrary)
+        x = x.as_strided(x.shape, (x.shape[1], 1))
+    return x
+
+
+def _stoi_launch(ref, deg, d_len, mode, ratio, return_segments):
+    """The five launches of stoi_batch on validated device tensors at 10 kHz; no host check, copy or wait in here."""
+    import torch
+    lib, st = _vc.lib(), _vc.current_stream()
+    B, Lmax = ref.shape
+    dev = ref.device
+    Fmax = max(stoi_frames(Lmax), 1)
+    Mmax = max(Fmax - 1, 1)
+    Smax = max(Mmax - STOI_SEG + 1, 1)
+    bands = _stoi_bands_device()
+    nb = int(bands.shape[0])
+    energy = torch.empty((B, Fmax), dtype=torch.float32, device=dev)
+    n_frames = torch.empty((B,), dtype=torch.int32, device=dev)
+    index = torch.empty((B, Fmax), dtype=torch.int32, device=dev)
+    n_kept = torch.empty((B,), dtype=torch.int32, device=dev)
+    T = torch.empty((2, B, Mmax, nb), dtype=torch.float32, device=dev)
+    seg = torch.empty((B, Smax), dtype=torch.float32, device=dev)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    n_seg = torch.empty((B,), dtype=torch.int32, device=dev)
+    _vc.check(lib.vc_stoi_energy_f32(_vc.ptr(ref), _vc.ptr(d_len), B, Lmax, Lmax, _vc.ptr(energy), _vc.ptr(n_frames), Fmax, st))
+    _vc.check(lib.vc_stoi_keep_f32(_vc.ptr(energy), _vc.ptr(n_frames), B, Fmax, ratio, _vc.ptr(index), _vc.ptr(n_kept), st))
+    _vc.check(lib.vc_stoi_bands_f32(_vc.ptr(ref), _vc.ptr(deg), B, Lmax, Lmax, _vc.ptr(index), _vc.ptr(n_kept), Fmax, _vc.ptr(bands),
+                                    nb, _vc.ptr(T), Mmax, st))
+    _vc.check(lib.vc_stoi_score_f32(_vc.ptr(T), _vc.ptr(n_kept), B, Fmax, Mmax, nb, mode, _vc.ptr(seg), Smax, _vc.ptr(score),
+                                    _vc.ptr(n_seg), st))
+    return _STOI(score, n_seg, n_kept, seg if return_segments else None)
+
+
+def stoi_batch(ref, deg, lens=None, wav_sr=10000, extended=False, dyn_range=40.0, res_type='kaiser_best', return_segments=False):
+    """Short-time objective intelligibility of a TIME-ALIGNED ragged batch: clean reference against processed signal (the
+    output of enhance.denoise_batch, of a resampler, of audio_lib.stft_filter_batch, ...).  STOI (Taal et al. 2011), or
+    ESTOI (Jensen & Taal 2016) with ``extended``; include/vc_hip.h, "Intelligibility", defines every step.
+
+    ref, deg [B, Lmax] float32 (numpy or tensors) and ONE ``lens`` for both, because the pair is aligned: host integers or,
+    at 10 kHz, an int32 [B] device tensor (None = all Lmax).  The scores are defined at 10 kHz.  With another ``wav_sr``
+    both sides go through audio_lib.resample_batch first (``res_type``): that resampler is this project's (librosa's
+    Kaiser-windowed sinc), NOT the polyphase filter of the papers' MATLAB code, so figures differ slightly from a published
+    implementation's, and its output lengths come back on the host, so ``lens`` must be host integers, each above 0.
+    dyn_range: frames of the reference more than this many dB below its loudest frame are removed from both signals.
+    Returns a namedtuple of device tensors: score [B] float32; n_segments [B] int32, the 30-frame segments averaged (0: the
+    utterance is too short or silent and its score is 0, not NaN); n_kept [B] int32, the frames that survived the removal;
+    seg [B, S] float32, the per-segment values, zeros beyond n_segments (None unless return_segments).
+    After the resampling nothing is copied back and the host waits for nothing.  At most 16,384 frames (209 s) per
+    utterance."""
+    import torch
+    import audio_lib
+    what = 'stoi_batch'
+    wav_sr = audio_lib._check_rate(wav_sr, 'wav_sr')
+    res = wav_sr != STOI_SR
+    B, Lmax = _check_pair(what, ref, deg, lens, allow_device_lens=not res)
+    if isinstance(dyn_range, bool) or not isinstance(dyn_range, (int, float, np.integer, np.floating)) or not 0.0 < dyn_range <= 300.0:
+        raise ValueError(' - ERROR, {}: dyn_range must be a number of dB in (0, 300], got {!r}'.format(what, dyn_range))
+    ratio = float(np.float32(10.0 ** (-float(dyn_range) / 10.0)))
+    if not 0.0 < ratio < 1.0:
+        raise ValueError(' - ERROR, {}: dyn_range {!r} leaves no float32 ratio inside (0, 1)'.format(what, dyn_range))
+    if res:
+        audio_lib._res_params(res_type)
+        if lens is not None and np.asarray(lens.cpu() if torch.is_tensor(lens) else lens).min() <= 0:
+            raise ValueError(' - ERROR, {}: every length must be above 0 when the pair is resampled'.format(what))
+    L10 = audio_lib.resample_len(Lmax, wav_sr, STOI_SR) if res else Lmax
+    if stoi_frames(L10) > MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: {} samples at 10 kHz give more than {} frames; score shorter stretches'.format(
+            what, L10, MAX_FRAMES))
+    _need_gpu(what)
+    ref, deg = _pair_device(ref), _pair_device(deg)
+    if res:
+        h = None if lens is None else np.asarray(lens.cpu() if torch.is_tensor(lens) else lens, dtype=np.int64)
+        ref, h10 = audio_lib.resample_batch(ref, h, sr_in=wav_sr, sr_out=STOI_SR, res_type=res_type)
+        deg, _ = audio_lib.resample_batch(deg, h, sr_in=wav_sr, sr_out=STOI_SR, res_type=res_type)
+        lens = h10
+    d_len = None if lens is None else audio_lib._int32_device(lens, B, 'lens')
+    return _stoi_launch(ref, deg, d_len, 1 if extended else 0, ratio, bool(return_segments))
+
+
+def si_sdr_batch(ref, deg, lens=None, zero_mean=True):
+    """Scale-invariant signal-to-distortion ratio (Le Roux et al. 2019) of a time-aligned ragged batch, in dB:
+    10 log10(|a x|^2 / |a x - y|^2) with a = <y, x> / <x, x> over each utterance's first ``len`` samples; with zero_mean
+    each signal loses its own mean first.  ref, deg [B, Lmax] float32 (numpy or tensors); lens: host integers or an int32
+    [B] device tensor (None = all Lmax).  Returns a namedtuple of device tensors (si_sdr [B] float32, valid [B] uint8):
+    valid 0 and si_sdr 0 for an empty utterance or a reference of zeros; +inf when deg is a multiple of ref, -inf when deg
+    holds nothing of it.  The sums are float64 on the device; nothing is copied back and the host waits for nothing."""
+    import torch
+    import audio_lib
+    what = 'si_sdr_batch'
+    B, Lmax = _check_pair(what, ref, deg, lens)
+    if not isinstance(zero_mean, (bool, np.bool_)):
+        raise ValueError(' - ERROR, {}: zero_mean must be True or False, got {!r}'.format(what, zero_mean))
+    _need_gpu(what)
+    ref, deg = _pair_device(ref), _pair_device(deg)
+    d_len = None if lens is None else audio_lib._int32_device(lens, B, 'lens')
+    out = torch.empty((B,), dtype=torch.float32, device=ref.device)
+    valid = torch.empty((B,), dtype=torch.uint8, device=ref.device)
+    _vc.check(_vc.lib().vc_si_sdr_f32(_vc.ptr(ref), _vc.ptr(deg), _vc.ptr(d_len), B, Lmax, Lmax, int(bool(zero_mean)), _vc.ptr(out),
+                                      _vc.ptr(valid), _vc.current_stream()))
+    return _SI_SDR(out, valid)
