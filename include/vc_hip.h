@@ -1980,6 +1980,112 @@ int vc_stoi_score_f32(const float* d_T, const int32_t* d_n_kept, int32_t batch, 
 int vc_si_sdr_f32(const float* d_ref, const float* d_deg, const int32_t* d_lens, int32_t batch, int32_t max_len, int32_t ld,
                   int32_t zero_mean, float* d_si_sdr, uint8_t* d_valid, void* stream);
 
+/* Spectral mapping.  The conversion that needs no encoder and no decoder: a joint-density Gaussian mixture over pairs of
+ * source and target feature vectors, fitted by EM along DTW paths of a few parallel sentences, and maximum-likelihood
+ * parameter generation (MLPG) of the target's static cepstra from the conditional statistics (Toda, Black and Tokuda
+ * 2007).  Added without a version bump.  DESIGN.md section 32; csrc/vc_mapping.hip.
+ *
+ * Features are vc_spk_features_f32's with deltas = 1, cmn = 0: n cepstra and their regression over +-2 frames, D = 2 n.
+ * Limits (VC_ERR_UNSUPPORTED beyond them): 1 <= M <= 256; 1 <= D <= 64; n <= 32; batch <= 65,535; frames * D <= 2^30;
+ * max_path <= 2^24; MLPG max_frames <= 2^20.  Lengths are int32 [batch] ON THE DEVICE and clamped to [0, max].
+ *
+ * The model: d_w [M]; d_mu_x, d_mu_y, d_var_x, d_var_y, d_cov_xy [M, D], float32.  Sxx, Syy and Sxy of a component are
+ * diagonal: dimension d of component m carries the 2 x 2 covariance (sxx, sxy; sxy, syy) with det = sxx syy - sxy^2 > 0.
+ *
+ * vc_jd_prepare_f32 writes the table the other launches read, vc_jd_table_floats(M, D) = 10 M D + 2 M floats.  All of it is
+ * float64 arithmetic on the widened parameters WITHOUT contraction, each output rounded once:
+ *     [d][m] x 6:  mu_x; mu_y; a = syy / det; b = sxy / det; g = sxx / det; 1 / sxx          (det = sxx * syy - sxy * sxy)
+ *     [m]    x 2:  c_m  = log w_m - 0.5 * sum_d log((2 pi)^2 det_md);  cx_m = log w_m - 0.5 * sum_d log(2 pi sxx_md)
+ *                  (d ascending from +0; the constants 39.478417604357434 and 6.283185307179586 times det or sxx, then log)
+ *     [m][d] x 4:  mu_x; mu_y; A = sxy / sxx; 1 / Dv with Dv = syy - (sxy * sxy) / sxx
+ *
+ * vc_jd_accumulate_f32: the E-step over the cells of a path.  d_feat_a [batch, max_a, D], d_feat_b [batch, max_b, D];
+ * d_path [batch, max_path, 2] int32 with d_path_len [batch] as vc_dtw_backtrack / vc_path_map write them, or both NULL
+ * with max_path = 0 for the cells (p, p), p < min(len_a, len_b).  A cell (i, j) with i outside [0, len_a) or j outside
+ * [0, len_b) -- (-1, -1) included -- is skipped: nothing is read through it.  Per cell, float32:
+ *     l_m = c_m - 0.5 * q,  q = sum_d [ (a dx) dx + ((-2 b) dx) dy + (g dy) dy ],  dx = x_d - mu_x, dy = y_d - mu_y:
+ *           d ascending from +0; per d three fused multiply-adds in that order, the first factor of each a rounded
+ *           product; then l_m = fma(-0.5, q, c_m)
+ *     ll, gamma_m = exp(l_m - ll): as vc_gmm_loglik_f32 / vc_gmm_accumulate_f32
+ * Outputs, FLOAT64: d_N [M] = sum gamma; d_S [5, M, D] = the sums of gamma x, gamma y, gamma x^2, gamma y^2, gamma x y
+ * (gx = gamma * x rounded; then fma(gx, x, .), fma(gy, y, .), fma(gx, y, .)); d_L [2] = the sum of ll and the number of
+ * cells kept.  Nothing of size cells x M or cells x D is stored.  Grid = ceil(M / 64) x 128 partitions: tile k (32 cells)
+ * of pair b goes to partition (b + k) mod 128; a partition walks its pairs and tiles ascending, cell by cell; the 128
+ * partial sums of an element meet in the order 0 .. 127 in a second launch.  Lane (m, r) of 512 owns component m of the
+ * chunk and the dimensions r, r + 8, ...: 40 float64 sums and N in registers.  With M > 64 every chunk forms all M
+ * likelihoods of its tiles again (ll needs them).  Workspace: vc_jd_workspace_size(M, D) =
+ *     128 * ceil(M / 64) * (64 (1 + 5 D) + 2) * 8 bytes rounded up to 256:
+ * independent of the number of frames and of batch; 8-byte aligned; need not be cleared.  VC_ERR_WORKSPACE when too small.
+ *
+ * vc_jd_update_f32: elementwise, float64 without contraction, each output rounded once.
+ *     w_m = max(N_m / sum_k N_k, 2^-40)  (k ascending; not renormalised);  mu = S / N;
+ *     var = max(S2 / N - mu * mu, floor[d]) with the unrounded mu (d_floor_x, d_floor_y [D]);
+ *     cov = min(max(Sxy / N - mu_x * mu_y, -lim), lim),  lim = rho_max * sqrt(var_x * var_y) of the floored variances.
+ * A component with N_m < min_count, or N_m = 0, keeps its means, variances and covariance bit for bit; its weight is
+ * still set from N (else the weights would no longer sum to 1).
+ *
+ * vc_jd_map_f32: conversion statistics per frame of d_feat [batch, max_frames, D].  l_m = cx_m - 0.5 sum_d (x - mu_x)^2 *
+ * (1 / sxx) and ll exactly as vc_gmm_loglik_f32; gamma_m = exp(l_m - ll).  With E_md = fma(A, x_d - mu_x, mu_y) and
+ * gp = gamma_m * (1 / Dv_md) (one rounded product), m ascending from +0:
+ *     P[t, d] = P + gp;   R[t, d] = fma(gp, E, R);   mmse[t, d] = fma(gamma_m, E, mmse)
+ * mixture = 0 ("soft") sums over all m; mixture = 1 ("best") takes the one term of the arg-max of l_m (ties to the
+ * smallest m) with gamma = 1.  d_best [batch, max_frames] int32 receives the arg-max (required for mixture = 1, else
+ * optional); d_mmse may be NULL.  Rows at or beyond the length are 0 in every output.  One workgroup per (utterance, tile
+ * of vc_jd_tile() = 32 frames); nothing of size frames x M is stored.
+ *
+ * vc_mlpg_f32: per utterance and static dimension j < n the trajectory y [F] that minimises
+ *     sum_t Ps_t (y_t - Es_t)^2 + Pd_t ((W y)_t - Ed_t)^2,   Ps = P[., j], Pd = P[., n + j], Rs = R[., j], Rd = R[., n + j]
+ * (R = P E), W the regression window of vc_spk_features_f32.  With c(t, i) the integer weight of y_i in 10 (W y)_t,
+ *     c(t, i) = [i = min(t+1, F-1)] - [i = max(t-1, 0)] + 2 [i = min(t+2, F-1)] - 2 [i = max(t-2, 0)]   in {-3 .. 3},
+ *     A[i, k] = Ps_i [i = k] + (sum_t (c(t, i) c(t, k)) Pd_t) / 100,     b_i = Rs_i + (sum_t c(t, i) Rd_t) / 10,
+ * both sums over t = max(i-2, 0) .. min(i+2, F-1) ascending from +0, the integer product converted, then multiplied; a term
+ * whose integer weight is 0 is left out (nothing is multiplied by 0).
+ * A is symmetric positive definite with half-bandwidth 4.  The solve, in FLOAT64 without contraction, IEEE division,
+ * for i = 0 .. F-1 ascending (entries with a negative index are 0, their d is 1):
+ *     for s = 0 .. 3, k = i-4+s:  v_s = A[i, k] - v_0 L[k, i-4] - ... - v_{s-1} L[k, k-1]   (left to right);
+ *                                 L[i, k] = v_s / d_k
+ *     d_i = A[i, i] - v_0 L[i, i-4] - v_1 L[i, i-3] - v_2 L[i, i-2] - v_3 L[i, i-1]
+ *     z_i = b_i - L[i, i-4] z_{i-4} - L[i, i-3] z_{i-3} - L[i, i-2] z_{i-2} - L[i, i-1] z_{i-1};     u_i = z_i / d_i
+ * then for i = F-1 .. 0:  y_i = u_i - L[i+1, i] y_{i+1} - L[i+2, i] y_{i+2} - L[i+3, i] y_{i+3} - L[i+4, i] y_{i+4}
+ * (terms beyond F-1 are 0), rounded once to float32.  A pivot d_i that is not positive and finite sets bit 0 of
+ * d_flags[b] (written 0 otherwise) and that dimension's whole trajectory becomes Rs_t / Ps_t (float64 quotient, rounded
+ * once).  d_y [batch, max_frames, n]; rows at or beyond the length are 0.  One wave per utterance, one lane per
+ * dimension; the inputs of a row are loaded three rows ahead of the elimination; the factor goes to the workspace by
+ * COLUMNS, [utterance][i][5][n] float64 = L[i+4, i], L[i+3, i], L[i+2, i], L[i+1, i], u_i -- what the back substitution of
+ * row i reads, again three rows ahead --, so that a wave's accesses are consecutive.  vc_mlpg_workspace_size(batch, max_frames, n) = batch * max_frames * 5 * n * 8 bytes rounded up to 256.
+ *
+ * vc_cep_gain_f32: converted static cepstra d_cep_pred and the source's d_cep_src [batch, max_frames, n] to the gain
+ * [batch, max_frames, n_bins] of vc_stft_filter_f32.  float32, every product and sum rounded on its own, ascending from +0:
+ *     dmel_k = sum_i d_dct[i, k] * (y_i - x_i)            d_dct [n, n_mels]: the rows of the DCT the cepstra were made with
+ *     dbin   = (1 - w) * dmel[i0] + w * dmel[i0 + 1]      d_bin_i0 int32 [n_bins] (clamped to [0, n_mels - 2]), d_bin_w [n_bins]
+ *     s      = min(max((alpha * db_scale) * dbin, -max_cut_db), max_boost_db);     G = exp2f(s * float32(log2(10) / 20))
+ * Rows at or beyond d_n_frames[b] (NULL: none) are 0.  n_mels in [2, 128], n_bins <= 2049.
+ *
+ * None of the launches allocates, sets memory, uses atomics or synchronises; every output element is written exactly
+ * once; all are capturable and bit-identical alone, in any batch and under graph replay (the E-step's sums depend on
+ * the batch they are taken over, by definition).  Arguments are checked before any HIP call. */
+int vc_jd_tile(void);
+size_t vc_jd_table_floats(int32_t M, int32_t D);
+size_t vc_jd_workspace_size(int32_t M, int32_t D);
+size_t vc_mlpg_workspace_size(int32_t batch, int32_t max_frames, int32_t n_coef);
+int vc_jd_prepare_f32(const float* d_w, const float* d_mu_x, const float* d_mu_y, const float* d_var_x, const float* d_var_y,
+                      const float* d_cov_xy, int32_t M, int32_t D, float* d_table, void* stream);
+int vc_jd_accumulate_f32(const float* d_feat_a, const float* d_feat_b, const int32_t* d_len_a, const int32_t* d_len_b,
+                         const int32_t* d_path, const int32_t* d_path_len, int32_t batch, int32_t max_a, int32_t max_b,
+                         int32_t max_path, int32_t D, const float* d_table, int32_t M, double* d_N, double* d_S, double* d_L,
+                         void* d_workspace, size_t workspace_bytes, void* stream);
+int vc_jd_update_f32(const double* d_N, const double* d_S, int32_t M, int32_t D, const float* d_mu_x_in, const float* d_mu_y_in,
+                     const float* d_var_x_in, const float* d_var_y_in, const float* d_cov_in, const float* d_floor_x,
+                     const float* d_floor_y, float rho_max, float min_count, float* d_w_out, float* d_mu_x_out, float* d_mu_y_out,
+                     float* d_var_x_out, float* d_var_y_out, float* d_cov_out, void* stream);
+int vc_jd_map_f32(const float* d_feat, const int32_t* d_len, int32_t batch, int32_t max_frames, int32_t D, const float* d_table,
+                  int32_t M, int32_t mixture, float* d_P, float* d_R, float* d_mmse, int32_t* d_best, void* stream);
+int vc_mlpg_f32(const float* d_P, const float* d_R, const int32_t* d_len, int32_t batch, int32_t max_frames, int32_t n_coef,
+                float* d_y, int32_t* d_flags, void* d_workspace, size_t workspace_bytes, void* stream);
+int vc_cep_gain_f32(const float* d_cep_pred, const float* d_cep_src, const int32_t* d_n_frames, int32_t batch, int32_t max_frames,
+                    int32_t n_coef, const float* d_dct, int32_t n_mels, const int32_t* d_bin_i0, const float* d_bin_w, int32_t n_bins,
+                    float alpha, float db_scale, float max_boost_db, float max_cut_db, float* d_gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,6 +338,18 @@ _SIGS = {
     'vc_stoi_bands_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P]),
     'vc_stoi_score_f32': (C.c_int, [_P, _P] + [C.c_int32] * 5 + [_P, C.c_int32, _P, _P, _P]),
     'vc_si_sdr_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    # spectral mapping (csrc/vc_mapping.hip)
+    'vc_jd_tile': (C.c_int, []),
+    'vc_jd_table_floats': (C.c_size_t, [C.c_int32] * 2),
+    'vc_jd_workspace_size': (C.c_size_t, [C.c_int32] * 2),
+    'vc_mlpg_workspace_size': (C.c_size_t, [C.c_int32] * 3),
+    'vc_jd_prepare_f32': (C.c_int, [_P] * 6 + [C.c_int32, C.c_int32, _P, _P]),
+    'vc_jd_accumulate_f32': (C.c_int, [_P] * 6 + [C.c_int32] * 5 + [_P, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]),
+    'vc_jd_update_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32] + [_P] * 7 + [C.c_float, C.c_float] + [_P] * 7),
+    'vc_jd_map_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    'vc_mlpg_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
+    'vc_cep_gain_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32] + [C.c_float] * 4
+                        + [_P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -373,7 +385,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then vc_stft_power_f32 / vc_noise_gain_f32, then the vc_stoi_* launches and vc_si_sdr_f32, then the
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then vc_stft_power_f32 / vc_noise_gain_f32, then the vc_stoi_* launches and vc_si_sdr_f32, then the spectral-mapping launches (vc_jd_*, vc_mlpg_f32, vc_cep_gain_f32), then the
                 # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '

@@ -1912,3 +1912,92 @@ def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mo
                                              res_type)
     return _POST_NT(None, y_wav_pred, n_samples, mel_true, mel_pred, stft_true, stft_pred, phn_pred, [int(v) for v in plan.n_out],
                     stft_raw)
+
+
+# --------------------------------------------------------------------------- spectral mapping (csrc/vc_mapping.hip)
+_GMM_DIFF_NT = namedtuple('convert_gmm_diff', 'y_wav_pred n_samples mel_true cep_src cep_pred gain n_frames')
+
+
+def convert_gmm_diff_batch(model, wav, lens=None, cfg_d=None, mixture='soft', mlpg=True, alpha=1.0, max_boost_db=20.0, max_cut_db=30.0,
+                           wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None, n_coef=None, first_coef=1):
+    """Waveform in, waveform out, with no encoder and no decoder: the source's mel cepstra are
+    converted by a joint-density mixture (mapping.fit / mapping.fit_wav; mapping.convert_cepstra_batch with ``mixture`` and
+    ``mlpg``), the cepstral difference becomes the gain of the differential filter (mapping.cepstra_gain_batch with alpha,
+    max_boost_db, max_cut_db) and the source recording is filtered by it (audio_lib.stft_filter_batch): sprocket's DIFFVC.
+    The framing is convert_diff_batch's with every frame used: frame u of the gain is frame u of the source's front-end,
+    n_frames = 1 + len // hop per utterance and the output holds hop * (n_frames - 1) samples of it.
+
+    model: a mapping.JDGMM over D = 2 n features; n_coef: None = n.  wav, lens, wav_sr, out_sr, res_type, denoise: as
+    convert_diff_batch's.  Pitch and durations are not offered here: call pitch_shift_batch / time_scale_batch on the result.
+    Returns a namedtuple: y_wav_pred [B, hop * (Fmax - 1)] (the filtered source at the level convert_batch sets, zero beyond
+    an utterance's n_samples), n_samples (host, at out_sr when given), mel_true [B, Fmax, n_mels], cep_src and cep_pred
+    [B, Fmax, n], gain [B, Fmax, bins] and n_frames (host).  Every check and table is made on the host before the first
+    launch; after the uploads nothing is copied to the host and the host waits for nothing."""
+    import torch
+    import audio_lib
+    import evaluation
+    import mapping
+    what = 'convert_gmm_diff_batch'
+    _need_cfg(cfg_d, what)
+    alpha, boost, cut = _check_diff_args(alpha, max_boost_db, max_cut_db, what)
+    mix = mapping._check_mixture(mixture, what)
+    if not (isinstance(model, tuple) and len(model) == 6 and getattr(model[1], 'ndim', 0) == 2):
+        raise ValueError(' - ERROR, {}: model must be a mapping.JDGMM'.format(what))
+    D = int(model[1].shape[1])
+    n = mapping._check_even(D, what)
+    if n_coef is not None and int(n_coef) != n:
+        raise ValueError(' - ERROR, {}: the model converts {} coefficients, n_coef is {}'.format(what, n, n_coef))
+    M = mapping._check_model(model, D, what)
+    first_coef = int(first_coef)
+    dct, i0, w, scale = mapping._gain_args(cfg_d, n, first_coef, what)
+    if getattr(wav, 'ndim', 0) != 2 or min(wav.shape) < 1:
+        raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
+    B, Lmax = int(wav.shape[0]), int(wav.shape[1])
+    hop, sr = int(cfg_d['hop_length']), cfg_d['sample_rate']
+    n_fft = cfg_d['n_fft'] or cfg_d['win_length']
+    audio_lib._res_params(res_type)
+    res_in = wav_sr is not None and audio_lib._ratio(wav_sr, sr) != (1, 1)
+    res_out = out_sr is not None and audio_lib._ratio(sr, out_sr) != (1, 1)
+    h_lens = np.full((B,), Lmax, dtype=np.int64) if lens is None else np.asarray(lens, dtype=np.int64).reshape(-1)
+    if h_lens.shape != (B,) or h_lens.min() <= 0 or h_lens.max() > Lmax:
+        raise ValueError(' - ERROR, {}: lens must be [B] with 0 < len <= Lmax'.format(what))
+    h_lens_in = None
+    if res_in:
+        h_lens_in, h_lens, Lmax = h_lens, audio_lib.resample_len(h_lens, wav_sr, sr), int(audio_lib.resample_len(Lmax, wav_sr, sr))
+    denoise = _check_denoise(what, denoise, cfg_d, B)
+    if denoise is not None:
+        h_lens = hop * (h_lens // hop)
+    n_use = 1 + h_lens // hop
+    h_nsamp = hop * (n_use - 1)
+    if int(h_nsamp.min()) <= n_fft // 2:
+        raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples at {} Hz'.format(what, sr))
+    Fmax = 1 + Lmax // hop
+    if B > 65535 or Fmax > mapping.MLPG_MAX_FRAMES:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances of at most 2^20 frames'.format(what))
+    _need_gpu(what)
+
+    # ---- uploads: the waveforms if they are on the host, one table of lengths, the gain's tables
+    if not torch.is_tensor(wav):
+        wav = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32))
+    wav = wav.to(device='cuda', dtype=torch.float32).contiguous()
+    tabs = evaluation._upload_lens(*([h_lens_in] if res_in else []), h_lens, n_use, h_nsamp)
+    d_lens, d_nuse, d_nsamp = tabs[-3:]
+    d_i0, d_w = mapping._gain_upload(i0, w)
+    model = mapping._model_to_device(model)
+    h = _HOST_NT(None, B, hop, n_fft, 1 + n_fft // 2, h_lens, h_lens_in, h_nsamp, None, res_in, res_out, None, denoise)
+    up = _UP_NT(wav, d_lens, None, None, None, None, None, None, tabs[:1])
+    h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)
+    h, up = _denoise_input(h, up, cfg_d, h.denoise)
+    x = up.wav
+
+    # ---- front-end, cepstra, the mapping, gain, filter, level
+    mel_true = evaluation._mel_launch(x, d_lens, cfg_d)
+    cep_src = evaluation._cepstra_launch(mel_true, n, first_coef)
+    cep_pred, _ = mapping._convert_device(model, mapping._prepare_launch(model), cep_src, d_nuse, mix, bool(mlpg))
+    gain = mapping._gain_launch(cep_pred, cep_src, d_nuse, evaluation._dct_device(int(cfg_d['n_mels']), n, first_coef), d_i0, d_w, alpha,
+                                scale, boost, cut)
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
+    F = gain.shape[1]
+    y = _deemphasis_level(vplan, audio_lib._stft_filter_launch(vplan, x, d_lens, gain, d_nuse), d_nuse, F, cfg_d, 0.0)
+    y, n_samples = _resample_output(y, h_nsamp, d_nsamp, res_out, cfg_d, out_sr, res_type)
+    return _GMM_DIFF_NT(y, n_samples, mel_true, cep_src, cep_pred, gain, [int(v) for v in n_use])
