@@ -2086,6 +2086,97 @@ int vc_cep_gain_f32(const float* d_cep_pred, const float* d_cep_src, const int32
                     int32_t n_coef, const float* d_dct, int32_t n_mels, const int32_t* d_bin_i0, const float* d_bin_w, int32_t n_bins,
                     float alpha, float db_scale, float max_boost_db, float max_cut_db, float* d_gain, void* stream);
 
+/* Dereverberation.  Late reverberation follows the speech, so the noise tracker above cannot take it out.  Weighted
+ * prediction error (WPE; Nakatani et al. 2010, in the formulation of Drude et al. 2018, nara_wpe) does: per frequency bin a
+ * delayed linear predictor over past STFT frames, estimated by iteratively re-weighted least squares, is subtracted.  It is
+ * linear, keeps the phase and needs no training.  Three launches: the complex STFT, the solver, the inverse.  Added
+ * without a version bump.  tests/dereverb_ref.py restates all three in float64 numpy, the solver in the order below.
+ *
+ * vc_stft_complex_f32: Z = stft(x) with exactly the framing of vc_stft_filter_f32 and vc_stft_power_f32 above: the plan's
+ * padded window, reflect padding by N / 2 about sample 0 and about sample len - 1 (len = d_len[b] clamped to
+ * [0, wav_stride]), F_b = min(n_frames[b], max_frames, 1 + len / hop) (d_n_frames NULL: without the first; a negative count
+ * counts as 0) and the "short" rule: len <= N / 2 or hop * (F_b - 1) <= N / 2 gives F_b = 0.  d_frames_out [batch] int32
+ * receives F_b.  The spectrum is planar and BIN-MAJOR: d_re, d_im [batch, n_bins, max_frames] float32, n_bins = 1 + N / 2
+ * -- the solver walks time for one bin, and a tile of 16 frames still stores runs of 64 bytes.  Every element is written
+ * once, frames at or beyond F_b as 0.  One launch, no workspace: the forward half of the filter kernels (16 frames per
+ * workgroup and the 25 x 16 transform at n_fft == 400, 4 frames and the direct transform otherwise), statement for statement
+ * that of vc_stft_power_f32, so that re^2 + im^2 of this launch is that launch's power up to the rounding of the two squares
+ * and their sum.  VC_ERR_INVALID before the launch for a NULL pointer (d_n_frames excepted), batch outside [1, 65535],
+ * max_frames < 1 or wav_stride < 1.
+ *
+ * vc_istft_complex_f32: y = istft(Z), the filter's inverse half: inverse transform and synthesis window into the frame
+ * buffer, then the vocoder's overlap-add kernel.  F_b = d_n_frames[b] clamped to [0, max_frames] (NULL: max_frames), and 0
+ * where hop * (F_b - 1) <= N / 2.  Output as vc_stft_filter_f32's: hop * (F_b - 1) samples, then zeros up to out_stride;
+ * every element of d_out [batch, out_stride] is written once.  The imaginary parts of bin 0 and of bin N / 2 are IGNORED
+ * (a real frame has none); nothing else of a frame at or beyond F_b is read.  Workspace: vc_stft_filter_workspace_bytes,
+ * used as the filter uses it.  VC_ERR_INVALID for a NULL pointer (d_n_frames excepted), batch outside [1, 65535],
+ * max_frames < 1 or out_stride < hop * (max_frames - 1); VC_ERR_WORKSPACE for a workspace that is too small.
+ *
+ * vc_wpe_f32: the solver.  d_re, d_im [batch, n_bins, max_frames] as above; F = d_n_frames[b] clamped to [0, max_frames]
+ * (NULL: max_frames); K = taps, D = delay, I = iterations, c = context.  Per (b, k), with x_t the input bin converted to
+ * float64 and xt_t[i] = x_{t - D - i}, i < K, where a term whose index t - D - i is negative is LEFT OUT of every sum below
+ * (nothing is multiplied by an absent frame):
+ *     m    = (sum_t |x_t|^2, t = 0 .. F - 1 ascending from +0) / F            |z|^2 = re * re + im * im
+ *     lam0 = double(floor_rel) * m
+ *     p_t  = |x_t|^2
+ *     repeat I times:
+ *         lam_t   = (sum of p_u, u = max(t - c, 0) .. min(t + c, F - 1) ascending from +0) / (number of terms);
+ *                   lam_t = lam0 unless lam_t > lam0
+ *         R[i][j] = sum_t (xt_t[i] * conj(xt_t[j])) / lam_t      i <= j;  t = D + j .. F - 1 ascending from +0
+ *         q[i]    = sum_t (xt_t[i] * conj(x_t)) / lam_t          t = D + i .. F - 1 ascending from +0
+ *                   a * conj(b) = (ar * br + ai * bi,  ai * br - ar * bi); the real and the imaginary part are each divided
+ *                   by lam_t, then added to their sums
+ *         tr = sum_i R[i][i].re (i ascending from +0);  R[i][i].re += (double(load_rel) * tr) / K
+ *         R = L L^H, for j = 0 .. K - 1:
+ *             d    = R[j][j].re - |L[j][0]|^2 - ... - |L[j][j-1]|^2          left to right; R[j][j].im is not read
+ *             a pivot d that is not positive and finite ends the bin with status 1
+ *             L[j][j] = sqrt(d)
+ *             L[i][j] = (conj(R[j][i]) - L[i][0] * conj(L[j][0]) - ... - L[i][j-1] * conj(L[j][j-1])) / L[j][j]    i > j
+ *         L z = q:    z[i] = (q[i] - L[i][0] * z[0] - ... - L[i][i-1] * z[i-1]) / L[i][i]                  i ascending
+ *                     a * b = (ar * br - ai * bi,  ar * bi + ai * br)
+ *         L^H g = z:  g[i] = (z[i] - conj(L[K-1][i]) * g[K-1] - ... - conj(L[i+1][i]) * g[i+1]) / L[i][i]  i descending
+ *                     conj(a) * b = (ar * br + ai * bi,  ar * bi - ai * br)
+ *         y_t = x_t - (sum_i conj(g[i]) * xt_t[i], i = 0 .. min(K, t - D + 1) - 1 ascending from +0);   p_t = |y_t|^2
+ * Everything is float64 without contraction: a complex product is four real products and two sums, each rounded once and
+ * subtracted (or added) as a whole, real and imaginary part on their own; division and square root are IEEE; a complex
+ * number is divided by a real one part by part.  y stays float64 between iterations and is rounded to float32 once, at the
+ * end.  d_out_re, d_out_im [batch, n_bins, max_frames]: y, frames at or beyond F as 0.  d_taps [batch, n_bins, K, 2] float32
+ * (optional): the last iteration's g, (re, im).  d_status [batch, n_bins] int32: 0 solved; 1 a pivot that was not positive
+ * and finite in any iteration (an all-zero bin is one: m == 0, and 0 / 0 reaches the first pivot); 2 F <= D, no history at
+ * all.  With status 1 or 2 the bin is passed through -- y = x bit for bit -- and its taps are 0.  Every element of every
+ * output is written exactly once.
+ * Hence: scaling the input by 2^n scales the output by exactly 2^n and leaves taps and status bit-identical (R and q are
+ * ratios, the floor and the load are relative; away from overflow and underflow); the result is a function of its own
+ * (utterance, bin) alone, bit-identical alone, in any batch and under graph replay.
+ * One launch, one workgroup per (utterance, bin): the bin's frames are staged once in LDS from the contiguous row; each of
+ * the K (K + 1) / 2 sums of R and the K sums of q has one lane for its owner and walks t; the factorisation and the
+ * substitutions run a lane per row, a column per step, out of LDS; lam and y take a lane per frame.  The frames live in
+ * LDS, 24 bytes each behind 8 (2 K^2 + 2 K + 4) bytes of matrix, so max_frames is capped:
+ *     vc_wpe_max_frames(K) = (160 KiB - 8 (2 K^2 + 2 K + 4)) / 24          6,121 at K = 32, 6,644 at K = 16 (0: K out of range)
+ * VC_ERR_INVALID before the launch for a NULL pointer (d_n_frames and d_taps excepted), batch outside [1, 65535], n_bins
+ * outside [2, 2049], max_frames < 1 or beyond the cap, taps outside [1, 32], delay outside [1, 64], iterations outside
+ * [1, 16], context outside [0, 8], floor_rel outside (0, 1], load_rel outside [0, 1].
+ *
+ * None of the launches allocates, sets memory, uses atomics or synchronises; the lengths are read on the device; all are
+ * capturable from the first call. */
+typedef struct vc_wpe_cfg {
+    int32_t taps;       /* K: length of the predictor */
+    int32_t delay;      /* D: frames between the newest predicting frame and the predicted one */
+    int32_t iterations; /* I: re-weighting passes */
+    int32_t context;    /* c: the power is averaged over the frames t - c .. t + c */
+    float floor_rel;    /* floor of the weight, relative to the bin's mean power */
+    float load_rel;     /* diagonal loading, relative to the mean of the diagonal */
+} vc_wpe_cfg;
+int vc_stft_complex_f32(const vc_vocoder_plan* plan, const float* d_wav, int32_t wav_stride, const int32_t* d_len,
+                        const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_re, float* d_im,
+                        int32_t* d_frames_out, void* stream);
+int vc_istft_complex_f32(const vc_vocoder_plan* plan, const float* d_re, const float* d_im, const int32_t* d_n_frames,
+                         int32_t batch, int32_t max_frames, float* d_out, int32_t out_stride, void* d_workspace,
+                         size_t workspace_bytes, void* stream);
+int32_t vc_wpe_max_frames(int32_t taps);
+int vc_wpe_f32(const float* d_re, const float* d_im, const int32_t* d_n_frames, int32_t batch, int32_t n_bins, int32_t max_frames,
+               const vc_wpe_cfg* cfg, float* d_out_re, float* d_out_im, float* d_taps, int32_t* d_status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

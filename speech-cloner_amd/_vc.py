@@ -42,6 +42,12 @@ class DenoiseCfg(C.Structure):
                 ('xi_h1', C.c_float), ('xi_min', C.c_float), ('gain_min', C.c_float), ('gamma_max', C.c_float)]
 
 
+class WpeCfg(C.Structure):
+    """struct vc_wpe_cfg (include/vc_hip.h, "Dereverberation")."""
+    _fields_ = [('taps', C.c_int32), ('delay', C.c_int32), ('iterations', C.c_int32), ('context', C.c_int32),
+                ('floor_rel', C.c_float), ('load_rel', C.c_float)]
+
+
 VC_F32, VC_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 GEMM_PLAIN, GEMM_HIGHWAY = 0, 1
@@ -350,6 +356,11 @@ _SIGS = {
     'vc_mlpg_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_size_t, _P]),
     'vc_cep_gain_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32] + [C.c_float] * 4
                         + [_P, _P]),
+    # dereverberation (csrc/vc_vocoder.hip, csrc/vc_dereverb.hip)
+    'vc_stft_complex_f32': (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'vc_istft_complex_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P]),
+    'vc_wpe_max_frames': (C.c_int32, [C.c_int32]),
+    'vc_wpe_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),

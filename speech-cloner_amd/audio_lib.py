@@ -600,6 +600,107 @@ def stft_power_batch(wav, lens, n_frames=None, win_length=400, hop_length=80, n_
     return _stft_power_launch(plan, wav, d_len, d_nf, Fmax)
 
 
+def _stft_complex_launch(plan, wav, d_len, d_nf, Fmax):
+    """vc_stft_complex_f32 on validated device tensors (as _stft_power_launch): (re, im [B, bins, Fmax], the frame counts the
+    device used, int32 [B]); no host check, copy or wait in here."""
+    import torch
+    B = wav.shape[0]
+    re = torch.empty((B, plan.n_bins, Fmax), dtype=torch.float32, device=wav.device)
+    im = torch.empty_like(re)
+    d_fout = torch.empty((B,), dtype=torch.int32, device=wav.device)
+    _vc.check(_vc.lib().vc_stft_complex_f32(plan.handle, _vc.ptr(wav), wav.shape[1], _vc.ptr(d_len), _vc.ptr(d_nf), B, Fmax,
+                                            _vc.ptr(re), _vc.ptr(im), _vc.ptr(d_fout), _vc.current_stream()))
+    return re, im, d_fout
+
+
+def stft_complex_batch(wav, lens, n_frames=None, win_length=400, hop_length=80, n_fft=None):
+    """Z = stft(wav) for a ragged batch (vc_stft_complex_f32, include/vc_hip.h, "Dereverberation"): exactly the frames
+    stft_filter_batch and stft_power_batch transform -- the same window, reflect padding and frame counts.
+
+    wav, lens, n_frames: as stft_power_batch's.  Returns (re, im, n_frames_device): the spectrum planar and BIN-MAJOR, two
+    float32 tensors [B, 1 + n_fft//2, 1 + Lmax // hop_length], and int32 [B], all on the device; frames at or beyond an
+    utterance's count are 0, and an utterance shorter than the reflect padding has the count 0.  Nothing is copied back and
+    the host waits for nothing."""
+    import torch
+    what = 'stft_complex_batch'
+    B, Lmax, Fmax, plan_key = _check_stft_wave_args(what, wav, lens, n_frames, win_length, hop_length, n_fft)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('stft_complex_batch needs a GPU (no CPU fallback)')
+    plan = _get_voc_plan(*plan_key)
+    wav, d_len, d_nf = _stft_wave_upload(wav, lens, n_frames, B, Lmax)
+    return _stft_complex_launch(plan, wav, d_len, d_nf, Fmax)
+
+
+def _istft_complex_launch(plan, re, im, d_nf):
+    """vc_istft_complex_f32 on validated device tensors (re, im [B, bins, Fmax] float32 contiguous, d_nf int32 [B] or None):
+    y [B, hop * (Fmax - 1)]; no host check, copy or wait in here."""
+    import torch
+    B, _, Fmax = re.shape
+    L = plan.hop_length * (Fmax - 1)
+    out = torch.empty((B, L), dtype=torch.float32, device=re.device)
+    ws = torch.empty(_vc.lib().vc_stft_filter_workspace_bytes(plan.handle, B, Fmax), dtype=torch.uint8, device=re.device)
+    _vc.check(_vc.lib().vc_istft_complex_f32(plan.handle, _vc.ptr(re), _vc.ptr(im), _vc.ptr(d_nf), B, Fmax, _vc.ptr(out), L,
+                                             _vc.ptr(ws), ws.numel(), _vc.current_stream()))
+    return out
+
+
+def _check_spectrum_args(what, re, im, n_frames, n_bins=None):
+    """The host checks of a planar bin-major spectrum and its frame counts: (B, bins, F).  ValueError before the GPU is
+    touched."""
+    import torch
+    if getattr(re, 'ndim', 0) != 3 or getattr(im, 'ndim', 0) != 3 or tuple(re.shape) != tuple(im.shape) or min(re.shape) < 1:
+        raise ValueError(' - ERROR, {}: re and im must be [B, bins, F], of one shape'.format(what))
+    B, nb, Fmax = (int(v) for v in re.shape)
+    if not 2 <= nb <= 2049 or (n_bins is not None and nb != n_bins):
+        raise ValueError(' - ERROR, {}: re and im must hold {} bins, got {}'.format(
+            what, 'between 2 and 2049' if n_bins is None else n_bins, nb))
+    if B > 65535:
+        raise ValueError(' - ERROR, {}: at most 65535 utterances'.format(what))
+    if n_frames is not None and torch.is_tensor(n_frames) and n_frames.is_cuda:
+        if n_frames.dtype != torch.int32 or tuple(n_frames.shape) != (B,):
+            raise ValueError(' - ERROR, {}: n_frames on the device must be int32 [{}]'.format(what, B))
+    elif n_frames is not None:
+        h = np.asarray(n_frames.cpu() if torch.is_tensor(n_frames) else n_frames)
+        if h.shape != (B,) or h.dtype.kind not in 'iu' or h.min() < 0 or h.max() > Fmax:
+            raise ValueError(' - ERROR, {}: n_frames must be {} integers in [0, {}]'.format(what, B, Fmax))
+    return B, nb, Fmax
+
+
+def _spectrum_upload(t):
+    import torch
+    if not torch.is_tensor(t):
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
+    return t.to(device='cuda', dtype=torch.float32).contiguous()
+
+
+def istft_complex_batch(re, im, n_frames, win_length=400, hop_length=80, n_fft=None):
+    """y = istft(re + i im) for a ragged batch, in librosa's sense (vc_istft_complex_f32): the inverse of stft_complex_batch.
+
+    re, im [B, 1 + n_fft//2, F] float32, F >= 2 (numpy or tensor); n_frames: host integers or an int32 [B] device tensor
+    (None = all F).  The imaginary parts of bin 0 and bin n_fft//2 are ignored.  Returns y [B, hop_length * (F - 1)] float32
+    on the device: hop_length * (frames - 1) samples per utterance, zeros beyond; a row of zeros where hop_length *
+    (frames - 1) <= n_fft//2.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    what = 'istft_complex_batch'
+    for v, name in ((win_length, 'win_length'), (hop_length, 'hop_length')):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(' - ERROR, {}: {} must be a positive integer, got {!r}'.format(what, name, v))
+    if n_fft is not None and (isinstance(n_fft, bool) or not isinstance(n_fft, (int, np.integer)) or n_fft < win_length):
+        raise ValueError(' - ERROR, {}: n_fft must be None or an integer >= win_length, got {!r}'.format(what, n_fft))
+    plan_key = (int(win_length), int(hop_length), int(n_fft or win_length))
+    if plan_key[2] % 2 or plan_key[2] > 4096 or plan_key[1] > plan_key[2]:
+        raise ValueError(' - ERROR, {}: need n_fft even, n_fft <= 4096 and hop_length <= n_fft (got {}, {})'.format(
+            what, plan_key[2], plan_key[1]))
+    B, _, Fmax = _check_spectrum_args(what, re, im, n_frames, 1 + plan_key[2] // 2)
+    if Fmax < 2:
+        raise ValueError(' - ERROR, {}: re and im must hold at least 2 frames'.format(what))
+    if not torch.cuda.is_available():
+        raise _vc.VCError('istft_complex_batch needs a GPU (no CPU fallback)')
+    plan = _get_voc_plan(*plan_key)
+    d_nf = None if n_frames is None else _int32_device(n_frames, B, 'n_frames')
+    return _istft_complex_launch(plan, _spectrum_upload(re), _spectrum_upload(im), d_nf)
+
+
 # --------------------------------------------------------------------------- harmonic-plus-noise vocoder
 HnmPlan = collections.namedtuple('HnmPlan', 'voiced inc slope phase flags')
 HnmSynth = collections.namedtuple('HnmSynth', 'y env_log theta plan gain')

@@ -262,7 +262,8 @@ def _numpy_phase(plan, n_bins, both):
     return ph
 
 
-_HOST_NT = namedtuple('convert_host', 'plan B hop n_fft n_bins h_lens h_lens_in h_nsamp utt_ids res_in res_out window_batch denoise')
+_HOST_NT = namedtuple('convert_host', 'plan B hop n_fft n_bins h_lens h_lens_in h_nsamp utt_ids res_in res_out window_batch denoise '
+                                      'dereverb', defaults=(None,))
 _UP_NT = namedtuple('convert_upload', 'wav d_lens d_clip d_nout d_ids d_win d_utt d_true d_extra')
 
 
@@ -320,11 +321,32 @@ def _check_denoise(what, denoise, cfg_d, B):
     return cfg, noise0
 
 
+def _check_dereverb(what, dereverb, cfg_d, Lmax):
+    """dereverb= of a conversion, on the host: None for None / False, else the vc_wpe_cfg.  True means
+    enhance.dereverb_batch's defaults for the data set's framing; a dict holds enhance.wpe_batch's keywords (enhance.WPE_KEYS
+    without return_taps: the conversion returns no predictor).  Lmax: the longest waveform at the model's rate."""
+    if dereverb is None or dereverb is False:
+        return None
+    import enhance
+    if dereverb is True:
+        dereverb = {}
+    if not isinstance(dereverb, dict):
+        raise ValueError(' - ERROR, {}: dereverb must be None, True or a dict of enhance.wpe_batch keywords, got {!r}'.format(
+            what, dereverb))
+    if 'return_taps' in dereverb:
+        raise ValueError(' - ERROR, {}: dereverb: return_taps is not offered here (call enhance.dereverb_batch)'.format(what))
+    hop = int(cfg_d['hop_length'])
+    cfg, _ = enhance.check_wpe_keywords(what + ': dereverb', dereverb, hop, cfg_d['sample_rate'], int(cfg_d['win_length']))
+    enhance._check_wpe_frames(what + ': dereverb', 1 + int(Lmax) // hop, cfg)
+    return cfg
+
+
 def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
-                  res_type, denoise=None):
+                  res_type, denoise=None, dereverb=None):
     """The host checks and tables that convert_batch and convert_duration_batch share, before anything touches the GPU.
-    denoise: the entry point's own argument (_check_denoise); when it is on, every length is cut to whole hops first --
-    len' = hop * (len // hop), what the noise filter returns -- so under one hop is dropped and no frame count changes."""
+    denoise, dereverb: the entry point's own arguments (_check_denoise, _check_dereverb); when either is on, every length is
+    cut to whole hops first -- len' = hop * (len // hop), what the filter and the inverse transform return -- so under one
+    hop is dropped and no frame count changes."""
     import audio_lib
     if getattr(wav, 'ndim', 0) != 2:
         raise ValueError(' - ERROR, {}: wav must be [B, Lmax]'.format(what))
@@ -348,11 +370,13 @@ def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, 
     if h_lens.shape != (B,) or h_lens.min() <= n_fft // 2 or h_lens.max() > Lmax:
         raise ValueError(' - ERROR, {}: lens must be [B] with n_fft//2 < len <= Lmax'.format(what))
     denoise = _check_denoise(what, denoise, cfg_d, B)
-    if denoise is not None:
+    dereverb = _check_dereverb(what, dereverb, cfg_d, Lmax)
+    if denoise is not None or dereverb is not None:
         h_lens = int(cfg_d['hop_length']) * (h_lens // int(cfg_d['hop_length']))
         if h_lens.min() <= n_fft // 2:
-            raise ValueError(' - ERROR, {}: denoise: every utterance needs more than n_fft//2 = {} samples after the cut to '
-                             'whole hops (shortest: {})'.format(what, n_fft // 2, int(h_lens.min())))
+            raise ValueError(' - ERROR, {}: {}: every utterance needs more than n_fft//2 = {} samples after the cut to '
+                             'whole hops (shortest: {})'.format(what, 'denoise' if denoise is not None else 'dereverb', n_fft // 2,
+                                                                int(h_lens.min())))
     if utt_ids is None:
         utt_ids = np.arange(B)
     utt_ids = np.asarray(utt_ids, dtype=np.int64).reshape(-1)
@@ -368,7 +392,7 @@ def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, 
     if vocode and hop * (int(plan.n_out.min()) - 1) <= n_fft // 2:
         raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples'.format(what))
     return _HOST_NT(plan, B, hop, n_fft, 1 + n_fft // 2, h_lens, h_lens_in, hop * (plan.n_out.astype(np.int64) - 1), utt_ids,
-                    res_in, res_out, window_batch, denoise)
+                    res_in, res_out, window_batch, denoise, dereverb)
 
 
 def _convert_upload(h, wav, extra):
@@ -407,9 +431,16 @@ def _denoise_input(h, up, cfg_d, denoise):
     output and h.denoise cleared.  denoise: h.denoise, the checked request of _convert_host (None: nothing is launched).
     Runs right after _resample_input, at the model's rate; an entry point that reads up.wav itself (a tracker, the
     differential filter) calls this before _convert_model, which then finds nothing left to do.  The lengths were cut to
-    whole hops on the host, so the filter's hop * (F - 1) samples are every utterance's whole length."""
+    whole hops on the host, so the filter's hop * (F - 1) samples are every utterance's whole length.
+    h.dereverb (the checked request of _check_dereverb) is served here too, BEFORE the noise suppression and under the same
+    rule: the waveform is replaced by enhance.dereverb_batch's output and h.dereverb cleared.  With both None nothing is
+    launched."""
     import audio_lib
     import enhance
+    if h.dereverb is not None:
+        plan = audio_lib._get_voc_plan(cfg_d['win_length'], h.hop, cfg_d['n_fft'])
+        r = enhance._dereverb_launch(plan, up.wav, up.d_lens, None, 1 + up.wav.shape[1] // h.hop, h.dereverb, False)
+        h, up = h._replace(dereverb=None), up._replace(wav=r.y)
     if denoise is None:
         return h, up
     cfg, noise0 = denoise
@@ -521,7 +552,8 @@ def _resample_output(y, h_nsamp, d_nsamp, res_out, cfg_d, out_sr, res_type):
 
 def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True,
                   giffin_lim_input=False, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64,
-                  vocode=True, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
+                  vocode=True, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None,
+                  dereverb=None):
     """``conversion2`` (two_pass) / ``conversion`` for a ragged batch, waveforms in, waveforms out, on the device.
 
     wav [B, Lmax] float32 (numpy or cuda tensor), lens: host ints (None = all Lmax).  cfg_d: the data-set
@@ -537,6 +569,9 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     wav_sr: the sample rate of ``wav`` (None = cfg_d['sample_rate']); another rate is resampled on the device first
     (audio_lib.resample_batch, ``res_type``), and ``lens`` then count samples at wav_sr.  out_sr: the rate of the returned
     waveforms (None = cfg_d['sample_rate']); n_samples is then reported at out_sr.
+    dereverb: None / False (today's launches and nothing else), True (enhance.dereverb_batch at the defaults of the data
+    set's framing) or a dict of enhance.wpe_batch's keywords: late reverberation is taken out of the input once, at the
+    model's rate and BEFORE the noise suppression, under denoise's rule (lengths cut to whole hops first).
     denoise: None / False (today's launches and nothing else), True (enhance.denoise_batch at its defaults) or a dict of its
     noise-suppression keywords: stationary noise is taken out of the input at the model's rate, right after the input
     resampler, before anything reads the waveform.  Every utterance is first cut to whole hops (under one hop is dropped, no
@@ -554,7 +589,7 @@ def convert_batch(decoder, wav, lens=None, cfg_d=None, t_s=0, t_e=60, n_iter=200
     _need_cfg(cfg_d, what)
     _check_phase(phase, what, None, ('device', 'numpy', 'spsi'))
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
-                      res_type, denoise)
+                      res_type, denoise, dereverb)
     plan, Fout, n_bins = h.plan, h.plan.Fout, h.n_bins
     both = bool(giffin_lim_input)
     _check_phase(phase, what, (h.B, Fout, n_bins), ('device', 'numpy', 'spsi'))
@@ -951,7 +986,8 @@ def _resample_output_device(y, n_samples, max_samples, res_out, cfg_d, out_sr, r
 def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio=None, gap_ratio=1.0, segments='decode',
                            decode=None, out_len=None, max_frames=None, mode='linear', t_s=0, t_e=60, n_iter=200, realse=1.0,
                            two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None, window_batch=64, encoder=None,
-                           wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
+                           wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None,
+                           dereverb=None):
     """``convert_batch`` with the timing changed as well: the stitched spectra are resampled along an integer time map
     (duration_map_batch, time_warp_batch) before the vocoder, which rebuilds the phase for the new timing.
 
@@ -986,7 +1022,7 @@ def convert_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, ratio
         raise ValueError(" - ERROR, {}: mode must be 'linear' or 'nearest', got {!r}".format(what, mode))
     req = _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type, denoise)
+                      res_type, denoise, dereverb)
     plan, B, hop, Fout = h.plan, h.B, h.hop, h.plan.Fout
     req = _duration_bound(what, req, plan.n_out.astype(np.int64), Fout, duration_min_frames(cfg_d), max_frames,
                           'the vocoder needs {}')
@@ -1327,7 +1363,8 @@ def _source_contour(up, d_fout, d_fsrc, Fout, tracker, stats_src, stats_tgt):
 
 def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None,
                         t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0, utt_ids=None,
-                        window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
+                        window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None,
+                        dereverb=None):
     """``convert_batch`` with the melody set as well: after the vocoder the converted waveform's F0
     is tracked (f0_track_batch's launches, at the model's rate and hop), and pitch_shift_batch's launches move it to the
     target before the output is resampled.
@@ -1360,7 +1397,7 @@ def convert_pitch_batch(decoder, wav, lens=None, cfg_d=None, pitch=None, stats_s
     w_floor = _check_w_floor(w_floor, what)
     tracker = _tracker_args(_tracker_keys(f0_args, what), cfg_d['sample_rate'], int(cfg_d['hop_length']), what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type, denoise)
+                      res_type, denoise, dereverb)
     plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
     Lout = hop * (Fout - 1)
     _check_pitch_sizes(B, Lout, Fout, hop, what)
@@ -1405,7 +1442,8 @@ _HNM_NT = namedtuple('convert_hnm', _BATCH_NT._fields + ('f0_target', 'env_log',
 def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats_src=None, stats_tgt=None, f0_args=None, order=24,
                       iters=16, voiced_cutoff_hz=4000.0, noise_level=1.0, realse=1.0, floor=1e-5, f0_lo=40.0, f0_hi=None, t_s=0,
                       t_e=60, two_pass=True, seed=0, utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None,
-                      res_type='kaiser_best', denoise=None):
+                      res_type='kaiser_best', denoise=None,
+                      dereverb=None):
     """``convert_batch`` with the harmonic-plus-noise vocoder in Griffin-Lim's place: the decoder's
     spectrum gives the envelope, an F0 contour the excitation, and audio_lib.hnm_synth_batch's launches write the waveform
     in one pass -- no phase iteration, and the pitch is the one asked for.
@@ -1434,7 +1472,7 @@ def convert_hnm_batch(decoder, wav, lens=None, cfg_d=None, pitch='source', stats
     sr, hop = int(cfg_d['sample_rate']), int(cfg_d['hop_length'])
     tracker = None if kind == 'contour' else _tracker_args(_tracker_keys(f0_args, what), sr, hop, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type, denoise)
+                      res_type, denoise, dereverb)
     plan, B, Fout, n_bins = h.plan, h.B, h.plan.Fout, h.n_bins
     n_fft, order, iters, floor = audio_lib._check_envelope_args(what, (B, Fout, n_bins), h.n_fft, order, iters, floor)
     _, _, f0_lo, f0_hi = audio_lib._check_plan_args(what, (B, Fout), sr, hop, f0_lo, f0_hi)
@@ -1569,7 +1607,8 @@ def diff_frames(plan, hop):
 
 def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None,
                        stats_src=None, stats_tgt=None, w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None,
-                       window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
+                       window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None,
+                       dereverb=None):
     """``convert_batch`` without a vocoder: the source recording is FILTERED by the difference between
     the converted and the source spectral envelope (diff_gain_batch, audio_lib.stft_filter_batch), so its excitation and
     phase stay natural and the waveform costs one transform pass instead of a Griffin-Lim run.  t_s is fixed at 0: output
@@ -1583,6 +1622,7 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
       [B, Fout] floats   the contour to reach, in Hz per frame, 0 = leave the frame as it is;
       'source'           the source's own contour mapped by f0_transform(., stats_src, stats_tgt): both are required.
     w_floor, f0_args: as convert_pitch_batch.  The other arguments are convert_batch's.
+    dereverb: as convert_batch's; the room of the source recording would otherwise pass straight to the output.
     denoise: as convert_batch's -- here it matters most: the filter passes the SOURCE recording, so with denoise the tracker
     and the filter read the denoised waveform, and mel_true / stft_true (hence the gain) are those of the denoised input.
     Returns a namedtuple: y_wav_pred [B, hop * (Fout - 1)] (the filtered source at the level convert_batch sets,
@@ -1609,7 +1649,7 @@ def convert_diff_batch(decoder, wav, lens=None, cfg_d=None, alpha=1.0, max_boost
     w_floor = _check_w_floor(w_floor, what)
     f0_kw = _tracker_keys(f0_args, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type,
-                      denoise)
+                      denoise, dereverb)
     plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
     n_use, h_nsamp = diff_frames(plan, hop)
     if int(h_nsamp.min()) <= h.n_fft // 2:
@@ -1813,7 +1853,8 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
                                 decode=None, out_len=None, max_frames=None, group=2, tol=None, qscale=32768.0, alpha=1.0,
                                 max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None, stats_src=None, stats_tgt=None,
                                 w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None, window_batch=64, encoder=None,
-                                wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None):
+                                wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None,
+                                dereverb=None):
     """``convert_diff_batch`` with the timing changed as well: the source is filtered exactly as there
     (gain, filter, level, and ``pitch=`` before the filter), then the FILTERED WAVEFORM is moved along an integer time map by
     time_scale_batch -- grains of the natural recording, so its excitation and local phase survive -- and only then
@@ -1832,7 +1873,7 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
     _need_cfg(cfg_d, what)
     req = _duration_request(what, rate, ratio, gap_ratio, segments, decode, out_len)
     h = _convert_host(what, decoder, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type,
-                      denoise)
+                      denoise, dereverb)
     B, hop, Fout = h.B, h.hop, h.plan.Fout
     n_use, h_nsamp = diff_frames(h.plan, hop)
     req = _duration_bound(what, req, n_use, Fout, 2, max_frames, 'at least {} are needed')
@@ -1844,7 +1885,7 @@ def convert_diff_duration_batch(decoder, wav, lens=None, cfg_d=None, rate=None, 
     d = convert_diff_batch(decoder, wav, lens=lens, cfg_d=cfg_d, alpha=alpha, max_boost_db=max_boost_db, max_cut_db=max_cut_db,
                            half_width=half_width, pitch=pitch, stats_src=stats_src, stats_tgt=stats_tgt, w_floor=w_floor,
                            f0_args=f0_args, t_e=t_e, two_pass=two_pass, utt_ids=utt_ids, window_batch=window_batch, encoder=encoder,
-                           wav_sr=wav_sr, out_sr=None, res_type=res_type, denoise=denoise)
+                           wav_sr=wav_sr, out_sr=None, res_type=res_type, denoise=denoise, dereverb=dereverb)
     d_nuse = _i32_device(n_use, (B,), what + ': n_use')
     d_nsamp = _i32_device(h_nsamp, (B,), what + ': n_samples')
     wsola_window(group * hop, d.y_wav_pred.device)
@@ -1866,7 +1907,7 @@ _POST_NT = namedtuple('convert_postfilter', _BATCH_NT._fields + ('stft_raw',))
 def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mode='ms', k=0.85, alpha=1.0, max_db=20.0, g_max=4.0,
                              t_s=0, t_e=60, n_iter=200, realse=1.0, two_pass=True, momentum=0.0, phase='device', seed=0,
                              utt_ids=None, window_batch=64, encoder=None, wav_sr=None, out_sr=None, res_type='kaiser_best',
-                             denoise=None):
+                             denoise=None, dereverb=None):
     """``convert_batch`` with the predicted spectrum postfiltered before the vocoder: the stitched ``stft_pred`` goes through
     postfilter.apply_batch (mode 'ms', 'gv' or 'ms+gv'; k, alpha, max_db, g_max are its arguments) with the frame counts the
     device already holds, then through vc_power_to_amp (``realse`` still applies) and the vocoder.
@@ -1892,7 +1933,7 @@ def convert_postfilter_batch(decoder, wav, lens=None, cfg_d=None, model=None, mo
     _check_phase(phase, what)
     postfilter.check_apply_args(mode, k, alpha, max_db, g_max, what)
     h = _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr,
-                      res_type, denoise)
+                      res_type, denoise, dereverb)
     plan, Fout, n_bins = h.plan, h.plan.Fout, h.n_bins
     if Fout > postfilter.MAX_FRAMES:
         raise ValueError(' - ERROR, {}: at most {} stitched frames per utterance (got {})'.format(what, postfilter.MAX_FRAMES, Fout))
@@ -1919,7 +1960,8 @@ _GMM_DIFF_NT = namedtuple('convert_gmm_diff', 'y_wav_pred n_samples mel_true cep
 
 
 def convert_gmm_diff_batch(model, wav, lens=None, cfg_d=None, mixture='soft', mlpg=True, alpha=1.0, max_boost_db=20.0, max_cut_db=30.0,
-                           wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None, n_coef=None, first_coef=1):
+                           wav_sr=None, out_sr=None, res_type='kaiser_best', denoise=None, n_coef=None, first_coef=1,
+                           dereverb=None):
     """Waveform in, waveform out, with no encoder and no decoder: the source's mel cepstra are
     converted by a joint-density mixture (mapping.fit / mapping.fit_wav; mapping.convert_cepstra_batch with ``mixture`` and
     ``mlpg``), the cepstral difference becomes the gain of the differential filter (mapping.cepstra_gain_batch with alpha,
@@ -1927,7 +1969,7 @@ def convert_gmm_diff_batch(model, wav, lens=None, cfg_d=None, mixture='soft', ml
     The framing is convert_diff_batch's with every frame used: frame u of the gain is frame u of the source's front-end,
     n_frames = 1 + len // hop per utterance and the output holds hop * (n_frames - 1) samples of it.
 
-    model: a mapping.JDGMM over D = 2 n features; n_coef: None = n.  wav, lens, wav_sr, out_sr, res_type, denoise: as
+    model: a mapping.JDGMM over D = 2 n features; n_coef: None = n.  wav, lens, wav_sr, out_sr, res_type, denoise, dereverb: as
     convert_diff_batch's.  Pitch and durations are not offered here: call pitch_shift_batch / time_scale_batch on the result.
     Returns a namedtuple: y_wav_pred [B, hop * (Fmax - 1)] (the filtered source at the level convert_batch sets, zero beyond
     an utterance's n_samples), n_samples (host, at out_sr when given), mel_true [B, Fmax, n_mels], cep_src and cep_pred
@@ -1965,7 +2007,8 @@ def convert_gmm_diff_batch(model, wav, lens=None, cfg_d=None, mixture='soft', ml
     if res_in:
         h_lens_in, h_lens, Lmax = h_lens, audio_lib.resample_len(h_lens, wav_sr, sr), int(audio_lib.resample_len(Lmax, wav_sr, sr))
     denoise = _check_denoise(what, denoise, cfg_d, B)
-    if denoise is not None:
+    dereverb = _check_dereverb(what, dereverb, cfg_d, Lmax)
+    if denoise is not None or dereverb is not None:
         h_lens = hop * (h_lens // hop)
     n_use = 1 + h_lens // hop
     h_nsamp = hop * (n_use - 1)
@@ -1984,7 +2027,7 @@ def convert_gmm_diff_batch(model, wav, lens=None, cfg_d=None, mixture='soft', ml
     d_lens, d_nuse, d_nsamp = tabs[-3:]
     d_i0, d_w = mapping._gain_upload(i0, w)
     model = mapping._model_to_device(model)
-    h = _HOST_NT(None, B, hop, n_fft, 1 + n_fft // 2, h_lens, h_lens_in, h_nsamp, None, res_in, res_out, None, denoise)
+    h = _HOST_NT(None, B, hop, n_fft, 1 + n_fft // 2, h_lens, h_lens_in, h_nsamp, None, res_in, res_out, None, denoise, dereverb)
     up = _UP_NT(wav, d_lens, None, None, None, None, None, None, tabs[:1])
     h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)
     h, up = _denoise_input(h, up, cfg_d, h.denoise)

@@ -351,6 +351,66 @@ __device__ __forceinline__ void sf_gather_tile(const SfArgs& a, const float* x, 
     }
 }
 
+// The inverse half of the 400-point tile kernels and the generic path's two sums as functions: what the complex STFT and its
+// inverse (further down) are made of.  The filter and power kernels below hold the same statements in line and keep them:
+// moved onto functions they compile to other contraction choices (seen in their ISA), so their outputs would change in
+// the last bit; for the same reason the complex STFT repeats the power kernel's forward half word for word -- the two
+// must produce the same re and im.  Are / Aim are the tile's [VG * 13][VA_STRIDE] rows, tw the plan's [2][208] twiddles.
+// the 16 slots zr / zi of row tid < VG * 13: inverse 16-point stage, conjugate twiddle -> B[k1][n2] in A's place
+__device__ __forceinline__ void sf_inverse400_cols(float* zr, float* zi, const float* tw, float* Are, float* Aim, int tid, int k1) {
+    float yr[16], yi[16];
+    vcfe::cidft16(zr, zi, yr, yi);
+#pragma unroll
+    for (int n2 = 0; n2 < 16; ++n2) {
+        vcfe::cmul(yr[n2], yi[n2], tw[k1 * 16 + n2], -tw[208 + k1 * 16 + n2]);
+        Are[VA_STRIDE * tid + n2] = yr[n2];
+        Aim[VA_STRIDE * tid + n2] = yi[n2];
+    }
+}
+
+// thread (g, n2), g < nvalid: hermitian 25-point inverse, synthesis window, store the frame; tile: the first frame's [400]
+__device__ __forceinline__ void sf_inverse400_rows(const float* Are, const float* Aim, const float* win, float* tile, int nvalid,
+                                                   int tid) {
+    const int g = tid >> 4, n2 = tid & 15;
+    if (g < nvalid) {
+        float br[13], bi[13], x[25];
+        const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+        for (int k1 = 0; k1 < 13; ++k1) { br[k1] = Are[i0 + VA_STRIDE * k1]; bi[k1] = Aim[i0 + VA_STRIDE * k1]; }
+        vcfe::hdft25_real(br, bi, x);
+        float* out = tile + (size_t)g * 400 + n2;
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) out[16 * n1] = x[n1] * win[16 * n1 + n2] * (1.0f / 400.0f);
+    }
+}
+
+// The generic path's two sums.  Bin k of the frame at xp: sum_n (x[n] w[n]) exp(-2 pi i k n / N)
+__device__ __forceinline__ void sf_forward_generic_bin(const float* xp, const float* win, const float* twr, const float* twi, int k,
+                                                       int N, float& re, float& im) {
+    re = 0.0f; im = 0.0f;
+    int m = 0;
+    for (int n = 0; n < N; ++n) {
+        const float xv = xp[n] * win[n];
+        re = fmaf(xv, twr[m], re);
+        im = fmaf(xv, twi[m], im);
+        m += k; if (m >= N) m -= N;
+    }
+}
+
+// Sample n of the windowed inverse of the spectrum sr / si [nb]; the imaginary parts of bin 0 and bin N / 2 are not read
+__device__ __forceinline__ float sf_inverse_generic_sample(const float* sr, const float* si, const float* win, const float* twr,
+                                                           const float* twi, int n, int N, int nb, float invN) {
+    float acc = 0.0f;
+    int m = n;
+    for (int k = 1; k < nb - 1; ++k) {
+        acc = fmaf(sr[k], twr[m], acc);
+        acc = fmaf(si[k], twi[m], acc);
+        m += n; if (m >= N) m -= N;
+    }
+    const float edge = sr[0] + ((n & 1) ? -sr[nb - 1] : sr[nb - 1]);
+    return (edge + 2.0f * acc) * invN * win[n];
+}
+
 __global__ void __launch_bounds__(VT)
 stft_filter400_kernel(SfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -603,6 +663,219 @@ stft_power_generic_kernel(SfArgs a, float* __restrict__ power) {
             }
         }
         dst[idx] = re * re + im * im;
+    }
+}
+
+// ---- complex STFT and its inverse (include/vc_hip.h, "Dereverberation"): the two halves of the filter kernels on their
+// own, with the spectrum in global memory between them, planar and BIN-MAJOR: re, im [B][nb][maxF].  A tile of 16 frames
+// goes through LDS as [bin][16], so every bin's run of the tile is 64 contiguous bytes on either side.
+constexpr int ZT = 201 * VG;                           // elements of a 400-point tile, [bin][VG]
+static_assert(ZT <= VG * 13 * VA_STRIDE, "the spectrum tile must fit the transform's rows");
+
+__global__ void __launch_bounds__(VT)
+stft_complex400_kernel(SfArgs a, float* __restrict__ re, float* __restrict__ im) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NROW = VG * 13;
+    float* win = reinterpret_cast<float*>(smem);       // [400]
+    float* tw = win + 400;                             // [2][208]
+    float* Are = tw + 416;                             // [NROW*17]; later the tile's spectrum [201][VG]
+    float* Aim = Are + NROW * VA_STRIDE;
+    float* xs = Aim + NROW * VA_STRIDE;                // [span]
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int len;
+    const int F = sf_frames(a, b, len);
+    const int f0 = blockIdx.x * VG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    const int ncols = min(VG, a.maxF - f0);            // frames of the outputs this tile owns
+    const size_t base = (size_t)b * 201 * a.maxF + f0;
+    if (f0 >= F) {
+        for (int i = tid; i < ZT; i += VT) {
+            const int bin = i >> 4, g = i & 15;
+            if (g < ncols) { re[base + (size_t)bin * a.maxF + g] = 0.0f; im[base + (size_t)bin * a.maxF + g] = 0.0f; }
+        }
+        return;
+    }
+    const int nvalid = min(VG, F - f0);
+
+    copy_lds(win, a.window, 816);
+    __syncthreads();
+    sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
+    __syncthreads();
+    // The forward half in stft_power400_kernel's own words, not in a function: the two launches must store and
+    // square the SAME re and im, and the compiler contracts the same statements differently once they sit in a function.
+    {   // forward step 1+2: thread (g, n2)
+        const int g = tid >> 4, n2 = tid & 15;
+        const float* xp = xs + g * a.hop + n2;
+        float v[25], ar[13], ai[13];
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
+        vcfe::rdft25_13(v, ar, ai);
+        const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+        for (int k1 = 0; k1 < 13; ++k1) {
+            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
+            Are[i0 + VA_STRIDE * k1] = ar[k1];
+            Aim[i0 + VA_STRIDE * k1] = ai[k1];
+        }
+    }
+    __syncthreads();
+    // thread (g, k1): forward 16-point stage; its 16 slots are the bins k1 + 25 k2 and the mirrors of those above 200
+    float yr[16], yi[16];
+    if (tid < NROW) {
+        float zr[16], zi[16];
+#pragma unroll
+        for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = Are[VA_STRIDE * tid + n2]; zi[n2] = Aim[VA_STRIDE * tid + n2]; }
+        vcfe::cdft16(zr, zi, yr, yi);
+    }
+    __syncthreads();                                   // every row of Are has been read
+    if (tid < NROW) {
+        const int g = tid / 13, k1 = tid - g * 13;
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            bool cj;
+            const int bin = vcfe::src_bin(k1, k2, cj);
+            // a slot above 200 holds the conjugate of its bin; each bin is stored by one slot (stft_power400_kernel)
+            if (!cj || k1 != 0) {
+                Are[bin * VG + g] = yr[k2];
+                Aim[bin * VG + g] = cj ? -yi[k2] : yi[k2];
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < ZT; i += VT) {
+        const int bin = i >> 4, g = i & 15;
+        if (g < ncols) {
+            re[base + (size_t)bin * a.maxF + g] = g < nvalid ? Are[i] : 0.0f;
+            im[base + (size_t)bin * a.maxF + g] = g < nvalid ? Aim[i] : 0.0f;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(VT)
+stft_complex_generic_kernel(SfArgs a, float* __restrict__ re, float* __restrict__ im) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int N = a.N, nb = a.nb;
+    float* win = reinterpret_cast<float*>(smem);       // [N]
+    float* twr = win + N;                              // [N]
+    float* twi = twr + N;                              // [N]
+    float* xs = twi + N;                               // [span]
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int len;
+    const int F = sf_frames(a, b, len);
+    const int f0 = blockIdx.x * VGG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    const int ncols = min(VGG, a.maxF - f0);
+    const int nvalid = min(VGG, max(F - f0, 0));
+    const size_t base = (size_t)b * nb * a.maxF + f0;
+    if (nvalid > 0) {
+        copy_lds(win, a.window, N);
+        copy_lds(twr, a.window + N + 416, 2 * N);
+        __syncthreads();
+        sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
+        __syncthreads();
+    }
+    for (int idx = tid; idx < VGG * nb; idx += VT) {
+        const int k = idx / VGG, g = idx - k * VGG;
+        if (g >= ncols) continue;
+        float vr = 0.0f, vi = 0.0f;
+        if (g < nvalid) sf_forward_generic_bin(xs + g * a.hop, win, twr, twi, k, N, vr, vi);
+        re[base + (size_t)k * a.maxF + g] = vr;
+        im[base + (size_t)k * a.maxF + g] = vi;
+    }
+}
+
+// The inverse half.  F_b = n_frames[b] clamped to [0, maxF] (null: maxF), 0 under the filter's "short" rule.
+struct IzArgs {
+    const float* re;         // [B][nb][maxF]
+    const float* im;
+    const int32_t* n_frames; // [B] or null
+    float* frames;           // [B][maxF][N]
+    int32_t* f_out;          // [B]: F_b for the overlap-add launch behind this one
+    const float* window;     // [N] | tw400[416] | twg[2N]
+    int maxF, nb, N, hop;
+};
+
+__device__ __forceinline__ int iz_frames(const IzArgs& a, int b) {
+    const int F = a.n_frames ? min(max(a.n_frames[b], 0), a.maxF) : a.maxF;
+    return a.hop * (F - 1) <= a.N / 2 ? 0 : F;
+}
+
+__global__ void __launch_bounds__(VT)
+istft_complex400_kernel(IzArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int NROW = VG * 13;
+    float* win = reinterpret_cast<float*>(smem);       // [400]
+    float* tw = win + 400;                             // [2][208]
+    float* Are = tw + 416;                             // the tile's spectrum [201][VG], then [NROW*17]
+    float* Aim = Are + NROW * VA_STRIDE;
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int F = iz_frames(a, b);
+    const int f0 = blockIdx.x * VG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    if (f0 >= F) return;
+    const int nvalid = min(VG, F - f0);
+
+    copy_lds(win, a.window, 816);
+    const size_t base = (size_t)b * 201 * a.maxF + f0;
+    for (int i = tid; i < ZT; i += VT) {
+        const int bin = i >> 4, g = i & 15;
+        const bool live = g < nvalid;
+        Are[i] = live ? a.re[base + (size_t)bin * a.maxF + g] : 0.0f;
+        // the imaginary parts of bin 0 and bin N / 2 are not read: a real frame has none
+        Aim[i] = live && bin != 0 && bin != 200 ? a.im[base + (size_t)bin * a.maxF + g] : 0.0f;
+    }
+    __syncthreads();
+    float zr[16], zi[16];
+    const int gq = min(tid / 13, VG - 1), k1 = tid - (tid / 13) * 13;
+    if (tid < NROW) {
+#pragma unroll
+        for (int k2 = 0; k2 < 16; ++k2) {
+            bool cj;
+            const int bin = vcfe::src_bin(k1, k2, cj);
+            zr[k2] = Are[bin * VG + gq];
+            zi[k2] = cj ? -Aim[bin * VG + gq] : Aim[bin * VG + gq];
+        }
+    }
+    __syncthreads();                                   // the whole tile has been read
+    if (tid < NROW) sf_inverse400_cols(zr, zi, tw, Are, Aim, tid, k1);
+    __syncthreads();
+    sf_inverse400_rows(Are, Aim, win, a.frames + ((size_t)b * a.maxF + f0) * 400, nvalid, tid);
+}
+
+__global__ void __launch_bounds__(VT)
+istft_complex_generic_kernel(IzArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int N = a.N, nb = a.nb;
+    float* win = reinterpret_cast<float*>(smem);       // [N]
+    float* twr = win + N;                              // [N]
+    float* twi = twr + N;                              // [N]
+    float* Sr = twi + N;                               // [VGG][nb]
+    float* Si = Sr + VGG * nb;
+
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int F = iz_frames(a, b);
+    const int f0 = blockIdx.x * VGG;
+    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
+    if (f0 >= F) return;
+    const int nvalid = min(VGG, F - f0);
+    copy_lds(win, a.window, N);
+    copy_lds(twr, a.window + N + 416, 2 * N);
+    const size_t base = (size_t)b * nb * a.maxF + f0;
+    for (int idx = tid; idx < VGG * nb; idx += VT) {
+        const int k = idx / VGG, g = idx - k * VGG;
+        const bool live = g < nvalid;
+        Sr[g * nb + k] = live ? a.re[base + (size_t)k * a.maxF + g] : 0.0f;
+        Si[g * nb + k] = live ? a.im[base + (size_t)k * a.maxF + g] : 0.0f;
+    }
+    __syncthreads();
+    const float invN = 1.0f / (float)N;
+    for (int idx = tid; idx < nvalid * N; idx += VT) {
+        const int g = idx / N, n = idx - g * N;
+        a.frames[((size_t)b * a.maxF + f0 + g) * N + n] =
+            sf_inverse_generic_sample(Sr + g * nb, Si + g * nb, win, twr, twi, n, N, nb, invN);
     }
 }
 
@@ -1084,6 +1357,62 @@ int vc_stft_power_f32(const vc_vocoder_plan* p, const float* d_wav, int32_t wav_
     const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
     if (fast) hipLaunchKernelGGL(stft_power400_kernel, grid, dim3(VT), p->smem400, st, a, d_power);
     else hipLaunchKernelGGL(stft_power_generic_kernel, grid, dim3(VT), p->smem_gen, st, a, d_power);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+int vc_stft_complex_f32(const vc_vocoder_plan* p, const float* d_wav, int32_t wav_stride, const int32_t* d_len,
+                        const int32_t* d_n_frames, int32_t batch, int32_t max_frames, float* d_re, float* d_im,
+                        int32_t* d_frames_out, void* stream) {
+    const char* fn = "vc_stft_complex_f32";
+    VC_REQUIRE(p && d_wav && d_len && d_re && d_im && d_frames_out, "%s: NULL argument", fn);
+    VC_REQUIRE(batch >= 1 && batch <= 65535 && max_frames >= 1 && wav_stride >= 1,
+               "%s: bad shape (batch %d in [1, 65535], max_frames %d >= 1, wav_stride %d >= 1)", fn, batch, max_frames, wav_stride);
+    VC_REQUIRE((long long)p->hop * (max_frames - 1) + p->N < (1ll << 31), "%s: %d frames exceed 2^31 samples", fn, max_frames);
+    const bool fast = (p->N == 400);
+    if (int rc = vc::allow_dynamic_lds<stft_complex400_kernel, stft_complex_generic_kernel>(160 * 1024)) return rc;
+    SfArgs a;
+    a.wav = d_wav; a.len = d_len; a.gain = nullptr; a.n_frames = d_n_frames; a.frames = nullptr; a.f_out = d_frames_out;
+    a.window = p->d_tables;
+    a.wav_stride = wav_stride; a.maxF = max_frames; a.nb = p->nb; a.N = p->N; a.hop = p->hop;
+    a.span = fast ? p->span : p->span_g;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
+    if (fast) hipLaunchKernelGGL(stft_complex400_kernel, grid, dim3(VT), p->smem400, st, a, d_re, d_im);
+    else hipLaunchKernelGGL(stft_complex_generic_kernel, grid, dim3(VT), p->smem_gen, st, a, d_re, d_im);
+    VC_HIP_CHECK(hipGetLastError());
+    return VC_OK;
+}
+
+int vc_istft_complex_f32(const vc_vocoder_plan* p, const float* d_re, const float* d_im, const int32_t* d_n_frames,
+                         int32_t batch, int32_t max_frames, float* d_out, int32_t out_stride, void* d_workspace,
+                         size_t workspace_bytes, void* stream) {
+    const char* fn = "vc_istft_complex_f32";
+    VC_REQUIRE(p && d_re && d_im && d_out && d_workspace, "%s: NULL argument", fn);
+    VC_REQUIRE(batch >= 1 && batch <= 65535 && max_frames >= 1, "%s: bad shape (batch %d in [1, 65535], max_frames %d >= 1)", fn,
+               batch, max_frames);
+    VC_REQUIRE((long long)p->hop * (max_frames - 1) + p->N < (1ll << 31), "%s: %d frames exceed 2^31 samples", fn, max_frames);
+    VC_REQUIRE(out_stride >= p->hop * (max_frames - 1) && out_stride >= 1, "%s: out_stride %d < %d samples", fn, out_stride,
+               p->hop * (max_frames - 1));
+    VC_REQUIRE(((uintptr_t)d_workspace & 3) == 0, "%s: workspace must be 4-byte aligned", fn);
+    if (workspace_bytes < vc_stft_filter_workspace_bytes(p, batch, max_frames))
+        return vc::set_error(VC_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes,
+                             vc_stft_filter_workspace_bytes(p, batch, max_frames));
+    const bool fast = (p->N == 400);
+    if (int rc = vc::allow_dynamic_lds<istft_complex400_kernel, istft_complex_generic_kernel>(160 * 1024)) return rc;
+    IzArgs a;
+    a.re = d_re; a.im = d_im; a.n_frames = d_n_frames;
+    a.frames = reinterpret_cast<float*>(d_workspace);
+    a.f_out = reinterpret_cast<int32_t*>((char*)d_workspace + sf_frames_bytes(p, batch, max_frames));
+    a.window = p->d_tables;
+    a.maxF = max_frames; a.nb = p->nb; a.N = p->N; a.hop = p->hop;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(((unsigned)max_frames + (fast ? VG : VGG) - 1) / (fast ? VG : VGG), (unsigned)batch);
+    if (fast) hipLaunchKernelGGL(istft_complex400_kernel, grid, dim3(VT), p->smem400, st, a);
+    else hipLaunchKernelGGL(istft_complex_generic_kernel, grid, dim3(VT), p->smem_gen, st, a);
+    const dim3 ogrid(((unsigned)out_stride + VT - 1) / VT, (unsigned)batch);
+    hipLaunchKernelGGL(gl_ola_kernel, ogrid, dim3(VT), (size_t)p->N * sizeof(float), st, a.frames, a.f_out, p->d_tables,
+                       max_frames, p->N, p->hop, p->nov, d_out, out_stride, (const float*)nullptr, 0, (float*)nullptr);
     VC_HIP_CHECK(hipGetLastError());
     return VC_OK;
 }

@@ -1,5 +1,6 @@
-"""Noise suppression on the device (include/vc_hip.h, "Noise suppression"): stationary noise taken out of a waveform before it
-is analysed or converted.  Three launches and the overlap-add:
+"""Noise suppression and dereverberation on the device: what is taken out of a waveform before it is analysed or converted.
+
+Noise suppression (include/vc_hip.h, "Noise suppression"): stationary noise.  Three launches and the overlap-add:
 
     power   P = |stft(x)|^2                                     audio_lib.stft_power_batch   (vc_stft_power_f32)
     gain    noise tracker + suppression rule, one scan in time  noise_gain_batch             (vc_noise_gain_f32)
@@ -8,7 +9,20 @@ is analysed or converted.  Three launches and the overlap-add:
 The tracker is Gerkmann & Hendriks' speech-presence-probability estimator (2012), the rule Ephraim & Malah's log-MMSE
 amplitude estimator (or the Wiener gain) on the decision-directed a-priori SNR with Cappe's lower limit.  The defaults are
 the literature's, carried to this project's 5 ms hop (``smoothing``); nobody has listened to anything they produce.
-tests/denoise_ref.py restates both new launches in numpy.  There is no CPU fallback: without a GPU every call raises."""
+tests/denoise_ref.py restates both new launches in numpy.
+
+Dereverberation (include/vc_hip.h, "Dereverberation"): late reverberation, which follows the speech and which no noise
+tracker sees.  Weighted prediction error (Nakatani et al. 2010; nara_wpe's formulation): per bin a delayed linear predictor
+over past frames, re-weighted least squares, subtracted.  It sits in front of the noise suppression:
+
+    stft    Z = stft(x), planar and bin-major                   audio_lib.stft_complex_batch   (vc_stft_complex_f32)
+    wpe     the solver, one workgroup per (utterance, bin)      wpe_batch                      (vc_wpe_f32)
+    istft   y = istft(Z'), then the overlap-add                 audio_lib.istft_complex_batch  (vc_istft_complex_f32)
+
+Delay and taps are carried to this project's 5 ms hop (``wpe_defaults``); nobody has listened to anything this produces.
+tests/dereverb_ref.py restates the three launches in numpy.
+
+There is no CPU fallback: without a GPU every call raises."""
 import collections
 import math
 
@@ -169,3 +183,145 @@ def denoise_batch(wav, lens, sr=16000, win_length=400, hop_length=80, n_fft=None
     plan = audio_lib._get_voc_plan(*plan_key)
     wav, d_len, d_nf = audio_lib._stft_wave_upload(wav, lens, n_frames, B, Lmax)
     return _denoise_launch(plan, wav, d_len, d_nf, Fmax, cfg, None if noise0 is None else _as_cuda_f32(noise0), return_noise)
+
+
+# --------------------------------------------------------------------------- dereverberation
+WPE_MAX_TAPS, WPE_MAX_DELAY, WPE_MAX_ITERATIONS, WPE_MAX_CONTEXT = 32, 64, 16, 8     # include/vc_hip.h, vc_wpe_f32
+WPE_KEYS = ('taps', 'delay', 'iterations', 'context', 'floor_db', 'load', 'return_taps')
+_WPE_NT = collections.namedtuple('wpe', 're im status taps')
+_DEREVERB_NT = collections.namedtuple('dereverb', 'y n_frames status taps')
+
+
+def wpe_defaults(hop_length, sr, win_length, span_ms=80.0):
+    """(taps, delay) of the WPE predictor for this framing: delay = ceil(win_length / hop_length), taps = round(span_ms * sr /
+    1000 / hop_length), both clamped to the launch's limits (32 taps, 64 frames).
+
+    A prediction that starts inside the analysis window of the frame it predicts cancels the speech itself: frames closer
+    than one window share samples with it, so the delay is counted in windows, not in frames.  nara_wpe's 10 taps and delay
+    3 are meant for an 8 ms hop: 80 ms of history behind a window.  This is ``smoothing``'s argument made for WPE -- a constant
+    that was chosen at another hop is a time, and is carried over as a time.  At the shipped 400 / 80 / 16 kHz it gives
+    (16, 5)."""
+    for v, name in ((hop_length, 'hop_length'), (sr, 'sr'), (win_length, 'win_length'), (span_ms, 'span_ms')):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v <= 0:
+            raise ValueError(' - ERROR, wpe_defaults: {} must be a positive number, got {!r}'.format(name, v))
+    delay = int(math.ceil(float(win_length) / float(hop_length)))
+    taps = int(round(float(span_ms) * float(sr) / 1000.0 / float(hop_length)))
+    return min(max(taps, 1), WPE_MAX_TAPS), min(max(delay, 1), WPE_MAX_DELAY)
+
+
+def _wpe_int(v, what, name, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(' - ERROR, {}: {} must be an integer in [{}, {}], got {!r}'.format(what, name, lo, hi, v))
+    return int(v)
+
+
+def wpe_cfg(what, taps=None, delay=None, iterations=3, context=1, floor_db=-60.0, load=1e-8, hop_length=80, sr=16000,
+            win_length=400):
+    """The checked vc_wpe_cfg of a wpe_batch call (ValueError otherwise; no GPU).  taps / delay None: those of
+    ``wpe_defaults(hop_length, sr, win_length)``.  floor_db: the floor of the weight relative to the bin's mean power, in dB
+    (in [-200, 0]); load: the diagonal loading relative to the mean of the diagonal (in [0, 1])."""
+    d_taps, d_delay = wpe_defaults(hop_length, sr, win_length)
+    taps = d_taps if taps is None else _wpe_int(taps, what, 'taps', 1, WPE_MAX_TAPS)
+    delay = d_delay if delay is None else _wpe_int(delay, what, 'delay', 1, WPE_MAX_DELAY)
+    iterations = _wpe_int(iterations, what, 'iterations', 1, WPE_MAX_ITERATIONS)
+    context = _wpe_int(context, what, 'context', 0, WPE_MAX_CONTEXT)
+    floor_db, load = _number(floor_db, what, 'floor_db'), _number(load, what, 'load')
+    if not -200.0 <= floor_db <= 0.0:
+        raise ValueError(' - ERROR, {}: floor_db (relative to the mean power, in dB) must be in [-200, 0], got {!r}'.format(what, floor_db))
+    if not 0.0 <= load <= 1.0:
+        raise ValueError(' - ERROR, {}: load must be in [0, 1], got {!r}'.format(what, load))
+    return _vc.WpeCfg(taps, delay, iterations, context, 10.0 ** (floor_db / 10.0), load)
+
+
+def wpe_max_frames(taps):
+    """The most frames vc_wpe_f32 takes with this many taps (a bin's frames live in LDS): vc_wpe_max_frames, host only."""
+    return int(_vc.lib().vc_wpe_max_frames(_wpe_int(taps, 'wpe_max_frames', 'taps', 1, WPE_MAX_TAPS)))
+
+
+def check_wpe_keywords(what, kw, hop_length, sr, win_length):
+    """The wpe_batch keywords of a dereverberation request (a dict) checked on the host: (cfg, return_taps)."""
+    bad = sorted(set(kw) - set(WPE_KEYS))
+    if bad:
+        raise ValueError(' - ERROR, {}: unknown dereverberation keyword(s) {}; known: {}'.format(what, ', '.join(bad),
+                                                                                              ', '.join(WPE_KEYS)))
+    args = {k: v for k, v in kw.items() if k != 'return_taps'}
+    return wpe_cfg(what, hop_length=hop_length, sr=sr, win_length=win_length, **args), bool(kw.get('return_taps', False))
+
+
+def _check_wpe_frames(what, Fmax, cfg):
+    cap = wpe_max_frames(cfg.taps)
+    if Fmax > cap:
+        raise ValueError(' - ERROR, {}: {} frames exceed the {} that {} taps leave room for (vc_wpe_max_frames)'.format(
+            what, Fmax, cap, cfg.taps))
+
+
+def _wpe_launch(re, im, d_nf, cfg, return_taps):
+    """vc_wpe_f32 on validated device tensors: the namedtuple of wpe_batch; no host check, copy or wait in here."""
+    import ctypes
+    import torch
+    B, n_bins, Fmax = re.shape
+    out_re, out_im = torch.empty_like(re), torch.empty_like(im)
+    status = torch.empty((B, n_bins), dtype=torch.int32, device=re.device)
+    taps = torch.empty((B, n_bins, cfg.taps, 2), dtype=torch.float32, device=re.device) if return_taps else None
+    _vc.check(_vc.lib().vc_wpe_f32(_vc.ptr(re), _vc.ptr(im), _vc.ptr(d_nf), B, n_bins, Fmax, ctypes.byref(cfg), _vc.ptr(out_re),
+                                   _vc.ptr(out_im), _vc.ptr(taps), _vc.ptr(status), _vc.current_stream()))
+    return _WPE_NT(out_re, out_im, status, taps)
+
+
+def wpe_batch(re, im, n_frames, taps=None, delay=None, iterations=3, context=1, floor_db=-60.0, load=1e-8, return_taps=False):
+    """WPE dereverberation of a ragged batch of spectra (vc_wpe_f32): spectra in, spectra out.
+
+    re, im [B, bins, F] float32, planar and bin-major (audio_lib.stft_complex_batch); n_frames: host integers or an int32 [B]
+    device tensor (None = all F).  taps, delay: the predictor's length and the frames between its newest frame and the
+    predicted one (None: ``wpe_defaults(80, 16000, 400)``, the shipped framing); iterations: re-weighting passes; context:
+    the weight is the power averaged over +-context frames; floor_db: the weight's floor relative to the bin's mean power;
+    load: diagonal loading relative to the mean of the diagonal.
+    Returns a namedtuple of device tensors: re, im [B, bins, F] (frames at or beyond an utterance's count are 0), status int32
+    [B, bins] (0 solved; 1 the factorisation met a pivot that was not positive -- an all-zero bin is one; 2 no more frames
+    than the delay; with 1 or 2 the bin is passed through unchanged) and taps [B, bins, taps, 2] (None unless return_taps).
+    F is limited to wpe_max_frames(taps), at least 6121 (30 s at a 5 ms hop).  Nothing is copied back and the host waits
+    for nothing."""
+    import torch
+    import audio_lib
+    what = 'wpe_batch'
+    B, _, Fmax = audio_lib._check_spectrum_args(what, re, im, n_frames)
+    cfg = wpe_cfg(what, taps, delay, iterations, context, floor_db, load)
+    _check_wpe_frames(what, Fmax, cfg)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('wpe_batch needs a GPU (no CPU fallback)')
+    d_nf = None if n_frames is None else audio_lib._int32_device(n_frames, B, 'n_frames')
+    return _wpe_launch(audio_lib._spectrum_upload(re), audio_lib._spectrum_upload(im), d_nf, cfg, bool(return_taps))
+
+
+def _dereverb_launch(plan, wav, d_len, d_nf, Fmax, cfg, return_taps):
+    """stft, wpe, istft on validated device tensors: the namedtuple of dereverb_batch."""
+    import audio_lib
+    re, im, d_fout = audio_lib._stft_complex_launch(plan, wav, d_len, d_nf, Fmax)
+    r = _wpe_launch(re, im, d_fout, cfg, return_taps)
+    y = audio_lib._istft_complex_launch(plan, r.re, r.im, d_fout)
+    return _DEREVERB_NT(y, d_fout, r.status, r.taps)
+
+
+def dereverb_batch(wav, lens, sr=16000, win_length=400, hop_length=80, n_fft=None, n_frames=None, **wpe_kw):
+    """Late reverberation taken out of a ragged batch of waveforms: y = istft(wpe(stft(wav))).  Three launches and the
+    overlap-add.
+
+    wav, lens, n_frames: as denoise_batch's; the other keywords are wpe_batch's, with taps / delay defaulting to
+    ``wpe_defaults(hop_length, sr, win_length)``.
+    Returns a namedtuple of device tensors: y [B, hop_length * (F - 1)] with F = 1 + Lmax // hop_length (hop_length *
+    (frames - 1) samples per utterance, zeros beyond; a row of zeros for an utterance shorter than the reflect padding),
+    n_frames int32 [B], the frame counts the device used, status int32 [B, bins] and taps (None unless return_taps), as
+    wpe_batch's.  Nothing is copied back and the host waits for nothing."""
+    import torch
+    import audio_lib
+    what = 'dereverb_batch'
+    B, Lmax, Fmax, plan_key = audio_lib._check_stft_wave_args(what, wav, lens, n_frames, win_length, hop_length, n_fft)
+    if Fmax < 2:
+        raise ValueError(' - ERROR, {}: wav must hold at least hop_length = {} samples'.format(what, plan_key[1]))
+    cfg, return_taps = check_wpe_keywords(what, wpe_kw, plan_key[1], sr, plan_key[0])
+    _check_wpe_frames(what, Fmax, cfg)
+    if not torch.cuda.is_available():
+        raise _vc.VCError('dereverb_batch needs a GPU (no CPU fallback)')
+    plan = audio_lib._get_voc_plan(*plan_key)
+    wav, d_len, d_nf = audio_lib._stft_wave_upload(wav, lens, n_frames, B, Lmax)
+    return _dereverb_launch(plan, wav, d_len, d_nf, Fmax, cfg, return_taps)
