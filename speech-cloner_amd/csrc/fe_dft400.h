@@ -70,6 +70,22 @@ VC_HD void cdft5(float* zr, float* zi) {
     zr[3] = u2r - w2i; zi[3] = u2i + w2r;
 }
 
+// Stage B of rdft25_13 for c = 1, 2: where the outputs Z0..Z4 of the two complex 5-point DFTs go.
+VC_HD void rdft25_place(const float* t1r, const float* t1i, const float* t2r, const float* t2i, float* ar, float* ai) {
+    // c = 1: k1 = 1, 6, 11, 16 -> conj -> 9, 21 -> conj -> 4
+    ar[1] = t1r[0]; ai[1] = t1i[0];
+    ar[6] = t1r[1]; ai[6] = t1i[1];
+    ar[11] = t1r[2]; ai[11] = t1i[2];
+    ar[9] = t1r[3]; ai[9] = -t1i[3];
+    ar[4] = t1r[4]; ai[4] = -t1i[4];
+    // c = 2: k1 = 2, 7, 12, 17 -> conj -> 8, 22 -> conj -> 3
+    ar[2] = t2r[0]; ai[2] = t2i[0];
+    ar[7] = t2r[1]; ai[7] = t2i[1];
+    ar[12] = t2r[2]; ai[12] = t2i[2];
+    ar[8] = t2r[3]; ai[8] = -t2i[3];
+    ar[3] = t2r[4]; ai[3] = -t2i[4];
+}
+
 // Real-input 25-point DFT: v[0..24] real -> A[k1], k1 = 0..12 (re/im).
 VC_HD void rdft25_13(const float* v, float* ar, float* ai) {
     // stage A: for each b, DFT-5 over a of v[5a+b]; keep c = 0,1,2; twiddle by W25^(b c)
@@ -93,20 +109,9 @@ VC_HD void rdft25_13(const float* v, float* ar, float* ai) {
         ar[5] = r1; ai[5] = i1;
         ar[10] = r2; ai[10] = i2;
     }
-    // c = 1: k1 = 1, 6, 11, 16 -> conj -> 9, 21 -> conj -> 4
     cdft5(t1r, t1i);
-    ar[1] = t1r[0]; ai[1] = t1i[0];
-    ar[6] = t1r[1]; ai[6] = t1i[1];
-    ar[11] = t1r[2]; ai[11] = t1i[2];
-    ar[9] = t1r[3]; ai[9] = -t1i[3];
-    ar[4] = t1r[4]; ai[4] = -t1i[4];
-    // c = 2: k1 = 2, 7, 12, 17 -> conj -> 8, 22 -> conj -> 3
     cdft5(t2r, t2i);
-    ar[2] = t2r[0]; ai[2] = t2i[0];
-    ar[7] = t2r[1]; ai[7] = t2i[1];
-    ar[12] = t2r[2]; ai[12] = t2i[2];
-    ar[8] = t2r[3]; ai[8] = -t2i[3];
-    ar[3] = t2r[4]; ai[3] = -t2i[4];
+    rdft25_place(t1r, t1i, t2r, t2i, ar, ai);
 }
 
 // radix-4 butterfly (forward, W4 = -i): in place on 4 complex values.
@@ -208,5 +213,119 @@ VC_HD int src_bin(int k1, int k2, bool& conj) {
     conj = k > 200;
     return conj ? 400 - k : k;
 }
+
+// ---- pinned forms (vc_vocoder.hip) -----------------------------------------------------------------
+// The functions above leave to the compiler which product of a sum a*b + c*d is rounded and which is fused, and it decides by
+// what surrounds them: the same text gives other last bits in another kernel.  The forms below fix every rounding --
+// contraction off, each fused operation an fmaf -- and so compute the same bits wherever they are called.  Their choices are
+// those the vocoder's forward kernels were compiled to before the arithmetic was written down (profiles/vocoder_halves).
+#if defined(__clang__)
+#define VC_FP_PINNED _Pragma("clang fp contract(off)")
+#else
+#define VC_FP_PINNED
+#endif
+
+namespace pinned {
+
+// (r + i i)(wr + i wi).  Each part fuses the product that holds r; re_i / im_i: the one that holds i instead.
+VC_HD void cmul(float& r, float& i, float wr, float wi, bool re_i, bool im_i) {
+    VC_FP_PINNED
+    const float t = re_i ? fmaf(-i, wi, r * wr) : fmaf(r, wr, -(i * wi));
+    i = im_i ? fmaf(i, wr, r * wi) : fmaf(r, wi, i * wr);
+    r = t;
+}
+
+// X1 and X2 of a real 5-point DFT from x0 and the sums and differences of its pairs
+VC_HD void rdft5_tail(float x0, float p1, float p2, float q1, float q2, float& r1, float& i1, float& r2, float& i2) {
+    VC_FP_PINNED
+    r1 = fmaf(C5_2, p2, fmaf(C5_1, p1, x0));
+    i1 = -fmaf(S5_2, q2, S5_1 * q1);
+    r2 = fmaf(C5_1, p2, fmaf(C5_2, p1, x0));
+    i2 = -fmaf(S5_2, q1, -(S5_1 * q2));
+}
+
+VC_HD void cdft5(float* zr, float* zi) {
+    VC_FP_PINNED
+    const float p1r = zr[1] + zr[4], p1i = zi[1] + zi[4];
+    const float p2r = zr[2] + zr[3], p2i = zi[2] + zi[3];
+    const float q1r = zr[1] - zr[4], q1i = zi[1] - zi[4];
+    const float q2r = zr[2] - zr[3], q2i = zi[2] - zi[3];
+    const float u1r = fmaf(C5_2, p2r, fmaf(C5_1, p1r, zr[0])), u1i = fmaf(C5_2, p2i, fmaf(C5_1, p1i, zi[0]));
+    const float u2r = fmaf(C5_1, p2r, fmaf(C5_2, p1r, zr[0])), u2i = fmaf(C5_1, p2i, fmaf(C5_2, p1i, zi[0]));
+    const float w1r = fmaf(S5_1, q1r, S5_2 * q2r), w1i = fmaf(S5_1, q1i, S5_2 * q2i);
+    const float w2r = fmaf(S5_2, q1r, -(S5_1 * q2r)), w2i = fmaf(S5_2, q1i, -(S5_1 * q2i));
+    zr[0] = zr[0] + p1r + p2r;
+    zi[0] = zi[0] + p1i + p2i;
+    zr[1] = u1r + w1i; zi[1] = u1i - w1r;
+    zr[4] = u1r - w1i; zi[4] = u1i + w1r;
+    zr[2] = u2r + w2i; zi[2] = u2i - w2r;
+    zr[3] = u2r - w2i; zi[3] = u2i + w2r;
+}
+
+// rdft25_13 of the windowed samples x[n1] * w[n1].  Samples and window come apart: the window product of the first sample
+// of every pair is fused into the pair's sum and difference.
+VC_HD void rdft25_13_win(const float* x, const float* w, float* ar, float* ai) {
+    VC_FP_PINNED
+    float t0[5], t1r[5], t1i[5], t2r[5], t2i[5];
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+        const float v0 = x[b] * w[b], v3 = x[15 + b] * w[15 + b], v4 = x[20 + b] * w[20 + b];
+        const float p1 = fmaf(x[5 + b], w[5 + b], v4), q1 = fmaf(x[5 + b], w[5 + b], -v4);
+        const float p2 = fmaf(x[10 + b], w[10 + b], v3), q2 = fmaf(x[10 + b], w[10 + b], -v3);
+        t0[b] = fmaf(x[b], w[b], p1) + p2;
+        rdft5_tail(v0, p1, p2, q1, q2, t1r[b], t1i[b], t2r[b], t2i[b]);
+        cmul(t1r[b], t1i[b], W25_RE[b], W25_IM[b], b == 0, false);
+        cmul(t2r[b], t2i[b], W25_RE[2 * b], W25_IM[2 * b], b == 0 || b == 4, false);
+    }
+    {
+        const float p1 = t0[1] + t0[4], p2 = t0[2] + t0[3], q1 = t0[1] - t0[4], q2 = t0[2] - t0[3];
+        ar[0] = t0[0] + p1 + p2; ai[0] = 0.0f;
+        rdft5_tail(t0[0], p1, p2, q1, q2, ar[5], ai[5], ar[10], ai[10]);
+    }
+    cdft5(t1r, t1i);
+    cdft5(t2r, t2i);
+    rdft25_place(t1r, t1i, t2r, t2i, ar, ai);
+}
+
+// Step 2 on row k1: the imaginary part fuses i * wr in the rows of IM_I_ROWS, r * wi in the others.  Short-time power and
+// complex STFT were compiled to TW_POWER, STFT filter and Griffin-Lim iteration to TW_FILTER; each keeps its bits.
+constexpr unsigned TW_POWER = 0x18C7u;   // rows 0, 1, 2, 6, 7, 11, 12: those whose A[k1] rdft25_13_win does not conjugate
+constexpr unsigned TW_FILTER = 0u;
+template <unsigned IM_I_ROWS>
+VC_HD void twiddle400(float& r, float& i, float wr, float wi, int k1) {
+    cmul(r, i, wr, wi, false, (IM_I_ROWS >> k1) & 1u);
+}
+
+// cdft16 as stft_power400_kernel and stft_complex400_kernel were compiled to it
+VC_HD void cdft16(const float* zr, const float* zi, float* yr, float* yi) {
+    float ur[4][4], ui[4][4];              // [q][r]
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float r0 = zr[q], i0 = zi[q], r1 = zr[4 + q], i1 = zi[4 + q];
+        float r2 = zr[8 + q], i2 = zi[8 + q], r3 = zr[12 + q], i3 = zi[12 + q];
+        bfly4(r0, i0, r1, i1, r2, i2, r3, i3);
+        ur[q][0] = r0; ui[q][0] = i0; ur[q][1] = r1; ui[q][1] = i1;
+        ur[q][2] = r2; ui[q][2] = i2; ur[q][3] = r3; ui[q][3] = i3;
+    }
+    cmul(ur[1][1], ui[1][1], C16_1, -S16_1, false, true);
+    cmul(ur[1][2], ui[1][2], R2, -R2, true, true);
+    cmul(ur[1][3], ui[1][3], S16_1, -C16_1, false, true);
+    cmul(ur[2][1], ui[2][1], R2, -R2, true, true);
+    { const float t = ur[2][2]; ur[2][2] = ui[2][2]; ui[2][2] = -t; }
+    cmul(ur[2][3], ui[2][3], -R2, -R2, true, true);
+    cmul(ur[3][1], ui[3][1], S16_1, -C16_1, false, true);
+    cmul(ur[3][2], ui[3][2], -R2, -R2, true, true);
+    cmul(ur[3][3], ui[3][3], -C16_1, S16_1, false, false);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float r0 = ur[0][r], i0 = ui[0][r], r1 = ur[1][r], i1 = ui[1][r];
+        float r2 = ur[2][r], i2 = ui[2][r], r3 = ur[3][r], i3 = ui[3][r];
+        bfly4(r0, i0, r1, i1, r2, i2, r3, i3);
+        yr[r] = r0; yi[r] = i0; yr[r + 4] = r1; yi[r + 4] = i1;
+        yr[r + 8] = r2; yi[r + 8] = i2; yr[r + 12] = r3; yi[r + 12] = i3;
+    }
+}
+
+}  // namespace pinned
 
 }  // namespace vcfe

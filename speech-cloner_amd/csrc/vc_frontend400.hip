@@ -529,6 +529,8 @@ fe400_kernel(Fe400Args a) {
     // the operand order the optimiser settles on -- inside a helper it settles on another one (measured: 28 of a
     // block's LDS row stores and 3 of its power stores then hold other expressions; the features move by up to
     // 2.4e-6).  Both copies must stay textually equal: the forms agree to rounding only as long as they are.
+    // The way out is vcfe::pinned of fe_dft400.h (the vocoder's forward kernels are on it): read the choices these two
+    // copies were compiled to out of their ISA, write them down as fmaf, and one definition serves both.
     float mw_[14], pw[16];
 #pragma unroll
     for (int j = 0; j < 14; ++j) mw_[j] = 0.0f;

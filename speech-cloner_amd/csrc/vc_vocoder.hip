@@ -97,20 +97,136 @@ __device__ __forceinline__ void gather_tile(const GlArgs& a, const float* fr, co
     }
 }
 
+// ---- the transform halves every STFT-domain kernel below is made of: one definition each, its roundings written down
+// (explicit fmaf, nothing left to contract: fe_dft400.h "pinned forms"), the same bits in every caller.
+// LDS of a 400-point tile: the plan's window [400] and twiddles [2][208], the transform's rows Are, Aim [NROW][VA_STRIDE], then
+// the kernel's own (the gathered samples [span]; INIT: the magnitude and the phase tile)
+constexpr int NROW = VG * 13;
+struct Tile400 { float *win, *tw, *Are, *Aim, *rest; };
+__device__ __forceinline__ Tile400 carve400(char* smem) {
+    float* win = reinterpret_cast<float*>(smem);
+    return {win, win + 400, win + 816, win + 816 + NROW * VA_STRIDE, win + 816 + 2 * NROW * VA_STRIDE};
+}
+
+// Thread (g, k1) = tid / 13, tid % 13 holds the 16 slots S[k1 + 25 k2] of frame g.  Their values from rows [VG][201] of
+// per-bin magnitudes or gains (a conjugate slot: the value of its mirror bin); 0 in a thread without a live frame.
+__device__ __forceinline__ void load_slots400(const float* rows, int nvalid, int tid, float* v) {
+    const int g = min(tid / 13, VG - 1), k1 = tid - (tid / 13) * 13;
+    const bool live = tid < NROW && g < nvalid;
+    const float* src = rows + (size_t)(live ? g : 0) * 201;
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) {
+        bool cj;
+        const int bin = vcfe::src_bin(live ? k1 : 0, k2, cj);
+        const float x = src[bin];
+        v[k2] = live ? x : 0.0f;
+    }
+}
+
+// Forward steps 1 and 2, thread (g, n2): frame g of the samples xs, windowed -> A[k1][n2] W400^(n2 k1); TW: vcfe::pinned::twiddle400
+template <unsigned TW>
+__device__ __forceinline__ void forward400_rows(const Tile400& t, const float* xs, int hop, int tid) {
+    const int g = tid >> 4, n2 = tid & 15;
+    const float* xp = xs + g * hop + n2;
+    float x[25], w[25], ar[13], ai[13];
+#pragma unroll
+    for (int n1 = 0; n1 < 25; ++n1) { x[n1] = xp[16 * n1]; w[n1] = t.win[16 * n1 + n2]; }
+    vcfe::pinned::rdft25_13_win(x, w, ar, ai);
+    const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+    for (int k1 = 0; k1 < 13; ++k1) {
+        vcfe::pinned::twiddle400<TW>(ar[k1], ai[k1], t.tw[k1 * 16 + n2], t.tw[208 + k1 * 16 + n2], k1);
+        t.Are[i0 + VA_STRIDE * k1] = ar[k1];
+        t.Aim[i0 + VA_STRIDE * k1] = ai[k1];
+    }
+}
+
+// Forward step 3, row tid < NROW: its 16 slots are the bins k1 + 25 k2 and the conjugates of the mirrors of those above 200
+__device__ __forceinline__ void forward400_cols(const Tile400& t, int tid, float* yr, float* yi) {
+    float zr[16], zi[16];
+#pragma unroll
+    for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = t.Are[VA_STRIDE * tid + n2]; zi[n2] = t.Aim[VA_STRIDE * tid + n2]; }
+    vcfe::pinned::cdft16(zr, zi, yr, yi);
+}
+
+// the 16 slots zr / zi of row tid < NROW: inverse 16-point stage, conjugate twiddle -> B[k1][n2] in A's place
+__device__ __forceinline__ void inverse400_cols(float* zr, float* zi, const float* tw, float* Are, float* Aim, int tid, int k1) {
+    float yr[16], yi[16];
+    vcfe::cidft16(zr, zi, yr, yi);
+#pragma unroll
+    for (int n2 = 0; n2 < 16; ++n2) {
+        vcfe::cmul(yr[n2], yi[n2], tw[k1 * 16 + n2], -tw[208 + k1 * 16 + n2]);
+        Are[VA_STRIDE * tid + n2] = yr[n2];
+        Aim[VA_STRIDE * tid + n2] = yi[n2];
+    }
+}
+
+// thread (g, n2), g < nvalid: hermitian 25-point inverse, synthesis window, store the frame; tile: the first frame's [400]
+__device__ __forceinline__ void inverse400_rows(const float* Are, const float* Aim, const float* win, float* tile, int nvalid,
+                                                int tid) {
+    const int g = tid >> 4, n2 = tid & 15;
+    if (g < nvalid) {
+        float br[13], bi[13], x[25];
+        const int i0 = VA_STRIDE * (g * 13) + n2;
+#pragma unroll
+        for (int k1 = 0; k1 < 13; ++k1) { br[k1] = Are[i0 + VA_STRIDE * k1]; bi[k1] = Aim[i0 + VA_STRIDE * k1]; }
+        vcfe::hdft25_real(br, bi, x);
+        float* out = tile + (size_t)g * 400 + n2;
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) out[16 * n1] = x[n1] * win[16 * n1 + n2] * (1.0f / 400.0f);
+    }
+}
+
+// LDS of a generic-path tile: the plan's window [N] and twiddle table twr, twi [N] each, then the kernel's own
+struct TileGen { float *win, *twr, *twi, *rest; };
+__device__ __forceinline__ TileGen carve_generic(char* smem, int N) {
+    float* win = reinterpret_cast<float*>(smem);
+    return {win, win + N, win + 2 * N, win + 3 * N};
+}
+__device__ __forceinline__ void load_generic(const TileGen& t, const float* tables, int N) {
+    copy_lds(t.win, tables, N);
+    copy_lds(t.twr, tables + N + 416, 2 * N);
+}
+
+// The generic path's two sums.  Bin k of the frame at xp: sum_n (x[n] w[n]) exp(-2 pi i k n / N)
+__device__ __forceinline__ void forward_generic_bin(const float* xp, const float* win, const float* twr, const float* twi, int k,
+                                                    int N, float& re, float& im) {
+    re = 0.0f; im = 0.0f;
+    int m = 0;
+    for (int n = 0; n < N; ++n) {
+        const float xv = xp[n] * win[n];
+        re = fmaf(xv, twr[m], re);
+        im = fmaf(xv, twi[m], im);
+        m += k; if (m >= N) m -= N;
+    }
+}
+
+// Sample n of the windowed inverse of sr / si [nb] (Im of bin 0 and bin N / 2 not read), twr = cos, twi = -sin:
+// x[n] = (1/N) [S0 + (-1)^n S_{N/2} + 2 sum_{k=1}^{N/2-1} (Sr cos(2 pi k n/N) - Si sin(2 pi k n/N))]
+__device__ __forceinline__ float inverse_generic_sample(const float* sr, const float* si, const float* win, const float* twr,
+                                                        const float* twi, int n, int N, int nb, float invN) {
+    float acc = 0.0f;
+    int m = n;                                        // (k n) mod N for k = 1
+    for (int k = 1; k < nb - 1; ++k) {
+        acc = fmaf(sr[k], twr[m], acc);
+        acc = fmaf(si[k], twi[m], acc);
+        m += n; if (m >= N) m -= N;
+    }
+    const float edge = sr[0] + ((n & 1) ? -sr[nb - 1] : sr[nb - 1]);
+    return (edge + 2.0f * acc) * invN * win[n];
+}
+
 // 400-point iteration (INIT: spectrum = amp * exp(i phase0) instead of the analysis of prev).
 template <bool INIT, int MOM>
 __global__ void __launch_bounds__(VT)
 gl_iter400_kernel(GlArgs a) {
     static_assert(!INIT || MOM == MOM_OFF, "the initial spectrum has no momentum");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NROW = VG * 13;
-    float* win = reinterpret_cast<float*>(smem);       // [400]
-    float* tw = win + 400;                             // [2][208]
-    float* Are = tw + 416;                             // [NROW*17]
-    float* Aim = Are + NROW * VA_STRIDE;
+    const Tile400 t = carve400(smem);
+    float *win = t.win, *tw = t.tw, *Are = t.Are, *Aim = t.Aim;
     // INIT keeps the magnitude tile and the phase tile in LDS; the iteration kernel holds each
     // thread's 16 target magnitudes in registers instead (38 KB of LDS: four blocks per CU)
-    float* amps = Aim + NROW * VA_STRIDE;              // INIT: [VG][201]
+    float* amps = t.rest;    // INIT: [VG][201]
     float* xs = INIT ? amps + VG * 201 : amps;         // [span]  (INIT: phase tile [VG][201])
 
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -127,39 +243,19 @@ gl_iter400_kernel(GlArgs a) {
         const float* ps = a.phase0 + ((size_t)b * a.maxF + f0) * 201;
         for (int i = tid; i < VG * 201; i += VT) xs[i] = (i < nvalid * 201) ? ps[i] : 0.0f;
     } else {
-        const int g = min(tid / 13, VG - 1), k1 = tid - (tid / 13) * 13;
-        const bool live = tid < NROW && g < nvalid;
-        const float* src = a.amp + ((size_t)b * a.maxF + f0 + (live ? g : 0)) * 201;
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) {
-            bool cj;
-            const int bin = vcfe::src_bin(live ? k1 : 0, k2, cj);
-            const float v = src[bin];
-            amr[k2] = live ? v : 0.0f;
-        }
+        load_slots400(a.amp + ((size_t)b * a.maxF + f0) * 201, nvalid, tid, amr);
     }
     __syncthreads();
     if (!INIT) {
         gather_tile(a, a.prev + (size_t)b * a.maxF * 400, win, F, f0, xs);
         __syncthreads();
-        // forward step 1+2: thread (g, n2)
-        const int g = tid >> 4, n2 = tid & 15;
-        const float* xp = xs + g * a.hop + n2;
-        float v[25], ar[13], ai[13];
-#pragma unroll
-        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
-        vcfe::rdft25_13(v, ar, ai);
-        const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-        for (int k1 = 0; k1 < 13; ++k1) {
-            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
-            Are[i0 + VA_STRIDE * k1] = ar[k1];
-            Aim[i0 + VA_STRIDE * k1] = ai[k1];
-        }
+        forward400_rows<vcfe::pinned::TW_FILTER>(t, xs, a.hop, tid);
         __syncthreads();
     }
     // thread (g, k1): forward 16-point stage, projection onto the target magnitude, inverse
-    // 16-point stage, conjugate twiddle -> B[k1][n2]
+    // 16-point stage, conjugate twiddle -> B[k1][n2].  In line, here and in stft_filter400_kernel: the products of the
+    // projection (am * ur, gr * yr) are fused into the first additions of cidft16, and the cdft16 before them was compiled
+    // to other choices than vcfe::pinned::cdft16 holds (one of its eight twiddles); these two kernels keep their bits.
     if (tid < NROW) {
         const int g = tid / 13, k1 = tid - g * 13;
         float zr[16], zi[16], yr[16], yi[16];
@@ -215,20 +311,7 @@ gl_iter400_kernel(GlArgs a) {
         }
     }
     __syncthreads();
-    // thread (g, n2): hermitian 25-point inverse, synthesis window, store the frame
-    {
-        const int g = tid >> 4, n2 = tid & 15;
-        if (g < nvalid) {
-            float br[13], bi[13], x[25];
-            const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-            for (int k1 = 0; k1 < 13; ++k1) { br[k1] = Are[i0 + VA_STRIDE * k1]; bi[k1] = Aim[i0 + VA_STRIDE * k1]; }
-            vcfe::hdft25_real(br, bi, x);
-            float* out = a.next + ((size_t)b * a.maxF + f0 + g) * 400 + n2;
-#pragma unroll
-            for (int n1 = 0; n1 < 25; ++n1) out[16 * n1] = x[n1] * win[16 * n1 + n2] * (1.0f / 400.0f);
-        }
-    }
+    inverse400_rows(Are, Aim, win, a.next + ((size_t)b * a.maxF + f0) * 400, nvalid, tid);
 }
 
 // Generic path (any even n_fft): direct O(N^2) DFTs from the LDS twiddle table twg[m] =
@@ -239,10 +322,8 @@ gl_iter_generic_kernel(GlArgs a) {
     static_assert(!INIT || MOM == MOM_OFF, "the initial spectrum has no momentum");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, nb = a.nb;
-    float* win = reinterpret_cast<float*>(smem);       // [N]
-    float* twr = win + N;                              // [N]
-    float* twi = twr + N;                              // [N]
-    float* Sr = twi + N;                               // [VGG][nb]
+    const TileGen t = carve_generic(smem, N);
+    float *win = t.win, *twr = t.twr, *twi = t.twi, *Sr = t.rest;    // [VGG][nb]
     float* Si = Sr + VGG * nb;
     float* xs = Si + VGG * nb;                         // [span]
 
@@ -251,8 +332,7 @@ gl_iter_generic_kernel(GlArgs a) {
     const int f0 = blockIdx.x * VGG;
     if (f0 >= F) return;
     const int nvalid = min(VGG, F - f0);
-    copy_lds(win, a.window, N);
-    copy_lds(twr, a.window + N + 416, 2 * N);
+    load_generic(t, a.window, N);
     __syncthreads();
     if (!INIT) {
         gather_tile(a, a.prev + (size_t)b * a.maxF * N, win, F, f0, xs);
@@ -267,6 +347,7 @@ gl_iter_generic_kernel(GlArgs a) {
             sincosf(a.phase0[((size_t)b * a.maxF + f0 + g) * nb + k], &s, &c);
             ur = c; ui = s;
         } else {
+            // forward_generic_bin's sum in line: which square of m2 below is fused follows this text, differently per flavour
             const float* xp = xs + g * a.hop;
             float re = 0.0f, im = 0.0f;
             int m = 0;
@@ -298,18 +379,8 @@ gl_iter_generic_kernel(GlArgs a) {
     const float invN = 1.0f / (float)N;
     for (int idx = tid; idx < nvalid * N; idx += VT) {
         const int g = idx / N, n = idx - g * N;
-        const float* sr = Sr + g * nb;
-        const float* si = Si + g * nb;
-        // x[n] = (1/N) [S0 + (-1)^n S_{N/2} + 2 sum_{k=1}^{N/2-1} (Sr cos(2 pi k n/N) - Si sin(2 pi k n/N))]
-        float acc = 0.0f;
-        int m = n;                                    // (k n) mod N for k = 1
-        for (int k = 1; k < nb - 1; ++k) {
-            acc = fmaf(sr[k], twr[m], acc);           // twr = cos
-            acc = fmaf(si[k], twi[m], acc);           // twi = -sin
-            m += n; if (m >= N) m -= N;
-        }
-        const float edge = sr[0] + ((n & 1) ? -sr[nb - 1] : sr[nb - 1]);
-        a.next[((size_t)b * a.maxF + f0 + g) * N + n] = (edge + 2.0f * acc) * invN * win[n];
+        a.next[((size_t)b * a.maxF + f0 + g) * N + n] =
+            inverse_generic_sample(Sr + g * nb, Si + g * nb, win, twr, twi, n, N, nb, invN);
     }
 }
 
@@ -327,12 +398,14 @@ struct SfArgs {
     int wav_stride, maxF, nb, N, hop, span;
 };
 
-// F_b, 0 for an utterance the reflect padding does not fit; len: the clamped sample count
+// F_b, 0 for an utterance the reflect padding does not fit; len: the clamped sample count.  The first workgroup records F_b.
 __device__ __forceinline__ int sf_frames(const SfArgs& a, int b, int& len) {
     len = min(max(a.len[b], 0), a.wav_stride);
     int F = min(a.maxF, 1 + len / a.hop);
     if (a.n_frames) F = min(F, max(a.n_frames[b], 0));
-    return (len <= a.N / 2 || a.hop * (F - 1) <= a.N / 2) ? 0 : F;
+    if (len <= a.N / 2 || a.hop * (F - 1) <= a.N / 2) F = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.f_out[b] = F;
+    return F;
 }
 
 // Samples of the reflect-padded signal x[0, len) this tile needs -> xs[0..span); len > N / 2, F >= 2
@@ -351,118 +424,29 @@ __device__ __forceinline__ void sf_gather_tile(const SfArgs& a, const float* x, 
     }
 }
 
-// The inverse half of the 400-point tile kernels and the generic path's two sums as functions: what the complex STFT and its
-// inverse (further down) are made of.  The filter and power kernels below hold the same statements in line and keep them:
-// moved onto functions they compile to other contraction choices (seen in their ISA), so their outputs would change in
-// the last bit; for the same reason the complex STFT repeats the power kernel's forward half word for word -- the two
-// must produce the same re and im.  Are / Aim are the tile's [VG * 13][VA_STRIDE] rows, tw the plan's [2][208] twiddles.
-// the 16 slots zr / zi of row tid < VG * 13: inverse 16-point stage, conjugate twiddle -> B[k1][n2] in A's place
-__device__ __forceinline__ void sf_inverse400_cols(float* zr, float* zi, const float* tw, float* Are, float* Aim, int tid, int k1) {
-    float yr[16], yi[16];
-    vcfe::cidft16(zr, zi, yr, yi);
-#pragma unroll
-    for (int n2 = 0; n2 < 16; ++n2) {
-        vcfe::cmul(yr[n2], yi[n2], tw[k1 * 16 + n2], -tw[208 + k1 * 16 + n2]);
-        Are[VA_STRIDE * tid + n2] = yr[n2];
-        Aim[VA_STRIDE * tid + n2] = yi[n2];
-    }
-}
-
-// thread (g, n2), g < nvalid: hermitian 25-point inverse, synthesis window, store the frame; tile: the first frame's [400]
-__device__ __forceinline__ void sf_inverse400_rows(const float* Are, const float* Aim, const float* win, float* tile, int nvalid,
-                                                   int tid) {
-    const int g = tid >> 4, n2 = tid & 15;
-    if (g < nvalid) {
-        float br[13], bi[13], x[25];
-        const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-        for (int k1 = 0; k1 < 13; ++k1) { br[k1] = Are[i0 + VA_STRIDE * k1]; bi[k1] = Aim[i0 + VA_STRIDE * k1]; }
-        vcfe::hdft25_real(br, bi, x);
-        float* out = tile + (size_t)g * 400 + n2;
-#pragma unroll
-        for (int n1 = 0; n1 < 25; ++n1) out[16 * n1] = x[n1] * win[16 * n1 + n2] * (1.0f / 400.0f);
-    }
-}
-
-// The generic path's two sums.  Bin k of the frame at xp: sum_n (x[n] w[n]) exp(-2 pi i k n / N)
-__device__ __forceinline__ void sf_forward_generic_bin(const float* xp, const float* win, const float* twr, const float* twi, int k,
-                                                       int N, float& re, float& im) {
-    re = 0.0f; im = 0.0f;
-    int m = 0;
-    for (int n = 0; n < N; ++n) {
-        const float xv = xp[n] * win[n];
-        re = fmaf(xv, twr[m], re);
-        im = fmaf(xv, twi[m], im);
-        m += k; if (m >= N) m -= N;
-    }
-}
-
-// Sample n of the windowed inverse of the spectrum sr / si [nb]; the imaginary parts of bin 0 and bin N / 2 are not read
-__device__ __forceinline__ float sf_inverse_generic_sample(const float* sr, const float* si, const float* win, const float* twr,
-                                                           const float* twi, int n, int N, int nb, float invN) {
-    float acc = 0.0f;
-    int m = n;
-    for (int k = 1; k < nb - 1; ++k) {
-        acc = fmaf(sr[k], twr[m], acc);
-        acc = fmaf(si[k], twi[m], acc);
-        m += n; if (m >= N) m -= N;
-    }
-    const float edge = sr[0] + ((n & 1) ? -sr[nb - 1] : sr[nb - 1]);
-    return (edge + 2.0f * acc) * invN * win[n];
-}
-
 __global__ void __launch_bounds__(VT)
 stft_filter400_kernel(SfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NROW = VG * 13;
-    float* win = reinterpret_cast<float*>(smem);       // [400]
-    float* tw = win + 400;                             // [2][208]
-    float* Are = tw + 416;                             // [NROW*17]
-    float* Aim = Are + NROW * VA_STRIDE;
-    float* xs = Aim + NROW * VA_STRIDE;                // [span]
+    const Tile400 t = carve400(smem);
+    float *win = t.win, *tw = t.tw, *Are = t.Are, *Aim = t.Aim, *xs = t.rest;
 
     const int b = blockIdx.y, tid = threadIdx.x;
     int len;
     const int F = sf_frames(a, b, len);
     const int f0 = blockIdx.x * VG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     if (f0 >= F) return;
     const int nvalid = min(VG, F - f0);
 
     copy_lds(win, a.window, 816);
     float gr[16];                                      // the gains of this thread's 16 slots, as amr[] of the iteration kernel
-    {
-        const int g = min(tid / 13, VG - 1), k1 = tid - (tid / 13) * 13;
-        const bool live = tid < NROW && g < nvalid;
-        const float* src = a.gain + ((size_t)b * a.maxF + f0 + (live ? g : 0)) * 201;
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) {
-            bool cj;
-            const int bin = vcfe::src_bin(live ? k1 : 0, k2, cj);      // a conjugate slot: the gain of its mirror bin
-            const float v = src[bin];
-            gr[k2] = live ? v : 0.0f;
-        }
-    }
+    load_slots400(a.gain + ((size_t)b * a.maxF + f0) * 201, nvalid, tid, gr);
     __syncthreads();
     sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
     __syncthreads();
-    {   // forward step 1+2: thread (g, n2)
-        const int g = tid >> 4, n2 = tid & 15;
-        const float* xp = xs + g * a.hop + n2;
-        float v[25], ar[13], ai[13];
-#pragma unroll
-        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
-        vcfe::rdft25_13(v, ar, ai);
-        const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-        for (int k1 = 0; k1 < 13; ++k1) {
-            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
-            Are[i0 + VA_STRIDE * k1] = ar[k1];
-            Aim[i0 + VA_STRIDE * k1] = ai[k1];
-        }
-    }
+    forward400_rows<vcfe::pinned::TW_FILTER>(t, xs, a.hop, tid);
     __syncthreads();
-    // thread (g, k1): forward 16-point stage, G * Z, inverse 16-point stage, conjugate twiddle -> B[k1][n2]
+    // thread (g, k1): forward 16-point stage, G * Z, inverse 16-point stage, conjugate twiddle -> B[k1][n2]; in line for
+    // the reason given in gl_iter400_kernel
     if (tid < NROW) {
         const int k1 = tid - (tid / 13) * 13;
         float zr[16], zi[16], yr[16], yi[16];
@@ -483,30 +467,15 @@ stft_filter400_kernel(SfArgs a) {
         }
     }
     __syncthreads();
-    // thread (g, n2): hermitian 25-point inverse, synthesis window, store the frame
-    {
-        const int g = tid >> 4, n2 = tid & 15;
-        if (g < nvalid) {
-            float br[13], bi[13], x[25];
-            const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-            for (int k1 = 0; k1 < 13; ++k1) { br[k1] = Are[i0 + VA_STRIDE * k1]; bi[k1] = Aim[i0 + VA_STRIDE * k1]; }
-            vcfe::hdft25_real(br, bi, x);
-            float* out = a.frames + ((size_t)b * a.maxF + f0 + g) * 400 + n2;
-#pragma unroll
-            for (int n1 = 0; n1 < 25; ++n1) out[16 * n1] = x[n1] * win[16 * n1 + n2] * (1.0f / 400.0f);
-        }
-    }
+    inverse400_rows(Are, Aim, win, a.frames + ((size_t)b * a.maxF + f0) * 400, nvalid, tid);
 }
 
 __global__ void __launch_bounds__(VT)
 stft_filter_generic_kernel(SfArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, nb = a.nb;
-    float* win = reinterpret_cast<float*>(smem);       // [N]
-    float* twr = win + N;                              // [N]
-    float* twi = twr + N;                              // [N]
-    float* Sr = twi + N;                               // [VGG][nb]
+    const TileGen t = carve_generic(smem, N);
+    float *win = t.win, *twr = t.twr, *twi = t.twi, *Sr = t.rest;    // [VGG][nb]
     float* Si = Sr + VGG * nb;
     float* xs = Si + VGG * nb;                         // [span]
 
@@ -514,26 +483,17 @@ stft_filter_generic_kernel(SfArgs a) {
     int len;
     const int F = sf_frames(a, b, len);
     const int f0 = blockIdx.x * VGG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     if (f0 >= F) return;
     const int nvalid = min(VGG, F - f0);
-    copy_lds(win, a.window, N);
-    copy_lds(twr, a.window + N + 416, 2 * N);
+    load_generic(t, a.window, N);
     __syncthreads();
     sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
     __syncthreads();
     for (int idx = tid; idx < nvalid * nb; idx += VT) {
         const int g = idx / nb, k = idx - g * nb;
         const float gn = a.gain[((size_t)b * a.maxF + f0 + g) * nb + k];
-        const float* xp = xs + g * a.hop;
-        float re = 0.0f, im = 0.0f;
-        int m = 0;
-        for (int n = 0; n < N; ++n) {
-            const float xv = xp[n] * win[n];
-            re = fmaf(xv, twr[m], re);
-            im = fmaf(xv, twi[m], im);
-            m += k; if (m >= N) m -= N;
-        }
+        float re, im;
+        forward_generic_bin(xs + g * a.hop, win, twr, twi, k, N, re, im);
         Sr[idx] = gn * re;
         Si[idx] = gn * im;
     }
@@ -541,17 +501,8 @@ stft_filter_generic_kernel(SfArgs a) {
     const float invN = 1.0f / (float)N;
     for (int idx = tid; idx < nvalid * N; idx += VT) {
         const int g = idx / N, n = idx - g * N;
-        const float* sr = Sr + g * nb;
-        const float* si = Si + g * nb;
-        float acc = 0.0f;
-        int m = n;
-        for (int k = 1; k < nb - 1; ++k) {
-            acc = fmaf(sr[k], twr[m], acc);
-            acc = fmaf(si[k], twi[m], acc);
-            m += n; if (m >= N) m -= N;
-        }
-        const float edge = sr[0] + ((n & 1) ? -sr[nb - 1] : sr[nb - 1]);
-        a.frames[((size_t)b * a.maxF + f0 + g) * N + n] = (edge + 2.0f * acc) * invN * win[n];
+        a.frames[((size_t)b * a.maxF + f0 + g) * N + n] =
+            inverse_generic_sample(Sr + g * nb, Si + g * nb, win, twr, twi, n, N, nb, invN);
     }
 }
 
@@ -565,19 +516,14 @@ __device__ __forceinline__ void sp_zero_rows(float* dst, int n) {
 __global__ void __launch_bounds__(VT)
 stft_power400_kernel(SfArgs a, float* __restrict__ power) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NROW = VG * 13;
-    float* win = reinterpret_cast<float*>(smem);       // [400]
-    float* tw = win + 400;                             // [2][208]
-    float* Are = tw + 416;                             // [NROW*17]; later the tile's power [VG][201]
-    float* Aim = Are + NROW * VA_STRIDE;
-    float* xs = Aim + NROW * VA_STRIDE;                // [span]
+    const Tile400 t = carve400(smem);
+    float *win = t.win, *Are = t.Are, *xs = t.rest;    // Are: later the tile's power [VG][201]
     static_assert(VG * 201 <= NROW * VA_STRIDE, "the power tile must fit the transform's rows");
 
     const int b = blockIdx.y, tid = threadIdx.x;
     int len;
     const int F = sf_frames(a, b, len);
     const int f0 = blockIdx.x * VG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     const int nrows = min(VG, a.maxF - f0);            // rows of d_power this tile owns
     float* dst = power + ((size_t)b * a.maxF + f0) * 201;
     if (f0 >= F) { sp_zero_rows(dst, nrows * 201); return; }
@@ -587,30 +533,10 @@ stft_power400_kernel(SfArgs a, float* __restrict__ power) {
     __syncthreads();
     sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
     __syncthreads();
-    {   // forward step 1+2: thread (g, n2)
-        const int g = tid >> 4, n2 = tid & 15;
-        const float* xp = xs + g * a.hop + n2;
-        float v[25], ar[13], ai[13];
-#pragma unroll
-        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
-        vcfe::rdft25_13(v, ar, ai);
-        const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-        for (int k1 = 0; k1 < 13; ++k1) {
-            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
-            Are[i0 + VA_STRIDE * k1] = ar[k1];
-            Aim[i0 + VA_STRIDE * k1] = ai[k1];
-        }
-    }
+    forward400_rows<vcfe::pinned::TW_POWER>(t, xs, a.hop, tid);
     __syncthreads();
-    // thread (g, k1): forward 16-point stage; its 16 slots are the bins k1 + 25 k2 and the mirrors of those above 200
     float yr[16], yi[16];
-    if (tid < NROW) {
-        float zr[16], zi[16];
-#pragma unroll
-        for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = Are[VA_STRIDE * tid + n2]; zi[n2] = Aim[VA_STRIDE * tid + n2]; }
-        vcfe::cdft16(zr, zi, yr, yi);
-    }
+    if (tid < NROW) forward400_cols(t, tid, yr, yi);
     __syncthreads();                                   // every row of Are has been read
     if (tid < NROW) {
         const int g = tid / 13, k1 = tid - g * 13;
@@ -630,22 +556,18 @@ __global__ void __launch_bounds__(VT)
 stft_power_generic_kernel(SfArgs a, float* __restrict__ power) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, nb = a.nb;
-    float* win = reinterpret_cast<float*>(smem);       // [N]
-    float* twr = win + N;                              // [N]
-    float* twi = twr + N;                              // [N]
-    float* xs = twi + N;                               // [span]
+    const TileGen t = carve_generic(smem, N);
+    float *win = t.win, *twr = t.twr, *twi = t.twi, *xs = t.rest;    // [span]
 
     const int b = blockIdx.y, tid = threadIdx.x;
     int len;
     const int F = sf_frames(a, b, len);
     const int f0 = blockIdx.x * VGG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     const int nrows = min(VGG, a.maxF - f0);
     float* dst = power + ((size_t)b * a.maxF + f0) * nb;
     if (f0 >= F) { sp_zero_rows(dst, nrows * nb); return; }
     const int nvalid = min(VGG, F - f0);
-    copy_lds(win, a.window, N);
-    copy_lds(twr, a.window + N + 416, 2 * N);
+    load_generic(t, a.window, N);
     __syncthreads();
     sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
     __syncthreads();
@@ -653,16 +575,9 @@ stft_power_generic_kernel(SfArgs a, float* __restrict__ power) {
         float re = 0.0f, im = 0.0f;
         if (idx < nvalid * nb) {
             const int g = idx / nb, k = idx - g * nb;
-            const float* xp = xs + g * a.hop;
-            int m = 0;
-            for (int n = 0; n < N; ++n) {
-                const float xv = xp[n] * win[n];
-                re = fmaf(xv, twr[m], re);
-                im = fmaf(xv, twi[m], im);
-                m += k; if (m >= N) m -= N;
-            }
+            forward_generic_bin(xs + g * a.hop, win, twr, twi, k, N, re, im);
         }
-        dst[idx] = re * re + im * im;
+        dst[idx] = fmaf(im, im, re * re);              // the square this launch has always fused
     }
 }
 
@@ -675,18 +590,13 @@ static_assert(ZT <= VG * 13 * VA_STRIDE, "the spectrum tile must fit the transfo
 __global__ void __launch_bounds__(VT)
 stft_complex400_kernel(SfArgs a, float* __restrict__ re, float* __restrict__ im) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NROW = VG * 13;
-    float* win = reinterpret_cast<float*>(smem);       // [400]
-    float* tw = win + 400;                             // [2][208]
-    float* Are = tw + 416;                             // [NROW*17]; later the tile's spectrum [201][VG]
-    float* Aim = Are + NROW * VA_STRIDE;
-    float* xs = Aim + NROW * VA_STRIDE;                // [span]
+    const Tile400 t = carve400(smem);
+    float *win = t.win, *Are = t.Are, *Aim = t.Aim, *xs = t.rest;      // Are / Aim: later the tile's spectrum [201][VG]
 
     const int b = blockIdx.y, tid = threadIdx.x;
     int len;
     const int F = sf_frames(a, b, len);
     const int f0 = blockIdx.x * VG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     const int ncols = min(VG, a.maxF - f0);            // frames of the outputs this tile owns
     const size_t base = (size_t)b * 201 * a.maxF + f0;
     if (f0 >= F) {
@@ -702,32 +612,11 @@ stft_complex400_kernel(SfArgs a, float* __restrict__ re, float* __restrict__ im)
     __syncthreads();
     sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
     __syncthreads();
-    // The forward half in stft_power400_kernel's own words, not in a function: the two launches must store and
-    // square the SAME re and im, and the compiler contracts the same statements differently once they sit in a function.
-    {   // forward step 1+2: thread (g, n2)
-        const int g = tid >> 4, n2 = tid & 15;
-        const float* xp = xs + g * a.hop + n2;
-        float v[25], ar[13], ai[13];
-#pragma unroll
-        for (int n1 = 0; n1 < 25; ++n1) v[n1] = xp[16 * n1] * win[16 * n1 + n2];
-        vcfe::rdft25_13(v, ar, ai);
-        const int i0 = VA_STRIDE * (g * 13) + n2;
-#pragma unroll
-        for (int k1 = 0; k1 < 13; ++k1) {
-            vcfe::cmul(ar[k1], ai[k1], tw[k1 * 16 + n2], tw[208 + k1 * 16 + n2]);
-            Are[i0 + VA_STRIDE * k1] = ar[k1];
-            Aim[i0 + VA_STRIDE * k1] = ai[k1];
-        }
-    }
+    // stft_power400_kernel's forward half: the two launches store and square the same re and im
+    forward400_rows<vcfe::pinned::TW_POWER>(t, xs, a.hop, tid);
     __syncthreads();
-    // thread (g, k1): forward 16-point stage; its 16 slots are the bins k1 + 25 k2 and the mirrors of those above 200
     float yr[16], yi[16];
-    if (tid < NROW) {
-        float zr[16], zi[16];
-#pragma unroll
-        for (int n2 = 0; n2 < 16; ++n2) { zr[n2] = Are[VA_STRIDE * tid + n2]; zi[n2] = Aim[VA_STRIDE * tid + n2]; }
-        vcfe::cdft16(zr, zi, yr, yi);
-    }
+    if (tid < NROW) forward400_cols(t, tid, yr, yi);
     __syncthreads();                                   // every row of Are has been read
     if (tid < NROW) {
         const int g = tid / 13, k1 = tid - g * 13;
@@ -756,22 +645,18 @@ __global__ void __launch_bounds__(VT)
 stft_complex_generic_kernel(SfArgs a, float* __restrict__ re, float* __restrict__ im) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, nb = a.nb;
-    float* win = reinterpret_cast<float*>(smem);       // [N]
-    float* twr = win + N;                              // [N]
-    float* twi = twr + N;                              // [N]
-    float* xs = twi + N;                               // [span]
+    const TileGen t = carve_generic(smem, N);
+    float *win = t.win, *twr = t.twr, *twi = t.twi, *xs = t.rest;    // [span]
 
     const int b = blockIdx.y, tid = threadIdx.x;
     int len;
     const int F = sf_frames(a, b, len);
     const int f0 = blockIdx.x * VGG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     const int ncols = min(VGG, a.maxF - f0);
     const int nvalid = min(VGG, max(F - f0, 0));
     const size_t base = (size_t)b * nb * a.maxF + f0;
     if (nvalid > 0) {
-        copy_lds(win, a.window, N);
-        copy_lds(twr, a.window + N + 416, 2 * N);
+        load_generic(t, a.window, N);
         __syncthreads();
         sf_gather_tile(a, a.wav + (size_t)b * a.wav_stride, len, F, f0, xs);
         __syncthreads();
@@ -780,7 +665,7 @@ stft_complex_generic_kernel(SfArgs a, float* __restrict__ re, float* __restrict_
         const int k = idx / VGG, g = idx - k * VGG;
         if (g >= ncols) continue;
         float vr = 0.0f, vi = 0.0f;
-        if (g < nvalid) sf_forward_generic_bin(xs + g * a.hop, win, twr, twi, k, N, vr, vi);
+        if (g < nvalid) forward_generic_bin(xs + g * a.hop, win, twr, twi, k, N, vr, vi);
         re[base + (size_t)k * a.maxF + g] = vr;
         im[base + (size_t)k * a.maxF + g] = vi;
     }
@@ -798,23 +683,21 @@ struct IzArgs {
 };
 
 __device__ __forceinline__ int iz_frames(const IzArgs& a, int b) {
-    const int F = a.n_frames ? min(max(a.n_frames[b], 0), a.maxF) : a.maxF;
-    return a.hop * (F - 1) <= a.N / 2 ? 0 : F;
+    int F = a.n_frames ? min(max(a.n_frames[b], 0), a.maxF) : a.maxF;
+    if (a.hop * (F - 1) <= a.N / 2) F = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.f_out[b] = F;
+    return F;
 }
 
 __global__ void __launch_bounds__(VT)
 istft_complex400_kernel(IzArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NROW = VG * 13;
-    float* win = reinterpret_cast<float*>(smem);       // [400]
-    float* tw = win + 400;                             // [2][208]
-    float* Are = tw + 416;                             // the tile's spectrum [201][VG], then [NROW*17]
-    float* Aim = Are + NROW * VA_STRIDE;
+    const Tile400 t = carve400(smem);
+    float *win = t.win, *tw = t.tw, *Are = t.Are, *Aim = t.Aim;        // Are / Aim: first the tile's spectrum [201][VG]
 
     const int b = blockIdx.y, tid = threadIdx.x;
     const int F = iz_frames(a, b);
     const int f0 = blockIdx.x * VG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     if (f0 >= F) return;
     const int nvalid = min(VG, F - f0);
 
@@ -840,29 +723,25 @@ istft_complex400_kernel(IzArgs a) {
         }
     }
     __syncthreads();                                   // the whole tile has been read
-    if (tid < NROW) sf_inverse400_cols(zr, zi, tw, Are, Aim, tid, k1);
+    if (tid < NROW) inverse400_cols(zr, zi, tw, Are, Aim, tid, k1);
     __syncthreads();
-    sf_inverse400_rows(Are, Aim, win, a.frames + ((size_t)b * a.maxF + f0) * 400, nvalid, tid);
+    inverse400_rows(Are, Aim, win, a.frames + ((size_t)b * a.maxF + f0) * 400, nvalid, tid);
 }
 
 __global__ void __launch_bounds__(VT)
 istft_complex_generic_kernel(IzArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = a.N, nb = a.nb;
-    float* win = reinterpret_cast<float*>(smem);       // [N]
-    float* twr = win + N;                              // [N]
-    float* twi = twr + N;                              // [N]
-    float* Sr = twi + N;                               // [VGG][nb]
+    const TileGen t = carve_generic(smem, N);
+    float *win = t.win, *twr = t.twr, *twi = t.twi, *Sr = t.rest;    // [VGG][nb]
     float* Si = Sr + VGG * nb;
 
     const int b = blockIdx.y, tid = threadIdx.x;
     const int F = iz_frames(a, b);
     const int f0 = blockIdx.x * VGG;
-    if (blockIdx.x == 0 && tid == 0) a.f_out[b] = F;
     if (f0 >= F) return;
     const int nvalid = min(VGG, F - f0);
-    copy_lds(win, a.window, N);
-    copy_lds(twr, a.window + N + 416, 2 * N);
+    load_generic(t, a.window, N);
     const size_t base = (size_t)b * nb * a.maxF + f0;
     for (int idx = tid; idx < VGG * nb; idx += VT) {
         const int k = idx / VGG, g = idx - k * VGG;
@@ -875,7 +754,7 @@ istft_complex_generic_kernel(IzArgs a) {
     for (int idx = tid; idx < nvalid * N; idx += VT) {
         const int g = idx / N, n = idx - g * N;
         a.frames[((size_t)b * a.maxF + f0 + g) * N + n] =
-            sf_inverse_generic_sample(Sr + g * nb, Si + g * nb, win, twr, twi, n, N, nb, invN);
+            inverse_generic_sample(Sr + g * nb, Si + g * nb, win, twr, twi, n, N, nb, invN);
     }
 }
 
