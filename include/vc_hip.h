@@ -2177,6 +2177,72 @@ int32_t vc_wpe_max_frames(int32_t taps);
 int vc_wpe_f32(const float* d_re, const float* d_im, const int32_t* d_n_frames, int32_t batch, int32_t n_bins, int32_t max_frames,
                const vc_wpe_cfg* cfg, float* d_out_re, float* d_out_im, float* d_taps, int32_t* d_status, void* stream);
 
+/* Exemplar conversion.  The non-parallel route: the target speaker is a bank of their own frames, each keyed by the phoneme
+ * recogniser's posterior; every source frame is replaced by the mean of the k bank frames whose posteriors are nearest
+ * (PPG-based exemplar conversion; kNN-VC, Baas et al. 2023, with posteriorgrams in place of WavLM features).  The
+ * Bhattacharyya coefficient sum_c sqrt(p_c q_c) of two posteriors is the dot product of their square roots; with the roots
+ * in 8 bits the search is an int8 matrix product, and integer arithmetic makes EVERYTHING below exact: the device equals the
+ * numpy restatement tests/exemplar_ref.py bit for bit, tie-breaks included, whatever the tiling.  Three launches
+ * (csrc/vc_knn.hip), added without a version bump.
+ *
+ * Key.  p[c] float32 posteriors of C <= 128 classes; Kp = vc_knn_key_width(C) = 64 for C <= 64, else 128 (0: C out of range).
+ *     key[c]  = p[c] > 0 ? (int8) min(127, rintf(127.0f * sqrtf(p[c]))) : 0       c < C;     key[c] = 0,  C <= c < Kp
+ *     norm    = sum_c key[c]^2                                                    int32
+ * The square root is correctly rounded, the product is one float32 product, rintf rounds half to even; a NaN, a negative
+ * value and -0 give 0, +inf gives 127.
+ * vc_ppg_key_i8: d_ppg [batch, max_frames, C] float32 and d_n_frames [batch] to d_key [batch, max_frames, Kp] int8 and d_norm
+ * [batch, max_frames] int32.  A row f >= d_n_frames[b] gets the zero key and norm 0, and its posteriors are not read.  A
+ * bank is keyed by the same launch (batch = 1 serves a compacted bank).  Every output element is written once.
+ *
+ * Distance.  d(q, j) = norm_q + norm_j - 2 * sum_c q[c] * b_j[c], int32, in [0, 4,129,024]; d / (2 * 127^2) approximates the
+ * squared Hellinger distance 1 - sum_c sqrt(p_c q_c).  The distance and not the bare dot product: quantised norms vary by a
+ * few per cent and a dot product favours long keys, while under the distance a key's own copy lies at 0 and nothing is
+ * closer.  Key bytes must lie in [0, 127] (vc_ppg_key_i8 writes no others); with other bytes the result is unspecified,
+ * though nothing is read or written out of bounds.
+ *
+ * Selection (vc_knn_i8).  Query row m = b * max_frames + f of d_qkey [batch * max_frames, Kp] is valid when f < d_n_frames[b].
+ * Its candidates are the bank rows j in [0, n_bank) outside [excl[b][0], excl[b][1]); (0, 0) -- or no table -- excludes
+ * nothing; the exclusion gives leave-one-out when the bank holds the query's own recording.  Candidates are ordered by
+ * (d, j) ascending, a total order; d_idx [Mq, k] and d_dist [Mq, k] (Mq = batch * max_frames, 1 <= k <= 16) receive the first
+ * k of them, slots without a candidate -1 and -1, rows that are not valid -1 throughout.  Every element of both is written
+ * once.  The result is a function of the inputs alone: not of tile sizes, nor of n_splits.
+ * The exclusion table is passed twice, as h_excl (host, [batch, 2] int32: the launcher checks it) and as d_excl (its device
+ * copy: the kernel reads it); both or neither.  n_splits: over how many workgroup columns the bank is split; 0 leaves the
+ * choice to the launcher (vc_knn_splits reports it), a positive value up to 1,024 is honoured, also beyond the number of
+ * 16-row tiles of the bank (such splits are empty).  Workspace: vc_knn_workspace_bytes(Mq, n_bank, k, n_splits) bytes (0 for
+ * arguments the launcher would refuse), 16-byte aligned, as are d_qkey, d_bkey and d_bnorm.
+ * Two launches.  Sweep: grid (query tiles of 16 / 4, splits), one wave per query tile; v_mfma_i32_16x16x64_i8 with 16 bank
+ * rows as A and the 16 queries, resident in registers and negated once, as B; lane l supplies bytes 16 (l >> 4) .. + 15 of row
+ * l & 15 on both sides (and those at + 64 in a second instruction at Kp = 128), reads one query (l & 15) and the four bank
+ * rows 4 (l >> 4) + reg from the accumulator, keeps a sorted list of its best in registers (1, 4, 8 or 16 long, the first
+ * that holds k), and compares the minimum of its four new values with the list's last before it inserts.  The four lane
+ * groups of a query exchange and merge their lists at the end and write them to the workspace [split][m][slot] as (d, j).
+ * Merge: one lane per query row merges the splits' lists and writes the first k.  No LDS, no atomics.
+ *
+ * Mean (vc_knn_mean_f32).  d_values [n_bank, dim] float32.  The list of row m ends before the first slot i that holds an
+ * index outside [0, n_bank) (-1 is one) or, for i >= 1 and d_max >= 0, a distance above d_max; n = the number of slots
+ * before that (a filled slot 0 always counts; d_max < 0: no gate).
+ *     out[m][c] = (((v[idx_0][c] + v[idx_1][c]) + v[idx_2][c]) + ...) / (float) n        float32 additions in slot order,
+ *                                                                                         one IEEE division;  n = 0: zeros
+ * d_out [n_queries, dim] float32 and d_n_used [n_queries] int32 are written once each.  One wave per row, lanes along dim.
+ *
+ * VC_ERR_INVALID before any launch for: a NULL pointer (the exclusion pair excepted), one of h_excl / d_excl without the
+ * other, k outside [1, 16], n_classes outside [1, 128], key_width other than 64 or 128, a row count (batch * max_frames,
+ * n_queries, n_bank) outside [1, 2^24], dim outside [1, 65536], n_splits outside [0, 1024], a pointer that misses its
+ * alignment, an exclusion that is not 0 <= excl[b][0] <= excl[b][1] <= n_bank; VC_ERR_WORKSPACE for a workspace that is too
+ * small.  None of the launches allocates, sets memory, uses atomics or synchronises; the frame counts are read on the
+ * device; all are capturable from the first call. */
+int32_t vc_knn_key_width(int32_t n_classes);
+int vc_ppg_key_i8(const float* d_ppg, const int32_t* d_n_frames, int32_t batch, int32_t max_frames, int32_t n_classes, int8_t* d_key,
+                  int32_t* d_norm, void* stream);
+int32_t vc_knn_splits(int32_t n_queries, int32_t n_bank, int32_t n_splits);
+size_t vc_knn_workspace_bytes(int32_t n_queries, int32_t n_bank, int32_t k, int32_t n_splits);
+int vc_knn_i8(const int8_t* d_qkey, const int32_t* d_qnorm, const int32_t* d_n_frames, const int32_t* h_excl, const int32_t* d_excl,
+              int32_t batch, int32_t max_frames, const int8_t* d_bkey, const int32_t* d_bnorm, int32_t n_bank, int32_t key_width,
+              int32_t k, int32_t n_splits, void* d_workspace, size_t workspace_bytes, int32_t* d_idx, int32_t* d_dist, void* stream);
+int vc_knn_mean_f32(const int32_t* d_idx, const int32_t* d_dist, int32_t n_queries, int32_t k, int32_t d_max, const float* d_values,
+                    int32_t n_bank, int32_t dim, float* d_out, int32_t* d_n_used, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -361,6 +361,13 @@ _SIGS = {
     'vc_istft_complex_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P]),
     'vc_wpe_max_frames': (C.c_int32, [C.c_int32]),
     'vc_wpe_f32': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    # exemplar conversion (csrc/vc_knn.hip)
+    'vc_knn_key_width': (C.c_int32, [C.c_int32]),
+    'vc_ppg_key_i8': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    'vc_knn_splits': (C.c_int32, [C.c_int32] * 3),
+    'vc_knn_workspace_bytes': (C.c_size_t, [C.c_int32] * 4),
+    'vc_knn_i8': (C.c_int, [_P] * 5 + [C.c_int32, C.c_int32, _P, _P] + [C.c_int32] * 4 + [_P, C.c_size_t, _P, _P, _P]),
+    'vc_knn_mean_f32': (C.c_int, [_P, _P] + [C.c_int32] * 3 + [_P, C.c_int32, C.c_int32, _P, _P, _P]),
     'vc_f0_yin_f32': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_float, _P, _P, C.c_int32, _P]),
     'vc_f0_metrics_f32': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
@@ -396,7 +403,7 @@ def lib():
                 fn = getattr(h, name)
             except AttributeError:
                 # exports added without a version bump (vc_resample_*, then vc_mel_cepstra / vc_dtw_* / vc_frame_mcd_f32, then
-                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then vc_stft_power_f32 / vc_noise_gain_f32, then the vc_stoi_* launches and vc_si_sdr_f32, then the spectral-mapping launches (vc_jd_*, vc_mlpg_f32, vc_cep_gain_f32), then the
+                # vc_f0_*, then the speech-activity launches, then the content launches, then vc_spk_* / vc_gmm_*, then the pitch-tracking launches, then vc_align_*, then vc_fullsum_*, then vc_decode_*, then vc_duration_map / vc_time_warp, then vc_psola_*, then vc_spectral_diff_gain_f32 / vc_stft_filter_*, then vc_wsola_*, then the postfilter launches, then the vc_hnm_* launches, then vc_stft_power_f32 / vc_noise_gain_f32, then the vc_stoi_* launches and vc_si_sdr_f32, then the spectral-mapping launches (vc_jd_*, vc_mlpg_f32, vc_cep_gain_f32), then the exemplar launches (vc_ppg_key_i8, vc_knn_*), then the
                 # packed-weights recurrence calls vc_gru_form / vc_gru_pack / vc_gru_bidir_packed): a build older than this binding
                 # lacks them
                 raise VCError('native library %s does not export %s -- it was built from older sources, rebuild it '

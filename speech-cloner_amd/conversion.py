@@ -342,8 +342,9 @@ def _check_dereverb(what, dereverb, cfg_d, Lmax):
 
 
 def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, window_batch, vocode, encoder, wav_sr, out_sr,
-                  res_type, denoise=None, dereverb=None):
+                  res_type, denoise=None, dereverb=None, need_decoder=True):
     """The host checks and tables that convert_batch and convert_duration_batch share, before anything touches the GPU.
+    need_decoder=False: the decoder-free entry point (convert_knn_diff_batch), which checks its own encoder / ppg pair.
     denoise, dereverb: the entry point's own arguments (_check_denoise, _check_dereverb); when either is on, every length is
     cut to whole hops first -- len' = hop * (len // hop), what the filter and the inverse transform return -- so under one
     hop is dropped and no frame count changes."""
@@ -385,7 +386,7 @@ def _convert_host(what, decoder, wav, lens, cfg_d, t_s, t_e, two_pass, utt_ids, 
     window_batch = int(window_batch)
     if window_batch <= 0:
         raise ValueError(' - ERROR, {}: window_batch must be positive'.format(what))
-    if (decoder.encoder is None) == (encoder is None):
+    if need_decoder and (decoder.encoder is None) == (encoder is None):
         raise ValueError(' - ERROR, {}: pass encoder= exactly when the decoder was built without one'.format(what))
     plan = convert_plan(h_lens, cfg_d, t_s, t_e, two_pass)
     hop = int(cfg_d['hop_length'])
@@ -2044,3 +2045,130 @@ def convert_gmm_diff_batch(model, wav, lens=None, cfg_d=None, mixture='soft', ml
     y = _deemphasis_level(vplan, audio_lib._stft_filter_launch(vplan, x, d_lens, gain, d_nuse), d_nuse, F, cfg_d, 0.0)
     y, n_samples = _resample_output(y, h_nsamp, d_nsamp, res_out, cfg_d, out_sr, res_type)
     return _GMM_DIFF_NT(y, n_samples, mel_true, cep_src, cep_pred, gain, [int(v) for v in n_use])
+
+
+# --------------------------------------------------------------------------- exemplar conversion (csrc/vc_knn.hip)
+_KNN_DIFF_NT = namedtuple('convert_knn_diff', _DIFF_NT._fields + ('idx', 'dist', 'n_used'))
+
+
+def convert_knn_diff_batch(bank, wav, lens=None, cfg_d=None, encoder=None, ppg=None, k=4, d_max=None, exclude=None, n_splits=0,
+                           alpha=1.0, max_boost_db=20.0, max_cut_db=30.0, half_width=8, pitch=None, stats_src=None, stats_tgt=None,
+                           w_floor=0.5, f0_args=None, t_e=60, two_pass=True, utt_ids=None, window_batch=64, wav_sr=None, out_sr=None,
+                           res_type='kaiser_best', denoise=None, dereverb=None):
+    """``convert_diff_batch`` without a decoder: every source frame's spectrum is predicted as the mean
+    of the k frames of the target speaker's ``bank`` (exemplar.build_bank / exemplar.bank_wav) whose posteriors are nearest
+    to its own, and the source recording is filtered by the difference, as convert_diff_batch filters it.
+
+    Exactly one of encoder (the phoneme recogniser; the windows go through it as in convert_batch) and ppg ([B, Fout, C]
+    float32 posteriors that are already there, frame u = front-end frame u) is given; C must be the bank's n_classes.
+    k, exclude, n_splits: exemplar.knn_batch's (exclude=bank.rows[...] leaves an utterance's own recording out).  d_max:
+    exemplar.mean_batch's.  The mean is taken in the domain of the bank's values, the front-end's normalised dB spectrum
+    and mel: a geometric mean of powers.
+    Framing, the frames used (n_use = min(n_out, n_clip) of convert_plan with t_s = 0) and every other argument are
+    convert_diff_batch's.  Returns its namedtuple -- stft_pred / mel_pred are the retrieved means, phn_pred the posteriors
+    that were searched with -- followed by idx, dist [B, Fout, k] and n_used [B, Fout] (int32, on the device; -1 / 0 in
+    frames at or beyond n_use).  Every check and table is made on the host before the first launch; after the uploads
+    nothing is copied to the host and the host waits for nothing."""
+    import torch
+    import audio_lib
+    import evaluation
+    import exemplar
+    what = 'convert_knn_diff_batch'
+    _need_cfg(cfg_d, what)
+    alpha, boost, cut = _check_diff_args(alpha, max_boost_db, max_cut_db, what)
+    h_taps = _check_diff_taps(half_width, None, what)
+    if hasattr(pitch, 'item') and getattr(pitch, 'ndim', None) == 0:
+        pitch = pitch.item()
+    kind, pitch = _parse_pitch(pitch, stats_src, stats_tgt, what, True, ('source',),
+                               "None, a ratio, a [B, Fout] contour or 'source'", "pitch='source'")
+    if kind == 'source' and stats_src is None:
+        raise ValueError(" - ERROR, {}: pitch='source' needs stats_src and stats_tgt (the source's own contour unmapped changes nothing)".format(what))
+    if kind == 'source' and (len(stats_src) != 3 or len(stats_tgt) != 3):
+        raise ValueError(' - ERROR, {}: stats must be (count, mean, std) as f0_stats_batch returns them'.format(what))
+    w_floor = _check_w_floor(w_floor, what)
+    f0_kw = _tracker_keys(f0_args, what)
+    if (encoder is None) == (ppg is None):
+        raise ValueError(' - ERROR, {}: pass exactly one of encoder and ppg'.format(what))
+    N, Kp = exemplar._check_bank(bank, what)
+    k, n_splits = exemplar._check_k(k, what), exemplar._check_splits(n_splits, what)
+    d_max = exemplar._check_d_max(d_max, what)
+    h = _convert_host(what, None, wav, lens, cfg_d, 0, t_e, two_pass, utt_ids, window_batch, True, encoder, wav_sr, out_sr, res_type,
+                      denoise, dereverb, need_decoder=False)
+    plan, B, hop, Fout, sr = h.plan, h.B, h.hop, h.plan.Fout, cfg_d['sample_rate']
+    C = int(ppg.shape[2]) if ppg is not None and getattr(ppg, 'ndim', 0) == 3 else int(encoder.cfg_d['n_output']) if encoder is not None else 0
+    if ppg is not None and evaluation._check_ppg(ppg, what + ': ppg') != (B, Fout, C):
+        raise ValueError(' - ERROR, {}: ppg must be [{}, {}, C]'.format(what, B, Fout))
+    if C != int(bank.n_classes) or exemplar.key_width(C) != Kp:
+        raise ValueError(' - ERROR, {}: the bank was keyed over {} classes, the posteriors hold {}'.format(what, bank.n_classes, C))
+    for t, name, width in ((bank.stft, 'stft', h.n_bins), (bank.mel, 'mel', int(cfg_d['n_mels']))):
+        if getattr(t, 'ndim', 0) != 2 or tuple(t.shape) != (N, width) or str(t.dtype) not in ('torch.float32', 'float32'):
+            raise ValueError(' - ERROR, {}: bank.{} must be float32 [{}, {}]'.format(what, name, N, width))
+    if B * Fout > exemplar.MAX_ROWS:
+        raise ValueError(' - ERROR, {}: at most 2^24 query frames (got {} x {})'.format(what, B, Fout))
+    h_excl = exemplar._check_exclude(exclude, B, N, what)
+    n_use, h_nsamp = diff_frames(plan, hop)
+    if int(h_nsamp.min()) <= h.n_fft // 2:
+        raise ValueError(' - ERROR, {}: every utterance needs hop_length*(frames-1) > n_fft//2 samples'.format(what))
+    Lmax = int(audio_lib.resample_len(int(wav.shape[1]), wav_sr, sr)) if h.res_in else int(wav.shape[1])
+    if kind is not None:
+        tracker = _tracker_args(f0_kw, sr, hop, what)
+        _check_pitch_sizes(B, Lmax, 1 + Lmax // hop, hop, what)
+        if Lmax > evaluation.F0_MAX_SAMPLES:
+            raise ValueError(' - ERROR, {}: the tracker takes at most {} samples per utterance'.format(what, evaluation.F0_MAX_SAMPLES))
+        _check_contour(kind, pitch, B, Fout, what, 'frame')
+    _need_gpu(what)
+
+    # ---- uploads: the waveforms if they are on the host, one table, the taps, a contour, the posteriors, the bank
+    extra = [n_use, h_nsamp, plan.n_src] + ([] if h_excl is None else [h_excl])
+    up = _convert_upload(h, wav, extra)
+    if up.wav.shape[0] == 1:                                        # (the stride of a one-row tensor is arbitrary)
+        up = up._replace(wav=up.wav.as_strided(up.wav.shape, (up.wav.shape[1], 1)))
+    d_nuse, d_nsamp, d_fsrc = up.d_extra[-len(extra):][:3]
+    d_excl = None if h_excl is None else up.d_extra[-1]
+    d_taps = torch.from_numpy(h_taps).pin_memory().to('cuda', non_blocking=True)
+    pitch = _contour_upload(kind, pitch)
+    if kind is not None:
+        psola_window('cuda')
+    if ppg is not None:
+        ppg = evaluation._to_device(ppg, torch.float32)
+    bank = bank._replace(key=exemplar._dev(bank.key, torch.int8), norm=exemplar._dev(bank.norm, torch.int32),
+                         stft=exemplar._dev(bank.stft, torch.float32), mel=exemplar._dev(bank.mel, torch.float32))
+    h, up = _resample_input(h, up, cfg_d, wav_sr, res_type)
+    h, up = _denoise_input(h, up, cfg_d, h.denoise)
+
+    # ---- front-end, windows, the recogniser
+    mfcc, mel, pdb = evaluation._fe_launch(up.wav, up.d_lens, cfg_d)
+    mel_true = cut_windows(mel, up.d_true, up.d_clip, Fout)
+    stft_true = cut_windows(pdb, up.d_true, up.d_clip, Fout)
+    if ppg is None:
+        win = cut_windows(mfcc, up.d_win, up.d_clip, plan.T)
+        ys = [encoder.forward(win[i:i + h.window_batch])['y_pred'] for i in range(0, win.shape[0], h.window_batch)]
+        ppg = compound_stitch(ys[0] if len(ys) == 1 else torch.cat(ys, 0), up.d_utt, Fout)
+
+    # ---- keys, search, the two means
+    keys, norms = exemplar._key_launch(ppg, d_nuse)
+    idx, dist = exemplar._knn_launch(keys, norms, d_nuse, h_excl, d_excl, bank, k, n_splits)
+    stft_pred, n_used = exemplar._mean_launch(idx, dist, bank.stft, d_max)
+    mel_pred, _ = exemplar._mean_launch(idx, dist, bank.mel, d_max)
+
+    # ---- the source's fundamental, moved before the filter
+    x, f0_src = up.wav, None
+    if kind is not None:
+        f0_src = evaluation._f0_track_launch(x, up.d_lens, d_fsrc, *tracker)[0]
+        target = None
+        if kind == 'source':
+            target = f0_transform(f0_src, stats_src, stats_tgt)
+        elif kind == 'contour':
+            n = min(Fout, f0_src.shape[1])
+            target = torch.zeros_like(f0_src)
+            target[:, :n] = pitch[:, :n].to(torch.float32)
+        per, rat = pitch_tables(f0_src, sr, ratio=pitch if kind == 'ratio' else None, target_f0=target, hop_length=hop)
+        x = _psola_ola_launch(x, up.d_lens, _psola_plan_launch(per, rat, up.d_lens, x.shape[1], hop), w_floor)
+
+    # ---- gain, filter, level
+    gain = _diff_gain_launch(stft_pred, stft_true, d_nuse, float(cfg_d['P_dB_norm_factor']), alpha, boost, cut, d_taps)
+    vplan = audio_lib._get_voc_plan(cfg_d['win_length'], hop, cfg_d['n_fft'])
+    y = _deemphasis_level(vplan, audio_lib._stft_filter_launch(vplan, x, up.d_lens, gain, d_nuse), d_nuse, Fout, cfg_d, 0.0)
+    y, n_samples = _resample_output(y, h_nsamp, d_nsamp, h.res_out, cfg_d, out_sr, res_type)
+    return _KNN_DIFF_NT(y, n_samples, mel_true, mel_pred, stft_true, stft_pred, ppg, gain, [int(v) for v in n_use], f0_src, idx, dist,
+                        n_used)
